@@ -7,6 +7,7 @@ Default workload = the per-GPU shard of BASELINE.json configs[2]: T=243, J=17, D
 B=64 sequences per GPU (weak scaling: the 8-GPU run is the full B=512 of that config).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   (also writes the last timed step's outputs: dump_outputs())
     python bench.py --gpus N ...            (no launcher: bench.py starts its N rank processes itself, self_launch())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -496,6 +497,34 @@ def self_launch(n: int) -> int:
     return 0
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000      # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, pred, err, cnt, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last timed step returned to its caller, as <out_dir>/<name>.npy.
+
+    pred.npy         float32 (B, F, J, 3): the sampled poses of the (gathered) batch -- every sequence, or, when they would not fit
+                     in `limit`, a fixed sample of sequences (seeded, so equal arguments give equal rows; listed in the returned dict)
+    mpjpe_sums.npy   float64 (2,): the two sums of the MPJPE reduction (error sum, joint count)
+    The inputs are a pure function of the arguments (synth_state_dict / synth_inputs_rows), so two builds run with the same
+    arguments can be compared file for file.  Returns a small dict for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    p = pred.detach().float().cpu().numpy()
+    sums = np.array([err, cnt], dtype=np.float64)
+    rows = None
+    budget = limit - sums.nbytes - 2 * 4096                      # (room for the two .npy headers)
+    row_bytes = max(p[:1].nbytes, 1)
+    if p.nbytes > budget:
+        k = max(budget // row_bytes, 0)
+        rows = np.sort(np.random.default_rng(0).choice(p.shape[0], size=k, replace=False))
+        p = p[rows]
+    np.save(os.path.join(out_dir, "pred.npy"), np.ascontiguousarray(p, dtype=np.float32))
+    np.save(os.path.join(out_dir, "mpjpe_sums.npy"), sums)
+    return {"dir": out_dir, "files": {"pred": list(p.shape), "mpjpe_sums": list(sums.shape)},
+            "pred_rows": "all" if rows is None else rows.tolist()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -529,7 +558,13 @@ def main():
                     help="time the main leg with hipGraph replay of the whole S-step loop (BASELINE configs[3]); per-kernel event "
                          "timing is off then, so the roofline object carries the whole-path figure only")
     ap.add_argument("--no-selfcheck", action="store_true", help="skip the bitwise batch-vs-pair check (profiling passes: keeps the kernel tables to the timed workload)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0; see dump_outputs())")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if a.cpu_worker:                 # child of cpu_baseline_concurrent: CPU only
         T_, seed_, th_, run_ = a.cpu_worker.split(",")
@@ -670,7 +705,7 @@ def main():
         if not first_done:
             first_done.append(time.time())
             _mark_ready()
-        return res
+        return res, pred
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -695,10 +730,11 @@ def main():
         power.start()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        err, cnt = step(record=True)
+        (err, cnt), last_pred = step(record=True)
     fence()
     elapsed = time.perf_counter() - t0
     power_stats = power.stop() if power else None
+    dumped = dump_outputs(a.dump_outputs, last_pred, err, cnt) if (a.dump_outputs and rank == 0) else None
     rank_ms = elapsed / a.steps * 1e3
     try:                                          # process creation -> first sampling (and its reduction) done on this rank
         import psutil
@@ -891,6 +927,8 @@ def main():
                                       "emulation instead).  Not a headline number.")
         if a.graph:
             line["graph_replay"] = True
+        if dumped:
+            line["dump_outputs"] = dumped
         if not d["ms"]:
             roof["note"] = "no profiled pass (--profile-steps 0): 'achieved' is the whole-path figure of the timed region"
             roof.update({"kernel": "whole path", "achieved": round(whole, 2), "frac": round(whole / PEAK_TFLOPS[a.precision], 4),

@@ -220,3 +220,31 @@ def test_bench_self_launch_watchdog_is_quiet_when_every_rank_reports():
     """All ranks report their first sampling: the watchdog never fires even with a tiny limit once they have all reported."""
     run = _bench(["--gpus", "2"], {"D3D_BENCH_LAUNCH_CHECK": "1", "D3D_BENCH_STARTUP_TIMEOUT_S": "30"})
     assert run.returncode == 0 and "had not finished" not in run.stderr, run.stderr
+
+
+def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """bench.py --dump-outputs: the last timed step's prediction (float32) and MPJPE sums (float64) as .npy files; a prediction over
+    the size limit is cut to a seeded sample of whole sequences, the same rows on every call, and the files stay under the limit."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    pred = torch.arange(6 * 5 * 17 * 3, dtype=torch.float32).reshape(6, 5, 17, 3)
+    info = bench.dump_outputs(str(tmp_path / "all"), pred, 12.5, 1530)
+    assert info["pred_rows"] == "all"
+    got = np.load(tmp_path / "all" / "pred.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, pred.numpy())
+    sums = np.load(tmp_path / "all" / "mpjpe_sums.npy")
+    assert sums.dtype == np.float64 and sums.tolist() == [12.5, 1530.0]
+    limit = 3 * pred[:1].numpy().nbytes + 16 + 2 * 4096          # room for three sequences
+    cut = [bench.dump_outputs(str(tmp_path / f"cut{i}"), pred, 12.5, 1530, limit=limit) for i in range(2)]
+    assert cut[0]["pred_rows"] == cut[1]["pred_rows"] and len(cut[0]["pred_rows"]) == 3
+    got = np.load(tmp_path / "cut0" / "pred.npy")
+    assert np.array_equal(got, pred.numpy()[cut[0]["pred_rows"]])
+    assert sum(f.stat().st_size for f in (tmp_path / "cut0").iterdir()) <= limit
+
+
+def test_bench_refuses_zero_steps():
+    run = _bench(["--gpus", "1", "--steps", "0"], {"D3D_BENCH_LAUNCH_CHECK": "1"})
+    assert run.returncode != 0 and "--steps" in run.stderr

@@ -117,6 +117,20 @@ def _clean_env(**extra):
 COMMON = ["--steps", "1", "--warmup", "0", "--frames", "27", "--sampling", "3", "--no-cpu-baseline", "--no-extras"]
 
 
+def test_bench_dump_outputs_is_the_timed_result_and_repeats(tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments write the same files, bit for bit; --steps sets the timed steps; the
+    dumped sums are the ones behind the line's MPJPE, and the dumped prediction is the batch's (B, T, J, 3) poses."""
+    args = ["--gpus", "1", "--batch", "4", "--steps", "2", "--warmup", "1", "--frames", "27", "--sampling", "3", "--no-cpu-baseline",
+            "--no-extras", "--profile-steps", "0"]
+    lines = [_bench_line(args + ["--dump-outputs", str(tmp_path / f"run{i}")], _clean_env()) for i in range(2)]
+    assert all(l["steps"] == 2 and l["ms_per_step"] > 0 for l in lines)
+    pred = [np.load(tmp_path / f"run{i}" / "pred.npy") for i in range(2)]
+    sums = [np.load(tmp_path / f"run{i}" / "mpjpe_sums.npy") for i in range(2)]
+    assert pred[0].dtype == np.float32 and pred[0].shape == (4, 27, 17, 3) and np.isfinite(pred[0]).all()
+    assert np.array_equal(pred[0], pred[1]) and np.array_equal(sums[0], sums[1])
+    assert lines[0]["mpjpe_vs_synthetic_gt"] == round(sums[0][0] / sums[0][1], 6)
+
+
 def test_bench_self_launch_two_ranks_on_one_device():
     """`python bench.py --gpus 2` -- NO torchrun in the command: bench.py starts its two rank processes itself (before torch or HIP
     are touched), they share cuda:0 through gloo (D3D_BENCH_ONE_DEVICE=1), rank 0's single JSON line is relayed, and the gathered
