@@ -36,6 +36,12 @@ def test_allgather_entry_rejects_bad_arguments_without_touching_rccl():
     assert b"bad argument" in L.d3d_last_error()
 
 
+def test_retired_option_key_is_rejected():
+    """A key of a removed experiment switch fails loudly instead of being ignored."""
+    L = _lib.lib()
+    assert L.d3d_engine_set_option(None, b"fc2_ring_op", 1) == -1      # D3D_EINVAL
+
+
 def test_ddim_times_bit_exact_for_every_S():
     g = gold("ddim_times_N1000")
     flat, offs = g["flat"], g["offsets"]
