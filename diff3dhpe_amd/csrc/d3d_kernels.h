@@ -159,15 +159,11 @@ hipError_t launch_gemm_bf16q(const void* A, const void* W, const float* bias, vo
 hipError_t launch_f32_to_bf16(const float* x, void* y, size_t n, hipStream_t s);
 hipError_t launch_bf16_to_f32(const void* x, float* y, size_t n, hipStream_t s);
 hipError_t launch_scale_cols(float* x, size_t rows, int cols, int ncols_scaled, float f, hipStream_t s);   // op hooks only
-// diagnostic launches (variant 13): per (workgroup, wave) six u64 stamps {clk, 100 MHz} x {start, k-loop end, end}
-void set_linear_x3_diag(unsigned long long* dev_buf);
-void attn_x3_diag_report();   // -DD3D_ATTN_DIAG_BUILD builds only: prints the step stamps of the last staggered temporal-attention launch
 
 // ---- kernels_qkv_sattn.hip: spatial blocks, qkv GEMM (LayerNorm-folded) + 17-key attention in one kernel --------------------
 // Apair: the residual stream planes (rows up to 255 * ceil(frames / 15) + 1 are staged); W / bias / csum HEAD-MAJOR (row 192 h +
 // 64 part + d); st_in / st_np / eps as X3Fold; out_x3: attention output in the pair layout.  M = frames * J tokens.
 bool qkv_sattn_ok(int J, int D, int H, int K);
-void set_qkv_sattn_diag(int on);   // "qs_diag" option: in-kernel stamp report of every 50th launch on stderr
 hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, const float* bias_hm, const float* csum_hm, const float* st_in,
                             int st_np, float eps, int w_exp, void* out_x3, int M, int K, int J, int D, int H, hipStream_t s);
 // kernels_qkv_tattn.hip: the temporal counterpart -- the LayerNorm-folded qkv GEMM of one (batch, joint) group (T in 193..255 frames; T <= 127:
@@ -183,7 +179,6 @@ bool fc1_x3_ok(int N, int K);
 hipError_t launch_fc1_x3(const void* Apair, const void* Wpair, const float* bias_f, const float* csum, const float* st_in, int st_np,
                          float eps, int w_exp, void* out_pair, int M, int N, int K, hipStream_t s);
 bool qkv_tattn_ok(int T, int J, int D, int H, int K);
-void set_qkv_tattn_diag(int on);   // "qt_diag": in-kernel stamp report of every 50th launch
 hipError_t launch_qkv_tattn(const void* Apair, const void* Wpair_tileorder, const float* bias_to, const float* csum_to, const float* st_in,
                             int st_np, float eps, int w_exp, void* out_x3, int B, int T, int J, int K, int D, int H, hipStream_t s);
 

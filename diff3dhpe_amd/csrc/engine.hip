@@ -20,8 +20,6 @@ using namespace d3d;
 namespace {
 
 thread_local std::string g_err;
-// process-wide diagnostic switches (d3d_engine_set_option with a NULL engine): in-kernel stamp reports of the op hooks
-std::atomic<int> g_opt_gemm_diag{0}, g_opt_attn_diag{0};
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -1319,10 +1317,6 @@ int d3d_ddim_sample(d3d_engine* e, const float* x2d, const float* init_noise, co
 int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   if (!key) return fail(D3D_EINVAL, "null key");
   const std::string k(key);
-  if (k == "gemm_diag") { g_opt_gemm_diag = value != 0; return D3D_OK; }     // process-wide: e may be NULL
-  if (k == "attn_diag") { g_opt_attn_diag = value != 0; return D3D_OK; }
-  if (k == "qs_diag") { set_qkv_sattn_diag(value != 0); return D3D_OK; }
-  if (k == "qt_diag") { set_qkv_tattn_diag(value != 0); return D3D_OK; }
   if (k == "deep_stages") { set_x3q_deep_stages(value != 0); return D3D_OK; }      // 3 / 4 operand stages in the one-tile-per-workgroup GEMM launches
   if (!e) return fail(D3D_EINVAL, "null engine");
   if (k == "fused_postnorm") e->opt_fused_postnorm = value != 0;
@@ -1726,70 +1720,6 @@ int d3d_op_linear_bench(const float* A, const float* W, const float* bias, const
     return launch_linear_x3p(ap.dev, wp.dev, bias, R, C, nullptr, nullptr, M, N, K, epi, 0, 0, variant, s, nullptr, wp.wexp);
   };
   HIP_TRY(once());
-  if (g_opt_gemm_diag && precision == D3D_PREC_F16X3 && (variant == 13)) {
-    // diagnostic: in-kernel clock and k-loop / epilogue split from s_memtime / s_memrealtime stamps (256x256 tiles, 8 waves)
-    const size_t nwg = (size_t)(((M + 255) / 256 + 7) / 8 * 8) * ((N + 255) / 256), nrec = nwg * 8;
-    unsigned long long* dbuf = nullptr;
-    HIP_TRY(hipMalloc(&dbuf, nrec * 6 * sizeof(unsigned long long)));
-    for (int i = 0; i < 20; ++i) HIP_TRY(once());              // warm clocks
-    HIP_TRY(hipMemsetAsync(dbuf, 0, nrec * 6 * sizeof(unsigned long long), s));
-    set_linear_x3_diag(dbuf);
-    hipError_t le = once();
-    set_linear_x3_diag(nullptr);
-    HIP_TRY(le);
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> h(nrec * 6);
-    HIP_TRY(hipMemcpy(h.data(), dbuf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    (void)hipFree(dbuf);
-    std::vector<double> ghz, loop_us, epi_us;
-    unsigned long long rmin = ~0ull, rmax = 0;
-    for (size_t i = 0; i < nrec; ++i) {
-      const unsigned long long* d = &h[i * 6];
-      if (!d[1]) continue;
-      ghz.push_back((double)(d[4] - d[0]) / (double)(d[5] - d[1]) * 0.1);
-      loop_us.push_back((double)(d[3] - d[1]) * 0.01);
-      epi_us.push_back((double)(d[5] - d[3]) * 0.01);
-      rmin = std::min(rmin, d[1]); rmax = std::max(rmax, d[5]);
-    }
-    auto med = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; };
-    fprintf(stderr, "[gemm diag] N=%d K=%d v%d: waves %zu, in-kernel clock %.3f GHz, k-loop %.2f us, epilogue %.2f us (medians), "
-            "kernel span %.1f us\n", N, K, variant, ghz.size(), med(ghz), med(loop_us), med(epi_us), (double)(rmax - rmin) * 0.01);
-  }
-  if (g_opt_gemm_diag && precision == D3D_PREC_F16X3 && variant == 0) {
-    // diagnostic: start / end stamps (100 MHz) of the persistent walk's workgroups -- how evenly do the CUs finish?
-    unsigned long long* dbuf = nullptr;
-    const size_t nwg = 1024;
-    HIP_TRY(hipMalloc(&dbuf, nwg * 2 * sizeof(unsigned long long)));
-    for (int i = 0; i < 20; ++i) HIP_TRY(once());
-    HIP_TRY(hipMemsetAsync(dbuf, 0, nwg * 2 * sizeof(unsigned long long), s));
-    set_linear_x3_diag(dbuf);
-    hipError_t le = once();
-    set_linear_x3_diag(nullptr);
-    HIP_TRY(le);
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> h(nwg * 2);
-    HIP_TRY(hipMemcpy(h.data(), dbuf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    (void)hipFree(dbuf);
-    unsigned long long t0 = ~0ull, t1 = 0;
-    size_t n = 0;
-    for (size_t i = 0; i < nwg; ++i)
-      if (h[2 * i]) { t0 = std::min(t0, h[2 * i]); t1 = std::max(t1, h[2 * i + 1]); ++n; }
-    if (n) {
-      std::vector<double> endv, xcd_end(8, 0.0);
-      for (size_t i = 0; i < nwg; ++i)
-        if (h[2 * i]) {
-          const double e = (double)(h[2 * i + 1] - t0) * 0.01;
-          endv.push_back(e);
-          xcd_end[i & 7] = std::max(xcd_end[i & 7], e);
-        }
-      std::sort(endv.begin(), endv.end());
-      fprintf(stderr, "[walk diag] N=%d K=%d: %zu workgroups, span %.1f us; workgroup end times (us after the first start): "
-              "min %.1f  p10 %.1f  median %.1f  p90 %.1f  max %.1f; last end per XCD:", N, K, n, (double)(t1 - t0) * 0.01,
-              endv.front(), endv[n / 10], endv[n / 2], endv[n * 9 / 10], endv.back());
-      for (int x = 0; x < 8; ++x) fprintf(stderr, " %.0f", xcd_end[x]);
-      fprintf(stderr, "\n");
-    }
-  }
   if (avg_ms) {
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
@@ -1915,7 +1845,6 @@ int d3d_op_attention(const float* qkv, float* out, int32_t B, int32_t T, int32_t
     (void)hipFree(tmp);
     HIP_TRY(e3);
     HIP_TRY(e4);
-    if (g_opt_attn_diag) attn_x3_diag_report();
     return D3D_OK;
   }
   if (!force_generic && !temporal && attn_spatial_fast_ok(J, D, H)) {

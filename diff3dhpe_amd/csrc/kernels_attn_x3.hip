@@ -16,7 +16,6 @@
 #include "d3d_kernels.h"
 
 #include <math.h>
-#include <stdio.h>
 #include <utility>
 
 namespace d3d {
@@ -661,7 +660,7 @@ constexpr int ATTN_PRIO_S = 2, ATTN_PRIO_PV = 1, ATTN_PRIO_SOFT = 0;
 template <int NKT, int HALF>
 __device__ __forceinline__ void attn_x3s_half(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, _Float16* __restrict__ out_x3,
                                               int T, int J, int H, int D, int units, unsigned char* const lds, const int wave,
-                                              unsigned long long* diag, unsigned* rw) {
+                                              unsigned* rw) {
   constexpr int TP = 32 * NKT;
   constexpr int PLANE = TP * 128;
   unsigned char* const sKh = lds;                 // K hi plane; lo plane at + PLANE
@@ -673,19 +672,10 @@ __device__ __forceinline__ void attn_x3s_half(const _Float16* __restrict__ Ph, c
   const int D3 = 3 * D;
   const int u0 = (int)blockIdx.x, ustep = (int)gridDim.x;
   const int n = (units - u0 + ustep - 1) / ustep;              // units of this workgroup (>= 1)
-#ifdef D3D_ATTN_DIAG_BUILD   // timing experiments: shader-clock stamps at the arrival at and the release from every step barrier
-  unsigned long long stamp[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const bool rec = diag && blockIdx.x < 8 && (wave & 3) == 0;
-#define D3D_STAMP(k) do { if (rec) stamp[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define D3D_STAMP(k) do { } while (0)
-#endif
 #define D3D_STEP_SYNC(k)                                                                                       \
   do {                                                                                                         \
-    D3D_STAMP(2 * (k));                                                                                        \
     __builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0): last step's DMA has landed, stores are acknowledged */    \
     __syncthreads();                                                                                           \
-    D3D_STAMP(2 * (k) + 1);                                                                                    \
     asm volatile("" : "+v"(lane));                                                                             \
     r = lane & 31; h = lane >> 5; tq = 32 * wave + r;                                                          \
   } while (0)
@@ -910,7 +900,6 @@ __device__ __forceinline__ void attn_x3s_half(const _Float16* __restrict__ Ph, c
     __builtin_amdgcn_s_setprio(ATTN_PRIO_SOFT);
     if (has_next) dma(HALF == 0 ? 1 : 2, tok0_n, hd_n);
     if (has_next) load_q(tok0_n, hd_n);
-    D3D_STAMP(10);
     // ---- O = O^T / (2^13 l) - v_query, packed as hi/lo of 8*o; stored in the next score step
     {
       // 8 o = oacc * (8 inv) - (vq_hi + vq_lo): the planes hold 8 v, so this is 8 * fma(oacc, inv, -v) bit for bit (powers of
@@ -955,20 +944,10 @@ __device__ __forceinline__ void attn_x3s_half(const _Float16* __restrict__ Ph, c
       po_ptr = out_x3 + (tok0 + (size_t)(32 * wave + (lane >> 3)) * J) * 2 * D + hd * 2 * XDH + 8 * (lane & 7);
       po_valid = true;
     }
-    D3D_STAMP(12);
     hd = hd_n; tok0 = tok0_n;
-#ifdef D3D_ATTN_DIAG_BUILD
-    if (rec && i < 8 && (threadIdx.x & 63) == 0) {
-      stamp[13] = __builtin_amdgcn_s_memrealtime();
-      stamp[14] = __builtin_amdgcn_s_memtime();
-      unsigned long long* d = diag + (((size_t)blockIdx.x * 2 + HALF) * 8 + i) * 16;
-      for (int k = 0; k < 16; ++k) d[k] = stamp[k];
-    }
-#endif
   }
   if (HALF == 0) D3D_STEP_SYNC(4);      // global step 4n: half 1's last output step
 #undef D3D_STEP_SYNC
-#undef D3D_STAMP
   {   // outputs of the last unit
 #pragma unroll
     for (int it = 0; it < 4; ++it)
@@ -982,7 +961,7 @@ __device__ __forceinline__ void attn_x3s_half(const _Float16* __restrict__ Ph, c
 template <int NKT>
 __global__ __launch_bounds__(64 * NKT) void k_attn_temporal_x3s(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl,
                                                                 _Float16* __restrict__ out_x3, int T, int J, int H, int D, int units,
-                                                                unsigned long long* diag, unsigned* rw) {
+                                                                unsigned* rw) {
   static_assert(NKT == 8, "two halves of four waves");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_s[];
   constexpr int TP = 32 * NKT;
@@ -993,8 +972,8 @@ __global__ __launch_bounds__(64 * NKT) void k_attn_temporal_x3s(const _Float16* 
     *reinterpret_cast<uint4*>(lds_s + pl * PLANE + (T + (rem >> 3)) * 128 + ((rem & 7) << 4)) = make_uint4(0, 0, 0, 0);
   }
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // 32-query tile of the unit
-  if (wave < 4) attn_x3s_half<NKT, 0>(Ph, Pl, out_x3, T, J, H, D, units, lds_s, wave, diag, rw);
-  else attn_x3s_half<NKT, 1>(Ph, Pl, out_x3, T, J, H, D, units, lds_s, wave, diag, rw);
+  if (wave < 4) attn_x3s_half<NKT, 0>(Ph, Pl, out_x3, T, J, H, D, units, lds_s, wave, rw);
+  else attn_x3s_half<NKT, 1>(Ph, Pl, out_x3, T, J, H, D, units, lds_s, wave, rw);
 }
 
 bool attn_temporal_x3_ok(int T, int D, int H) { return T >= 1 && T <= 256 && H > 0 && D == H * XDH; }
@@ -1046,35 +1025,6 @@ static hipError_t launch_x3p_nkt(const _Float16* ph, const _Float16* pl, _Float1
   return hipGetLastError();
 }
 
-#ifdef D3D_ATTN_DIAG_BUILD
-static unsigned long long* g_attn_diag = nullptr;
-constexpr size_t ATTN_DIAG_WORDS = 8 * 2 * 8 * 16;   // [workgroup < 8][half][unit < 8][6 stamps, 100 MHz stamp, clock stamp]
-#endif
-void attn_x3_diag_report() {
-#ifdef D3D_ATTN_DIAG_BUILD
-  if (!g_attn_diag) return;
-  static unsigned long long h[ATTN_DIAG_WORDS];
-  if (hipMemcpy(h, g_attn_diag, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
-  for (int wg = 0; wg < 8; wg += 3)
-    for (int half = 0; half < 2; ++half) {
-      double ghz = 0;
-      {
-        const unsigned long long* a = &h[((wg * 2 + half) * 8 + 2) * 16];
-        const unsigned long long* b = &h[((wg * 2 + half) * 8 + 7) * 16];
-        if (b[13] > a[13]) ghz = (double)(b[14] - a[14]) / (double)(b[13] - a[13]) * 0.1;
-      }
-      fprintf(stderr, "[attn diag] wg %d half %d clock %.3f GHz; per unit, cycles wait|work: scores  softmax  PV products  outputs\n", wg, half, ghz);
-      for (int i = 2; i < 7; ++i) {
-        const unsigned long long* d = &h[((wg * 2 + half) * 8 + i) * 16];
-        const unsigned long long* n = &h[((wg * 2 + half) * 8 + i + 1) * 16];
-        fprintf(stderr, "   unit %d: %6llu|%6llu  %6llu|%6llu  %6llu|%6llu  %6llu|%6llu   (unit %llu cycles)  output step: issue %llu  arithmetic %llu\n",
-                i, d[1] - d[0], d[2] - d[1], d[3] - d[2], d[4] - d[3], d[5] - d[4], d[6] - d[5], d[7] - d[6], n[0] - d[7], n[0] - d[0],
-                d[10] - d[7], d[12] - d[10]);
-      }
-    }
-#endif
-}
-
 static hipError_t launch_x3s(const _Float16* ph, const _Float16* pl, _Float16* ox, int B, int T, int J, int D, int H, hipStream_t s) {
   constexpr int NKT = 8;
   const size_t lds_bytes = (size_t)4 * 32 * NKT * 128 + NKT * 4096;   // K / V planes + one 4 KiB output patch per wave = 160 KiB
@@ -1085,13 +1035,7 @@ static hipError_t launch_x3s(const _Float16* ph, const _Float16* pl, _Float16* o
   const long long units = (long long)B * J * H;
   if (units > 0x7fffffffLL / 4) return hipErrorInvalidValue;
   const long long grid = units < n_cu ? units : n_cu;
-  unsigned long long* diag = nullptr;
-#ifdef D3D_ATTN_DIAG_BUILD
-  if (!g_attn_diag) { if (hipMalloc(&g_attn_diag, ATTN_DIAG_WORDS * 8) != hipSuccess) return hipErrorOutOfMemory; }
-  (void)hipMemsetAsync(g_attn_diag, 0, ATTN_DIAG_WORDS * 8, s);
-  diag = g_attn_diag;
-#endif
-  hipLaunchKernelGGL((k_attn_temporal_x3s<NKT>), dim3((unsigned)grid), dim3(64 * NKT), lds_bytes, s, ph, pl, ox, T, J, H, D, (int)units, diag, launch_range_word());
+  hipLaunchKernelGGL((k_attn_temporal_x3s<NKT>), dim3((unsigned)grid), dim3(64 * NKT), lds_bytes, s, ph, pl, ox, T, J, H, D, (int)units, launch_range_word());
   return hipGetLastError();
 }
 

@@ -127,8 +127,8 @@ template <int TM, int WM, int WN, int EPI, int OUTSPLIT, int FX, bool PERSIST = 
 __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const _Float16* __restrict__ Wp,
                                          const float* __restrict__ bias, const float* R, float* C, _Float16* Ch, _Float16* Cl,
                                          int M, int N, int K, int m0, int n0, int nt, int ntiles, int qcols,
-                                         unsigned long long* diag, const X3Tail& fx, bool has_next = false, int m0n = 0,
-                                         int n0n = 0, int tid_in = -1, int sub_wm = -1, int g_lo = 0, int g_hi = TM) {
+                                         const X3Tail& fx, bool has_next = false, int m0n = 0, int n0n = 0, int tid_in = -1,
+                                         int sub_wm = -1, int g_lo = 0, int g_hi = TM) {
   // SUB -- split tail tile (k_linear_x3q_persist): only the m-tiles [g_lo, g_hi) (g_lo even) of the waves in wave-row sub_wm (-1:
   // every wave-row) are computed and stored; the other waves still stage W pieces and meet the barriers.  A pieces outside
   // the computed rows are not staged (after the first k-tile, which the previous tile staged in full).
@@ -144,11 +144,6 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
   static_assert(NST == 2 || (!PERSIST && !SUB && NST >= 2 && NST <= 4), "deeper staging: one tile per workgroup");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
-  const int bid = blockIdx.x;
-  // diag (diagnostic launches only, experiments/gemm_bench.py): shader-clock and 100 MHz stamps around the k-loop and the
-  // epilogue of every workgroup, into a buffer nothing else reads
-  unsigned long long st_c0 = 0, st_r0 = 0;
-  if (diag) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
   // beyond the operand stages and the persistent walk's epilogue patches, which start at stage 1 and take 64 KiB (allocated only for
   // the folded forms)
   constexpr int LDS_X = (PERSIST && STAGE + NW * 2 * 16 * 64 * 4 > 2 * STAGE) ? STAGE + NW * 2 * 16 * 64 * 4 : NST * STAGE;
@@ -605,8 +600,6 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
   float* Ct = C ? C + tbase : nullptr;
   _Float16* Cht = Ch ? Ch + (OUTSPLIT == 2 ? 2 * tbase : tbase) : nullptr;
   _Float16* Clt = Cl ? Cl + tbase : nullptr;
-  unsigned long long st_c1 = 0, st_r1 = 0;
-  if (diag) { st_c1 = __builtin_amdgcn_s_memtime(); st_r1 = __builtin_amdgcn_s_memrealtime(); }
   float* patch = reinterpret_cast<float*>(lds + (PERSIST ? STAGE : 0)) + wave * (2 * 16 * 64);
   // row-statistics form: a wave-private kilobyte behind the patches collects the wave's (sum, sum of squares) rows (x3q_epilogue8)
   float2* const statp = ((FX & FX_SO) && !(FX & FX_LNF)) ? reinterpret_cast<float2*>(lds_x) + wave * 128 : nullptr;
@@ -659,14 +652,6 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
       x3q_epilogue<TM, WM, WN, EPI, OUTSPLIT, FX, true>(acc, patch, lds_x, bias, Rt, Ct, Cht, Clt, Rpt, fx.csum, fx.st_out, mt0,
                                                        nt0, mt0 - m0, lane, M, N, qcols, gl, gh, fx.out_scale, fx.range);
   }
-  if (diag) {
-    __builtin_amdgcn_s_waitcnt(0);   // the wave's own stores issued and acknowledged
-    const unsigned long long c2 = __builtin_amdgcn_s_memtime(), r2 = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0) {
-      unsigned long long* d = diag + ((size_t)bid * NW + wave) * 6;
-      d[0] = st_c0; d[1] = st_r0; d[2] = st_c1; d[3] = st_r1; d[4] = c2; d[5] = r2;
-    }
-  }
 }
 
 // The SUB instantiation (tail slices, ragged edge tiles): it carries the checked epilogues, so that the whole-tile path of the
@@ -677,8 +662,8 @@ __device__ __forceinline__ void x3q_tile_sub(const _Float16* __restrict__ Ap, co
                                                        _Float16* Cl, int M, int N, int K, int m0, int n0, int nt, int ntiles,
                                                        int qcols, const X3Tail& fx, bool has_next, int m0n, int n0n, int tid_in,
                                                        int sub_wm, int g_lo, int g_hi) {
-  x3q_tile<TM, WM, WN, EPI, OUTSPLIT, FX, true, true>(Ap, Wp, bias, R, C, Ch, Cl, M, N, K, m0, n0, nt, ntiles, qcols, nullptr, fx,
-                                                      has_next, m0n, n0n, tid_in, sub_wm, g_lo, g_hi);
+  x3q_tile<TM, WM, WN, EPI, OUTSPLIT, FX, true, true>(Ap, Wp, bias, R, C, Ch, Cl, M, N, K, m0, n0, nt, ntiles, qcols, fx, has_next,
+                                                      m0n, n0n, tid_in, sub_wm, g_lo, g_hi);
 }
 
 // Uniform launch: every workgroup one BM x BN tile; blockIdx -> tile keeps all N-tiles of an M-tile on one XCD.
@@ -686,7 +671,7 @@ template <int TM, int WM, int WN, int EPI, int OUTSPLIT, int FX, int NST = 2>
 __global__ __launch_bounds__(64 * WM * WN) void k_linear_x3q(const _Float16* __restrict__ Ap, const _Float16* __restrict__ Wp,
                                                              const float* __restrict__ bias, const float* R, float* C,
                                                              _Float16* Ch, _Float16* Cl, int M, int N, int K, int mtiles,
-                                                             int ntiles, int qcols, unsigned long long* diag, X3Tail fx) {
+                                                             int ntiles, int qcols, X3Tail fx) {
   constexpr int BM = 16 * TM * WM, BN = 64 * WN;
   const int bid = blockIdx.x;
   const int xcd = bid & 7, slot = bid >> 3;
@@ -694,7 +679,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_linear_x3q(const _Float16* __r
   const int nt = slot % ntiles;
   if (mt >= mtiles) return;
   x3q_tile<TM, WM, WN, EPI, OUTSPLIT, FX, false, false, false, NST>(Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mt * BM, nt * BN, nt, ntiles,
-                                                                    qcols, diag, fx);
+                                                                    qcols, fx);
 }
 
 // Persistent launch (one 8-wave workgroup per CU): the workgroup walks the tiles blockIdx, blockIdx + gridDim, ... of the
@@ -704,7 +689,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_linear_x3q(const _Float16* __r
 // slices handled by split * rem <= gridDim workgroups (x3q_tile's sub_wm / g_lo / g_hi), so the round that would keep rem CUs
 // busy for a whole tile time keeps split * rem CUs busy for a fraction of it.  A slice runs the same MFMAs in the same
 // order for its rows as the whole tile would: values do not change.
-struct X3Walk { int nfull, rem, split; unsigned long long* stamps; };   // stamps: diagnostic (100 MHz start / end per workgroup)
+struct X3Walk { int nfull, rem, split; };
 
 template <int TM, int WM, int WN, int EPI, int OUTSPLIT, int FX>
 __global__ __launch_bounds__(512) void k_linear_x3q_persist(const _Float16* __restrict__ Ap, const _Float16* __restrict__ Wp,
@@ -732,14 +717,6 @@ __global__ __launch_bounds__(512) void k_linear_x3q_persist(const _Float16* __re
   };
   const int nitems = wk.nfull + (b < wk.split * wk.rem ? 1 : 0);
   if (nitems == 0) return;
-  const unsigned long long t_begin = wk.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  auto stamp_end = [&]() {
-    if (wk.stamps && threadIdx.x == 0) {
-      __builtin_amdgcn_s_waitcnt(0);
-      wk.stamps[2 * b] = t_begin;
-      wk.stamps[2 * b + 1] = __builtin_amdgcn_s_memrealtime();
-    }
-  };
   // item k of this workgroup: a whole tile (k < nfull) or a slice of a tail tile
   auto item_of = [&](int k, int& mt, int& nt, int& sub_wm, int& g_lo, int& g_hi) {
     sub_wm = -1; g_lo = 0; g_hi = TM;
@@ -778,24 +755,19 @@ __global__ __launch_bounds__(512) void k_linear_x3q_persist(const _Float16* __re
     int mtn = 0, ntn = 0, swn = -1, gln = 0, ghn = TM;
     if (has_next) item_of(k + 1, mtn, ntn, swn, gln, ghn);
     if ((mt + 1) * BM <= M && (nt + 1) * BN <= N)   // (wave-uniform) whole tile inside the matrix: the unchecked instantiation
-      x3q_tile<TM, WM, WN, EPI, OUTSPLIT, FX, true, false, true>(Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mt * BM, nt * BN, nt, ntiles, qcols,
-                                                                 nullptr, fx, has_next, mtn * BM, ntn * BN, tid_o);
+      x3q_tile<TM, WM, WN, EPI, OUTSPLIT, FX, true, false, true>(Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mt * BM, nt * BN, nt, ntiles, qcols, fx,
+                                                                 has_next, mtn * BM, ntn * BN, tid_o);
     else                                            // ragged edge tile: the checked epilogue lives in the SUB instantiation
       x3q_tile_sub<TM, WM, WN, EPI, OUTSPLIT, FX>(Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mt * BM, nt * BN, nt, ntiles, qcols, fx, has_next,
                                                   mtn * BM, ntn * BN, tid_o, -1, 0, TM);
-    if (!has_next) { stamp_end(); return; }
+    if (!has_next) return;
     ++k; mt = mtn; nt = ntn; sub_wm = swn; g_lo = gln; g_hi = ghn;
     __syncthreads();   // the epilogue's patches (stage 1) are read before the next tile's second k-tile is staged there
   }
   asm volatile("" : "+v"(tid_o));
   x3q_tile_sub<TM, WM, WN, EPI, OUTSPLIT, FX>(Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mt * BM, nt * BN, nt, ntiles, qcols, fx, false, 0, 0,
                                               tid_o, sub_wm, g_lo, g_hi);
-  stamp_end();
 }
-
-// Diagnostic stamp buffer for the next launches (experiments/gemm_bench.py through d3d_op_linear_bench): variant 13 -> per-wave
-// k-loop / epilogue stamps; the persistent walk -> start / end per workgroup.
-static unsigned long long* g_x3_diag = nullptr;
 
 thread_local LaunchCtx tl_launch_ctx;
 static std::atomic<bool> g_x3q_deep{true};
@@ -803,7 +775,7 @@ void set_x3q_deep_stages(bool on) { g_x3q_deep = on; }
 
 // walk of `tiles` tiles over `grid` persistent workgroups
 static X3Walk x3q_walk(int tiles, int grid, bool four_way = true) {
-  X3Walk w{tiles / grid, tiles % grid, 1, g_x3_diag};
+  X3Walk w{tiles / grid, tiles % grid, 1};
   if (w.rem > 0 && tl_launch_ctx.tail_slices) w.split = (four_way && 4 * w.rem <= grid) ? 4 : ((2 * w.rem <= grid) ? 2 : 1);
   return w;
 }
@@ -811,7 +783,7 @@ static X3Walk x3q_walk(int tiles, int grid, bool four_way = true) {
 template <int TM, int WM, int WN, int NST = 2>
 static hipError_t launch_x3q(const _Float16* Ap, const _Float16* Wp, const float* bias, const float* R, float* C, _Float16* Ch,
                              _Float16* Cl, int M, int N, int K, int epi, int outsplit, int qcols, hipStream_t s,
-                             unsigned long long* diag = nullptr, const X3Fold* fold = nullptr, int w_exp = 12, bool bf16 = false) {
+                             const X3Fold* fold = nullptr, int w_exp = 12, bool bf16 = false) {
   constexpr int BM = 16 * TM * WM, BN = 64 * WN;
   const int mtiles = (M + BM - 1) / BM, ntiles = (N + BN - 1) / BN;
   const int grid = ((mtiles + 7) / 8) * 8 * ntiles;
@@ -836,7 +808,7 @@ static hipError_t launch_x3q(const _Float16* Ap, const _Float16* Wp, const float
     static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                       \
     if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;                   \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * WM * WN), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles,    \
-                       ntiles, qcols, diag, tail);                                                                        \
+                       ntiles, qcols, tail);                                                                              \
   } while (0)
 #define D3D_X3Q_LAUNCH(EPI_, OS_) D3D_X3Q_LAUNCH_FX(EPI_, OS_, 0)
   if (bf16) {   // bf16 operand mode: the three forms its block flow uses (launch_linear_bf16)
@@ -963,7 +935,6 @@ static hipError_t launch_x3q_pn(const _Float16* Ap, const _Float16* Wp, const fl
   tail.range = launch_range_word();
   tail.Rp = (const _Float16*)fold->Rp; tail.st_out = fold->st_out; tail.pn = fold->pn;
   const int qcols = 0;
-  unsigned long long* diag = nullptr;
   _Float16* Cl = nullptr;
   const float* R = nullptr;
 #define D3D_X3PN_LAUNCH(OS_)                                                                                              \
@@ -979,13 +950,13 @@ static hipError_t launch_x3q_pn(const _Float16* Ap, const _Float16* Wp, const fl
       static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                     \
       if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_small, attr_done)) return ae;                 \
       hipLaunchKernelGGL(kfn, dim3(vtiles64), dim3(512), lds_small, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles64, ntiles, \
-                         qcols, diag, tail);                                                                              \
+                         qcols, tail);                                                                                    \
     } else {                                                                                                              \
       auto kfn = k_linear_x3q<8, 1, 8, EPI_RESIDUAL, OS_, FX_RP | FX_PN>;                                                 \
       static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                     \
       if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;                 \
       hipLaunchKernelGGL(kfn, dim3(vtiles), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles, ntiles, \
-                         qcols, diag, tail);                                                                              \
+                         qcols, tail);                                                                                    \
     }                                                                                                                     \
   } while (0)
   if (outsplit == 2) D3D_X3PN_LAUNCH(2);
@@ -1026,7 +997,6 @@ hipError_t launch_linear_bf16_rows(const void* A, const void* W, const float* bi
   tail.range = launch_range_word();
   tail.pn = pn;
   const int qcols = 0;
-  unsigned long long* diag = nullptr;
   constexpr int FXB = FX_PN | FX_BF16;
   if (persist) {
     auto kfn = k_linear_x3q_persist<8, 1, 8, EPI_RESIDUAL, 0, FXB>;
@@ -1037,12 +1007,12 @@ hipError_t launch_linear_bf16_rows(const void* A, const void* W, const float* bi
     auto kfn = k_linear_x3q<4, 1, 8, EPI_RESIDUAL, 0, FXB>;
     static std::atomic<unsigned long long> attr_done{0};
     if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_small, attr_done)) return ae;
-    hipLaunchKernelGGL(kfn, dim3(vtiles64), dim3(512), lds_small, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K2, mtiles64, ntiles, qcols, diag, tail);
+    hipLaunchKernelGGL(kfn, dim3(vtiles64), dim3(512), lds_small, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K2, mtiles64, ntiles, qcols, tail);
   } else {
     auto kfn = k_linear_x3q<8, 1, 8, EPI_RESIDUAL, 0, FXB>;
     static std::atomic<unsigned long long> attr_done{0};
     if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;
-    hipLaunchKernelGGL(kfn, dim3(vtiles), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K2, mtiles, ntiles, qcols, diag, tail);
+    hipLaunchKernelGGL(kfn, dim3(vtiles), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K2, mtiles, ntiles, qcols, tail);
   }
   return hipGetLastError();
 }
@@ -1068,17 +1038,17 @@ static hipError_t launch_x3q_auto(const _Float16* ap, const _Float16* wp, const 
     return launch_x3q_persist<6>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp);
   if (x3q_big(M, N) && (K / PBK) % 2 == 0)
     return launch_x3q_persist(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp);
-  if (x3q_big(M, N)) return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, fold, w_exp);
+  if (x3q_big(M, N)) return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp);
   // Smallest launches (a batch of one sequence: the visualisation scripts, the ragged last batch of evaluate()): where 128 x 128 tiles
   // (<2,4,2>: eight waves of 32 x 64) still find a CU each, the launch is as long as ONE tile takes and that tile is shorter -- proj at
   // B = 1, T = 243: 26 -> 20.7 us per launch.  Beyond that (two such workgroups sharing a CU) the shape loses: fc1 at B = 1 28.7 -> 38.2 us
   // (NOTES round 6).  Values do not depend on the tile shape.
   const bool deep = g_x3q_deep.load(std::memory_order_relaxed);
   if (x3q_small(M, N))
-    return deep ? launch_x3q<2, 4, 2, 4>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, fold, w_exp)
-                : launch_x3q<2, 4, 2>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, fold, w_exp);
-  return deep ? launch_x3q<4, 4, 2, 3>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, fold, w_exp)
-              : launch_x3q<4, 4, 2>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, fold, w_exp);
+    return deep ? launch_x3q<2, 4, 2, 4>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp)
+                : launch_x3q<2, 4, 2>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp);
+  return deep ? launch_x3q<4, 4, 2, 3>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp)
+              : launch_x3q<4, 4, 2>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp);
 }
 
 // ---- bf16 operand mode (D3D_PREC_BF16) ---------------------------------------------------------------------------------
@@ -1099,8 +1069,8 @@ hipError_t launch_linear_bf16(const void* A, const void* W, const float* bias, c
   const int K2 = K / 2;                     // pair columns: 4 K2 bytes per row, K2 / 32 staged lines per row
   if (x3q_big(M, N) && (K2 / PBK) % 2 == 0)
     return launch_x3q_persist(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, true);
-  if (x3q_big(M, N)) return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, nullptr, 12, true);
-  return launch_x3q<4, 4, 2>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, nullptr, 12, true);
+  if (x3q_big(M, N)) return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, true);
+  return launch_x3q<4, 4, 2>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, true);
 }
 
 // fp32 [rows, cols] -> bf16 (round to nearest even), and back: weight commit on the device side of the op hooks, tests
@@ -1134,10 +1104,8 @@ hipError_t launch_bf16_to_f32(const void* x, float* y, size_t n, hipStream_t s) 
   return hipGetLastError();
 }
 
-void set_linear_x3_diag(unsigned long long* dev_buf) { g_x3_diag = dev_buf; }
-
 // variant: 0 = auto (launch_x3q_auto); the two production shapes forced, one workgroup per tile (experiments/gemm_bench.py):
-// 13 = 256x256 (with the per-wave diagnostic stamps when set_linear_x3_diag() armed them), 4 = 256x128
+// 13 = 256x256, 4 = 256x128
 hipError_t launch_linear_x3p(const void* Ap_, const void* Wp_, const float* bias, const float* R, float* C, void* Ch, void* Cl,
                              int M, int N, int K, int epi, int outsplit, int qcols, int variant, hipStream_t s,
                              const X3Fold* fold, int w_exp) {
@@ -1154,8 +1122,8 @@ hipError_t launch_linear_x3p(const void* Ap_, const void* Wp_, const float* bias
   }
   switch (variant) {
     case 0: return launch_x3q_auto(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp);
-    case 13: return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, g_x3_diag, nullptr, w_exp);
-    case 4: return launch_x3q<4, 4, 2>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, nullptr, w_exp);
+    case 13: return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, w_exp);
+    case 4: return launch_x3q<4, 4, 2>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, nullptr, w_exp);
     default: return hipErrorInvalidValue;
   }
 }

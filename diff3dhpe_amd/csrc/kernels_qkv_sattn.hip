@@ -25,8 +25,6 @@
 #include "qkv_fused_kloop.h"
 
 #include <math.h>
-#include <stdio.h>
-#include <vector>
 
 namespace d3d {
 namespace {
@@ -122,8 +120,6 @@ struct QsArgs {
   _Float16* out;           // attention output, pair layout [M][2 D] of 8 o
   int M, K, F, mtiles, D;  // tokens, GEMM depth, frames (M / 17), M-tiles (ceil(F / 15)), model width (8 heads x 64)
   unsigned* range;         // the engine's range-guard word
-  unsigned long long* diag;   // diagnostic launches only ("qs_diag"): per workgroup 8 words -- cycles of wave 0 in the k-loop, the
-                              // statistics step, write 0, attention 0, write 1 (+ prefetch), attention 1, tiles, 100 MHz ticks
 };
 
 #define QS_GLDS(SRC, DSTOFF)                                                                                            \
@@ -328,16 +324,7 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
     for (int it = 0; it < QS_BIT; ++it) QS_GLDS(sgpr_ptr(ubB + it * it_stride) + lofs, QS_AREG + wave * 1024 + lane * 16 + it * 8192);
   }
   int tid_o = (int)threadIdx.x;
-  unsigned long long dg[6] = {0, 0, 0, 0, 0, 0};
-  const unsigned long long dg_r0 = a.diag ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#define QS_STAMP(I)                                                         \
-  if (a.diag) {                                                             \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();           \
-    dg[I] += now_ - dg_t;                                                   \
-    dg_t = now_;                                                            \
-  }
   for (int item = 0; item < nitems; ++item) {
-    unsigned long long dg_t = a.diag ? __builtin_amdgcn_s_memtime() : 0ull;
     asm volatile("" : "+v"(tid_o));   // per-lane offsets are re-derived in every tile instead of being hoisted (and spilled)
     const int tid = tid_o;
     const int lane = tid & 63;
@@ -440,10 +427,8 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
 #undef QF_PIECE
 #undef QS_PIECE
     __builtin_amdgcn_s_setprio(0);
-    QS_STAMP(0);
 
     __syncthreads();   // statistics visible; every wave is out of the k-loop: stage 1 and the LDS behind it become the frame slots
-    QS_STAMP(1);
 
     float2 st[QS_TM];
 #pragma unroll
@@ -506,10 +491,8 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
     };
     write_pass(0);
     __syncthreads();
-    QS_STAMP(2);
     attend(0);
     __syncthreads();
-    QS_STAMP(3);
     write_pass(1);
     {
       float amax = 0.0f;
@@ -518,24 +501,13 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
       if (amax > X3_HALF_MAX) range_raise(a.range, RANGE_BIT_ACT);
     }
     __syncthreads();
-    QS_STAMP(4);
     attend(1);
     mt = mtn; hd = hdn;
     __syncthreads();   // the slots are read before the next tile's statistics block and second k-tile are staged over them
-    QS_STAMP(5);
-  }
-#undef QS_STAMP
-  if (a.diag && threadIdx.x == 0) {
-    for (int i = 0; i < 6; ++i) a.diag[8 * b + i] = dg[i];
-    a.diag[8 * b + 6] = (unsigned long long)nitems;
-    a.diag[8 * b + 7] = __builtin_amdgcn_s_memrealtime() - dg_r0;
   }
 }
 
 }  // namespace
-
-static std::atomic<int> g_qs_diag{0};
-void set_qkv_sattn_diag(int on) { g_qs_diag = on; }
 
 bool qkv_sattn_ok(int J, int D, int H, int K) { return J == QS_J && H == 8 && D == 512 && K % 64 == 0 && K >= 128; }
 
@@ -556,33 +528,6 @@ hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, cons
   if (n_cu <= 0) return hipErrorUnknown;
   const int tiles = a.mtiles * 8;
   const int grid = tiles < n_cu ? tiles : n_cu;
-  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;   // the stamp report allocates, synchronises and copies: illegal inside a
-  (void)hipStreamIsCapturing(s, &cap_st);                          // hipGraph capture (d3d_engine_set_graph_mode) -- plain launch there
-  if (g_qs_diag.load() > 0 && cap_st == hipStreamCaptureStatusNone) {   // "qs_diag" option: every 50th launch with stamps, summarised on stderr (synchronises the stream)
-    static std::atomic<int> count{0};
-    if (count.fetch_add(1) % 50 == 10) {
-      unsigned long long* buf = nullptr;
-      if (hipMalloc(&buf, (size_t)grid * 64) != hipSuccess) return hipErrorOutOfMemory;
-      (void)hipMemsetAsync(buf, 0, (size_t)grid * 64, s);
-      a.diag = buf;
-      hipLaunchKernelGGL(k_qkv_sattn, dim3(grid), dim3(512), QS_LDS, s, a);
-      (void)hipStreamSynchronize(s);
-      std::vector<unsigned long long> h((size_t)grid * 8);
-      (void)hipMemcpy(h.data(), buf, h.size() * 8, hipMemcpyDeviceToHost);
-      (void)hipFree(buf);
-      double sum[6] = {0}, tiles_n = 0, cyc = 0, ticks = 0;
-      for (int g = 0; g < grid; ++g) {
-        for (int i = 0; i < 6; ++i) { sum[i] += (double)h[8 * g + i]; cyc += (double)h[8 * g + i]; }
-        tiles_n += (double)h[8 * g + 6]; ticks += (double)h[8 * g + 7];
-      }
-      const double ghz = ticks > 0 ? cyc / (ticks * 10.0) : 0.0;   // cycles per ns (100 MHz ticks = 10 ns)
-      fprintf(stderr, "[qs diag] M=%d tiles %d on %d workgroups, clock %.2f GHz; per tile (us, wave 0): k-loop %.2f  stats %.2f  write0 %.2f  "
-              "attn0 %.2f  write1+prefetch %.2f  attn1 %.2f  | total %.2f\n", M, tiles, grid, ghz,
-              sum[0] / tiles_n / ghz / 1e3, sum[1] / tiles_n / ghz / 1e3, sum[2] / tiles_n / ghz / 1e3, sum[3] / tiles_n / ghz / 1e3,
-              sum[4] / tiles_n / ghz / 1e3, sum[5] / tiles_n / ghz / 1e3, cyc / tiles_n / ghz / 1e3);
-      return hipGetLastError();
-    }
-  }
   hipLaunchKernelGGL(k_qkv_sattn, dim3(grid), dim3(512), QS_LDS, s, a);
   return hipGetLastError();
 }

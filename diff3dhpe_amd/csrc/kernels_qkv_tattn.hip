@@ -17,7 +17,7 @@
 // two waves of a SIMD drift through their MFMA and VALU steps out of phase by themselves (the second half starts an exchange later); the
 // halves meet at two LDS counters in a pad row of the V lo plane (key 255: T <= 255), not at workgroup barriers, which held the first
 // half at the second half's pace.  The next tile's first k-tile goes into the dead K planes, every wave's pieces issued by the first
-// half after its outputs (it idles there until the second half is through).  In-kernel stamps: "qt_diag" option.
+// half after its outputs (it idles there until the second half is through).
 //
 // T <= 127 (the T = 81 / 27 configurations): the GROUPED form k_qkv_tattn<true> -- the frames of G = 255 / T joints of ONE batch element per
 // tile (tile row R = frame R % T of joint jt G + R / T), the same k-loop / plane writes / exchange; a query sees the keys of its own joint
@@ -28,9 +28,7 @@
 #include "qkv_fused_kloop.h"
 
 #include <math.h>
-#include <stdio.h>
 #include <utility>
-#include <vector>
 
 namespace d3d {
 namespace {
@@ -117,8 +115,6 @@ struct QtArgs {
                            // element, Tinv = 65536 / T + 1: R / T = (R Tinv) >> 16 for every tile row R < 256 (the fraction of R / T is at most
                            // 126 / 127, the product's excess below 256 / 65536)
   unsigned* range;         // the engine's range-guard word
-  unsigned long long* diag;   // diagnostic launches only ("qs_diag"): per workgroup 8 words -- cycles of wave 0 in the k-loop, the statistics
-                              // step, the plane writes, the query exchange, scores + softmax, the rest of the attention, tiles, 100 MHz ticks
 };
 
 #define QT_GLDS(SRC, DSTOFF)                                                                                            \
@@ -492,16 +488,7 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
   };
   stage_first(bj, hd, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6));
   int tid_o = (int)threadIdx.x;
-  unsigned long long dg[6] = {0, 0, 0, 0, 0, 0};
-  const unsigned long long dg_r0 = a.diag ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#define QT_STAMP(I)                                                         \
-  if (a.diag) {                                                             \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();           \
-    dg[I] += now_ - dg_t;                                                   \
-    dg_t = now_;                                                            \
-  }
   for (int item = 0; item < nitems; ++item) {
-    unsigned long long dg_t = a.diag ? __builtin_amdgcn_s_memtime() : 0ull;
     asm volatile("" : "+v"(tid_o));   // per-lane offsets are re-derived in every tile instead of being hoisted (and spilled)
     const int tid = tid_o;
     const int lane = tid & 63;
@@ -634,7 +621,6 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
     __builtin_amdgcn_s_setprio(0);
     if constexpr (GRP) asm volatile("" : "+v"(lofsAg_[0]), "+v"(lofsAg_[1]), "+v"(lofsAg_[2]), "+v"(lofsAg_[3]));
     else asm volatile("" : "+v"(lofsA_), "+v"(lofsA3_));
-    QT_STAMP(0);
 
     __syncthreads();   // statistics visible; every wave is out of the k-loop: the LDS becomes planes + exchange
     float2 st[QT_TM];
@@ -647,7 +633,6 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
       cs4[j] = *reinterpret_cast<const float4*>(a.csum + n);
       b4[j] = *reinterpret_cast<const float4*>(a.bias + n);
     }
-    QT_STAMP(1);
 
     // ---- q / k / v -> LDS (LayerNorm fold and hi / lo split of x3q_epilogue8; column tile j of a wave is q / k / v: plane and scale
     // are compile-time per j).  Lane: rows 128 wm + 16 i + r16, head dims 16 wn + 4 q .. + 3 = 8 bytes of 16-byte chunk 2 wn + (q >> 1).
@@ -707,7 +692,6 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
       reinterpret_cast<volatile unsigned*>(xsync)[1] = 0u;
     }
     __syncthreads();                                   // B1: K, V, Q(half 0) written
-    QT_STAMP(2);
     // From here the two halves run separate instruction streams that meet at ONE barrier (B2) and two counters (B3', B4'); from then on the two
     // waves of a SIMD (w and w + 4) are about a step apart -- one in an MFMA step, one in a VALU step:
     //   half 0: read Q | B2 | scores, softmax                          | B4' (no wait) | products, outputs, both halves' prefetch pieces
@@ -750,12 +734,10 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
       // prefetch below); a counter it raised long before this point, not a barrier it would have to wait at
       while (reinterpret_cast<volatile unsigned*>(xsync)[1] < 4u) __builtin_amdgcn_s_sleep(1);
       asm volatile("" ::: "memory");
-      QT_STAMP(3);
       if constexpr (GRP) qt_products_outputs<0, true>(lds, wave, lane, T, J, a.D, sacc, lsum, out_unit, a.range, kt_lo, kt_hi, orow);
       else qt_products_outputs<0>(lds, wave, lane, T, J, a.D, sacc, lsum, out_unit, a.range);
       // the next tile's first k-tile into the dead K planes: both halves' pieces from this half, which is a step ahead and would idle
       if (more) { stage_first(bjn, hdn, wave); stage_first(bjn, hdn, wave + 4); }
-      QT_STAMP(4);
     } else {
       __builtin_amdgcn_s_barrier();                    // B2
       write_rows(true, false);
@@ -774,29 +756,16 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane == 0) atomicAdd(xsync + 1, 1u);         // B4'
-      QT_STAMP(3);
       qt_softmax<QT_PB1, GRP>(lane, T, sacc, lsum, kt_lo, kt_hi, klo, khi);
       if constexpr (GRP) qt_products_outputs<QT_PB1, true>(lds, wave, lane, T, J, a.D, sacc, lsum, out_unit, a.range, kt_lo, kt_hi, orow);
       else qt_products_outputs<QT_PB1>(lds, wave, lane, T, J, a.D, sacc, lsum, out_unit, a.range);
-      QT_STAMP(4);
     }
     bj = bjn; hd = hdn;
     __syncthreads();   // planes and patches are read before the next tile's statistics block and second k-tile are staged over them
-    QT_STAMP(5);
-  }
-#undef QT_STAMP
-  if (a.diag && (threadIdx.x == 0 || threadIdx.x == 256)) {   // wave 0 (first half) and wave 4 (second half)
-    unsigned long long* d = a.diag + 16 * b + (threadIdx.x ? 8 : 0);
-    for (int i = 0; i < 6; ++i) d[i] = dg[i];
-    d[6] = (unsigned long long)nitems;
-    d[7] = __builtin_amdgcn_s_memrealtime() - dg_r0;
   }
 }
 
 }  // namespace
-
-static std::atomic<int> g_qt_diag{0};
-void set_qkv_tattn_diag(int on) { g_qt_diag = on; }
 
 // T in 193 ... 255: one joint's frames per tile; T in 2 ... 127: the frames of 255 / T joints per tile (grouped form)
 bool qkv_tattn_ok(int T, int J, int D, int H, int K) {
@@ -830,39 +799,6 @@ hipError_t launch_qkv_tattn(const void* Apair, const void* Wpair_tileorder, cons
   if (n_cu <= 0) return hipErrorUnknown;
   const int tiles = a.BJ * 8;
   const int grid = tiles < n_cu ? tiles : n_cu;
-  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;   // the stamp report allocates, synchronises and copies: illegal inside a
-  (void)hipStreamIsCapturing(s, &cap_st);                          // hipGraph capture (d3d_engine_set_graph_mode) -- plain launch there
-  if (g_qt_diag.load() > 0 && cap_st == hipStreamCaptureStatusNone) {   // "qt_diag" option: every 50th launch with stamps of wave 0, summarised on stderr (synchronises the stream)
-    static std::atomic<int> count{0};
-    if (count.fetch_add(1) % 50 == 10) {
-      unsigned long long* buf = nullptr;
-      if (hipMalloc(&buf, (size_t)grid * 128) != hipSuccess) return hipErrorOutOfMemory;
-      (void)hipMemsetAsync(buf, 0, (size_t)grid * 128, s);
-      a.diag = buf;
-      if (grp) hipLaunchKernelGGL(k_qkv_tattn<true>, dim3(grid), dim3(512), QT_LDS, s, a);
-      else hipLaunchKernelGGL(k_qkv_tattn<false>, dim3(grid), dim3(512), QT_LDS, s, a);
-      (void)hipStreamSynchronize(s);
-      std::vector<unsigned long long> h((size_t)grid * 16);
-      (void)hipMemcpy(h.data(), buf, h.size() * 8, hipMemcpyDeviceToHost);
-      (void)hipFree(buf);
-      for (int half = 0; half < 2; ++half) {
-        double sum[6] = {0}, tiles_n = 0, cyc = 0, ticks = 0;
-        for (int g = 0; g < grid; ++g) {
-          const unsigned long long* d = &h[16 * (size_t)g + 8 * half];
-          for (int i = 0; i < 6; ++i) { sum[i] += (double)d[i]; cyc += (double)d[i]; }
-          tiles_n += (double)d[6]; ticks += (double)d[7];
-        }
-        const double ghz = ticks > 0 ? cyc / (ticks * 10.0) : 0.0;   // cycles per ns (100 MHz ticks = 10 ns)
-        fprintf(stderr, "[qt diag] half %d (wave %d): B J = %d, tiles %d on %d workgroups, clock %.2f GHz; per tile (us): k-loop %.2f  statistics -> registers %.2f  "
-                "plane writes %.2f  %s %.2f  %s %.2f  end barrier %.2f  | total %.2f\n", half, 4 * half, a.BJ, tiles, grid, ghz,
-                sum[0] / tiles_n / ghz / 1e3, sum[1] / tiles_n / ghz / 1e3, sum[2] / tiles_n / ghz / 1e3,
-                half ? "wait + query exchange + scores" : "query read + scores + softmax", sum[3] / tiles_n / ghz / 1e3,
-                half ? "softmax + products + outputs" : "products + outputs + prefetch issue", sum[4] / tiles_n / ghz / 1e3,
-                sum[5] / tiles_n / ghz / 1e3, cyc / tiles_n / ghz / 1e3);
-      }
-      return hipGetLastError();
-    }
-  }
   if (grp) hipLaunchKernelGGL(k_qkv_tattn<true>, dim3(grid), dim3(512), QT_LDS, s, a);
   else hipLaunchKernelGGL(k_qkv_tattn<false>, dim3(grid), dim3(512), QT_LDS, s, a);
   return hipGetLastError();

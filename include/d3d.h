@@ -161,14 +161,11 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     one the engine owns, forked and joined by events: the caller sees ONE asynchronous operation on its stream;
  *                     bit-identical to one stream -- every output element is independent of the batch it is computed in; measured
  *                     +2.9 % at T=243 / B=64, neutral at T=81 / T=27).  Per-kernel profiling and the trace force one stream.
- * Process-wide switch (e may be NULL): "deep_stages" 1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches (batches of a few
- * sequences: proj on 128 x 128 tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead of two, the wait
- * in front of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243: 20.8 -> 17.6 us per
- * launch; a 9-step sampling 18.9 -> 18.3 ms at B = 1, 75.7 -> 72.2 at B = 8).  Bit-identical.
- * Process-wide diagnostics (e may be NULL): "gemm_diag", "attn_diag" 0 / 1: the op hooks print in-kernel stamp reports to stderr
- * (attn_diag needs a -DD3D_ATTN_DIAG_BUILD library); "qs_diag" / "qt_diag" 0 / 1: every 50th launch of the fused spatial / fused temporal kernel
- * runs with per-step stamps and prints their summary to stderr (that launch synchronises its stream; launches inside a hipGraph capture
- * are never stamped).  The diagnostic switches are PROCESS-wide: they act on every engine.  Unknown key: D3D_EINVAL. */
+ * Process-wide switch, the only key accepted with a NULL e: "deep_stages" 1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches
+ * (batches of a few sequences: proj on 128 x 128 tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead
+ * of two, the wait in front of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243:
+ * 20.8 -> 17.6 us per launch; a 9-step sampling 18.9 -> 18.3 ms at B = 1, 75.7 -> 72.2 at B = 8).  Bit-identical.
+ * Unknown key: D3D_EINVAL. */
 int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value);
 
 /* q_sample (DIFF:360-366, extract DIFF:21-24): out = sqrt_ac[t_b] * x_start + sqrt(1-ac)[t_b] * noise, per row b.

@@ -36,10 +36,11 @@ def test_allgather_entry_rejects_bad_arguments_without_touching_rccl():
     assert b"bad argument" in L.d3d_last_error()
 
 
-def test_retired_option_key_is_rejected():
+@pytest.mark.parametrize("key", ["fc2_ring_op", "gemm_diag", "attn_diag", "qs_diag", "qt_diag"])
+def test_retired_option_key_is_rejected(key):
     """A key of a removed experiment switch fails loudly instead of being ignored."""
     L = _lib.lib()
-    assert L.d3d_engine_set_option(None, b"fc2_ring_op", 1) == -1      # D3D_EINVAL
+    assert L.d3d_engine_set_option(None, key.encode(), 1) == -1      # D3D_EINVAL
 
 
 def test_ddim_times_bit_exact_for_every_S():
