@@ -8,13 +8,17 @@ B=64 sequences per GPU (weak scaling: the 8-GPU run is the full B=512 of that co
 
     python bench.py --gpus 1 --steps 3 --warmup 1
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   (also writes the last timed step's outputs: dump_outputs())
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full               (also everything beyond the headline, see below)
     python bench.py --gpus N ...            (no launcher: bench.py starts its N rank processes itself, self_launch())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task statement).  The timed region runs the engine exactly as a user gets
-it (per-kernel event timing OFF; `headline_under` names the launch mode: eager / graph / 2-stream); `roofline` comes from a
-separate profiled pass right after it (same batch, ONE stream, HIP events around every kernel on the launch stream), and
-`cpu_baseline` is the CPU oracle (a port of the reference's op sequence) timed on this node's host cores on a bounded sample.
+it (per-kernel event timing OFF; `headline_under` names the launch mode: eager / graph / 2-stream).  A plain run does only what
+the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line; its `roofline` is the whole-path figure of the
+timed region.  --full adds, after the timed region: a separate profiled pass behind the per-kernel `roofline` (same batch, ONE
+stream, HIP events around every kernel on the launch stream), the batch-vs-pair self-check, and on one GPU the companion legs
+(companion_legs()), `machine_probes` and `cpu_baseline`, the CPU oracle (a port of the reference's op sequence) timed on this
+node's host cores on a bounded sample.  --profile-steps, --no-selfcheck, --no-extras and --no-cpu-baseline trim a --full run.
 """
 import argparse
 import json
@@ -202,7 +206,7 @@ def cpu_baseline_concurrent(T, S, seed, best_th, avail, step_s_alone, run_s=8.0,
 
 def companion_legs(a, diff, net, eng, x2d, noise, gt, dev, T, S, Bl):
     """Short legs after the timed region, so that the numbers DESIGN.md quotes beside the headline are observed by whoever
-    runs bench.py (single GPU only; each leg: 1 warm call, then 2 timed calls between device synchronisations):
+    runs bench.py --full (single GPU only; each leg: 1 warm call, then 2 timed calls between device synchronisations):
       graph_vs_eager              the same sampling with profiling off, as eager launches and as ONE hipGraph replay of the whole
                                   S-step loop (BASELINE configs[3]: d3d_engine_set_graph_mode), outputs compared bit for bit
       evaluate_equiv_frames_per_s the reference evaluate() unit (RUN:575-621): two samplings per window (flip-TTA) + un-flip /
@@ -545,19 +549,24 @@ def main():
     ap.add_argument("--streams", type=int, default=2, choices=[1, 2],
                     help="2 (default): the sampling runs as two half-batches on two HIP streams inside the engine (bit-identical, "
                          "fills the partly idle kernel tails); 1: one stream")
-    ap.add_argument("--profile-steps", type=int, default=2, help="samplings of the separate profiled pass behind the roofline object (0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the profiled pass, the self-check and (one GPU) the companion legs, machine "
+                         "probes and CPU baseline; a plain run does only what the headline needs")
+    ap.add_argument("--profile-steps", type=int, default=2,
+                    help="with --full: samplings of the separate profiled pass behind the roofline object (0: none)")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
                     help="d3d_engine_set_option switch for A/B runs (experiments/ab_option.sh), e.g. fused_postnorm=0")
     ap.add_argument("--seq2frame", action="store_true", help="BASELINE configs[4]: ...S2F... model, (B,1,J,3) targets")
     ap.add_argument("--no-time-emb", action="store_true", help="with_time_emb=False (3DHP command lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=40.0, help="seconds of CPU work for the cpu_baseline leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the companion legs after the timed region (fp32 mode, hipGraph replay, evaluate()-equivalent)")
+                    help="with --full: skip the companion legs after the timed region (fp32 mode, hipGraph replay, evaluate()-equivalent) "
+                         "and the machine probes")
     ap.add_argument("--graph", action="store_true",
                     help="time the main leg with hipGraph replay of the whole S-step loop (BASELINE configs[3]); per-kernel event "
                          "timing is off then, so the roofline object carries the whole-path figure only")
-    ap.add_argument("--no-selfcheck", action="store_true", help="skip the bitwise batch-vs-pair check (profiling passes: keeps the kernel tables to the timed workload)")
+    ap.add_argument("--no-selfcheck", action="store_true", help="with --full: skip the bitwise batch-vs-pair check (profiling passes: keeps the kernel tables to the timed workload)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0; see dump_outputs())")
     a = ap.parse_args()
@@ -774,22 +783,23 @@ def main():
         elapsed = float(tmax[0])
     if a.graph:
         eng.set_graph_mode(False)
-    # ---- profiled pass (outside the timed region): same batch, ONE stream, HIP events around every kernel
+    # ---- profiled pass (--full; outside the timed region): same batch, ONE stream, HIP events around every kernel
+    profile_steps = a.profile_steps if a.full else 0
     eng.profile_reset()
-    if a.profile_steps > 0:
+    if profile_steps > 0:
         eng.set_option("streams", 1)
         eng.set_profiling(True)
-        for _ in range(a.profile_steps):
+        for _ in range(profile_steps):
             eng.ddim_sample(x2d, noise)
         torch.cuda.synchronize(dev)
         eng.set_profiling(False)
         eng.set_option("streams", a.streams)
     prof = eng.profile_read()
-    psteps = max(a.profile_steps, 1)
-    # self-check of the timed configuration (no oracle runs at this size): the first two sequences of the batch, sampled
+    psteps = max(profile_steps, 1)
+    # self-check of the timed configuration (--full; no oracle runs at this size): the first two sequences of the batch, sampled
     # again as a batch of two (the small-problem kernels the golden-vector tests cover), must come out bit-identical
     selfcheck = None
-    if not a.no_selfcheck and Bl >= 2:
+    if a.full and not a.no_selfcheck and Bl >= 2:
         pred_big = eng.ddim_sample(x2d, noise)
         pred_two = eng.ddim_sample(x2d[:2].contiguous(), noise[:2].contiguous())
         selfcheck = bool(torch.equal(pred_big[:2], pred_two)) and bool(torch.isfinite(pred_big).all())
@@ -816,7 +826,7 @@ def main():
         if prof_fam and dom in fam:
             d, dom_name = prof_fam, "gemm family: " + " + ".join(fam)
             dom = "linear"
-        if not d["ms"]:                         # --profile-steps 0: no per-kernel events; the whole-path figures are filled in below
+        if not d["ms"]:                         # no profiled pass: no per-kernel events; the whole-path figures are filled in below
             roof = {"bound": "mfma", "achieved": None, "peak": round(PEAK_TFLOPS[a.precision], 1), "unit": "TFLOP/s", "frac": None}
         elif dom == "linear" or dom == "attn_temporal":
             ach = d["flops"] / (d["ms"] * 1e-3) / 1e12
@@ -843,7 +853,7 @@ def main():
             roof = {"bound": "hbm", "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4)}
         roof.update({"kernel": dom_name, "launches": d["launches"], "avg_launch_ms": round(d["ms"] / max(d["launches"], 1), 4),
                      "share_of_gpu_time": round(d["ms"] / tot_ms, 4), "traffic": None,
-                     "timed_in": f"separate profiled pass of {a.profile_steps} samplings right after the timed region (one stream, HIP events "
+                     "timed_in": f"separate profiled pass of {profile_steps} samplings right after the timed region (one stream, HIP events "
                                  "around every kernel on the launch stream)",
                      "by_kernel_ms_per_step": {k: round(v["ms"] / psteps, 3) for k, v in prof.items() if v["launches"]}})
         if prof.get("qkv_sattn", {}).get("launches"):   # spatial blocks: qkv GEMM + 17-key attention in one kernel ("fused_spatial")
@@ -866,7 +876,7 @@ def main():
         # HBM bytes per launch cannot be counted from inside the process: they come from the separate rocprofv3 --pmc passes of
         # profiles/collect.sh (FETCH_SIZE doubled per the gfx950 correction + WRITE_SIZE) and are labelled as such
         tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tfile):
+        if d["ms"] and os.path.exists(tfile):
             try:
                 tj = json.load(open(tfile))
                 key = f"{dom}:T{T}:B{Bl}:{a.precision}"
@@ -930,11 +940,11 @@ def main():
         if dumped:
             line["dump_outputs"] = dumped
         if not d["ms"]:
-            roof["note"] = "no profiled pass (--profile-steps 0): 'achieved' is the whole-path figure of the timed region"
+            roof["note"] = ("no profiled pass (a plain run, or --full --profile-steps 0): 'achieved' is the whole-path figure of the "
+                            "timed region")
             roof.update({"kernel": "whole path", "achieved": round(whole, 2), "frac": round(whole / PEAK_TFLOPS[a.precision], 4),
                          "launches": a.steps, "avg_launch_ms": round(elapsed / a.steps * 1e3, 3), "share_of_gpu_time": 1.0,
-                         "by_kernel_ms_per_step": {}, "traffic": None})
-            roof.pop("traffic_source", None)
+                         "by_kernel_ms_per_step": {}, "traffic": None, "timed_in": "the timed region (whole path)"})
         if use_dist:
             try:
                 rccl = ".".join(str(v) for v in torch.cuda.nccl.version()) if backend == "nccl" else None
@@ -946,12 +956,12 @@ def main():
                             "one_process_per_gpu": not bool(os.environ.get("D3D_BENCH_ONE_DEVICE")),
                             "collectives": ["barrier", "all_gather_into_tensor", "all_reduce(MAX)"]}
     extras = None
-    if world == 1 and not a.no_extras:
+    if world == 1 and a.full and not a.no_extras:
         extras = companion_legs(a, diff, net, eng, x2d, noise, gt, dev, T, S, Bl)
     if rank == 0:
         if extras:
             line.update(extras)
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
             # what THIS chip sustains today for the two resources that co-limit the F16X3 / bf16 GEMM k-loop (d3d_probe_machine): fp16
             # MFMA work in register loops at the power-limited clock, and the k-loop's L2 -> LDS staging stream alone.  Beside the
             # nominal peaks, not instead of them: roofline.frac stays against MI355X_MICROARCH.md's 2.5 PFLOP/s.
@@ -969,7 +979,7 @@ def main():
                 line["machine_probes"] = mp
             except Exception as ex:      # a probe never fails a bench run
                 line["machine_probes"] = {"error": str(ex)[:200]}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cb = cpu_baseline(T, S, 0, a.cpu_budget)
             acc = cb.get("all_cores_concurrent") or {}
             allc = cb["value"] if acc.get("equal_to_single_process") else acc.get("value")

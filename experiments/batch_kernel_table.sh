@@ -5,7 +5,7 @@
 BS=${@:-1 2 3 4 6 8 12 16 24 32 48 64}
 for b in $BS; do
   for st in 2 1; do
-    python bench.py --batch $b --steps 6 --warmup 2 --streams $st --no-cpu-baseline --no-selfcheck --no-extras --profile-steps $((st == 2 ? 2 : 0)) $BENCH_EXTRA 2>/dev/null | python -c "
+    python bench.py --batch $b --steps 6 --warmup 2 --streams $st --full --no-cpu-baseline --no-selfcheck --no-extras --profile-steps $((st == 2 ? 2 : 0)) $BENCH_EXTRA 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

@@ -2,7 +2,7 @@
 # experiments/batch_sweep.sh B...   (on the GPU box): the headline shape at several batch sizes -- per-GEMM-kind launch times against the
 # number of tile rounds each batch gives (round 5: what the partly filled last round costs each form, one-stream profiled pass)
 for b in "$@"; do
-  python bench.py --batch $b --steps 2 --warmup 1 --no-cpu-baseline --no-selfcheck --no-extras 2>/dev/null | python -c "
+  python bench.py --batch $b --steps 2 --warmup 1 --full --no-cpu-baseline --no-selfcheck --no-extras 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); g = d['roofline'].get('by_gemm', {}); r = d['roofline']
 M = $b * 243 * 17

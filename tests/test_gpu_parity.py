@@ -585,7 +585,7 @@ def test_bench_two_ranks_on_one_device():
     import json, os, subprocess, sys
     from conftest import ROOT
     env = dict(os.environ, D3D_BENCH_ONE_DEVICE="1", D3D_DIST_BACKEND="gloo")
-    common = ["--steps", "1", "--warmup", "0", "--frames", "27", "--sampling", "3", "--no-cpu-baseline", "--no-extras"]
+    common = ["--steps", "1", "--warmup", "0", "--frames", "27", "--sampling", "3", "--full", "--no-cpu-baseline", "--no-extras"]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "3"] + common,
                          capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
@@ -656,7 +656,7 @@ def test_bench_graph_flag_times_the_main_leg_under_replay():
     import json, os, subprocess, sys
     from conftest import ROOT
     common = ["--gpus", "1", "--batch", "4", "--steps", "2", "--warmup", "1", "--frames", "27", "--sampling", "5",
-              "--no-cpu-baseline", "--no-extras"]
+              "--full", "--no-cpu-baseline", "--no-extras"]
     env = {k: v for k, v in os.environ.items() if k != "D3D_FORCE_DIST"}
     lines = []
     for extra in ([], ["--graph"]):
