@@ -139,6 +139,23 @@ hipError_t launch_linear_x3p(const void* Apair, const void* Wpair, const float* 
                              void* Cl, int M, int N, int K, int epi, int outsplit, int qcols, int variant, hipStream_t s,
                              const X3Fold* fold = nullptr, int w_exp = 12);
 int x3q_ntiles(int M, int N);   // statistics partials per row an st_out launch writes
+// ---- latency mode (engine option "latency_mode"): fc2 + post-norm of a SMALL call as a split-K x split-N GEMM + an ordered reduce ----
+// The whole-row post-norm tile stages all of W2 per workgroup, whatever its height: a launch that cannot fill one round of those tiles
+// lasts K/32 k-tiles at one CU's L2 -> LDS rate with most of the chip idle.  Here 128 x 128 tiles x S k-ranges spread the staging:
+//   launch_linear_x3p_splitk : P[ks][M][N] (fp32, un-scaled) = A[:, k-range ks] . W[:, k-range ks]^T          (kernels_gemm_x3p.hip)
+//   launch_splitk_postnorm   : y = LN(r + bias + P[0] + P[1] + ... + P[S-1]) [+ pos] [+ tvec], the additions in exactly that order; the
+//                              operations, outputs and range-guard reporting of launch_layernorm (y_x3 + stats, or fp32 y)  (kernels_fc2_splitk.hip)
+// fc2_splitk_choose: S in {2, 4}, or 0 = keep the whole-row form.  A pure function of (M, N, K, CU count) -- the same for eager and
+// captured runs --: among S in {1, 2, 4} with K/32/S >= 4 k-tiles and W = ceil(M/128) (N/128) S workgroups, cost(S) = K/32/S where
+// W <= CUs, 1.45 K/32/S where W <= 2 CUs (two co-resident 128 x 128 workgroups take 1.33-1.45x a lone one: experiments/NOTES.md), excluded
+// beyond; cheapest, the smaller on a tie; 0 unless that is >= 2, the post-norm tile shape applies and ceil(M/64) < CUs.
+int fc2_splitk_choose(int M, int N, int K, int n_cu);
+bool fc2_splitk_ok(int N, int K, int S);   // shapes the pair of kernels exists for
+hipError_t launch_linear_x3p_splitk(const void* Apair, const void* Wpair, float* P, int M, int N, int K, int S, hipStream_t s, int w_exp = 12);
+// Rp: residual planes [M][2N] of 8r; Yp (with stats: [M][2], one (sum, sum of squares) per row) may be Rp; Y (fp32) may alias Rp's
+// bytes row for row.  Exactly one of Yp / Y.
+hipError_t launch_splitk_postnorm(const float* P, int S, const void* Rp, const float* bias, const X3PostNorm& pn, float* Y, void* Yp,
+                                  float* stats, int M, int N, hipStream_t s);
 hipError_t launch_split_x3(const float* x, void* pair, size_t rows, int cols, hipStream_t s);
 hipError_t launch_unsplit_x3(const void* pair, float* x, size_t rows, int cols, const float* part, int np, float* stats,
                              hipStream_t s);   // op hooks only

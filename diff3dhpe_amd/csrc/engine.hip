@@ -96,6 +96,11 @@ struct d3d_engine {
   // "head_fence": that fence on (round 5's default).  Off since round 6: the deviation it guarded against is identified (a packed fp32
   // form beside another wave's MFMAs) and its absence from every kernel is a build-time test
   int opt_head_fence = 0;
+  // "latency_mode" (off by default): in the F16X3 folded flow, fc2 + post-norm of a forward too small to fill one round of whole-row
+  // tiles runs as a split-K x split-N GEMM + an ordered reduce / post-norm row kernel (d3d_kernels.h fc2_splitk_choose).  Changes the
+  // order of additions: results stay inside the parity gate but are no longer bit-identical to the default path's.
+  bool opt_latency_mode = false;
+  int fc2_split_last = 0;         // the S of the most recent forward (0: the whole-row fc2 ran): d3d_engine_get_info
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int device = -1;                // ordinal of the device the weights were committed on
@@ -351,6 +356,18 @@ int attention(d3d_engine* e, const float* qkv, float* out, void* out_x3, int B, 
   return D3D_OK;
 }
 
+// whether a forward of this engine takes the plane-resident, LayerNorm-folded F16X3 flow (run_blocks_fold)
+bool fold_flow(const d3d_engine* e) {
+  return e->cfg.precision == D3D_PREC_F16X3 && attn_temporal_x3_ok(e->T, e->D, e->H) && attn_temporal_x3_ok(e->J, e->D, e->H) &&
+         e->D % 32 == 0 && e->opt_fold_layernorm;
+}
+// "latency_mode": the k-split of fc2 + post-norm in a B-sequence forward, 0 = today's whole-row kernel.  Depends on (M, D, Dm, CU
+// count) only, so an eager run, a capture and a replay agree.
+int fc2_split_for(const d3d_engine* e, int B) {
+  if (!e->opt_latency_mode || !e->opt_fused_postnorm || !fold_flow(e)) return 0;
+  return fc2_splitk_choose(B * e->T * e->J, e->D, e->Dm, device_cu_count());
+}
+
 // F16X3 production flow ("plane-resident, LayerNorm-folded"): the residual stream lives in the GEMM operand (pair) layout
 // in w.X, so it is at once the A operand of the qkv / fc1 GEMMs and the residual input of the proj / fc2 epilogues; norm1
 // and norm2 are folded into those two GEMMs (X3Fold), their row statistics coming from the producer of the stream (the
@@ -404,6 +421,10 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
   int np1 = 1;                                          // ... per row in w.ST1 (1 after a row kernel)
   // post-norm inside the fc2 epilogue (X3PostNorm) where the tile shape for it exists; else fp32 + the row kernel
   const bool pn = e->opt_fused_postnorm && x3q_postnorm_ok(D, e->Dm);
+  // latency mode: S k-ranges of fc2 as fp32 partials + the ordered reduce / post-norm row kernel.  The partials take w.HN (the attention
+  // output, dead since proj) and on into w.QKV (q / k / v planes, dead since attention): (Mp + 3 M) D floats >= 4 M D, contiguous.
+  const int ksplit = pn ? fc2_split_for(e, B) : 0;
+  float* const PART = w.HN;
   for (int k = 0; k < e->nblk; ++k) {
     const BlockW& bw = e->blk[k];
     const bool temporal = (k & 1) != 0;
@@ -471,6 +492,26 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
     const float* pn_g = temporal ? e->tn_g : e->sn_g;
     const float* pn_b = temporal ? e->tn_b : e->sn_b;
     const bool last = k + 1 == e->nblk;
+    if (ksplit) {
+      {
+        Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)D * e->Dm, 4.0 * ((double)M * e->Dm + (double)D * e->Dm + (double)ksplit * M * D), s,
+               D3D_KC_LINEAR_FC2);
+        HIP_TRY(launch_linear_x3p_splitk(HIDx, bw.fc2_x3, PART, M, D, e->Dm, ksplit, s, bw.fc2_e));
+      }
+      TRACE(k, 6, 0, PART, (size_t)ksplit * MDb);
+      X3PostNorm q{};
+      q.g = pn_g; q.b = pn_b; q.eps = e->ln_eps; q.pos_div = 1; q.pos_mod = 1; q.rows_per_batch = T * J;
+      if (k == 0) { q.pos = e->tpos; q.pos_div = J; q.pos_mod = T; }
+      if (!last && tvec) { q.tvec = tvec + (size_t)(k + 1) * D; q.tvec_stride = tvec_stride; }
+      {
+        Prof p(e, D3D_KC_LAYERNORM, 8.0 * M * D, MD4 * (2 + ksplit), s);
+        HIP_TRY(launch_splitk_postnorm(PART, ksplit, XP, bw.fc2b, q, last ? w.X : nullptr, last ? nullptr : XP, last ? nullptr : w.ST1, M, D, s));
+      }
+      np1 = 1;
+      TRACE(k, 7, 0, w.X, MDb);
+      if (!last) TRACE(k, 7, 1, w.ST1, (size_t)M * 8);
+      continue;
+    }
     if (pn) {  // x = post_norm(x + hidden W2^T + b2) [+ Temporal_pos_embed] [+ next block's time vector], all in the fc2 epilogue
       X3Fold f{};
       f.Rp = XP;
@@ -624,8 +665,7 @@ int run_blocks(d3d_engine* e, const float* x2d, const float* y, int y_bcast, con
   const int T = e->T, J = e->J, D = e->D;
   const int M = B * T * J;
   const double MD4 = (double)M * D * 4.0;
-  if (e->cfg.precision == D3D_PREC_F16X3 && attn_temporal_x3_ok(T, D, e->H) && attn_temporal_x3_ok(J, D, e->H) && D % 32 == 0 &&
-      e->opt_fold_layernorm)
+  if (fold_flow(e))
     return run_blocks_fold(e, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
   if (e->cfg.precision == D3D_PREC_BF16) return run_blocks_bf16(e, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
   {
@@ -1122,6 +1162,7 @@ int d3d_denoise(d3d_engine* e, const float* x2d, const float* y, int32_t y_frame
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   RangeScope range_scope(e);
   Workspace w = carve(e, B, ws);
+  e->fc2_split_last = fc2_split_for(e, B);
   const float* tvec = nullptr;
   int64_t stride = 0;
   if (e->Dt) {
@@ -1247,6 +1288,7 @@ int d3d_ddim_sample(d3d_engine* e, const float* x2d, const float* init_noise, co
   const size_t xin_row = (size_t)e->T * e->J * e->cfg.in_chans;                 // x2d elements per sequence
   SplitWs sw{};
   if (split) sw = carve_split(e, B, ws);
+  e->fc2_split_last = fc2_split_for(e, split ? sw.B0 : B);   // (two half-batches: the first half's -- the one that holds sequence 0)
   const size_t xin0 = split ? (size_t)sw.B0 * xin_row : 0, y0 = split ? (size_t)head_rows(e, sw.B0) * 3 : 0;
   if (!use_graph) {
     if (split)
@@ -1335,6 +1377,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
     e->ln_eps = v;
   }
   else if (k == "bf16_gemm_kernel") e->opt_bf16_gemm_kernel = value != 0;
+  else if (k == "latency_mode") e->opt_latency_mode = value != 0;
   else if (k == "streams") {
     if (value != 1 && value != 2) return fail(D3D_EINVAL, "streams must be 1 or 2");
     e->opt_streams = (int)value;
@@ -1391,6 +1434,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "graphs_captured") *value = (int64_t)e->graphs_captured;
   else if (k == "streams") *value = e->opt_streams;
   else if (k == "device") *value = e->device;
+  else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
+  else if (k == "fc2_split_last") *value = e->fc2_split_last;
   else return fail(D3D_EINVAL, "unknown info key: " + k);
   return D3D_OK;
 }
@@ -1783,6 +1828,56 @@ int d3d_op_linear_postnorm(const float* A, const float* W, const float* bias, co
   if (le == hipSuccess && stats) le = launch_unsplit_x3(yp.dev, Y, (size_t)M, N, part, np, stats, s);
   hipError_t se = hipStreamSynchronize(s);
   if (part) (void)hipFree(part);
+  HIP_TRY(le);
+  HIP_TRY(se);
+  return D3D_OK;
+}
+
+int d3d_op_linear_splitk_postnorm(const float* A, const float* W, const float* bias, const float* R, const float* gamma,
+                                  const float* beta, float eps, const float* pos, int32_t pos_div, int32_t pos_mod, const float* tvec,
+                                  int64_t tvec_stride, int32_t rows_per_batch, float* Y, float* stats, int32_t M, int32_t N, int32_t K,
+                                  int32_t S, float* partials, int32_t reps, float* avg_ms, void* stream) {
+  if (!A || !W || !bias || !R || !gamma || !beta || !Y || !partials || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
+  if (!fc2_splitk_ok(N, K, S)) return fail(D3D_EUNSUP, "the split-K fc2 + post-norm pair exists for N == 512, S in {2, 4}, (K / 32) % S == 0");
+  if ((pos && (pos_div < 1 || pos_mod < 1)) || (tvec && tvec_stride != 0 && rows_per_batch < 1))
+    return fail(D3D_EINVAL, "bad row-class arguments");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  TmpPair ap, wp, rp, yp;
+  int rc = make_pair(wp, W, N, K, true, s);
+  if (!rc) rc = make_pair(ap, A, M, K, false, s);
+  if (!rc) rc = make_pair(rp, R, M, N, false, s);
+  if (!rc && stats) rc = make_pair(yp, R, M, N, false, s);   // (any initialised pair buffer of the output's size)
+  if (rc) return rc;
+  float* st1 = nullptr;
+  if (stats) HIP_TRY(hipMalloc(&st1, (size_t)M * 2 * sizeof(float)));
+  X3PostNorm q{};
+  q.g = gamma; q.b = beta; q.eps = eps;
+  q.pos = pos; q.pos_div = pos ? pos_div : 1; q.pos_mod = pos ? pos_mod : 1;
+  q.tvec = tvec; q.tvec_stride = tvec_stride; q.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
+  auto gemm = [&]() -> hipError_t { return launch_linear_x3p_splitk(ap.dev, wp.dev, partials, M, N, K, S, s, wp.wexp); };
+  auto rowk = [&]() -> hipError_t {
+    return launch_splitk_postnorm(partials, S, rp.dev, bias, q, stats ? nullptr : Y, stats ? yp.dev : nullptr, st1, M, N, s);
+  };
+  auto once = [&]() -> hipError_t {   // (the row kernel reads rp and writes yp / Y: repeats see the same input)
+    const hipError_t ge = gemm();
+    return ge == hipSuccess ? rowk() : ge;
+  };
+  hipError_t le = once();
+  if (le == hipSuccess && avg_ms) {
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, s);
+    for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
+    (void)hipEventRecord(e1, s);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    *avg_ms = ms / reps;
+  }
+  if (le == hipSuccess && stats) le = launch_unsplit_x3(yp.dev, Y, (size_t)M, N, st1, 1, stats, s);
+  hipError_t se = hipStreamSynchronize(s);
+  if (st1) (void)hipFree(st1);
   HIP_TRY(le);
   HIP_TRY(se);
   return D3D_OK;

@@ -123,12 +123,15 @@ __device__ __forceinline__ void x3_mma(f32x4& acc, const h8& bh, const h8& bl, c
 // NST (one tile per workgroup only): operand stages of the one-barrier loop.  2: k-tile t + 1 is requested while k-tile t is multiplied
 // (a k-tile then lasts at least one DMA round trip -- what bounds the launches whose every tile has a CU of its own: B = 1); 3 / 4:
 // k-tiles t + 1 .. t + NST - 1 are in flight, the wait in front of a k-tile's barrier is a counted vmcnt that leaves the younger ones out.
-template <int TM, int WM, int WN, int EPI, int OUTSPLIT, int FX, bool PERSIST = false, bool SUB = false, bool FULL = false, int NST = 2>
+template <int TM, int WM, int WN, int EPI, int OUTSPLIT, int FX, bool PERSIST = false, bool SUB = false, bool FULL = false, int NST = 2,
+          bool KSPLIT = false>
 __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const _Float16* __restrict__ Wp,
                                          const float* __restrict__ bias, const float* R, float* C, _Float16* Ch, _Float16* Cl,
                                          int M, int N, int K, int m0, int n0, int nt, int ntiles, int qcols,
                                          const X3Tail& fx, bool has_next = false, int m0n = 0, int n0n = 0, int tid_in = -1,
-                                         int sub_wm = -1, int g_lo = 0, int g_hi = TM) {
+                                         int sub_wm = -1, int g_lo = 0, int g_hi = TM, int nk_in = 0) {
+  // KSPLIT (k_linear_x3q_splitk only): the workgroup walks nk_in k-tiles, Ap / Wp already advanced to the first of them; K stays the row
+  // length of both operands.
   // SUB -- split tail tile (k_linear_x3q_persist): only the m-tiles [g_lo, g_hi) (g_lo even) of the waves in wave-row sub_wm (-1:
   // every wave-row) are computed and stored; the other waves still stage W pieces and meet the barriers.  A pieces outside
   // the computed rows are not staged (after the first k-tile, which the previous tile staged in full).
@@ -236,7 +239,7 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
   // fragment offsets: rows r16 + 16 i all share the swizzle key r16>>1
   const int foff = (q ^ (r16 >> 1)) << 4;
   const int aoff = (wm * 16 * TM + r16) * 128 + foff, boff = A_REG + (wn * 64 + r16) * 128 + foff;
-  const int nk = K / PBK;
+  const int nk = KSPLIT ? nk_in : K / PBK;
   if (!PERSIST) {
 #pragma unroll
     for (int kt0 = 0; kt0 < NST - 1; ++kt0)
@@ -682,6 +685,25 @@ __global__ __launch_bounds__(64 * WM * WN) void k_linear_x3q(const _Float16* __r
                                                                     qcols, fx);
 }
 
+// Split-K x split-N launch (engine option "latency_mode": fc2 of a call too small to fill one round of whole-row tiles): workgroup
+// (mt, nt, ks) runs the 128 x 128 stage of the template over k-tiles [ks nks, (ks + 1) nks) and writes its un-scaled fp32 partial to
+// P[ks][M][N] -- no bias, no residual; the ordered reduce + post-norm row kernel (kernels_fc2_splitk.hip) adds the partials in index
+// order.  Two operand stages (64 KiB) and at most 128 VGPRs, so that two of these workgroups share a CU where the launch has more
+// workgroups than the chip has CUs.  blockIdx -> (mt, nt, ks) keeps everything of an M-tile on one XCD.
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_linear_x3q_splitk(const _Float16* __restrict__ Ap, const _Float16* __restrict__ Wp, float* __restrict__ P, int M, int N, int K,
+                         int mtiles, int ntiles, int S, int nks, X3Tail fx) {
+  const int bid = blockIdx.x;
+  const int xcd = bid & 7, slot = bid >> 3;
+  const int per = ntiles * S;
+  const int mt = (slot / per) * 8 + xcd;
+  const int nt = (slot % per) / S, ks = slot % S;
+  if (mt >= mtiles) return;
+  const size_t kofs = (size_t)ks * nks * (2 * PBK);   // fp16 elements into a pair-layout row
+  x3q_tile<2, 4, 2, EPI_NONE, 0, 0, false, false, false, 2, true>(Ap + kofs, Wp + kofs, nullptr, nullptr, P + (size_t)ks * M * N, nullptr, nullptr,
+                                                           M, N, K, mt * 128, nt * 128, nt, ntiles, 0, fx, false, 0, 0, -1, -1, 0, 2, nks);
+}
+
 // Persistent launch (one 8-wave workgroup per CU): the workgroup walks the tiles blockIdx, blockIdx + gridDim, ... of the
 // uniform launch's order (so it stays on its XCD class, gridDim % 8 == 0).  Saves the per-tile workgroup relaunch and hides
 // the first-k-tile staging latency of every tile but the first (x3q_tile, PERSIST).
@@ -962,6 +984,24 @@ static hipError_t launch_x3q_pn(const _Float16* Ap, const _Float16* Wp, const fl
   if (outsplit == 2) D3D_X3PN_LAUNCH(2);
   else D3D_X3PN_LAUNCH(0);
 #undef D3D_X3PN_LAUNCH
+  return hipGetLastError();
+}
+
+// d3d_kernels.h: the split-K x split-N partial GEMM behind launch_fc2_splitk_postnorm.  A rows padded to 256 as everywhere.
+hipError_t launch_linear_x3p_splitk(const void* Apair, const void* Wpair, float* P, int M, int N, int K, int S, hipStream_t s, int w_exp) {
+  if (w_exp < -14 || w_exp > 12) return hipErrorInvalidValue;
+  if (M <= 0 || N <= 0 || (N % 128) != 0 || K <= 0 || (K % PBK) != 0 || !Apair || !Wpair || !P) return hipErrorInvalidValue;
+  if ((S != 1 && S != 2 && S != 4) || (K / PBK) % S != 0 || K / PBK / S < 1) return hipErrorInvalidValue;
+  const int mtiles = (M + 127) / 128, ntiles = N / 128;
+  const int grid = ((mtiles + 7) / 8) * 8 * ntiles * S;
+  const size_t lds_bytes = 2 * (size_t)((128 + 128) * 128);
+  X3Tail tail{};
+  tail.out_scale = ldexpf(1.0f, -(3 + w_exp));
+  tail.range = launch_range_word();
+  static std::atomic<unsigned long long> attr_done{0};   // one bit per device
+  if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(k_linear_x3q_splitk), lds_bytes, attr_done)) return ae;
+  hipLaunchKernelGGL(k_linear_x3q_splitk, dim3(grid), dim3(512), lds_bytes, s, (const _Float16*)Apair, (const _Float16*)Wpair, P, M, N, K,
+                     mtiles, ntiles, S, K / PBK / S, tail);
   return hipGetLastError();
 }
 

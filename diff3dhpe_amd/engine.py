@@ -103,6 +103,11 @@ class Engine:
             self._ws_B = B
         return self._ws
 
+    def release_workspace(self) -> None:
+        """Drop the cached workspace; the next call allocates one for its own batch size."""
+        self._ws = None
+        self._ws_B = 0
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -162,11 +167,12 @@ class Engine:
         _lib.check(_lib.lib().d3d_engine_set_graph_mode(self._h, int(on)))
 
     def set_option(self, key: str, value: int) -> None:
-        """Explicit engine switch (include/d3d.h: "fused_postnorm", "fold_layernorm", "streams"); the library reads no environment."""
+        """Explicit engine switch (include/d3d.h: "fused_postnorm", "fold_layernorm", "streams", "latency_mode"); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     def info(self, key: str) -> int:
-        """Read-only engine facts (include/d3d.h d3d_engine_get_info): "graphs_cached", "graphs_captured", "streams", "device"."""
+        """Read-only engine facts (include/d3d.h d3d_engine_get_info): "graphs_cached", "graphs_captured", "streams", "device",
+        "latency_mode", "fc2_split_last"."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -406,6 +412,32 @@ def op_linear_postnorm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, res
             _ptr(A), _ptr(W), _ptr(bias), _ptr(residual), _ptr(gamma), _ptr(beta), float(eps), _ptr(pos), int(pos_div),
             int(pos.shape[0]) if pos is not None else 1, _ptr(tvec), stride, int(rows_per_batch), _ptr(out), _ptr(stats), M, N, K,
             int(reps), C.byref(ms), st))
+    return out, stats, ms.value
+
+
+def op_linear_splitk_postnorm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, residual: torch.Tensor, gamma: torch.Tensor,
+                              beta: torch.Tensor, eps: float = 1e-6, S: int = 2, pos: Optional[torch.Tensor] = None, pos_div: int = 1,
+                              tvec: Optional[torch.Tensor] = None, rows_per_batch: int = 1, with_stats: bool = False, reps: int = 1):
+    """op_linear_postnorm's result from the kernel pair of "latency_mode": a split-K (S k-ranges) x split-N F16X3 GEMM into fp32
+    partials, then the ordered reduce + post-norm row kernel.  Returns (Y, stats or None, mean ms per pair of launches)."""
+    M, K = A.shape
+    N = W.shape[0]
+    dev = A.device
+    A, W, bias, residual = _f32c(A, dev), _f32c(W, dev), _f32c(bias, dev), _f32c(residual, dev)
+    gamma, beta = _f32c(gamma, dev), _f32c(beta, dev)
+    pos = _f32c(pos, dev) if pos is not None else None
+    tvec = _f32c(tvec, dev) if tvec is not None else None
+    stride = 0 if tvec is None or tvec.dim() == 1 or tvec.shape[0] == 1 else N
+    out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    stats = torch.empty((M, 2), dtype=torch.float32, device=dev) if with_stats else None
+    partials = torch.empty((max(int(S), 1), M, N), dtype=torch.float32, device=dev)
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_linear_splitk_postnorm(
+            _ptr(A), _ptr(W), _ptr(bias), _ptr(residual), _ptr(gamma), _ptr(beta), float(eps), _ptr(pos), int(pos_div),
+            int(pos.shape[0]) if pos is not None else 1, _ptr(tvec), stride, int(rows_per_batch), _ptr(out), _ptr(stats), M, N, K,
+            int(S), _ptr(partials), int(reps), C.byref(ms), st))
     return out, stats, ms.value
 
 

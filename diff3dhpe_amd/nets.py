@@ -67,6 +67,10 @@ class _MixSTEDenoiser(nn.Module):
     # are silently not fp32-accurate are not an option, hence the guard is on by default (D3D_CHECK_RANGE=0 or range_check = False
     # turns the read off: one ~2 us kernel + one event wait per call).
     precision = "auto"
+    # opt-in for small calls (a single clip: visualisation, serving): the F16X3 engine runs fc2 + post-norm of a forward that cannot fill
+    # the chip as a split-K GEMM + an ordered reduce (include/d3d.h "latency_mode").  Inside the 1e-4 gate, but not bit-identical to the
+    # default path.  Set on the class or an instance at any time; fp32 / bf16 engines (and the "auto" fallback) ignore it.
+    latency_mode = False
     range_check = os.environ.get("D3D_CHECK_RANGE", "1").strip().lower() not in ("0", "false", "no", "off")
     # One process per GPU is the supported multi-GPU form (torchrun; parallel.py).  nn.DataParallel over SEVERAL devices in one
     # process (RUN:216-218 with --gpu_id 0,1,...) would need one engine per device driven from DataParallel's worker threads:
@@ -195,6 +199,10 @@ class _MixSTEDenoiser(nn.Module):
                 eng.set_option("norm_eps_bits", struct.unpack("<I", struct.pack("<f", self._norm_eps))[0])
             engines[idx] = eng
             sigs[idx] = None
+        if not fallback and want == "f16x3" and getattr(eng, "_latency_mode", False) != bool(self.latency_mode):
+            eng.set_option("latency_mode", int(bool(self.latency_mode)))   # (drops the engine's captured graphs)
+            eng._latency_mode = bool(self.latency_mode)
+            eng.release_workspace()
         sig = self._src_sig if self._src_sig is not None else self._param_signature()
         if sigs.get(idx) != sig:
             eng.load_weights(self._named_tensors())

@@ -161,6 +161,16 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     one the engine owns, forked and joined by events: the caller sees ONE asynchronous operation on its stream;
  *                     bit-identical to one stream -- every output element is independent of the batch it is computed in; measured
  *                     +2.9 % at T=243 / B=64, neutral at T=81 / T=27).  Per-kernel profiling and the trace force one stream.
+ *   "latency_mode"    0 (default) / 1: F16X3 flow, small calls.  Where the whole-row fc2 + post-norm launch cannot fill one round of
+ *                     the chip (ceil(M / 64) workgroups < CU count; embedding width 512), each of its workgroups stages all of W2 alone and
+ *                     the launch lasts K / 32 k-tiles whatever M.  With the mode on such a forward runs fc2 as a split-K x split-N GEMM
+ *                     (128 x 128 tiles, S k-ranges, fp32 partials in workspace regions that are dead at that point) followed by a row kernel
+ *                     that adds residual, bias and the partials in a fixed order and applies the post-norm.  S in {2, 4} is a function of
+ *                     (M, D, mlp_hidden, CU count) alone -- the same for eager and captured runs; where the rule gives S = 1 (larger
+ *                     calls) exactly the default kernels run.  The order of additions differs from the default path's: results stay within
+ *                     the parity gate but are NOT bit-identical to the default, nor across calls that get different S; a sequence's
+ *                     result is bit-identical across calls that get the same S.  d3d_workspace_bytes does not change.  "fc2_split_last"
+ *                     (d3d_engine_get_info) reports the S of the latest forward.  Other precisions ignore it.
  * Process-wide switch, the only key accepted with a NULL e: "deep_stages" 1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches
  * (batches of a few sequences: proj on 128 x 128 tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead
  * of two, the wait in front of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243:
@@ -188,7 +198,9 @@ int d3d_repeat_batch(const float* x_dev, float* out_dev, int32_t B, int64_t n, i
 int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_t n, int32_t repeat_n, void* stream);
 
 /* Read-only engine facts: "graphs_cached" (captured hipGraphs held now, <= 4), "graphs_captured" (captures since creation),
- * "streams", "device".  Unknown key: D3D_EINVAL. */
+ * "streams", "device", "latency_mode", "fc2_split_last" (the k-split S of fc2 + post-norm in the most recent d3d_denoise /
+ * d3d_ddim_sample call, 0 when the default whole-row kernel ran; a sampling run as two half-batches reports the first half's).
+ * Unknown key: D3D_EINVAL. */
 int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value);
 
 /* evaluate() tail (RUN:583-590, LOSS:15-22): un-flip + average the TTA pair, multiply by scale, and reduce the masked
@@ -359,6 +371,16 @@ int d3d_op_linear_postnorm(const float* A_dev, const float* W_dev, const float* 
                            const float* gamma_dev, const float* beta_dev, float eps, const float* pos_dev, int32_t pos_div,
                            int32_t pos_mod, const float* tvec_dev, int64_t tvec_stride, int32_t rows_per_batch, float* Y_dev,
                            float* stats_dev, int32_t M, int32_t N, int32_t K, int32_t reps, float* avg_ms, void* stream);
+/* The same Y from the kernel pair of "latency_mode" (d3d_engine_set_option): a split-K x split-N F16X3 GEMM writes S fp32 partials
+ * P[ks][M][N] (128 x 128 tiles, k-range ks of S) into partials_dev (S * M * N floats), and an ordered reduce + post-norm row kernel forms
+ * R + bias + P[0] + ... + P[S-1] in exactly that order, then the LayerNorm and additions above.  A row's value depends on S, not on
+ * M or on the row's position.  N == 512, S in {2, 4}, (K / 32) % S == 0 (anything else: D3D_EUNSUP).  stats as above (one (sum, sum
+ * of squares) per row from the row kernel).  reps / avg_ms: mean time of the pair of launches. */
+int d3d_op_linear_splitk_postnorm(const float* A_dev, const float* W_dev, const float* bias_dev, const float* R_dev,
+                                  const float* gamma_dev, const float* beta_dev, float eps, const float* pos_dev, int32_t pos_div,
+                                  int32_t pos_mod, const float* tvec_dev, int64_t tvec_stride, int32_t rows_per_batch, float* Y_dev,
+                                  float* stats_dev, int32_t M, int32_t N, int32_t K, int32_t S, float* partials_dev, int32_t reps,
+                                  float* avg_ms, void* stream);
 /* Regression head of the engine's weights (S2S:217-220: LayerNorm eps 1e-5 + Linear D -> 3) on rows x D fp32 rows:
  * x0 (rows, 3), raw (no clamp, no DDIM update). */
 int d3d_op_head(d3d_engine* e, const float* X_dev, float* x0_dev, int32_t rows, void* stream);
