@@ -316,6 +316,15 @@ bool attn_spatial_fast_ok(int J, int D, int H);
 // Spatial blocks: call with (B * T, J, 1).  softmax - I is normalised and rounded to bf16 before the second product.
 hipError_t launch_attn_bf16(const void* qkv_bf16, void* out_bf16, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_bf16_ok(int T, int D, int H);
+// ---- kernels_qkv_attn_bf16.hip: the bf16 qkv GEMM and that attention in ONE kernel (k_qkv_sattn_bf16 / k_qkv_tattn_bf16): q / k / v stay
+// in LDS; bit-identical to launch_linear_bf16 / launch_gemm_bf16q (qcols = D) followed by launch_attn_bf16.  A: bf16 [groups * N][D]
+// (only those rows are read); W: bf16 [3 D][D]; out: bf16 [groups * N][D], NOT A (every head reads whole rows of A).  Group u holds rows
+// (u / stride) * N * stride + u % stride + t * stride, t < N -- spatial blocks: (B * T, J, 1), temporal blocks: (B * J, T, J).
+// The predicates: head width 64, D % 128 == 0, D >= 256, groups of <= 255 tokens (spatial: <= 32), B * T * J * D * 2 < 2^32.
+bool qkv_sattn_bf16_ok(int T, int J, int D, int H, int B);
+bool qkv_tattn_bf16_ok(int T, int J, int D, int H, int B);
+hipError_t launch_qkv_attn_bf16(const void* A, const void* W, const float* bias, void* out, int groups, int N, int stride, int D, int H,
+                                int temporal, hipStream_t s);
 bool attn_temporal_fast_ok(int T, int D, int H);
 
 }  // namespace d3d

@@ -76,6 +76,7 @@ struct d3d_engine {
   bool opt_fused_spatial = true;
   // "fused_temporal": the same for the temporal blocks where the frame count fits one tile (T in 193..255, or T <= 127 with several joints
   // per tile: kernels_qkv_tattn.hip)
+  // BF16 mode: both keys select the bf16 qkv GEMM + attention kernels (kernels_qkv_attn_bf16.hip) for their block type, every T <= 255
   bool opt_fused_temporal = true;
   // "fc1_kernel": fc1 on its own kernel (kernels_fc1_x3.hip) where the launch fills the chip for a few rounds; bit-identical
   bool opt_fc1_kernel = true;
@@ -101,6 +102,9 @@ struct d3d_engine {
   // order of additions: results stay inside the parity gate but are no longer bit-identical to the default path's.
   bool opt_latency_mode = false;
   int fc2_split_last = 0;         // the S of the most recent forward (0: the whole-row fc2 ran): d3d_engine_get_info
+  // BF16 mode: whether the most recent forward ran the fused qkv + attention kernel (kernels_qkv_attn_bf16.hip) in its spatial / temporal
+  // blocks ("fused_spatial" / "fused_temporal" and the shape predicates): d3d_engine_get_info "bf16_fused_spatial_last" / "..temporal_last"
+  int bf16_fused_sp_last = 0, bf16_fused_tp_last = 0;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int device = -1;                // ordinal of the device the weights were committed on
@@ -368,6 +372,15 @@ int fc2_split_for(const d3d_engine* e, int B) {
   return fc2_splitk_choose(B * e->T * e->J, e->D, e->Dm, device_cu_count());
 }
 
+// BF16 mode: which block types of a forward of B sequences run the fused qkv + attention kernel.  A pure function of the options and
+// the shape -- the same for eager and captured runs.
+bool bf16_fused_sp_for(const d3d_engine* e, int B) {
+  return e->cfg.precision == D3D_PREC_BF16 && e->opt_fused_spatial && qkv_sattn_bf16_ok(e->T, e->J, e->D, e->H, B);
+}
+bool bf16_fused_tp_for(const d3d_engine* e, int B) {
+  return e->cfg.precision == D3D_PREC_BF16 && e->opt_fused_temporal && qkv_tattn_bf16_ok(e->T, e->J, e->D, e->H, B);
+}
+
 // F16X3 production flow ("plane-resident, LayerNorm-folded"): the residual stream lives in the GEMM operand (pair) layout
 // in w.X, so it is at once the A operand of the qkv / fc1 GEMMs and the residual input of the proj / fc2 epilogues; norm1
 // and norm2 are folded into those two GEMMs (X3Fold), their row statistics coming from the producer of the stream (the
@@ -571,7 +584,7 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
   const int M = B * T * J;
   const double MD4 = (double)M * D * 4.0, MD2 = (double)M * D * 2.0;
   uint16_t* HNb = reinterpret_cast<uint16_t*>(w.HN);     // bf16 [Mp][D]: LayerNorm output, then the attention output
-  uint16_t* QKVb = reinterpret_cast<uint16_t*>(w.QKV);   // bf16 [M][3D]
+  uint16_t* QKVb = reinterpret_cast<uint16_t*>(w.QKV);   // bf16 [M][3D]; in a fused block (below) bf16 [M][D]: the attention output
   uint16_t* HIDb = reinterpret_cast<uint16_t*>(w.HID);   // bf16 [Mp][Dm]
   {
     Prof p(e, D3D_KC_EMBED, 2.0 * M * D * e->cin, MD4 + (double)M * e->cin * 4.0, s);
@@ -602,9 +615,20 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
     Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)D * K, 2.0 * ((double)M * K + (double)D * K) + (double)M * D * (Hb ? 10.0 : 8.0), s, sub);
     return launch_linear_bf16_rows(A, W, bias, w.X, Hb, M, D, K, pn, s);
   };
+  // qkv GEMM + attention of a block in ONE kernel (kernels_qkv_attn_bf16.hip; "fused_spatial" / "fused_temporal"): q / k / v never reach
+  // HBM.  Every head's tile reads whole rows of HNb, so the attention output cannot go there: it takes w.QKV, dead in such a block.
+  // Bit-identical to the two launches it replaces.
+  const bool fused_sp = bf16_fused_sp_for(e, B), fused_tp = bf16_fused_tp_for(e, B);
   for (int k = 0; k < e->nblk; ++k) {
     const BlockW& bw = e->blk[k];
     const bool temporal = (k & 1) != 0;
+    const uint16_t* AOb = HNb;                             // the attention output: proj's operand
+    if (temporal ? fused_tp : fused_sp) {
+      const int N = temporal ? T : J;
+      Prof p(e, temporal ? D3D_KC_QKV_TATTN : D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)N * D, 2.0 * MD2 + 2.0 * 3.0 * D * D, s);
+      HIP_TRY(launch_qkv_attn_bf16(HNb, bw.qkv_x3, bw.qkvb, QKVb, temporal ? B * J : B * T, N, temporal ? J : 1, D, e->H, temporal ? 1 : 0, s));
+      AOb = QKVb;
+    } else {
     HIP_TRY(linear(HNb, bw.qkv_x3, bw.qkvb, nullptr, nullptr, QKVb, 3 * D, D, EPI_NONE, D, D3D_KC_LINEAR_QKV));
     {
       const int N = temporal ? T : J;
@@ -612,11 +636,12 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       if (temporal) HIP_TRY(launch_attn_bf16(QKVb, HNb, B, T, J, D, e->H, s));
       else HIP_TRY(launch_attn_bf16(QKVb, HNb, B * T, J, 1, D, e->H, s));
     }
+    }
     if (rows) {
       {  // x += attn Wproj^T + b (fp32 stream in place); h = bf16(norm2(x)) over the attention output's rows (same tile rows: in place)
         X3PostNorm pn{};
         pn.g2 = bw.n2g; pn.b2 = bw.n2b; pn.eps2 = e->ln_eps; pn.pos_div = 1; pn.pos_mod = 1; pn.rows_per_batch = T * J;
-        HIP_TRY(linear_rows(HNb, bw.proj_x3, bw.projb, HNb, D, pn, D3D_KC_LINEAR_PROJ));
+        HIP_TRY(linear_rows(AOb, bw.proj_x3, bw.projb, HNb, D, pn, D3D_KC_LINEAR_PROJ));
       }
       HIP_TRY(linear(HNb, bw.fc1_x3, bw.fc1b, nullptr, nullptr, HIDb, e->Dm, D, EPI_GELU, 0, D3D_KC_LINEAR_FC1));
       {  // x = post_norm(x + hidden W2^T + b2) [+ Temporal_pos_embed] [+ next block's time vector]; h = bf16(next.norm1(x))
@@ -633,7 +658,7 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       }
       continue;
     }
-    HIP_TRY(linear(HNb, bw.proj_x3, bw.projb, w.X, w.X, nullptr, D, D, EPI_RESIDUAL, 0, D3D_KC_LINEAR_PROJ));
+    HIP_TRY(linear(AOb, bw.proj_x3, bw.projb, w.X, w.X, nullptr, D, D, EPI_RESIDUAL, 0, D3D_KC_LINEAR_PROJ));
     {  // h = bf16(norm2(x))
       LnArgs a{};
       a.x = w.X; a.h_bf16 = HNb; a.g1 = bw.n2g; a.b1 = bw.n2b; a.eps1 = e->ln_eps;
@@ -808,7 +833,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 131; }   // 131: d3d_pose_metrics
+int d3d_version(void) { return 132; }   // 132: d3d_op_qkv_attn_bf16, "bf16_fused_*_last"
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1163,6 +1188,8 @@ int d3d_denoise(d3d_engine* e, const float* x2d, const float* y, int32_t y_frame
   RangeScope range_scope(e);
   Workspace w = carve(e, B, ws);
   e->fc2_split_last = fc2_split_for(e, B);
+  e->bf16_fused_sp_last = bf16_fused_sp_for(e, B) ? 1 : 0;
+  e->bf16_fused_tp_last = bf16_fused_tp_for(e, B) ? 1 : 0;
   const float* tvec = nullptr;
   int64_t stride = 0;
   if (e->Dt) {
@@ -1289,6 +1316,8 @@ int d3d_ddim_sample(d3d_engine* e, const float* x2d, const float* init_noise, co
   SplitWs sw{};
   if (split) sw = carve_split(e, B, ws);
   e->fc2_split_last = fc2_split_for(e, split ? sw.B0 : B);   // (two half-batches: the first half's -- the one that holds sequence 0)
+  e->bf16_fused_sp_last = bf16_fused_sp_for(e, split ? sw.B0 : B) ? 1 : 0;
+  e->bf16_fused_tp_last = bf16_fused_tp_for(e, split ? sw.B0 : B) ? 1 : 0;
   const size_t xin0 = split ? (size_t)sw.B0 * xin_row : 0, y0 = split ? (size_t)head_rows(e, sw.B0) * 3 : 0;
   if (!use_graph) {
     if (split)
@@ -1436,6 +1465,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "device") *value = e->device;
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
   else if (k == "fc2_split_last") *value = e->fc2_split_last;
+  else if (k == "bf16_fused_spatial_last") *value = e->bf16_fused_sp_last;
+  else if (k == "bf16_fused_temporal_last") *value = e->bf16_fused_tp_last;
   else return fail(D3D_EINVAL, "unknown info key: " + k);
   return D3D_OK;
 }
@@ -1890,6 +1921,34 @@ int d3d_op_head(d3d_engine* e, const float* X, float* x0, int32_t rows, void* st
   h.g = e->hd_g; h.b = e->hd_b; h.eps = 1e-5f; h.Wh = e->hd_w; h.bh = e->hd_bias; h.D = e->D;
   h.X = X; h.rows = rows; h.x0_raw = x0; h.mode = 0;
   HIP_TRY(launch_head(h, reinterpret_cast<hipStream_t>(stream)));
+  return D3D_OK;
+}
+
+int d3d_op_qkv_attn_bf16(const float* A, const float* Wqkv, const float* bias, int32_t groups, int32_t N, int32_t stride, int32_t D,
+                         int32_t H, int32_t temporal, float* out, void* stream) {
+  if (!A || !Wqkv || !bias || !out || groups <= 0 || N <= 0 || stride <= 0 || D <= 0 || H <= 0 || groups % stride) return fail(D3D_EINVAL, "bad argument");
+  const int T = temporal ? N : groups / stride, J = temporal ? stride : N, B = temporal ? groups / stride : 1;
+  if (!(temporal ? qkv_tattn_bf16_ok(T, J, D, H, B) : qkv_sattn_bf16_ok(T, J, D, H, B)))
+    return fail(D3D_EUNSUP, "fused bf16 qkv + attention: head_dim 64, D % 128 == 0, D >= 256, groups of <= 255 tokens (spatial: <= 32)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // test hook: operands rounded to bf16 on the device into buffers of EXACTLY the operand sizes (the kernel reads no pad rows), the fused
+  // kernel alone, its bf16 output widened to fp32
+  const size_t rows = (size_t)groups * N, na = rows * D, nw = (size_t)3 * D * D;
+  struct DevBuf {
+    uint16_t* p = nullptr;
+    ~DevBuf() { (void)hipFree(p); }
+  } ab, wb, ob;
+  HIP_TRY(hipMalloc(&ab.p, na * 2));
+  HIP_TRY(hipMalloc(&wb.p, nw * 2));
+  HIP_TRY(hipMalloc(&ob.p, na * 2));
+  hipError_t le = launch_f32_to_bf16(A, ab.p, na, s);
+  if (le == hipSuccess) le = launch_f32_to_bf16(Wqkv, wb.p, nw, s);
+  if (le == hipSuccess) le = hipMemsetAsync(ob.p, 0xff, na * 2, s);   // (NaN: a row the kernel skipped shows)
+  if (le == hipSuccess) le = launch_qkv_attn_bf16(ab.p, wb.p, bias, ob.p, groups, N, stride, D, H, temporal ? 1 : 0, s);
+  if (le == hipSuccess) le = launch_bf16_to_f32(ob.p, out, na, s);
+  hipError_t se = hipStreamSynchronize(s);
+  HIP_TRY(le);
+  HIP_TRY(se);
   return D3D_OK;
 }
 

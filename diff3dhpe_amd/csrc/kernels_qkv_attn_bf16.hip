@@ -1,0 +1,437 @@
+// bf16 operand mode (D3D_PREC_BF16), fused: the qkv GEMM of a tile of token groups x ONE head and the GRAND attention of those groups in
+// one kernel -- q / k / v are rounded to bf16 where the un-fused qkv GEMM rounds them for its [M][3 D] output and stay in LDS; the
+// attention of k_attn_bf16 (kernels_attn_bf16.hip) then runs from LDS.  What it removes from the two-kernel flow: the [M][3 D] bf16
+// tensor written by the GEMM and read back by the attention kernel, and one launch per block.
+//
+// A tile = g = floor(255 / N) whole groups of N tokens (spatial blocks: N = J joints of a frame, token stride 1, 15 frames at J = 17;
+// temporal blocks: N = T frames of one (batch, joint), token stride J; 3 joints at T = 81, 1 at T = 243) x the 192 weight rows of one
+// head (q, k, v: 64 each).  The operand rows are GATHERED by the LDS-DMA's per-lane source addresses, so both block types share one
+// row map; stage rows behind the tile's last group (and groups behind the last one of the launch) repeat a real row: every staged
+// value is finite whenever the operand rows are, and nothing outside the M operand rows is read.
+//
+// The k-loop is the two-phase loop of qkv_fused_kloop.h on a 256 x 192 stage of 64-deep bf16 k-tiles (the stage shape of k_qkv_sattn,
+// the MFMA form of k_gemm_bf16q): eight waves (2 x 4), a wave owns 128 rows x 48 columns.  Stage row 48 wn + 16 part + x holds weight
+// row part * D + 64 head + 16 wn + x, so accumulator column tile j of wave wn IS part j (q, k, v) at head columns 16 wn .. + 15.  Per
+// output element: the same v_mfma_f32_16x16x32_bf16 products in the same k order as launch_gemm_bf16q / launch_linear_bf16, the same
+// epilogue arithmetic (fma(acc, 1, bias), q third times 2^-3, round to nearest even) -- the LDS planes hold bit for bit what the
+// un-fused GEMM writes to HBM.  The attention step is k_attn_bf16's arithmetic instruction for instruction on those planes.  Pad keys
+// of a group are other groups' rows here and zeros there: their scores are overwritten with -inf in both, and their V^T fragment
+// elements are replaced by zeros in registers before the second product, so a non-finite value of a neighbouring group (another frame,
+// joint or batch element) cannot reach this group's output -- as in the two-kernel flow, a sequence's result depends on its own rows
+// only.  The block is bit-identical to the two-kernel flow (tests/test_gpu_bf16_fused_attn.py).
+//
+// LDS map (156 KiB): [0, 56 K) stage 0 | [56 K, 112 K) stage 1 | from 56 K on, after the k-loop: Q plane (256 rows x 128 B), K plane
+// (256 rows), V plane (288 rows: rows 256 .. 287, read for the pad keys of the tile's last group, are zeroed).  Stage 0 stays free behind the
+// k-loop: the next tile's first k-tile lands there under this tile's attention step (persistent walk, one workgroup per CU).
+#include "d3d_kernels.h"
+typedef __bf16 qa_bf8 __attribute__((ext_vector_type(8)));
+#define QF_MMA(ACC, BH, BL, AH, AL)                                                                                                   \
+  do {                                                                                                                                \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(qa_bf8, BH), __builtin_bit_cast(qa_bf8, AH), ACC, 0, 0, 0);      \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(qa_bf8, BL), __builtin_bit_cast(qa_bf8, AL), ACC, 0, 0, 0);      \
+  } while (0)
+#include "qkv_fused_kloop.h"
+
+#include <math.h>
+
+namespace d3d {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
+typedef short s4v __attribute__((ext_vector_type(4)));
+
+constexpr int QA_BM = 256, QA_BN = 192, QA_TM = 8, QA_NJ = 3;
+constexpr int QA_AREG = QA_BM * 128, QA_STAGE = (QA_BM + QA_BN) * 128;   // 57344
+constexpr int QA_AIT = 4, QA_BIT = 3;                                    // 1-KiB DMA pieces per wave per k-tile
+constexpr int QA_ROWS = 255;                                             // token rows of a tile at most
+constexpr int QA_PQ = QA_STAGE, QA_PK = QA_PQ + 256 * 128, QA_PV = QA_PK + 256 * 128;
+constexpr int QA_VROWS = 288;
+constexpr int QA_LDS = QA_PV + QA_VROWS * 128;                           // 159744
+static_assert(QA_LDS <= 160 * 1024, "LDS map");
+
+// swizzles of kernels_attn_bf16.hip, on the tile's row index
+__device__ __forceinline__ int kswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
+__device__ __forceinline__ int vkey(int row) { return (((row >> 1) & 1) << 2) ^ ((row >> 2) & 3); }
+__device__ __forceinline__ int vswz(int row, int chunk) { return row * 128 + ((chunk ^ vkey(row)) << 4); }
+
+__device__ __forceinline__ const char* sgpr_ptr(const char* p) {
+  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
+}
+
+struct QaArgs {
+  const char* A;        // bf16 operand rows [M][D] (norm1(x))
+  const char* W;        // bf16 qkv weight rows [3 D][D]
+  const float* bias;    // [3 D]
+  __bf16* out;          // attention output, bf16 [M][D]
+  int D, H;             // model width (the GEMM depth), heads (D / 64)
+  int N, udiv;          // tokens of a group, token stride: token t of group u is row (u / udiv) * N * udiv + u % udiv + t * udiv
+  int g, units, mtiles; // groups per tile, groups of the launch, ceil(units / g)
+};
+
+#define QA_GLDS(SRC, DSTOFF)                                                                                            \
+  __builtin_amdgcn_global_load_lds((SRC), (__attribute__((address_space(3))) void*)(uintptr_t)(lds + (DSTOFF)), 16, 0, 0)
+
+__device__ __forceinline__ void wait_vm(int n) {   // s_waitcnt vmcnt(n), n wave-uniform
+  switch (n) {
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+  }
+}
+
+// first row of group `unit` (clamped to the launch's last group)
+__device__ __forceinline__ unsigned qa_unit_row(const QaArgs& a, int unit) {
+  if (unit >= a.units) unit = a.units - 1;
+  const int o = unit / a.udiv;
+  return (unsigned)(o * a.N * a.udiv + (unit - o * a.udiv));
+}
+// operand row of stage row i of M-tile mt: rows behind the tile's last group repeat that group's last row
+__device__ __forceinline__ unsigned qa_row(const QaArgs& a, int mt, int i) {
+  int u = i / a.N, t = i - u * a.N;
+  if (u >= a.g) { u = a.g - 1; t = a.N - 1; }
+  return qa_unit_row(a, mt * a.g + u) + (unsigned)(t * a.udiv);
+}
+// first weight row of the 8 stage rows [s0, s0 + 8): stage row 48 wn + 16 part + x <- weight row part * D + 64 hd + 16 wn + x
+__device__ __forceinline__ int qa_wrow(const QaArgs& a, int s0, int hd) {
+  const int wn = s0 / 48, rem = s0 - wn * 48;
+  return (rem >> 4) * a.D + 64 * hd + 16 * wn + (rem & 15);
+}
+
+// One 32-query tile `qt` of the group whose rows start at tile row rb: k_attn_bf16's arithmetic on the LDS planes.
+template <int NKT>
+__device__ __forceinline__ void qa_attention(const unsigned char* lds, int lane, int rb, int qt, int T, __bf16* out0, size_t tstride, bool store) {
+  const unsigned char* const sQ = lds + QA_PQ;
+  const unsigned char* const sK = lds + QA_PK;
+  const unsigned char* const sV = lds + QA_PV;
+  const int r = lane & 31, h = lane >> 5;
+  const int tq = 32 * qt + r;
+  bf8 qf[4];
+  {
+    const int qrow = rb + (tq < T ? tq : 0);                       // rows >= T reuse row 0: never stored
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf8*>(sQ + kswz(qrow, 2 * ks + h));
+  }
+  const unsigned char* kb[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) kb[ks] = sK + kswz(rb + r, 2 * ks + h);                    // + 4096 kt
+  const unsigned char* vb[2][2];
+  {
+    const int gi = lane & 15, tq_ = gi >> 2, tp_ = gi & 3;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      const int d0 = dt * 32 + 16 * ((lane >> 4) & 1);
+      const int ch = (d0 >> 3) + (tp_ >> 1), sb = (tp_ & 1) * 8;
+      vb[dt][0] = sV + vswz(rb + 4 * h + tq_, ch) + sb;                                      // + 2048 (2 kt + s)
+      vb[dt][1] = sV + vswz(rb + 4 * h + 8 + tq_, ch) + sb;
+    }
+  }
+  // ---- S^T tiles: rows = keys kt * 32 + (reg & 3) + 8 (reg >> 2) + 4 h, column = query tq
+  f32x16 sacc[NKT];
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sacc[kt][q] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const bf8 kf = *reinterpret_cast<const bf8*>(kb[ks] + kt * 4096);
+      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kt], 0, 0, 0);
+    }
+  }
+  // ---- exact softmax over the keys of this query column (fp32); only the last key tile can hold keys of other groups
+  float m = -INFINITY;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      if (kt == NKT - 1) {
+        const int key = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+        if (key >= T) sacc[kt][q] = -INFINITY;
+      }
+      m = fmaxf(m, sacc[kt][q]);
+    }
+  m = fmaxf(m, __shfl_xor(m, 32, 64));
+  constexpr float LOG2E = 1.4426950408889634f;
+  const float mb = m * LOG2E;
+  float l = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const float e = __builtin_amdgcn_exp2f(fmaf(sacc[kt][q], LOG2E, -mb));
+      sacc[kt][q] = e;
+      l += e;
+    }
+  l += __shfl_xor(l, 32, 64);
+  const float inv = 1.0f / l;
+  {  // softmax - I: the diagonal's numerator becomes e - l (k_attn_bf16)
+    const int didx = (((r >> 2) & 1) == h) ? (8 * (r >> 4) + 4 * ((r >> 3) & 1) + (r & 3)) : -1;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+      if (kt == qt) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) sacc[kt][q] -= (q == didx) ? l : 0.0f;
+      }
+  }
+  // ---- O^T[d][query] = sum_key V^T[d][key] (P - I)^T[key][query]
+  f32x16 oacc[2];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) { oacc[0][q] = 0.f; oacc[1][q] = 0.f; }
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      bf8 pf;
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) pf[jj] = (__bf16)(sacc[kt][8 * s + jj] * inv);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) {
+        const s4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(vb[dt][0] + (2 * kt + s) * 2048));
+        const s4v a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(vb[dt][1] + (2 * kt + s) * 2048));
+        bf8 vf;
+        const bf4 a0b = __builtin_bit_cast(bf4, a0), a1b = __builtin_bit_cast(bf4, a1);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { vf[e] = a0b[e]; vf[4 + e] = a1b[e]; }
+        if (kt == NKT - 1) {   // pad keys are other groups' rows here: zeros, as the two-kernel flow stages them (0 x NaN / Inf of a neighbour)
+#pragma unroll
+          for (int jj = 0; jj < 8; ++jj)
+            if (kt * 32 + 16 * s + 8 * (jj >> 2) + 4 * h + (jj & 3) >= T) vf[jj] = (__bf16)0.0f;
+        }
+        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[dt], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);   // keeps the conversions / V^T reads of later k-steps from being hoisted (VGPR pressure)
+    }
+  }
+  // ---- O rows out as bf16: lane (query tq, half h) holds d = dt * 32 + 8 g4 + 4 h + e
+  if (tq < T && store) {
+    __bf16* orow = out0 + (size_t)tq * tstride;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        bf4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = (__bf16)oacc[dt][4 * g4 + e];
+        *reinterpret_cast<bf4*>(orow + dt * 32 + 8 * g4 + 4 * h) = o;
+      }
+  }
+}
+
+template <int NKT>
+__device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
+  const int G = (int)gridDim.x, b = (int)blockIdx.x;
+  const int H = a.H;
+  const int tiles = a.mtiles * H;
+  if (b >= tiles) return;
+  const int nitems = (tiles - b + G - 1) / G;
+  const int vfull = (a.mtiles / 8) * 8 * H, mrem = a.mtiles % 8;
+  // tile ordinal -> (M-tile, head): all heads of an M-tile on one XCD, as the GEMMs walk (kernels_qkv_sattn.hip)
+  auto tile_of = [&](int o, int& mt, int& hd) {
+    if (o < vfull) {
+      const int xcd = o & 7, slot = o >> 3;
+      mt = (slot / H) * 8 + xcd;
+      hd = slot % H;
+    } else {
+      const int o2 = o - vfull;
+      mt = (a.mtiles / 8) * 8 + o2 % mrem;
+      hd = o2 / mrem;
+    }
+  };
+
+  const int K = a.D;
+  const unsigned rowB = 2u * (unsigned)K;         // bytes of an operand / weight row
+  const int nk = K / 64;
+  int mt = 0, hd = 0;
+  tile_of(b, mt, hd);
+  {   // first k-tile of the first tile
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int lr = lane >> 3, csrc = (lane & 7) ^ (((wave & 1) << 2) | (lr >> 1));
+#pragma unroll
+    for (int it = 0; it < QA_AIT; ++it)
+      QA_GLDS(sgpr_ptr(a.A) + (qa_row(a, mt, it * 64 + wave * 8 + lr) * rowB + (unsigned)csrc * 16u), wave * 1024 + lane * 16 + it * 8192);
+    const unsigned lofs = (unsigned)lr * rowB + (unsigned)csrc * 16u;
+#pragma unroll
+    for (int it = 0; it < QA_BIT; ++it)
+      QA_GLDS(sgpr_ptr(a.W + (size_t)qa_wrow(a, it * 64 + wave * 8, hd) * rowB) + lofs, QA_AREG + wave * 1024 + lane * 16 + it * 8192);
+  }
+  int tid_o = (int)threadIdx.x;
+  for (int item = 0; item < nitems; ++item) {
+    asm volatile("" : "+v"(tid_o));   // per-lane offsets are re-derived in every tile instead of being hoisted (and spilled)
+    const int tid = tid_o;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 2, wn = wave & 3;
+    const int r16 = lane & 15, q = lane >> 4;
+    const bool has_next = item + 1 < nitems;
+    int mtn = mt, hdn = hd;
+    if (has_next) tile_of((item + 1) * G + b, mtn, hdn);
+
+    // ---- DMA plan: A rows gathered through per-lane offsets from the operand base, W rows from a wave-uniform base per piece
+    const int lr_ = lane >> 3;
+    const int csrc_ = (lane & 7) ^ (((wave & 1) << 2) | (lr_ >> 1));
+    unsigned lofs_ = (unsigned)lr_ * rowB + (unsigned)csrc_ * 16u;
+    unsigned offA[QA_AIT], offAn[QA_AIT];
+#pragma unroll
+    for (int it = 0; it < QA_AIT; ++it) {
+      offA[it] = qa_row(a, mt, it * 64 + wave * 8 + lr_) * rowB + (unsigned)csrc_ * 16u;
+      offAn[it] = qa_row(a, mtn, it * 64 + wave * 8 + lr_) * rowB + (unsigned)csrc_ * 16u;
+    }
+    const int dstA = wave * 1024 + lane * 16, dstB = QA_AREG + wave * 1024 + lane * 16;
+    // piece IT (A: 0..3, W: 4..6) of k-tile KTT of this tile, or (KTT == nk) of k-tile 0 of the next one
+#define QA_PIECE(KTT, IT)                                                                                               \
+    do {                                                                                                                \
+      const bool nxt_ = (KTT) >= nk;                                                                                    \
+      const int st_ = ((KTT) & 1) * QA_STAGE;                                                                           \
+      const size_t kofs_ = nxt_ ? (size_t)0 : (size_t)(KTT) * 128;                                                      \
+      if ((IT) < QA_AIT) {                                                                                              \
+        QA_GLDS(sgpr_ptr(a.A + kofs_) + (nxt_ ? offAn[(IT) % QA_AIT] : offA[(IT) % QA_AIT]), st_ + dstA + (IT) * 8192);  \
+      } else {                                                                                                          \
+        const char* b_ = a.W + (size_t)qa_wrow(a, ((IT) - QA_AIT) * 64 + wave * 8, nxt_ ? hdn : hd) * rowB + kofs_;     \
+        QA_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstB + ((IT) - QA_AIT) * 8192);                                             \
+      }                                                                                                                 \
+    } while (0)
+
+    f32x4 acc[QA_TM][QA_NJ];
+#pragma unroll
+    for (int i = 0; i < QA_TM; ++i)
+#pragma unroll
+      for (int j = 0; j < QA_NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
+
+    const int foff = (q ^ (r16 >> 1)) << 4;
+    const int aoff = (wm * 128 + r16) * 128 + foff, boff = QA_AREG + (wn * 48 + r16) * 128 + foff;
+    h8 bh[QA_NJ], bl[QA_NJ], ah[2], al[2];
+    int issued_prev = 0;
+#define QF_STAGE QA_STAGE
+#define QF_NJ QA_NJ
+#define QF_TM QA_TM
+#define QF_AIT QA_AIT
+#define QF_BIT QA_BIT
+#define QF_PIECE(KTT, IT) QA_PIECE(KTT, IT)
+    QF_KLOOP_HEAD
+    QF_KLOOP_TAIL
+#undef QF_STAGE
+#undef QF_NJ
+#undef QF_TM
+#undef QF_AIT
+#undef QF_BIT
+#undef QF_PIECE
+#undef QA_PIECE
+    __builtin_amdgcn_s_setprio(0);
+
+    __syncthreads();   // every wave is out of the k-loop: stage 1 and the LDS behind it become the q / k / v planes
+
+    // ---- q / k / v -> planes: fma(acc, 1, bias), the q third times 2^-3, round to nearest even (x3q_epilogue8<.., FX_BF16>)
+    if (tid < 256) *reinterpret_cast<uint4*>(lds + QA_PV + 256 * 128 + tid * 16) = make_uint4(0, 0, 0, 0);
+    {
+      float4 b4[QA_NJ];
+#pragma unroll
+      for (int j = 0; j < QA_NJ; ++j) b4[j] = *reinterpret_cast<const float4*>(a.bias + j * a.D + 64 * hd + 16 * wn + 4 * q);
+      const int chunk = 2 * wn + (q >> 1), half8 = (q & 1) << 3;          // this lane's 8 bytes: 16-byte chunk d / 8, half (d & 4)
+#pragma unroll
+      for (int i = 0; i < QA_TM; ++i) {
+        const int R = wm * 128 + 16 * i + r16;
+        unsigned char* const pkq = lds + kswz(R, chunk) + half8;
+        unsigned char* const pv = lds + QA_PV + vswz(R, chunk) + half8;
+#pragma unroll
+        for (int j = 0; j < QA_NJ; ++j) {
+          const float osc = j == 0 ? 0.125f : 1.0f;
+          const float bj[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
+          bf4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (__bf16)(__builtin_fmaf(acc[i][j][e], 1.0f, bj[e]) * osc);
+          *reinterpret_cast<bf4*>(j == 0 ? pkq + QA_PQ : (j == 1 ? pkq + QA_PK : pv)) = o;
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- attention: (group, 32-query tile) jobs of the tile over the eight waves
+    {
+      const int jobs = a.g * NKT;
+      for (int job = wave; job < jobs; job += 8) {
+        const int u = job / NKT, qt = job - u * NKT;
+        if (32 * qt >= a.N) continue;
+        const int unit = mt * a.g + u;
+        const bool ok = unit < a.units;                                   // (wave-uniform)
+        if (!ok) continue;
+        __bf16* const out0 = a.out + (size_t)qa_unit_row(a, unit) * a.D + 64 * hd;
+        qa_attention<NKT>(lds, lane, u * a.N, qt, a.N, out0, (size_t)a.udiv * a.D, true);
+      }
+    }
+    mt = mtn; hd = hdn;
+    __syncthreads();   // the planes are read before the next tile's second k-tile is staged over them
+  }
+}
+
+}  // namespace
+
+// spatial blocks: groups of N <= 32 tokens (the joints of a frame), one key tile
+__global__ __launch_bounds__(512) void k_qkv_sattn_bf16(QaArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  qa_tiles<1>(a, lds);
+}
+// temporal blocks: groups of N <= 255 tokens (the frames of one joint), NKT = ceil(N / 32) key tiles
+template <int NKT>
+__global__ __launch_bounds__(512) void k_qkv_tattn_bf16(QaArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  qa_tiles<NKT>(a, lds);
+}
+
+// Shapes the fused kernels exist for: head width 64, GEMM depth D a multiple of 128 from 256 on (whole pairs of 64-deep k-tiles, as
+// launch_gemm_bf16q), groups of at most 255 tokens (one tile holds whole groups), operand offsets that fit 32 bits.
+static bool qkv_attn_bf16_shape_ok(long long groups, int N, int D, int H) {
+  return N >= 1 && N <= QA_ROWS && H > 0 && D == 64 * H && D % 128 == 0 && D >= 256 && groups >= 1 && groups * N * (long long)D * 2 < (1LL << 32);
+}
+bool qkv_sattn_bf16_ok(int T, int J, int D, int H, int B) { return J <= 32 && qkv_attn_bf16_shape_ok((long long)B * T, J, D, H); }
+bool qkv_tattn_bf16_ok(int T, int J, int D, int H, int B) { return qkv_attn_bf16_shape_ok((long long)B * J, T, D, H); }
+
+template <typename KF>
+static hipError_t qa_launch(KF kern, std::atomic<unsigned long long>& attr_done, const QaArgs& a, hipStream_t s) {
+  if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kern), QA_LDS, attr_done)) return ae;
+  int n_cu = device_cu_count();
+  if (n_cu <= 0) return hipErrorUnknown;
+  const long long tiles = (long long)a.mtiles * a.H;
+  if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+  const int grid = tiles < n_cu ? (int)tiles : n_cu;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), QA_LDS, s, a);
+  return hipGetLastError();
+}
+
+// A: bf16 [groups * N][D]; W: bf16 [3 D][D]; bias: [3 D]; out: bf16 [groups * N][D] (not A: every head reads whole rows of A).
+// Group u holds rows (u / stride) * N * stride + u % stride + t * stride, t < N -- spatial blocks: (B * T, J, 1), temporal: (B * J, T, J).
+hipError_t launch_qkv_attn_bf16(const void* A, const void* W, const float* bias, void* out, int groups, int N, int stride, int D, int H,
+                                int temporal, hipStream_t s) {
+  if (!A || !W || !bias || !out || A == out || stride < 1 || groups < 1 || groups % stride != 0) return hipErrorInvalidValue;
+  if (!qkv_attn_bf16_shape_ok(groups, N, D, H) || (!temporal && N > 32)) return hipErrorInvalidValue;
+  QaArgs a{};
+  a.A = (const char*)A; a.W = (const char*)W; a.bias = bias; a.out = (__bf16*)out;
+  a.D = D; a.H = H; a.N = N; a.udiv = stride;
+  a.g = QA_ROWS / N; a.units = groups; a.mtiles = (groups + a.g - 1) / a.g;
+  static std::atomic<unsigned long long> attr_done[9] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // one bit per device
+  if (!temporal) return qa_launch(k_qkv_sattn_bf16, attr_done[0], a, s);
+  switch ((N + 31) / 32) {
+    case 1: return qa_launch(k_qkv_tattn_bf16<1>, attr_done[1], a, s);
+    case 2: return qa_launch(k_qkv_tattn_bf16<2>, attr_done[2], a, s);
+    case 3: return qa_launch(k_qkv_tattn_bf16<3>, attr_done[3], a, s);
+    case 4: return qa_launch(k_qkv_tattn_bf16<4>, attr_done[4], a, s);
+    case 5: return qa_launch(k_qkv_tattn_bf16<5>, attr_done[5], a, s);
+    case 6: return qa_launch(k_qkv_tattn_bf16<6>, attr_done[6], a, s);
+    case 7: return qa_launch(k_qkv_tattn_bf16<7>, attr_done[7], a, s);
+    default: return qa_launch(k_qkv_tattn_bf16<8>, attr_done[8], a, s);
+  }
+}
+
+}  // namespace d3d

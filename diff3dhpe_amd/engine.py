@@ -172,7 +172,8 @@ class Engine:
 
     def info(self, key: str) -> int:
         """Read-only engine facts (include/d3d.h d3d_engine_get_info): "graphs_cached", "graphs_captured", "streams", "device",
-        "latency_mode", "fc2_split_last"."""
+        "latency_mode", "fc2_split_last", "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the most recent forward of a
+        bf16 engine ran the fused qkv + attention kernel in its spatial / temporal blocks)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -464,6 +465,21 @@ def op_attention(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bo
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib().d3d_op_attention(_ptr(q), _ptr(out), B, T, J, D, H, int(temporal),
                                                _lib.PRECISIONS[precision], int(force_generic), st))
+    return out
+
+
+def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, groups: int, N: int, stride: int, H: int,
+                     temporal: bool) -> torch.Tensor:
+    """The fused bf16 qkv GEMM + attention kernel alone (include/d3d.h d3d_op_qkv_attn_bf16): A (groups * N, D) token rows,
+    Wqkv (3 D, D), bias (3 D,) -> (groups * N, D).  Group u holds rows (u // stride) * N * stride + u % stride + t * stride."""
+    dev = A.device
+    D = A.shape[-1]
+    a = _f32c(A, dev).reshape(groups * N, D)
+    out = torch.empty((groups * N, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_qkv_attn_bf16(_ptr(a), _ptr(_f32c(Wqkv, dev)), _ptr(_f32c(bias, dev)), int(groups), int(N),
+                                                   int(stride), D, int(H), int(temporal), _ptr(out), st))
     return out
 
 

@@ -141,6 +141,13 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     T <= 127: the frames of 255 / T joints of one batch element per tile, every query on its own joint's keys -- as
  *                     accurate as the two-kernel flow but not bit-identical to it (sums grouped by tile position); a batch element's
  *                     result does not depend on its position in the batch either way.
+ *                     BF16 mode: both keys select, for their block type, the bf16 qkv GEMM + attention as ONE kernel (a tile of
+ *                     floor(255 / N) whole groups of N tokens x one head; q / k / v are rounded to bf16 where the qkv GEMM rounds them and
+ *                     stay in LDS; the attention output goes to the workspace region the q / k / v tensor would have taken) / as two
+ *                     kernels.  Shapes: head width 64, D % 128 == 0, D >= 256, T <= 255, J <= 32; others keep the two kernels whatever
+ *                     the keys say.  Bit-identical either way, for every T, non-finite activations included (a group's pad keys are
+ *                     masked to zeros in registers: a sequence's result depends on its own rows only).  "bf16_fused_spatial_last" / "bf16_fused_temporal_last"
+ *                     (d3d_engine_get_info) report what the latest forward ran.
  *   "fc1_kernel"      1 (default) / 0: fc1 (LayerNorm-folded, GELU) on its own kernel -- the hand-specialised k-loop of the fused kernels
  *                     with the token GEMM's own epilogue function, from two rounds of 256 x 256 tiles on -- / as a form of the token GEMM.
  *                     Bit-identical.
@@ -199,7 +206,10 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
 
 /* Read-only engine facts: "graphs_cached" (captured hipGraphs held now, <= 4), "graphs_captured" (captures since creation),
  * "streams", "device", "latency_mode", "fc2_split_last" (the k-split S of fc2 + post-norm in the most recent d3d_denoise /
- * d3d_ddim_sample call, 0 when the default whole-row kernel ran; a sampling run as two half-batches reports the first half's).
+ * d3d_ddim_sample call, 0 when the default whole-row kernel ran; a sampling run as two half-batches reports the first half's),
+ * "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the spatial / temporal blocks of the most recent d3d_denoise /
+ * d3d_ddim_sample call of a D3D_PREC_BF16 engine ran the fused qkv + attention kernel, else 0; 0 before the first call and in the
+ * other precisions).
  * Unknown key: D3D_EINVAL. */
 int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value);
 
@@ -392,6 +402,14 @@ int d3d_op_layernorm(const float* x_dev, const float* gamma_dev, const float* be
  * force_generic != 0 selects the slow any-shape kernel (cross-check). */
 int d3d_op_attention(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
                      int32_t temporal, int32_t precision, int32_t force_generic, void* stream);
+/* The fused qkv GEMM + attention kernel of the BF16 mode alone: out = attention(bf16(A) bf16(Wqkv)^T + bias) with q / k / v rounded to
+ * bf16 (q third times dh^-1/2) and kept on chip -- bit for bit d3d_op_linear (D3D_PREC_BF16) followed by d3d_op_attention (D3D_PREC_BF16)
+ * on the same tensors.  A: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias: (3 D); out: (groups * N, D) fp32.  Group u holds the N
+ * rows (u / stride) * N * stride + u % stride + t * stride: spatial blocks groups = B * T, N = J, stride = 1, temporal = 0; temporal
+ * blocks groups = B * J, N = T, stride = J, temporal = 1.  Head width D / H == 64, D % 128 == 0, D >= 256, N <= 255 (temporal = 0:
+ * N <= 32), groups % stride == 0; anything else: D3D_EUNSUP / D3D_EINVAL. */
+int d3d_op_qkv_attn_bf16(const float* A_dev, const float* Wqkv_dev, const float* bias_dev, int32_t groups, int32_t N, int32_t stride,
+                         int32_t D, int32_t H, int32_t temporal, float* out_dev, void* stream);
 
 /* ---- machine probes (measurement support; no reference counterpart) ------------------------------------------------ */
 /* What THIS device sustains for the two resources that co-limit the F16X3 GEMM k-loop, measured over about ms_target
