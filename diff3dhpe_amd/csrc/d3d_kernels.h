@@ -25,7 +25,7 @@ inline hipError_t lds_optin(const void* fn, size_t bytes, std::atomic<unsigned l
 }
 // compute units of the current device; 0 on error
 inline int device_cu_count() {
-  static std::atomic<int> cache[64];
+  static std::atomic<int> cache[64];   // race-free: every thread computes the same value for a device
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   int n = cache[dev & 63].load(std::memory_order_acquire);
@@ -49,11 +49,15 @@ inline int resident_workgroups_per_cu(const void* fn, int block, size_t dyn_lds)
 // two-stream loop turns them off.  Values do not depend on it.
 // range_word: the F16X3 range-guard word (device memory, below) of the ENGINE whose call is being served -- the C ABI entry points of
 // an engine set it around their launches; launches outside an engine (the single-op hooks) write to a per-device sink nobody reads.
-struct LaunchCtx { bool tail_slices = true; unsigned* range_word = nullptr; };
+// deep_stages: the "deep_stages" option of that engine (-1 outside an engine or when the engine has no value of its own: the
+// process-wide default below).
+struct LaunchCtx { bool tail_slices = true; unsigned* range_word = nullptr; int deep_stages = -1; };
 extern thread_local LaunchCtx tl_launch_ctx;
-// Process-wide switch (engine option "deep_stages", default on): the one-tile-per-workgroup GEMM launches (batches of a few sequences)
-// stage three (256 x 128 tiles) / four (128 x 128) k-tiles deep instead of two (kernels_gemm_x3p.hip, NST).  Values do not depend on it.
+// Option "deep_stages" (default on): the one-tile-per-workgroup GEMM launches (batches of a few sequences) stage three (256 x 128 tiles) /
+// four (128 x 128) k-tiles deep instead of two (kernels_gemm_x3p.hip, NST).  Values do not depend on it.  Each engine carries its own
+// setting (LaunchCtx::deep_stages); the process-wide default (one atomic, the key with a NULL engine) serves launches outside an engine.
 void set_x3q_deep_stages(bool on);
+bool x3q_deep_stages_default();
 unsigned* range_sink_word();   // engine.hip: 4 bytes of device memory per device, allocated on first use (nullptr if that failed)
 inline unsigned* launch_range_word() { return tl_launch_ctx.range_word ? tl_launch_ctx.range_word : range_sink_word(); }
 

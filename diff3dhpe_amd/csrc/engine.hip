@@ -101,6 +101,9 @@ struct d3d_engine {
   // tiles runs as a split-K x split-N GEMM + an ordered reduce / post-norm row kernel (d3d_kernels.h fc2_splitk_choose).  Changes the
   // order of additions: results stay inside the parity gate but are no longer bit-identical to the default path's.
   bool opt_latency_mode = false;
+  // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
+  // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
+  int opt_deep_stages = -1;
   int fc2_split_last = 0;         // the S of the most recent forward (0: the whole-row fc2 ran): d3d_engine_get_info
   // BF16 mode: whether the most recent forward ran the fused qkv + attention kernel (kernels_qkv_attn_bf16.hip) in its spatial / temporal
   // blocks ("fused_spatial" / "fused_temporal" and the shape predicates): d3d_engine_get_info "bf16_fused_spatial_last" / "..temporal_last"
@@ -187,11 +190,16 @@ struct d3d_engine {
 
 namespace {
 
-// Launches issued while one of these is alive report to the engine's range-guard word (d3d_kernels.h).
+// Launches issued while one of these is alive report to the engine's range-guard word and stage their small GEMMs as the engine's
+// "deep_stages" says (d3d_kernels.h LaunchCtx: the calling thread's own context, so concurrent calls on distinct engines do not mix).
 struct RangeScope {
   unsigned* saved;
-  explicit RangeScope(const d3d_engine* e) : saved(tl_launch_ctx.range_word) { tl_launch_ctx.range_word = e->range_dev; }
-  ~RangeScope() { tl_launch_ctx.range_word = saved; }
+  int saved_deep;
+  explicit RangeScope(const d3d_engine* e) : saved(tl_launch_ctx.range_word), saved_deep(tl_launch_ctx.deep_stages) {
+    tl_launch_ctx.range_word = e->range_dev;
+    tl_launch_ctx.deep_stages = e->opt_deep_stages;
+  }
+  ~RangeScope() { tl_launch_ctx.range_word = saved; tl_launch_ctx.deep_stages = saved_deep; }
 };
 
 void add_slot(d3d_engine* e, const std::string& name, int64_t numel) {
@@ -330,9 +338,11 @@ Workspace carve(const d3d_engine* e, int B, void* base) {
   size_t oXI = take(M * e->cfg.in_chans), oNI = take(M * 3), oOB = take(M * 3);   // graph-mode staging copies
   // row statistics of the LN-folded GEMMs; whole 256-row tiles, the persistent walk stages a tile's block of them by LDS-DMA
   size_t oS1 = take(Mp * 2 * (size_t)((D + 63) / 64)), oS2 = take(Mp * 2 * (size_t)((D + 63) / 64));
-  w.X = b + oX; w.HN = b + oHN; w.QKV = b + oQKV; w.HID = b + oHID; w.Y0 = b + oY0; w.Y1 = b + oY1;
-  w.TEMB = b + oTE; w.TSCR = b + oTS; w.RED = b + oRED; w.TIMES = b + oTI;
-  w.XIN = b + oXI; w.NIN = b + oNI; w.OUTB = b + oOB; w.ST1 = b + oS1; w.ST2 = b + oS2;
+  if (b) {   // (d3d_workspace_bytes asks for the size alone: no arithmetic on a null base -- UBSan, experiments/asan_host.sh)
+    w.X = b + oX; w.HN = b + oHN; w.QKV = b + oQKV; w.HID = b + oHID; w.Y0 = b + oY0; w.Y1 = b + oY1;
+    w.TEMB = b + oTE; w.TSCR = b + oTS; w.RED = b + oRED; w.TIMES = b + oTI;
+    w.XIN = b + oXI; w.NIN = b + oNI; w.OUTB = b + oOB; w.ST1 = b + oS1; w.ST2 = b + oS2;
+  }
   w.total_bytes = off * sizeof(float);
   return w;
 }
@@ -817,7 +827,7 @@ static inline uint32_t range_bits_to_abi(unsigned w, bool weights_clamped) {
 
 // Range-guard sink of launches that belong to no engine (the single-op hooks): one word per device, written, never read.
 unsigned* d3d::range_sink_word() {
-  static std::atomic<unsigned*> words[64];
+  static std::atomic<unsigned*> words[64];   // race-free: the loser of the compare-exchange frees its own allocation and takes the winner's
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
   unsigned* w = words[dev & 63].load(std::memory_order_acquire);
@@ -833,7 +843,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 132; }   // 132: d3d_op_qkv_attn_bf16, "bf16_fused_*_last"
+int d3d_version(void) { return 133; }   // 133: "deep_stages" with an engine is that engine's own setting (and drops its graphs)
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1388,8 +1398,12 @@ int d3d_ddim_sample(d3d_engine* e, const float* x2d, const float* init_noise, co
 int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   if (!key) return fail(D3D_EINVAL, "null key");
   const std::string k(key);
-  if (k == "deep_stages") { set_x3q_deep_stages(value != 0); return D3D_OK; }      // 3 / 4 operand stages in the one-tile-per-workgroup GEMM launches
+  // 3 / 4 operand stages in the one-tile-per-workgroup GEMM launches: NULL engine = the process-wide default (the single-op hooks and
+  // every engine that has not been given a value of its own), an engine = that engine alone
+  if (k == "deep_stages" && !e) { set_x3q_deep_stages(value != 0); return D3D_OK; }
   if (!e) return fail(D3D_EINVAL, "null engine");
+  if (k == "deep_stages") e->opt_deep_stages = value != 0 ? 1 : 0;
+  else
   if (k == "fused_postnorm") e->opt_fused_postnorm = value != 0;
   else if (k == "fold_layernorm") e->opt_fold_layernorm = value != 0;
   else if (k == "fused_spatial") e->opt_fused_spatial = value != 0;
@@ -1464,6 +1478,7 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "streams") *value = e->opt_streams;
   else if (k == "device") *value = e->device;
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
+  else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->fc2_split_last;
   else if (k == "bf16_fused_spatial_last") *value = e->bf16_fused_sp_last;
   else if (k == "bf16_fused_temporal_last") *value = e->bf16_fused_tp_last;

@@ -792,8 +792,9 @@ __global__ __launch_bounds__(512) void k_linear_x3q_persist(const _Float16* __re
 }
 
 thread_local LaunchCtx tl_launch_ctx;
-static std::atomic<bool> g_x3q_deep{true};
-void set_x3q_deep_stages(bool on) { g_x3q_deep = on; }
+static std::atomic<bool> g_x3q_deep_default{true};   // the process-wide default only: an engine's own value travels in tl_launch_ctx
+void set_x3q_deep_stages(bool on) { g_x3q_deep_default = on; }
+bool x3q_deep_stages_default() { return g_x3q_deep_default.load(std::memory_order_relaxed); }
 
 // walk of `tiles` tiles over `grid` persistent workgroups
 static X3Walk x3q_walk(int tiles, int grid, bool four_way = true) {
@@ -1083,7 +1084,7 @@ static hipError_t launch_x3q_auto(const _Float16* ap, const _Float16* wp, const 
   // (<2,4,2>: eight waves of 32 x 64) still find a CU each, the launch is as long as ONE tile takes and that tile is shorter -- proj at
   // B = 1, T = 243: 26 -> 20.7 us per launch.  Beyond that (two such workgroups sharing a CU) the shape loses: fc1 at B = 1 28.7 -> 38.2 us
   // (NOTES round 6).  Values do not depend on the tile shape.
-  const bool deep = g_x3q_deep.load(std::memory_order_relaxed);
+  const bool deep = tl_launch_ctx.deep_stages < 0 ? x3q_deep_stages_default() : tl_launch_ctx.deep_stages != 0;
   if (x3q_small(M, N))
     return deep ? launch_x3q<2, 4, 2, 4>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp)
                 : launch_x3q<2, 4, 2>(ap, wp, bias, R, C, ch, cl, M, N, K, epi, outsplit, qcols, s, fold, w_exp);

@@ -92,17 +92,26 @@ class GaussianDiffusion(nn.Module):
 
     # ------------------------------------------------------------------ engine plumbing
     def _engine(self, device: torch.device, fallback: bool = False):
-        eng = self.model.engine_for(device, fallback)
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        sig = (id(eng), (self.model._engine_sig_fb if fallback else self.model._engine_sig).get(idx),
-               self.sampling_timesteps, float(self.ddim_sampling_eta), bool(self.clip_denoised),
-               self.alphas_cumprod.data_ptr(), self.alphas_cumprod._version)
-        key = id(eng)
-        if self._sched_sig.get(key) != sig or eng.sampling_timesteps is None:
-            eng.set_schedule(self.alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.sampling_timesteps,
-                             self.ddim_sampling_eta, self.clip_denoised, sqrt_alphas_cumprod=self.sqrt_alphas_cumprod)
-            self._sched_sig[key] = sig
+        return self._scheduled(self.model.engine_for(device, fallback))
+
+    def _scheduled(self, eng):
+        """`eng` with this object's schedule set (a no-op when it already is).  Engines are shared between the threads that drive a
+        model: check and set_schedule() are one step under the engine's lock, and a call that depends on the schedule runs this again
+        inside its own hold of the lock (`_run`), so that a reload of the weights by another thread -- which clears the engine's
+        schedule -- cannot come between the check and the launch."""
+        with eng.lock:
+            sig = (id(eng), self.sampling_timesteps, float(self.ddim_sampling_eta), bool(self.clip_denoised),
+                   self.alphas_cumprod.data_ptr(), self.alphas_cumprod._version)
+            key = id(eng)
+            if self._sched_sig.get(key) != sig or eng.sampling_timesteps is None:      # (load_weights() resets sampling_timesteps)
+                eng.set_schedule(self.alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.sampling_timesteps,
+                                 self.ddim_sampling_eta, self.clip_denoised, sqrt_alphas_cumprod=self.sqrt_alphas_cumprod)
+                self._sched_sig[key] = sig
         return eng
+
+    def _run(self, dev, fn, what: str):
+        """fn(engine) as one guarded call of the model (nets._guarded: engine lock held from the launch to the posted ticket)."""
+        return self.model._guarded(lambda fb: self._engine(dev, fb), lambda eng: fn(self._scheduled(eng)), what)
 
     def ddim_times(self) -> List[int]:
         """Reversed integer schedule (DIFF:270-272), from the library's bit-exact host routine."""
@@ -136,16 +145,14 @@ class GaussianDiffusion(nn.Module):
     @torch.no_grad()
     def ddim_sample_loop(self, x_in, target_shape, init_noise=None, step_noise=None):
         dev, init_noise, step_noise = self._draw(x_in, target_shape, init_noise, step_noise)
-        y0 = self.model._guarded(lambda fb: self._engine(dev, fb), lambda eng: eng.ddim_sample(x_in, init_noise, step_noise),
-                                 "ddim_sample_loop")
+        y0 = self._run(dev, lambda eng: eng.ddim_sample(x_in, init_noise, step_noise), "ddim_sample_loop")
         return y0.to(x_in.device)
 
     @torch.no_grad()
     def ddim_sample_loop_ouput_reverse_diffusion(self, x_in, target_shape, init_noise=None, step_noise=None):
         dev, init_noise, step_noise = self._draw(x_in, target_shape, init_noise, step_noise)
-        y0, rev, x0s = self.model._guarded(lambda fb: self._engine(dev, fb),
-                                           lambda eng: eng.ddim_sample(x_in, init_noise, step_noise, trajectory=True),
-                                           "ddim_sample_loop_ouput_reverse_diffusion")
+        y0, rev, x0s = self._run(dev, lambda eng: eng.ddim_sample(x_in, init_noise, step_noise, trajectory=True),
+                                 "ddim_sample_loop_ouput_reverse_diffusion")
         if self.seq2frame:  # DIFF-S2F:319 records the initial noise as trajectory entry 0
             rev = torch.cat([init_noise.to(rev.device).unsqueeze(-1), rev], dim=-1)
         return y0.to(x_in.device), rev.to(x_in.device), x0s.to(x_in.device)
@@ -161,7 +168,9 @@ class GaussianDiffusion(nn.Module):
         if noise is None:
             noise = torch.randn_like(x_start)
         dev = self.model._compute_device(x_start, self.betas)
-        return self._engine(dev).q_sample(x_start, t, noise).to(x_start.device)
+        eng = self._engine(dev)
+        with eng.lock:      # (the schedule tables q_sample gathers from are this object's)
+            return self._scheduled(eng).q_sample(x_start, t, noise).to(x_start.device)
 
     @torch.no_grad()
     def get_noisy_pose(self, x_start, num_sample, noise=None):
@@ -198,7 +207,7 @@ class GaussianDiffusion(nn.Module):
             model_out = eng.denoise(pose_2d, x_noisy, t)                                 # y broadcast over T for seq2frame
             # the variable loss weight 1 + k_t, its clamp and the loss itself (DIFF:411-418) are one engine kernel (d3d_weighted_loss)
             return eng.weighted_loss(model_out, x_start, t, self.loss_type, self.clipLoss, check_t=False)
-        return self.model._guarded(lambda fb: self._engine(dev, fb), run, "p_losses").to(x_start.device)
+        return self._run(dev, run, "p_losses").to(x_start.device)
 
     # ------------------------------------------------------------------ forward (DIFF:421-449)
     def forward(self, clean_3d_pose, noisy_2d_pose, noise=None, output_reverse_diffusion_3d=False, output_loss=True,

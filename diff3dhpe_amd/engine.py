@@ -3,7 +3,9 @@ the current HIP stream and host<->device copies.  All arithmetic happens inside 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
+import threading
 from typing import Dict, Mapping, Optional
 
 import numpy as np
@@ -21,8 +23,24 @@ def _f32c(t: torch.Tensor, device) -> torch.Tensor:
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _locked(method):
+    """The method holds the engine's lock for the whole call (Engine.lock)."""
+    @functools.wraps(method)
+    def call(self, *a, **k):
+        with self.lock:
+            return method(self, *a, **k)
+    return call
+
+
 class Engine:
+    """One engine is driven by one host thread at a time (include/d3d.h "Threads"): it has ONE workspace, ONE ticket ring and one set of
+    streams.  `lock` (a threading.RLock) is how this layer keeps that: every method that launches work for the engine or changes its
+    state holds it for the whole call, so calls from several threads serialise instead of overwriting each other's activations.  A
+    caller that needs several methods to stay together -- a launch and the range ticket that is to cover it (nets._guarded) -- takes
+    the lock around them itself; it is re-entrant.  Distinct engines run concurrently."""
+
     def __init__(self, cfg: DenoiserConfig, precision: str = "fp32", device=None):
+        self.lock = threading.RLock()
         if not torch.cuda.is_available():
             raise _lib.D3DError("diff3dhpe_amd needs a HIP device: the engine has no CPU path")
         self.cfg = cfg
@@ -35,6 +53,8 @@ class Engine:
         self._h = h
         self._ws: Optional[torch.Tensor] = None
         self._ws_B = 0
+        self._last_stream = None
+        self._ws_stream = None
         self.sampling_timesteps = None
         self.num_timesteps = None
         self.weights_version = None
@@ -49,6 +69,7 @@ class Engine:
             self._h = None
 
     # ---------------------------------------------------------------- weights / schedule
+    @_locked
     def expected_weights(self):
         L = _lib.lib()
         out = []
@@ -58,6 +79,7 @@ class Engine:
             out.append((name.value.decode(), n.value))
         return out
 
+    @_locked
     def load_weights(self, sd: Mapping[str, object]) -> None:
         """sd: denoiser tensors keyed by reference state-dict names WITHOUT the 'model.' prefix."""
         L = _lib.lib()
@@ -77,16 +99,17 @@ class Engine:
             _lib.check(L.d3d_engine_commit_weights(self._h))
         self.sampling_timesteps = None
 
+    @_locked
     def set_schedule(self, alphas_cumprod: torch.Tensor, sqrt_one_minus_alphas_cumprod: torch.Tensor,
                      sampling_timesteps: int, eta: float, clip_denoised: bool,
                      sqrt_alphas_cumprod: Optional[torch.Tensor] = None) -> None:
         ac = np.ascontiguousarray(alphas_cumprod.detach().cpu().numpy(), dtype=np.float32)
         so = np.ascontiguousarray(sqrt_one_minus_alphas_cumprod.detach().cpu().numpy(), dtype=np.float32)
         with torch.cuda.device(self.device):
-            st = torch.cuda.current_stream(self.device)
+            # (through _stream(): the tables are rewritten behind the previous call's kernels, whichever stream those ran on)
             _lib.check(_lib.lib().d3d_engine_set_schedule(self._h, ac.size, ac.ctypes.data_as(C.c_void_p),
                                                          so.ctypes.data_as(C.c_void_p), int(sampling_timesteps),
-                                                         float(eta), int(bool(clip_denoised)), C.c_void_p(st.cuda_stream)))
+                                                         float(eta), int(bool(clip_denoised)), self._stream()))
             if sqrt_alphas_cumprod is not None:
                 sa = np.ascontiguousarray(sqrt_alphas_cumprod.detach().cpu().numpy(), dtype=np.float32)
                 _lib.check(_lib.lib().d3d_engine_set_sqrt_alphas_cumprod(self._h, sa.ctypes.data_as(C.c_void_p), sa.size))
@@ -101,19 +124,37 @@ class Engine:
             self._ws = None
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             self._ws_B = B
+            self._ws_stream = torch.cuda.current_stream(self.device)      # (the allocator hands the block back to THIS stream's pool)
         return self._ws
 
+    @_locked
     def release_workspace(self) -> None:
         """Drop the cached workspace; the next call allocates one for its own batch size."""
         self._ws = None
         self._ws_B = 0
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        """The caller's current stream.  The engine's lock orders HOST calls; its one workspace and its tables also need the DEVICE work
+        of consecutive calls ordered.  On one stream it is (every thread's default, what nn.DataParallel's threads use); a call that
+        arrives on another stream than the previous one (a thread pool with a stream per worker) first makes its stream wait for that
+        one, and a workspace used on another stream than the one it was allocated on is recorded there, so that the allocator does
+        not reuse it early once it is released.  Callers that stay on one stream pay one comparison.  Not ordered: a stream change
+        INSIDE a stream capture (torch.cuda.graph) -- a wait on a stream outside the capture would invalidate it, so none is made
+        there and the caller orders the streams itself."""
+        st = torch.cuda.current_stream(self.device)
+        last = self._last_stream
+        if last is not None and last != st and not torch.cuda.is_current_stream_capturing():
+            st.wait_stream(last)
+        ws = self._ws
+        if ws is not None and st != self._ws_stream:
+            ws.record_stream(st)
+        self._last_stream = st
+        return C.c_void_p(st.cuda_stream)
 
     def _out_frames(self) -> int:
         return 1 if self.cfg.seq2frame else self.cfg.num_frame
 
+    @_locked
     def denoise(self, x2d: torch.Tensor, y: torch.Tensor, time: Optional[torch.Tensor]) -> torch.Tensor:
         """forward_denoise on cat([x2d, y], -1): x2d (B,T,J,in), y (B,T,J,3) or (B,1,J,3) (broadcast over T), time (B,) or (1,)."""
         cfg = self.cfg
@@ -134,6 +175,7 @@ class Engine:
                                               ws.numel(), self._stream()))
         return out
 
+    @_locked
     def ddim_sample(self, x2d: torch.Tensor, init_noise: torch.Tensor, step_noise: Optional[torch.Tensor] = None,
                     trajectory: bool = False):
         """The whole S-step DDIM loop. Returns y0, or (y0, x_reverse_diffusion, x_start_est) with trajectory=True."""
@@ -162,14 +204,17 @@ class Engine:
         return (out, rev, x0s) if trajectory else out
 
     # ---------------------------------------------------------------- profiling (HIP events inside the library)
+    @_locked
     def set_graph_mode(self, on: bool) -> None:
         """Replay the whole DDIM loop as one hipGraph per (B, workspace) (eta == 0, no trajectory capture)."""
         _lib.check(_lib.lib().d3d_engine_set_graph_mode(self._h, int(on)))
 
+    @_locked
     def set_option(self, key: str, value: int) -> None:
         """Explicit engine switch (include/d3d.h: "fused_postnorm", "fold_layernorm", "streams", "latency_mode"); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
+    @_locked
     def info(self, key: str) -> int:
         """Read-only engine facts (include/d3d.h d3d_engine_get_info): "graphs_cached", "graphs_captured", "streams", "device",
         "latency_mode", "fc2_split_last", "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the most recent forward of a
@@ -178,6 +223,7 @@ class Engine:
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
 
+    @_locked
     def range_flags(self, clear: bool = True) -> int:
         """F16X3 range guard (include/d3d.h): _lib.RANGE_ACT | RANGE_WEIGHT | RANGE_STATS bits; synchronises the current stream.
         The flags belong to THIS engine (its own word of device memory), cleared on read."""
@@ -204,6 +250,7 @@ class Engine:
             raise _lib.D3DError("F16X3 operand range exceeded by " + self.describe_range_flags(f) +
                                 ": results are not fp32-accurate for this checkpoint/input -- use precision='fp32'")
 
+    @_locked
     def post_range(self) -> int:
         """Enqueue a snapshot (and reset) of this engine's range word behind everything on the current stream; returns its ticket
         (include/d3d.h d3d_engine_range_post).  No synchronisation."""
@@ -212,6 +259,7 @@ class Engine:
             _lib.check(_lib.lib().d3d_engine_range_post(self._h, self._stream(), C.byref(t)))
         return int(t.value)
 
+    @_locked
     def take_range(self, ticket: int, block: bool = True) -> Optional[int]:
         """Flags of a ticket; block=True waits for THAT snapshot's event only, block=False returns None while it has not run."""
         f, ready = C.c_uint32(0), C.c_int32(0)
@@ -219,12 +267,14 @@ class Engine:
             _lib.check(_lib.lib().d3d_engine_range_take(self._h, int(ticket), int(bool(block)), C.byref(f), C.byref(ready)))
         return int(f.value) if ready.value else None
 
+    @_locked
     def set_trace(self, capacity: int, views: int = 1) -> None:
         """Debug trace: checksum every buffer the block-flow kernels write (0 turns it off); views: see include/d3d.h."""
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().d3d_engine_set_trace(self._h, int(capacity), int(views)))
         self._trace_cap = int(capacity)
 
+    @_locked
     def trace_read(self):
         """[(tag, checksum)] in launch order since the last read; tag fields: see include/d3d.h."""
         cap = getattr(self, "_trace_cap", 0)
@@ -233,12 +283,15 @@ class Engine:
             _lib.check(_lib.lib().d3d_engine_trace_read(self._h, sums, tags, cap, C.byref(n), self._stream()))
         return [(int(tags[i]), int(sums[i])) for i in range(n.value)]
 
+    @_locked
     def set_profiling(self, on: bool) -> None:
         _lib.check(_lib.lib().d3d_engine_set_profiling(self._h, int(on)))
 
+    @_locked
     def profile_reset(self) -> None:
         _lib.check(_lib.lib().d3d_engine_profile_reset(self._h))
 
+    @_locked
     def profile_read(self) -> Dict[str, Dict[str, float]]:
         """Per kernel class: total event-timed ms, launches, algorithmic flops and bytes of the launches timed."""
         L = _lib.lib()
@@ -249,6 +302,7 @@ class Engine:
             out[L.d3d_kernel_class_name(c).decode()] = {"ms": ms.value, "launches": n.value, "flops": fl.value, "bytes": by.value}
         return out
 
+    @_locked
     def head(self, X: torch.Tensor) -> torch.Tensor:
         """Regression head (LayerNorm eps 1e-5 + Linear D -> 3, S2S:217-220) on (rows, D) rows: (rows, 3), raw."""
         X = _f32c(X, self.device).reshape(-1, self.cfg.embed_dim)
@@ -257,6 +311,7 @@ class Engine:
             _lib.check(_lib.lib().d3d_op_head(self._h, _ptr(X), _ptr(out), X.shape[0], self._stream()))
         return out
 
+    @_locked
     def time_embedding(self, times: torch.Tensor) -> torch.Tensor:
         """Per-block time vectors for the given timesteps: (n, 2*depth, D), execution order STE0, TTE0, STE1, ..."""
         cfg = self.cfg
@@ -284,6 +339,7 @@ class Engine:
                 raise IndexError(f"timestep index out of range: [{lo}, {hi}] outside [0, {n})")   # still bound-check every gather)
         return t.to(device=self.device, dtype=torch.int32).contiguous()
 
+    @_locked
     def q_sample(self, x_start: torch.Tensor, t: torch.Tensor, noise: torch.Tensor, check_t: bool = True) -> torch.Tensor:
         B = x_start.shape[0]
         xs, nz = _f32c(x_start, self.device), _f32c(noise, self.device)
@@ -295,6 +351,7 @@ class Engine:
         return out
 
 
+    @_locked
     def weighted_loss(self, model_out: torch.Tensor, target: torch.Tensor, t: torch.Tensor, loss_type: str, clip_loss: bool,
                       check_t: bool = True) -> torch.Tensor:
         """p_losses tail (DIFF:411-418): loss_fn(model_out, target, 'none') * min(1 + ac[t] / sqrt(1 - ac)[t], 3 if clip_loss)."""

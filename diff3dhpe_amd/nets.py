@@ -8,7 +8,9 @@ the HIP engine (libd3d_hip.so) and fails loudly when there is no HIP device.
 """
 from __future__ import annotations
 
+import copy
 import os
+import threading
 import warnings
 from contextlib import contextmanager
 from typing import Dict, Optional
@@ -54,6 +56,56 @@ class _BlockParams(_Holder):
         self.mlp = _MlpParams(dim, hidden)
 
 
+class _Guard(dict):
+    """Guard state of one model, ONE object shared (by reference) with its DataParallel replicas, which run in one host thread each.
+
+    Model-wide fields are the dict's items -- "fallback" (weights signature for which the guard fired: "auto" then runs the fp32 engine
+    directly; shared, so a decision made on one replica holds for all), "warned", "warned_recompute", "warned_multi_device" and the
+    counters "posted" / "flagged" / "reruns" / "recomputes".  Every read-modify-write of them holds `lock`.
+    Per-caller fields live in a threading.local (`mine`): "deferred" / "deferred_box" (the open deferred_range_checks() block of THIS
+    thread, None outside one) and "lazy" (tickets this thread posted on an engine that is read without waiting).  A block opened in one
+    thread therefore collects that thread's tickets only; a guarded call made meanwhile by another thread is read at once.
+
+    Lock order, the same everywhere: `engines_lock` (engine_for(): creating an engine, (re)loading weights) -> Engine.lock -> `lock`.
+    `lock` is a leaf: nothing else is taken while it is held, and engine_for() is never entered with an engine's lock held."""
+
+    def __init__(self):
+        super().__init__(fallback=None, warned=False, posted=0, flagged=0, reruns=0)
+        self.lock = threading.RLock()
+        self.engines_lock = threading.RLock()
+        self._tls = threading.local()
+
+    @property
+    def mine(self):
+        t = self._tls
+        if not hasattr(t, "lazy"):
+            t.deferred, t.deferred_box, t.lazy = None, None, []
+        return t
+
+    def bump(self, key: str) -> None:
+        with self.lock:
+            self[key] = self.get(key, 0) + 1
+
+    def __deepcopy__(self, memo):       # (locks and thread-locals are not copied: a copied model starts with its own)
+        g = _Guard()
+        g.update(copy.deepcopy(dict(self), memo))
+        return g
+
+    def __reduce__(self):
+        return (_guard_from_items, (dict(self),))
+
+
+def _guard_from_items(items):
+    g = _Guard()
+    g.update(items)
+    return g
+
+
+_MULTI_DEVICE_WARNING = ("diff3dhpe_amd: several devices in one process: host-side concurrency is tested on one device, the multi-device "
+                         "run itself is unmeasured on hardware (nn.DataParallel replica asked for cuda:{idx} beside cuda:{have}; one process "
+                         "per GPU is the measured form -- allow_multi_device = True / D3D_ALLOW_MULTI_DEVICE=1 silences this)")
+
+
 class _MixSTEDenoiser(nn.Module):
     _seq2frame = False
     # engine arithmetic mode; override per instance (or on the class) at any time:
@@ -72,10 +124,12 @@ class _MixSTEDenoiser(nn.Module):
     # default path.  Set on the class or an instance at any time; fp32 / bf16 engines (and the "auto" fallback) ignore it.
     latency_mode = False
     range_check = os.environ.get("D3D_CHECK_RANGE", "1").strip().lower() not in ("0", "false", "no", "off")
-    # One process per GPU is the supported multi-GPU form (torchrun; parallel.py).  nn.DataParallel over SEVERAL devices in one
-    # process (RUN:216-218 with --gpu_id 0,1,...) would need one engine per device driven from DataParallel's worker threads:
-    # that path has never run on hardware, so it fails loudly instead of being trusted.  Flip this (or export D3D_ALLOW_MULTI_DEVICE=1
-    # for the unchanged runner with --gpu_id 0,1,...) to try it anyway.
+    # One process per GPU is the measured multi-GPU form (torchrun; parallel.py).  nn.DataParallel over SEVERAL devices in one
+    # process (RUN:216-218 with --gpu_id 0,1,...) drives one engine per device from DataParallel's worker threads: everything that
+    # needs on the host side (engine locks, per-thread guard state) is tested on one device, the multi-device run itself is
+    # unmeasured on hardware -- a replica that asks for a second device gets a one-time RuntimeWarning saying so; a model that is
+    # NOT a replica and was not moved still fails loudly.  Flip this (or export D3D_ALLOW_MULTI_DEVICE=1 for the unchanged runner
+    # with --gpu_id 0,1,...) to allow both silently.
     allow_multi_device = os.environ.get("D3D_ALLOW_MULTI_DEVICE", "0").strip().lower() in ("1", "true", "yes", "on")
 
     def __init__(self, num_frame=9, num_joints=17, in_chans=2, embed_dim=32, depth=4, num_heads=8, mlp_ratio=2.,
@@ -125,9 +179,9 @@ class _MixSTEDenoiser(nn.Module):
         self._engine_sig: Dict[int, object] = {}
         self._engines_fb: Dict[int, Engine] = {}       # "auto": the exact-fp32 engines the guard falls back to, made on first need
         self._engine_sig_fb: Dict[int, object] = {}
-        # guard state, one dict shared (by reference) with DataParallel replicas: "fallback" = weights signature for which the guard
-        # fired ("auto" then runs the fp32 engine directly), "warned", "deferred" = open list of Pending checks (evaluate.py), "stats"
-        self._guard = {"fallback": None, "warned": False, "deferred": None, "posted": 0, "flagged": 0, "reruns": 0}
+        # guard state, one object shared (by reference) with DataParallel replicas (_Guard: model-wide fields under its lock, the
+        # deferred / lazy ticket lists per calling thread)
+        self._guard = _Guard()
         self._src_sig = None
 
     # ------------------------------------------------------------------ engine management
@@ -170,10 +224,16 @@ class _MixSTEDenoiser(nn.Module):
         return "f16x3" if self.precision == "auto" else self.precision
 
     def engine_for(self, device: torch.device, fallback: bool = False) -> Engine:
-        """The engine of this model on `device`; fallback=True: the exact-fp32 engine precision="auto" repeats a flagged call on."""
+        """The engine of this model on `device`; fallback=True: the exact-fp32 engine precision="auto" repeats a flagged call on.
+        Holds the guard's engines lock throughout: threads (replicas) that ask for one device's engine at the same time get ONE Engine
+        and one upload of the weights.  Never call it with an engine's lock held (_Guard: lock order)."""
         if device.type != "cuda":
             raise _lib.D3DError("engine_for() needs a HIP device")
         idx = device.index if device.index is not None else torch.cuda.current_device()
+        with self._guard.engines_lock:
+            return self._engine_for_locked(idx, fallback)
+
+    def _engine_for_locked(self, idx: int, fallback: bool) -> Engine:
         if not self.allow_multi_device and self._engines and idx not in self._engines:
             p = self._tensor("fusion_layer.weight")
             moved = self._src_sig is None and p.is_cuda and p.device.index == idx
@@ -182,11 +242,16 @@ class _MixSTEDenoiser(nn.Module):
                 self._engine_sig.clear()
                 self._engines_fb.clear()
                 self._engine_sig_fb.clear()
+            elif self._src_sig is not None:   # a DataParallel replica (RUN:216-218): proceed, and say once what is and is not known
+                with self._guard.lock:
+                    first, self._guard["warned_multi_device"] = not self._guard.get("warned_multi_device"), True
+                if first:
+                    warnings.warn(_MULTI_DEVICE_WARNING.format(idx=idx, have=next(iter(self._engines))), RuntimeWarning, stacklevel=4)
             else:
                 raise _lib.D3DError(
                     f"this model already runs on cuda:{next(iter(self._engines))} and is now asked to run on cuda:{idx}: diff3dhpe_amd "
                     "supports ONE device per process (launch one process per GPU: `python bench.py --gpus N`, torchrun --nproc-per-node "
-                    "N, or pass one id to --gpu_id); nn.DataParallel over several devices in one process is untested -- set "
+                    "N, or pass one id to --gpu_id); only nn.DataParallel replicas may use several devices in one process -- set "
                     "allow_multi_device = True on the model class (or D3D_ALLOW_MULTI_DEVICE=1) to try it (moving the whole module "
                     "with .to() is fine)")
         engines, sigs = (self._engines_fb, self._engine_sig_fb) if fallback else (self._engines, self._engine_sig)
@@ -200,9 +265,10 @@ class _MixSTEDenoiser(nn.Module):
             engines[idx] = eng
             sigs[idx] = None
         if not fallback and want == "f16x3" and getattr(eng, "_latency_mode", False) != bool(self.latency_mode):
-            eng.set_option("latency_mode", int(bool(self.latency_mode)))   # (drops the engine's captured graphs)
-            eng._latency_mode = bool(self.latency_mode)
-            eng.release_workspace()
+            with eng.lock:
+                eng.set_option("latency_mode", int(bool(self.latency_mode)))   # (drops the engine's captured graphs)
+                eng._latency_mode = bool(self.latency_mode)
+                eng.release_workspace()
         sig = self._src_sig if self._src_sig is not None else self._param_signature()
         if sigs.get(idx) != sig:
             eng.load_weights(self._named_tensors())
@@ -212,52 +278,57 @@ class _MixSTEDenoiser(nn.Module):
     # ------------------------------------------------------------------ the range guard, read by default
     def reset_precision_fallback(self) -> None:
         """precision="auto": go back to the F16X3 engine after the guard moved this model to the fp32 engine."""
-        self._guard["fallback"] = None
+        with self._guard.lock:
+            self._guard["fallback"] = None
 
     def _weights_sig(self):
         return self._src_sig if self._src_sig is not None else self._param_signature()
 
     def _on_fallback(self) -> bool:
-        return self.precision == "auto" and self._guard["fallback"] is not None and self._guard["fallback"] == self._weights_sig()
+        fb = self._guard["fallback"]
+        return self.precision == "auto" and fb is not None and fb == self._weights_sig()
 
     def _flagged(self, flags: int, what: str) -> bool:
         """A range flag was read for a call of this model: "auto" moves the model to the fp32 engine (True: the caller repeats the
-        call); every other precision raises.  False: nothing to repeat (only the head kernel's self-repaired recompute bit)."""
-        if flags & _lib.RANGE_RECOMPUTE:        # repaired inside the kernel: a fault indicator, not a precision matter -- say so, once
-            self._guard["recomputes"] = self._guard.get("recomputes", 0) + 1
-            if not self._guard.get("warned_recompute"):
-                self._guard["warned_recompute"] = True
-                warnings.warn(f"diff3dhpe_amd: {what}: " + Engine.describe_range_flags(_lib.RANGE_RECOMPUTE), RuntimeWarning, stacklevel=4)
-            flags &= ~_lib.RANGE_RECOMPUTE
-            if not flags:
-                return False
-        if flags & _lib.RANGE_INDEX:            # not a precision matter either: no engine computes a row whose timestep is outside the tables
-            raise IndexError(f"{what}: " + Engine.describe_range_flags(_lib.RANGE_INDEX) + " (the row's output is NaN; DIFF:21-24)")
-        self._guard["flagged"] += 1
-        msg = Engine.describe_range_flags(flags)
-        if self.precision != "auto":
-            raise _lib.D3DError(f"{what}: F16X3 operand range exceeded by {msg}: the result is not fp32-accurate for this checkpoint / "
-                                "input -- use precision='auto' (repeats such calls on the exact-fp32 engine) or precision='fp32'")
-        self._guard["fallback"] = self._weights_sig()
-        if not self._guard["warned"]:
-            self._guard["warned"] = True
-            warnings.warn(f"diff3dhpe_amd: {what}: the F16X3 range guard fired ({msg}); precision='auto' repeats the call on the "
-                          "exact-fp32 engine and keeps this model there until its weights change (reset_precision_fallback() to retry)",
-                          RuntimeWarning, stacklevel=4)
-        return True
+        call); every other precision raises.  False: nothing to repeat (only the head kernel's self-repaired recompute bit).
+        Holds the guard lock: of several threads that read a flag at the same time, one warns."""
+        g = self._guard
+        with g.lock:
+            if flags & _lib.RANGE_RECOMPUTE:        # repaired inside the kernel: a fault indicator, not a precision matter -- say so, once
+                g["recomputes"] = g.get("recomputes", 0) + 1
+                if not g.get("warned_recompute"):
+                    g["warned_recompute"] = True
+                    warnings.warn(f"diff3dhpe_amd: {what}: " + Engine.describe_range_flags(_lib.RANGE_RECOMPUTE), RuntimeWarning, stacklevel=4)
+                flags &= ~_lib.RANGE_RECOMPUTE
+                if not flags:
+                    return False
+            if flags & _lib.RANGE_INDEX:            # not a precision matter either: no engine computes a row whose timestep is outside the tables
+                raise IndexError(f"{what}: " + Engine.describe_range_flags(_lib.RANGE_INDEX) + " (the row's output is NaN; DIFF:21-24)")
+            g["flagged"] += 1
+            msg = Engine.describe_range_flags(flags)
+            if self.precision != "auto":
+                raise _lib.D3DError(f"{what}: F16X3 operand range exceeded by {msg}: the result is not fp32-accurate for this checkpoint / "
+                                    "input -- use precision='auto' (repeats such calls on the exact-fp32 engine) or precision='fp32'")
+            g["fallback"] = self._weights_sig()
+            if not g["warned"]:
+                g["warned"] = True
+                warnings.warn(f"diff3dhpe_amd: {what}: the F16X3 range guard fired ({msg}); precision='auto' repeats the call on the "
+                              "exact-fp32 engine and keeps this model there until its weights change (reset_precision_fallback() to retry)",
+                              RuntimeWarning, stacklevel=4)
+            return True
 
     # tickets of one engine that a deferred block may leave open: the engine keeps 256 slots (d3d_engine_range_post recycles the oldest)
     _MAX_OPEN_TICKETS = 192
 
-    def _lazy_read(self, eng, what: str) -> None:
+    def _lazy_read(self, eng, what: str, ticket: int) -> None:
         """Guard read for an engine on which no precision flag can rise (fp32, bf16, the "auto" fallback): only the fault indicators
         travel in its word -- the head fence's D3D_RANGE_RECOMPUTE and the bound check of the timestep gathers, D3D_RANGE_INDEX.  The
-        ticket is posted and the OPEN ones are polled without waiting, so the host does not synchronise with every call; a
-        raised bit is therefore reported at the next guarded call at the latest (the public q_sample / p_losses entry points check
-        their timesteps on the host beforehand: engine.py _timesteps)."""
-        lazy = self._guard.setdefault("lazy", [])
-        lazy.append((eng, eng.post_range(), what))
-        self._guard["posted"] += 1
+        ticket was posted by _guarded, under the engine lock that covered the call; here the calling thread's OPEN ones are polled without waiting, so the host does not synchronise with every call; a raised bit is therefore
+        reported at that thread's next guarded call at the latest (the public q_sample / p_losses entry points check their timesteps on
+        the host beforehand: engine.py _timesteps).  Engine lock (inside take_range) first, the guard's lock after it."""
+        mine = self._guard.mine
+        lazy = mine.lazy
+        lazy.append((eng, ticket, what))
         flags, first = 0, None
         keep = []
         for i, (e, t, w) in enumerate(lazy):
@@ -269,14 +340,16 @@ class _MixSTEDenoiser(nn.Module):
             elif f:
                 flags |= f
                 first = first or w
-        self._guard["lazy"] = keep
+        mine.lazy = keep
         if flags & (_lib.RANGE_RECOMPUTE | _lib.RANGE_INDEX):
             self._flagged(flags & (_lib.RANGE_RECOMPUTE | _lib.RANGE_INDEX), first)      # warns once / raises IndexError
 
     def flush_range_checks(self) -> None:
-        """Read (waiting on each one's own event) every guard ticket still open from calls on an engine that is read without waiting
-        (fp32, bf16, the "auto" fallback): a fault bit raised by an earlier call is reported now instead of at the next call."""
-        lazy, self._guard["lazy"] = self._guard.get("lazy", []), []
+        """Read (waiting on each one's own event) every guard ticket the CALLING THREAD still has open from calls on an engine that is
+        read without waiting (fp32, bf16, the "auto" fallback): a fault bit raised by an earlier call is reported now instead of at
+        the next call."""
+        mine = self._guard.mine
+        lazy, mine.lazy = mine.lazy, []
         flags, first = 0, None
         for e, t, w in lazy:
             f = e.take_range(t, block=True)
@@ -288,58 +361,63 @@ class _MixSTEDenoiser(nn.Module):
 
     def _guarded(self, get_engine, fn, what: str):
         """Run fn(engine) on the model's engine and READ the F16X3 range guard for it (no device-wide synchronisation: one one-lane
-        kernel behind the call, one wait on ITS event).  get_engine(fallback) -> a ready engine.  With an open deferred list
-        (deferred_range_checks(): evaluate() resolves it at its own per-batch synchronisation) the read is postponed.  Engines on which
-        no precision flag can rise (fp32, bf16, the fallback) are read without waiting (_lazy_read)."""
-        fb_sig = self._guard["fallback"]
-        if fb_sig is not None and fb_sig != self._weights_sig():      # new weights: back to the F16X3 engine, and a new fallback warns again
-            self._guard["fallback"] = None
-            self._guard["warned"] = False
-        if self._on_fallback():
-            eng = get_engine(True)
+        kernel behind the call, one wait on ITS event).  get_engine(fallback) -> a ready engine.  With a deferred list open IN THE
+        CALLING THREAD (deferred_range_checks(): evaluate() resolves it at its own per-batch synchronisation) the read is postponed.
+        Engines on which no precision flag can rise (fp32, bf16, the fallback) are read without waiting (_lazy_read).
+        Threads: the engine's lock is held from before the launch until the call's range ticket is POSTED -- no other thread's work
+        comes between, the ticket belongs to this call -- and released before the ticket is waited on.  get_engine() runs before it
+        (engine_for() takes the guard's engines lock), the guard's own lock only after it."""
+        g = self._guard
+        with g.lock:
+            fb_sig = g["fallback"]
+            if fb_sig is not None and fb_sig != self._weights_sig():      # new weights: back to the F16X3 engine, and a new fallback warns again
+                g["fallback"] = None
+                g["warned"] = False
+            on_fb = self._on_fallback()
+        eng = get_engine(on_fb)
+        with eng.lock:
             res = fn(eng)
-            if self.range_check:
-                self._lazy_read(eng, what)
+            if not self.range_check:
+                return res
+            ticket = eng.post_range()
+        g.bump("posted")
+        if on_fb or eng.precision != "f16x3":
+            self._lazy_read(eng, what, ticket)
             return res
-        eng = get_engine(False)
-        res = fn(eng)
-        if not self.range_check:
-            return res
-        if eng.precision != "f16x3":
-            self._lazy_read(eng, what)
-            return res
-        ticket = eng.post_range()
-        self._guard["posted"] += 1
-        pend = self._guard["deferred"]
+        mine = g.mine
+        pend = mine.deferred
         if pend is not None:
             pend.append((eng, ticket, what))
             if len(pend) >= self._MAX_OPEN_TICKETS:      # the engine's ticket ring is finite: fold the oldest half into the box now
-                self._guard["deferred_box"].fold(len(pend) // 2)
+                mine.deferred_box.fold(len(pend) // 2)
             return res
         flags = eng.take_range(ticket, block=True)
         if not flags:
             return res
         if not self._flagged(flags, what):      # raises unless "auto"
             return res
-        self._guard["reruns"] += 1
-        if self._guard["fallback"] is not None:
+        g.bump("reruns")
+        if g["fallback"] is not None:
             # the F16X3 engine's workspace (34 GB at B = 512, T = 243) is dead weight while the model runs on the fp32 engine: release it so
             # that the repeat -- which allocates the fp32 engine's own -- does not double the peak (ADVICE r05); it comes back lazily
-            eng._ws, eng._ws_B = None, 0
-        return fn(get_engine(True))
+            eng.release_workspace()
+        eng = get_engine(True)
+        with eng.lock:
+            return fn(eng)
 
     @contextmanager
     def deferred_range_checks(self):
-        """Inside: guarded calls only POST their range tickets.  The yielded object's resolve() -- call it behind a synchronisation
-        the caller makes anyway -- reads them all: False = every call was in range; True = precision="auto" has moved the model to
-        its fp32 engine and the caller must repeat the work of the block; other precisions raise D3DError."""
-        outer, outer_box = self._guard["deferred"], self._guard.get("deferred_box")
+        """Inside: guarded calls OF THE CALLING THREAD only POST their range tickets.  The yielded object's resolve() -- call it behind a
+        synchronisation the caller makes anyway -- reads them all: False = every call was in range; True = precision="auto" has moved
+        the model to its fp32 engine and the caller must repeat the work of the block; other precisions raise D3DError."""
+        mine = self._guard.mine
+        outer, outer_box = mine.deferred, mine.deferred_box
         box = _Deferred(self)
-        self._guard["deferred"], self._guard["deferred_box"] = box.items, box
+        mine.deferred, mine.deferred_box = box.items, box
         try:
             yield box
         finally:
-            self._guard["deferred"], self._guard["deferred_box"] = outer, outer_box
+            mine.deferred, mine.deferred_box = outer, outer_box
 
     def _compute_device(self, *tensors) -> torch.device:
         for t in tensors:
@@ -367,7 +445,8 @@ class _MixSTEDenoiser(nn.Module):
 
 
 class _Deferred:
-    """Range tickets posted inside _MixSTEDenoiser.deferred_range_checks()."""
+    """Range tickets posted inside _MixSTEDenoiser.deferred_range_checks(): those of the thread that opened the block (its `items` is
+    that thread's open list; no other thread appends to it)."""
 
     def __init__(self, net: _MixSTEDenoiser):
         self.net = net
@@ -397,7 +476,7 @@ class _Deferred:
             return False
         if not self.net._flagged(flags, what):  # raises unless "auto"
             return False
-        self.net._guard["reruns"] += 1
+        self.net._guard.bump("reruns")
         return True
 
 

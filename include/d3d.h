@@ -16,7 +16,7 @@
  *   - every function returns 0 on success, a negative D3D_E* code on failure; d3d_last_error() gives the message
  *     (thread-local).  No exception crosses the ABI.  Nothing here falls back to a CPU implementation: without a
  *     HIP device the compute entry points fail with D3D_EHIP.
- *   - one engine per device; an engine is not thread-safe, distinct engines are independent.
+ *   - one engine per device; see "Threads" below.
  *   - tensors are row-major fp32: x2d (B,T,J,in_chans), y / x0 / out (B,T,J,3) [(B,1,J,3) for seq2frame].
  */
 #ifndef D3D_H_
@@ -49,6 +49,20 @@ extern "C" {
                              * oracle's bf16-operand emulation instead (same rounding points).  Needs head_dim 64, num_frame <= 256,
                              * num_joints <= 32, widths % 64 == 0; never the default of the Python layer or of bench.py. */
 
+/*
+ * Threads
+ *   - Distinct engines may be driven from distinct host threads concurrently, on one device or on several: an engine owns its weights,
+ *     tables, streams, events, graph cache, ticket ring and range-guard word, every option is a field of the engine, and the launch
+ *     context of a call (range word, "deep_stages", tail slices) is thread-local.  What the library keeps per process is written once
+ *     per device and idempotently (the LDS opt-in bits, the CU-count caches, the range sink word, the cached ncclAllGather pointer)
+ *     or is a plain atomic default (the NULL-engine form of "deep_stages").
+ *   - ONE engine is driven by ONE thread at a time: every entry point that takes a d3d_engine* reads or writes its state without a
+ *     lock, and two concurrent calls would share one workspace.  The Python layer enforces this with a lock per engine
+ *     (Engine.lock); a C caller must serialise its calls per engine itself.  A ticket of d3d_engine_range_post covers the launches
+ *     since the previous post, so a caller that wants a ticket to describe ITS call keeps the engine from before the launch until
+ *     the post has returned.
+ *   - d3d_last_error() is per thread: it returns the message of the calling thread's most recent failed call.
+ */
 typedef struct d3d_engine d3d_engine;
 
 /* Shape-defining constructor arguments of the denoiser (S2S:140-142 / S2F ctor; runner passes them at RUN:178-180). */
@@ -178,10 +192,13 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     the parity gate but are NOT bit-identical to the default, nor across calls that get different S; a sequence's
  *                     result is bit-identical across calls that get the same S.  d3d_workspace_bytes does not change.  "fc2_split_last"
  *                     (d3d_engine_get_info) reports the S of the latest forward.  Other precisions ignore it.
- * Process-wide switch, the only key accepted with a NULL e: "deep_stages" 1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches
- * (batches of a few sequences: proj on 128 x 128 tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead
- * of two, the wait in front of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243:
- * 20.8 -> 17.6 us per launch; a 9-step sampling 18.9 -> 18.3 ms at B = 1, 75.7 -> 72.2 at B = 8).  Bit-identical.
+ *   "deep_stages"     1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches (batches of a few sequences: proj on 128 x 128
+ *                     tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead of two, the wait in front
+ *                     of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243: 20.8 ->
+ *                     17.6 us per launch; a 9-step sampling 18.9 -> 18.3 ms at B = 1, 75.7 -> 72.2 at B = 8).  Bit-identical.  Per engine
+ *                     since version 133: set on an engine it changes that engine alone (and drops its captured graphs, as every key
+ *                     does).  It is the only key accepted with a NULL e: that sets the process-wide default, which the single-op hooks
+ *                     use and which an engine follows until it is given a value of its own.
  * Unknown key: D3D_EINVAL. */
 int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value);
 
