@@ -160,6 +160,33 @@ hipError_t launch_linear_x3p_splitk(const void* Apair, const void* Wpair, float*
 // bytes row for row.  Exactly one of Yp / Y.
 hipError_t launch_splitk_postnorm(const float* P, int S, const void* Rp, const float* bias, const X3PostNorm& pn, float* Y, void* Yp,
                                   float* stats, int M, int N, hipStream_t s);
+// ---- latency mode, proj and fc1 (kernels_splitk_reduce.hip): the same split GEMM + an ordered reduce with the launch's own epilogue ----
+//   launch_splitk_residual : x = r + bias + P[0] + ... + P[S-1] -> stream planes Xp (may be Rp) + st_out, one (sum, sum of squares) per row
+//                            and 64 columns (x3q_ntiles per row: the st_in of the folded fc1); N == 512
+//   launch_splitk_gelu     : h = gelu(rstd (P[0] + ... + P[S-1]) - rstd mean csum + bias) -> Hp, accumulator-order pair layout (the A
+//                            operand of either fc2 form); mean / rstd from st_in[(m st_np + p)] over K columns; N % 512 == 0
+// proj_splitk_choose / fc1_splitk_choose: S in {2, 4}, or 0 = keep the present launch.  Pure functions of (M, N, K, CU count).  In units
+// of one k-tile of a lone 128 x 128 workgroup:
+//   present launch (launch_x3q_auto)  K/32 where ceil(M/128) (N/128) <= CUs (128 x 128 tiles), else 1.4 K/32 ceil(tiles of 256 x 128 / CUs)
+//   split, S in {2, 4}, K/32/S >= 4   K/32/S, x 1.45 where the W = ceil(M/128) (N/128) S workgroups exceed the CUs, + the reduce launch
+//                                     (PLACEHOLDERS, not tuned values: no measurement is on file yet -- the table is to be
+//                                     profiles/latency_mode_proj_fc1.json -- so both stand at 16, the present launch's own depth at
+//                                     K = 512: the model shows no gain and the rules return 0 everywhere until they are measured)
+// W > 2 CUs is excluded; fc1 also excludes W > CUs (two co-resident 128 x 128 workgroups of fc1 lose: NOTES round 6) and M S N beyond
+// the engine's scratch buffer.  The cheapest S wins if it beats the present launch, the smaller on a tie; 0 unless N, K are those of
+// the D = 512 flow.
+constexpr size_t FC1_SPLITK_SCRATCH_FLOATS = (size_t)8192 * 1024;   // fc1 partials, M S <= 8192 rows at Dm = 1024: 32 MiB
+int proj_splitk_choose(int M, int N, int K, int n_cu);
+int fc1_splitk_choose(int M, int N, int K, int n_cu);
+bool proj_splitk_ok(int N, int K, int S);                  // shapes the kernel pairs exist for (a forced S, the op hooks)
+bool fc1_splitk_ok(int N, int K, int S);
+bool proj_splitk_fits(int M, int N, int S, int n_cu);      // ... and calls they serve: W <= 2 CUs (fc1: and the scratch bound)
+bool fc1_splitk_fits(int M, int N, int S, int n_cu);
+hipError_t launch_splitk_residual(const float* P, int S, const void* Rp, const float* bias, void* Xp, float* st_out, int M, int N,
+                                  hipStream_t s);
+hipError_t launch_splitk_gelu(const float* P, int S, const float* st_in, int st_np, const float* csum, const float* bias, float eps,
+                              void* Hp, int M, int N, int K, hipStream_t s);
+hipError_t launch_unsplit_acc(const void* pair, float* x, size_t rows, int cols, hipStream_t s);   // op hooks only
 hipError_t launch_split_x3(const float* x, void* pair, size_t rows, int cols, hipStream_t s);
 hipError_t launch_unsplit_x3(const void* pair, float* x, size_t rows, int cols, const float* part, int np, float* stats,
                              hipStream_t s);   // op hooks only

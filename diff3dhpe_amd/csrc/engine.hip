@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <algorithm>
 #include <string>
@@ -105,6 +106,17 @@ struct d3d_engine {
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
   int fc2_split_last = 0;         // the S of the most recent forward (0: the whole-row fc2 ran): d3d_engine_get_info
+  // "proj_split" / "fc1_split" (read only while "latency_mode" is on): -1 = the rules of d3d_kernels.h (proj_splitk_choose /
+  // fc1_splitk_choose), 0 / 2 / 4 = that S wherever the call fits the kernel pair (else the present launch): measurements and tests
+  int opt_proj_split = -1, opt_fc1_split = -1;
+  int proj_split_last = 0, fc1_split_last = 0;   // as fc2_split_last
+  // fc1's partials (S M Dm floats) fit no region of the workspace that is dead at that point for every S: an engine-owned buffer,
+  // FC1_SPLITK_SCRATCH_FLOATS per slot, allocated when "latency_mode" is switched on and freed when it is switched off.  Slot 1 serves
+  // the second half-batch of a two-stream sampling (the halves run concurrently), allocated by the first such call.
+  float* lat_scratch[2] = {nullptr, nullptr};
+  void free_lat_scratch() {
+    for (auto& p : lat_scratch) { if (p) (void)hipFree(p); p = nullptr; }
+  }
   // BF16 mode: whether the most recent forward ran the fused qkv + attention kernel (kernels_qkv_attn_bf16.hip) in its spatial / temporal
   // blocks ("fused_spatial" / "fused_temporal" and the shape predicates): d3d_engine_get_info "bf16_fused_spatial_last" / "..temporal_last"
   int bf16_fused_sp_last = 0, bf16_fused_tp_last = 0;
@@ -173,6 +185,7 @@ struct d3d_engine {
 
   ~d3d_engine() {
     drop_graphs();
+    free_lat_scratch();
     (void)hipFree(trace_dev);
     (void)hipFree(range_dev);
     if (range_host) (void)hipHostFree(range_host);
@@ -382,6 +395,27 @@ int fc2_split_for(const d3d_engine* e, int B) {
   return fc2_splitk_choose(B * e->T * e->J, e->D, e->Dm, device_cu_count());
 }
 
+// the same for proj and fc1: the forced S of "proj_split" / "fc1_split" where the call fits, else the rule
+int proj_split_for(const d3d_engine* e, int B) {
+  if (!e->opt_latency_mode || !fold_flow(e) || e->D != 512) return 0;
+  const int M = B * e->T * e->J, cus = device_cu_count();
+  if (e->opt_proj_split < 0) return proj_splitk_choose(M, e->D, e->D, cus);
+  const int S = e->opt_proj_split;
+  return S && proj_splitk_ok(e->D, e->D, S) && proj_splitk_fits(M, e->D, S, cus) ? S : 0;
+}
+int fc1_split_for(const d3d_engine* e, int B) {
+  if (!e->opt_latency_mode || !fold_flow(e) || e->D != 512) return 0;
+  const int M = B * e->T * e->J, cus = device_cu_count();
+  if (e->opt_fc1_split < 0) return fc1_splitk_choose(M, e->Dm, e->D, cus);
+  const int S = e->opt_fc1_split;
+  return S && fc1_splitk_ok(e->Dm, e->D, S) && fc1_splitk_fits(M, e->Dm, S, cus) ? S : 0;
+}
+// the scratch slot a forward with fc1 split needs, allocated outside any capture (the eager pass of a graph call comes first)
+int ensure_lat_scratch(d3d_engine* e, int slot) {
+  if (!e->lat_scratch[slot]) HIP_TRY(hipMalloc(&e->lat_scratch[slot], FC1_SPLITK_SCRATCH_FLOATS * sizeof(float)));
+  return D3D_OK;
+}
+
 // BF16 mode: which block types of a forward of B sequences run the fused qkv + attention kernel.  A pure function of the options and
 // the shape -- the same for eager and captured runs.
 bool bf16_fused_sp_for(const d3d_engine* e, int B) {
@@ -448,6 +482,17 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
   // output, dead since proj) and on into w.QKV (q / k / v planes, dead since attention): (Mp + 3 M) D floats >= 4 M D, contiguous.
   const int ksplit = pn ? fc2_split_for(e, B) : 0;
   float* const PART = w.HN;
+  // ... and proj / fc1 (kernels_splitk_reduce.hip).  proj's partials take w.QKV (dead since attention) and on into w.HID (dead until
+  // fc1): 3 M D + Mp Dm floats >= 4 M D, contiguous -- not w.HN, which holds proj's own A operand.  fc1's take the engine's scratch
+  // buffer, the second half-batch of a two-stream sampling its own slot.
+  const int psplit = proj_split_for(e, B), fsplit = fc1_split_for(e, B);
+  float* const PPART = w.QKV;
+  const int fslot = (e->side_stream && s == e->side_stream) ? 1 : 0;
+  if (fsplit) {
+    const int rc = ensure_lat_scratch(e, fslot);
+    if (rc) return rc;
+  }
+  float* const FPART = e->lat_scratch[fslot];
   for (int k = 0; k < e->nblk; ++k) {
     const BlockW& bw = e->blk[k];
     const bool temporal = (k & 1) != 0;
@@ -486,7 +531,15 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       X3Fold f{};
       f.Rp = XP; f.st_out = w.ST2;
       const int Mw = (M / 192) * 192;     // rows in whole 192-row tiles
-      if (e->opt_proj_kernel && proj_x3_ok(D, D) && (size_t)(Mw / 192) * (size_t)(D / 256) >= 512) {
+      if (psplit) {
+        {
+          Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)D * D, 4.0 * ((double)M * D + (double)D * D + (double)psplit * M * D), s, D3D_KC_LINEAR_PROJ);
+          HIP_TRY(launch_linear_x3p_splitk(AOx, bw.proj_x3, PPART, M, D, D, psplit, s, bw.proj_e));
+        }
+        TRACE(k, 4, 2, PPART, (size_t)psplit * MDb);
+        Prof p(e, D3D_KC_LAYERNORM, 2.0 * M * D * (1 + psplit), MD4 * (2 + psplit), s);
+        HIP_TRY(launch_splitk_residual(PPART, psplit, XP, bw.projb, XP, w.ST2, M, D, s));
+      } else if (e->opt_proj_kernel && proj_x3_ok(D, D) && (size_t)(Mw / 192) * (size_t)(D / 256) >= 512) {
         Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)D * D, 4.0 * ((double)M * D + (double)D * D + 2.0 * M * D), s, D3D_KC_LINEAR_PROJ);
         HIP_TRY(launch_proj_x3(AOx, bw.proj_x3, bw.projb, XP, w.ST2, bw.proj_e, Mw, D, D, s));
         if (M > Mw) {   // the ragged rest: the template's checked forms, on the sub-matrix behind the whole tiles
@@ -504,7 +557,15 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
     {  // hidden = gelu(norm2(x) W1^T + b1), LayerNorm folded
       X3Fold f{};
       f.st_in = w.ST2; f.st_np = np2; f.csum = bw.fc1_cs; f.eps = e->ln_eps;
-      if (fc1_own) {
+      if (fsplit) {
+        {
+          Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)e->Dm * D, 4.0 * ((double)M * D + (double)e->Dm * D + (double)fsplit * M * e->Dm), s, D3D_KC_LINEAR_FC1);
+          HIP_TRY(launch_linear_x3p_splitk(XP, bw.fc1_f3, FPART, M, e->Dm, D, fsplit, s, bw.fc1_fe));
+        }
+        TRACE(k, 5, 2, FPART, (size_t)fsplit * M * e->Dm * 4);
+        Prof p(e, D3D_KC_LAYERNORM, 12.0 * M * e->Dm, 4.0 * (double)M * e->Dm * (1 + fsplit), s);
+        HIP_TRY(launch_splitk_gelu(FPART, fsplit, w.ST2, np2, bw.fc1_cs, bw.fc1_fb, e->ln_eps, HIDx, M, e->Dm, D, s));
+      } else if (fc1_own) {
         Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)e->Dm * D, 4.0 * ((double)M * D + (double)e->Dm * D + (double)M * e->Dm), s, D3D_KC_LINEAR_FC1);
         HIP_TRY(launch_fc1_x3(XP, bw.fc1_f3, bw.fc1_fb, bw.fc1_cs, w.ST2, np2, e->ln_eps, bw.fc1_fe, HIDx, M, e->Dm, D, s));
       } else {
@@ -843,7 +904,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 133; }   // 133: "deep_stages" with an engine is that engine's own setting (and drops its graphs)
+int d3d_version(void) { return 134; }   // 134: latency mode covers proj and fc1 ("proj_split" / "fc1_split", d3d_op_linear_splitk_residual / _gelu)
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1198,6 +1259,8 @@ int d3d_denoise(d3d_engine* e, const float* x2d, const float* y, int32_t y_frame
   RangeScope range_scope(e);
   Workspace w = carve(e, B, ws);
   e->fc2_split_last = fc2_split_for(e, B);
+  e->proj_split_last = proj_split_for(e, B);
+  e->fc1_split_last = fc1_split_for(e, B);
   e->bf16_fused_sp_last = bf16_fused_sp_for(e, B) ? 1 : 0;
   e->bf16_fused_tp_last = bf16_fused_tp_for(e, B) ? 1 : 0;
   const float* tvec = nullptr;
@@ -1326,6 +1389,8 @@ int d3d_ddim_sample(d3d_engine* e, const float* x2d, const float* init_noise, co
   SplitWs sw{};
   if (split) sw = carve_split(e, B, ws);
   e->fc2_split_last = fc2_split_for(e, split ? sw.B0 : B);   // (two half-batches: the first half's -- the one that holds sequence 0)
+  e->proj_split_last = proj_split_for(e, split ? sw.B0 : B);
+  e->fc1_split_last = fc1_split_for(e, split ? sw.B0 : B);
   e->bf16_fused_sp_last = bf16_fused_sp_for(e, split ? sw.B0 : B) ? 1 : 0;
   e->bf16_fused_tp_last = bf16_fused_tp_for(e, split ? sw.B0 : B) ? 1 : 0;
   const size_t xin0 = split ? (size_t)sw.B0 * xin_row : 0, y0 = split ? (size_t)head_rows(e, sw.B0) * 3 : 0;
@@ -1420,7 +1485,22 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
     e->ln_eps = v;
   }
   else if (k == "bf16_gemm_kernel") e->opt_bf16_gemm_kernel = value != 0;
-  else if (k == "latency_mode") e->opt_latency_mode = value != 0;
+  else if (k == "latency_mode") {
+    e->opt_latency_mode = value != 0;
+    if (!e->opt_latency_mode) {
+      if (e->lat_scratch[0] || e->lat_scratch[1]) (void)hipDeviceSynchronize();   // (a forward that reads the buffer may be in flight)
+      e->free_lat_scratch();
+    } else if (e->committed) {        // (an engine that exists on the host only has no device to allocate on: the first forward does it)
+      const int rc = ensure_lat_scratch(e, 0);
+      if (rc) { e->opt_latency_mode = false; return rc; }
+    }
+  }
+  else if (k == "proj_split" || k == "fc1_split") {
+    const bool proj = k == "proj_split";
+    if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
+      return fail(D3D_EUNSUP, k + ": -1 (the rule), 0, or S in {2, 4} with embed_dim / 32 / S >= 4 whole k-tiles, embed_dim 512");
+    (proj ? e->opt_proj_split : e->opt_fc1_split) = (int)value;
+  }
   else if (k == "streams") {
     if (value != 1 && value != 2) return fail(D3D_EINVAL, "streams must be 1 or 2");
     e->opt_streams = (int)value;
@@ -1480,6 +1560,10 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->fc2_split_last;
+  else if (k == "proj_split_last") *value = e->proj_split_last;
+  else if (k == "fc1_split_last") *value = e->fc1_split_last;
+  else if (k == "proj_split") *value = e->opt_proj_split;
+  else if (k == "fc1_split") *value = e->opt_fc1_split;
   else if (k == "bf16_fused_spatial_last") *value = e->bf16_fused_sp_last;
   else if (k == "bf16_fused_temporal_last") *value = e->bf16_fused_tp_last;
   else return fail(D3D_EINVAL, "unknown info key: " + k);
@@ -1924,6 +2008,126 @@ int d3d_op_linear_splitk_postnorm(const float* A, const float* W, const float* b
   if (le == hipSuccess && stats) le = launch_unsplit_x3(yp.dev, Y, (size_t)M, N, st1, 1, stats, s);
   hipError_t se = hipStreamSynchronize(s);
   if (st1) (void)hipFree(st1);
+  HIP_TRY(le);
+  HIP_TRY(se);
+  return D3D_OK;
+}
+
+namespace {
+// mean time of `once` over reps launches on s (the op hooks' avg_ms)
+hipError_t time_reps(const std::function<hipError_t()>& once, int reps, float* avg_ms, hipStream_t s) {
+  hipError_t le = hipSuccess;
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  (void)hipEventRecord(e0, s);
+  for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
+  (void)hipEventRecord(e1, s);
+  (void)hipEventSynchronize(e1);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  *avg_ms = ms / reps;
+  return le;
+}
+struct DevF32 {   // (freed on every return path)
+  float* p = nullptr;
+  ~DevF32() { (void)hipFree(p); }
+};
+}  // namespace
+
+int d3d_op_linear_splitk_residual(const float* A, const float* W, const float* bias, const float* R, float* Y, float* stats, int32_t M,
+                                  int32_t N, int32_t K, int32_t S, float* partials, int32_t reps, float* avg_ms, void* stream) {
+  if (!A || !W || !bias || !R || !Y || (S != 0 && !partials) || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
+  if (S == 0 ? !(N == 512 && K > 0 && K % 32 == 0) : !proj_splitk_ok(N, K, S))
+    return fail(D3D_EUNSUP, "the split-K proj pair exists for N == 512, S in {2, 4}, K / 32 / S >= 4 whole k-tiles (S == 0: the default kernel)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  TmpPair ap, wp, rp, yp;
+  int rc = make_pair(wp, W, N, K, true, s);
+  if (!rc) rc = make_pair(ap, A, M, K, false, s);
+  if (!rc) rc = make_pair(rp, R, M, N, false, s);
+  if (!rc) rc = make_pair(yp, R, M, N, false, s);   // (the output planes: the residual is read from rp, so repeats see the same input)
+  if (rc) return rc;
+  const int np = x3q_ntiles(M, N);
+  DevF32 part;   // (whole 256-row tiles, as the engine's statistics buffers)
+  HIP_TRY(hipMalloc(&part.p, ((size_t)M + 255) / 256 * 256 * np * 2 * sizeof(float)));
+  X3Fold f{};
+  f.Rp = rp.dev; f.st_out = part.p;
+  auto once = [&]() -> hipError_t {
+    if (S == 0) return launch_linear_x3p(ap.dev, wp.dev, bias, nullptr, nullptr, yp.dev, nullptr, M, N, K, EPI_RESIDUAL, 2, 0, 0, s, &f, wp.wexp);
+    const hipError_t ge = launch_linear_x3p_splitk(ap.dev, wp.dev, partials, M, N, K, S, s, wp.wexp);
+    return ge == hipSuccess ? launch_splitk_residual(partials, S, rp.dev, bias, yp.dev, part.p, M, N, s) : ge;
+  };
+  hipError_t le = once();
+  if (le == hipSuccess && avg_ms) le = time_reps(once, reps, avg_ms, s);
+  if (le == hipSuccess) le = launch_unsplit_x3(yp.dev, Y, (size_t)M, N, nullptr, 0, nullptr, s);
+  if (le == hipSuccess && stats) le = hipMemcpyAsync(stats, part.p, (size_t)M * np * 2 * sizeof(float), hipMemcpyDeviceToDevice, s);
+  hipError_t se = hipStreamSynchronize(s);
+  HIP_TRY(le);
+  HIP_TRY(se);
+  return D3D_OK;
+}
+
+int d3d_op_linear_splitk_gelu(const float* X, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
+                              float* H, int32_t M, int32_t N, int32_t K, int32_t S, float* partials, int32_t reps, float* avg_ms,
+                              void* stream) {
+  if (!X || !W || !bias || !gamma || !beta || !H || (S != 0 && !partials) || M < 1 || reps < 1 || !(eps > 0.f))
+    return fail(D3D_EINVAL, "bad argument");
+  if (S == 0 ? !(N > 0 && N % 512 == 0 && K > 0 && K % 64 == 0) : !fc1_splitk_ok(N, K, S))
+    return fail(D3D_EUNSUP, "the split-K fc1 pair exists for N % 512 == 0, K % 64 == 0, S in {2, 4}, K / 32 / S >= 4 whole k-tiles (S == 0: the default kernel)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // the LayerNorm fold of the weight commit: W diag(gamma) as planes, csum, b + W beta
+  const size_t nk = (size_t)N * K;
+  std::vector<float> hw(nk), hg(K), hb(K), hbias(N), wg(nk), fold(2 * (size_t)N);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(hw.data(), W, nk * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hg.data(), gamma, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hb.data(), beta, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hbias.data(), bias, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < (size_t)N; ++r) {
+    double c = 0.0, bsum = (double)hbias[r];
+    for (size_t q = 0; q < (size_t)K; ++q) {
+      const float wv = hw[r * K + q] * hg[q];
+      wg[r * K + q] = wv;
+      c += (double)wv;
+      bsum += (double)hw[r * K + q] * (double)hb[q];
+    }
+    fold[r] = (float)c;
+    fold[N + r] = (float)bsum;
+  }
+  TmpPair wp, xp, hp;
+  const size_t npad = ((size_t)N + 255) / 256 * 256, mpad = ((size_t)M + 255) / 256 * 256;
+  {
+    std::vector<uint16_t> pr(2 * npad * K, 0);
+    wp.wexp = split_weight_f16x3(wg.data(), N, K, pr.data());
+    HIP_TRY(hipMalloc(&wp.dev, pr.size() * sizeof(uint16_t)));
+    HIP_TRY(hipMemcpy(wp.dev, pr.data(), pr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMalloc(&xp.dev, 2 * mpad * K * sizeof(uint16_t)));
+  HIP_TRY(hipMemsetAsync(xp.dev, 0, 2 * mpad * K * sizeof(uint16_t), s));
+  HIP_TRY(hipMalloc(&hp.dev, 2 * mpad * N * sizeof(uint16_t)));
+  HIP_TRY(hipMemsetAsync(hp.dev, 0, 2 * mpad * N * sizeof(uint16_t), s));
+  DevF32 fd, st;
+  HIP_TRY(hipMalloc(&fd.p, fold.size() * sizeof(float)));
+  HIP_TRY(hipMemcpy(fd.p, fold.data(), fold.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(&st.p, mpad * 2 * sizeof(float)));
+  HIP_TRY(hipMemsetAsync(st.p, 0, mpad * 2 * sizeof(float), s));
+  {  // the stream entry row kernel: planes of 8 x + one (sum, sum of squares) per row
+    LnArgs a{};
+    a.x = X; a.skip_ln1 = 1; a.y_x3 = xp.dev; a.stats = st.p;
+    a.rows = M; a.D = K; a.rows_per_batch = M; a.pos_div = 1; a.pos_mod = 1;
+    HIP_TRY(launch_layernorm(a, s));
+  }
+  X3Fold f{};
+  f.st_in = st.p; f.st_np = 1; f.csum = fd.p; f.eps = eps;
+  auto once = [&]() -> hipError_t {
+    if (S == 0) return launch_linear_x3p(xp.dev, wp.dev, fd.p + N, nullptr, nullptr, hp.dev, nullptr, M, N, K, EPI_GELU, 2, 0, 0, s, &f, wp.wexp);
+    const hipError_t ge = launch_linear_x3p_splitk(xp.dev, wp.dev, partials, M, N, K, S, s, wp.wexp);
+    return ge == hipSuccess ? launch_splitk_gelu(partials, S, st.p, 1, fd.p, fd.p + N, eps, hp.dev, M, N, K, s) : ge;
+  };
+  hipError_t le = once();
+  if (le == hipSuccess && avg_ms) le = time_reps(once, reps, avg_ms, s);
+  if (le == hipSuccess) le = launch_unsplit_acc(hp.dev, H, (size_t)M, N, s);
+  hipError_t se = hipStreamSynchronize(s);
   HIP_TRY(le);
   HIP_TRY(se);
   return D3D_OK;

@@ -211,13 +211,14 @@ class Engine:
 
     @_locked
     def set_option(self, key: str, value: int) -> None:
-        """Explicit engine switch (include/d3d.h: "fused_postnorm", "fold_layernorm", "streams", "latency_mode"); the library reads no environment."""
+        """Explicit engine switch (include/d3d.h: "fused_postnorm", "fold_layernorm", "streams", "latency_mode", "proj_split",
+        "fc1_split"); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
     def info(self, key: str) -> int:
         """Read-only engine facts (include/d3d.h d3d_engine_get_info): "graphs_cached", "graphs_captured", "streams", "device",
-        "latency_mode", "fc2_split_last", "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the most recent forward of a
+        "latency_mode", "fc2_split_last", "proj_split_last", "fc1_split_last", "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the most recent forward of a
         bf16 engine ran the fused qkv + attention kernel in its spatial / temporal blocks)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
@@ -497,6 +498,45 @@ def op_linear_splitk_postnorm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tens
             int(pos.shape[0]) if pos is not None else 1, _ptr(tvec), stride, int(rows_per_batch), _ptr(out), _ptr(stats), M, N, K,
             int(S), _ptr(partials), int(reps), C.byref(ms), st))
     return out, stats, ms.value
+
+
+def op_linear_splitk_residual(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, residual: torch.Tensor, S: int = 2,
+                              with_stats: bool = False, reps: int = 1):
+    """proj of "latency_mode" alone: x = residual + bias + A W^T from the split-K (S k-ranges) x split-N F16X3 GEMM and the ordered
+    reduce that writes the stream planes.  S = 0 runs the default kernel on the same operands.  Returns (x un-split to fp32, the
+    (sum, sum of squares) partials per row and 64 columns -- shape (M, N / 64, 2) -- or None, mean ms per call)."""
+    M, K = A.shape
+    N = W.shape[0]
+    dev = A.device
+    A, W, bias, residual = _f32c(A, dev), _f32c(W, dev), _f32c(bias, dev), _f32c(residual, dev)
+    out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    stats = torch.empty((M, max(N // 64, 1), 2), dtype=torch.float32, device=dev) if with_stats else None
+    partials = torch.empty((max(int(S), 1), M, N), dtype=torch.float32, device=dev)
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_linear_splitk_residual(_ptr(A), _ptr(W), _ptr(bias), _ptr(residual), _ptr(out), _ptr(stats), M, N, K,
+                                                            int(S), _ptr(partials), int(reps), C.byref(ms), st))
+    return out, stats, ms.value
+
+
+def op_linear_splitk_gelu(x: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                          eps: float = 1e-6, S: int = 2, reps: int = 1):
+    """fc1 of "latency_mode" alone: h = gelu(LayerNorm(x; gamma, beta, eps) W^T + bias), the LayerNorm folded into the GEMM, from the
+    split-K GEMM and the ordered reduce that writes the hidden activation's planes.  S = 0 runs the default kernel.  Returns
+    (h un-split to fp32, mean ms per call)."""
+    M, K = x.shape
+    N = W.shape[0]
+    dev = x.device
+    x, W, bias, gamma, beta = _f32c(x, dev), _f32c(W, dev), _f32c(bias, dev), _f32c(gamma, dev), _f32c(beta, dev)
+    out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    partials = torch.empty((max(int(S), 1), M, N), dtype=torch.float32, device=dev)
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_linear_splitk_gelu(_ptr(x), _ptr(W), _ptr(bias), _ptr(gamma), _ptr(beta), float(eps), _ptr(out),
+                                                        M, N, K, int(S), _ptr(partials), int(reps), C.byref(ms), st))
+    return out, ms.value
 
 
 def op_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:

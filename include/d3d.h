@@ -192,6 +192,18 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     the parity gate but are NOT bit-identical to the default, nor across calls that get different S; a sequence's
  *                     result is bit-identical across calls that get the same S.  d3d_workspace_bytes does not change.  "fc2_split_last"
  *                     (d3d_engine_get_info) reports the S of the latest forward.  Other precisions ignore it.
+ *                     The mode covers proj and fc1 of such a forward too (embedding width 512): each may run as the same split GEMM
+ *                     (proj: partials in the workspace's q / k / v and hidden-activation regions, dead at that point; fc1: in a buffer the
+ *                     engine owns -- 32 MiB, a second one for the second half-batch of a two-stream sampling -- allocated when the mode
+ *                     is switched on and freed when it is switched off or the engine destroyed) plus a row kernel that adds the partials
+ *                     in a fixed order and applies the launch's own epilogue (proj: residual, stream planes, row statistics; fc1: the
+ *                     folded LayerNorm, GELU, hidden planes).  Each has its own rule, a function of (M, N, K, CU count) alone that
+ *                     compares the split against the launch it replaces; "proj_split_last" / "fc1_split_last" report what ran.  A
+ *                     sequence's result is bit-identical across calls that get the same three S.
+ *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
+ *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
+ *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
+ *                     measurements and tests.
  *   "deep_stages"     1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches (batches of a few sequences: proj on 128 x 128
  *                     tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead of two, the wait in front
  *                     of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243: 20.8 ->
@@ -224,6 +236,7 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
 /* Read-only engine facts: "graphs_cached" (captured hipGraphs held now, <= 4), "graphs_captured" (captures since creation),
  * "streams", "device", "latency_mode", "fc2_split_last" (the k-split S of fc2 + post-norm in the most recent d3d_denoise /
  * d3d_ddim_sample call, 0 when the default whole-row kernel ran; a sampling run as two half-batches reports the first half's),
+ * "proj_split_last" / "fc1_split_last" (the same for proj and fc1), "proj_split" / "fc1_split" (the option values),
  * "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the spatial / temporal blocks of the most recent d3d_denoise /
  * d3d_ddim_sample call of a D3D_PREC_BF16 engine ran the fused qkv + attention kernel, else 0; 0 before the first call and in the
  * other precisions).
@@ -408,6 +421,19 @@ int d3d_op_linear_splitk_postnorm(const float* A_dev, const float* W_dev, const 
                                   int32_t pos_mod, const float* tvec_dev, int64_t tvec_stride, int32_t rows_per_batch, float* Y_dev,
                                   float* stats_dev, int32_t M, int32_t N, int32_t K, int32_t S, float* partials_dev, int32_t reps,
                                   float* avg_ms, void* stream);
+/* proj and fc1 of "latency_mode" alone, fp32 in and out (operands are split and results un-split on the device).  S in {2, 4}: the
+ * split-K x split-N GEMM into partials_dev (S * M * N floats) + the ordered reduce; S == 0: the default kernel on the same operands
+ * (partials_dev unused).  reps / avg_ms: mean time of one call's launches.  Shapes outside the predicate: D3D_EUNSUP.
+ *   _residual: Y = R + bias + A W^T as the stream planes hold it; stats_dev (nullable): (sum, sum of squares) of Y per row and 64-column
+ *              block, M * (N / 64) * 2 floats.  N == 512, K % 32 == 0, (K / 32) % S == 0, K / 32 / S >= 4.
+ *   _gelu:     H = gelu(LayerNorm(X; gamma, beta, eps) W^T + bias), the LayerNorm folded into the GEMM (S2S:46-48 behind 101), H read
+ *              back from the accumulator-order planes fc2 consumes.  N % 512 == 0, K % 64 == 0, (K / 32) % S == 0, K / 32 / S >= 4. */
+int d3d_op_linear_splitk_residual(const float* A_dev, const float* W_dev, const float* bias_dev, const float* R_dev, float* Y_dev,
+                                  float* stats_dev, int32_t M, int32_t N, int32_t K, int32_t S, float* partials_dev, int32_t reps,
+                                  float* avg_ms, void* stream);
+int d3d_op_linear_splitk_gelu(const float* X_dev, const float* W_dev, const float* bias_dev, const float* gamma_dev,
+                              const float* beta_dev, float eps, float* H_dev, int32_t M, int32_t N, int32_t K, int32_t S,
+                              float* partials_dev, int32_t reps, float* avg_ms, void* stream);
 /* Regression head of the engine's weights (S2S:217-220: LayerNorm eps 1e-5 + Linear D -> 3) on rows x D fp32 rows:
  * x0 (rows, 3), raw (no clamp, no DDIM update). */
 int d3d_op_head(d3d_engine* e, const float* X_dev, float* x0_dev, int32_t rows, void* stream);
