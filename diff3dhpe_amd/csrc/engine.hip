@@ -1,5 +1,5 @@
 // Host side of libd3d_hip.so: engine object, weight registry/repack, DDIM schedule, per-step launch sequence and the
-// C ABI declared in include/d3d.h.  No CPU compute path exists here: every tensor operation is a kernel from
+// C ABI declared in include/d3d.h (its engine-free single-op hooks: engine_ops.hip).  No CPU compute path exists here: every tensor operation is a kernel from
 // kernels_*.hip; the only host arithmetic is the integer timestep schedule and table bookkeeping.
 #include <hip/hip_runtime.h>
 
@@ -7,7 +7,6 @@
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <algorithm>
 #include <string>
@@ -15,6 +14,7 @@
 
 #include "../../include/d3d.h"
 #include "d3d_kernels.h"
+#include "engine_internal.h"
 
 using namespace d3d;
 
@@ -22,17 +22,14 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
+}  // namespace
+
+int d3d::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-#define HIP_TRY(expr)                                                                                         \
-  do {                                                                                                        \
-    hipError_t _e = (expr);                                                                                   \
-    if (_e != hipSuccess)                                                                                     \
-      return fail(D3D_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-  } while (0)
+namespace {
 
 struct WeightSlot {
   std::string name;
@@ -57,6 +54,23 @@ struct BlockW {
   const float *qkv_csh = nullptr, *qkv_fbh = nullptr;
   // exponent k of each weight's planes (2^k w; 12 unless a weight exceeds 15.99: split_weight_f16x3)
   int qkv_e = 12, proj_e = 12, fc1_e = 12, fc2_e = 12, qkv_fe = 12, fc1_fe = 12;
+};
+
+// Which kernels one forward of B sequences runs: every choice the block loops branch on, made once by plan_blocks() from the options,
+// the shapes, B and the CU count.  The entry points keep the plan they ran; d3d_engine_get_info reads its "*_last" keys from it.
+struct BlockPlan {
+  enum Flow { PLAIN, FOLD, BF16 };
+  Flow flow = PLAIN;          // run_blocks / run_blocks_fold / run_blocks_bf16
+  // FOLD, BF16: the qkv GEMM and the attention of the spatial / temporal blocks as one kernel
+  bool fused_sp = false, fused_tp = false;
+  // PLAIN in F16X3: q / k / v go to the fp16-MFMA attention kernel as planes
+  bool attn_x3_sp = false, attn_x3_tp = false;
+  // FOLD: fc1 / proj on their own kernels; the post-norm inside the fc2 epilogue
+  bool fc1_own = false, proj_own = false, pn = false;
+  // FOLD with "latency_mode": the S of the split-K form of each GEMM, 0 = the launches above
+  int fc2_split = 0, proj_split = 0, fc1_split = 0;
+  // BF16: whole-row proj / fc2 with their LayerNorms in the epilogue; qkv / fc1 on the hand-specialised GEMM kernel
+  bool rows = false, bf16q_qkv = false, bf16q_fc1 = false;
 };
 
 }  // namespace
@@ -105,11 +119,9 @@ struct d3d_engine {
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
-  int fc2_split_last = 0;         // the S of the most recent forward (0: the whole-row fc2 ran): d3d_engine_get_info
   // "proj_split" / "fc1_split" (read only while "latency_mode" is on): -1 = the rules of d3d_kernels.h (proj_splitk_choose /
   // fc1_splitk_choose), 0 / 2 / 4 = that S wherever the call fits the kernel pair (else the present launch): measurements and tests
   int opt_proj_split = -1, opt_fc1_split = -1;
-  int proj_split_last = 0, fc1_split_last = 0;   // as fc2_split_last
   // fc1's partials (S M Dm floats) fit no region of the workspace that is dead at that point for every S: an engine-owned buffer,
   // FC1_SPLITK_SCRATCH_FLOATS per slot, allocated when "latency_mode" is switched on and freed when it is switched off.  Slot 1 serves
   // the second half-batch of a two-stream sampling (the halves run concurrently), allocated by the first such call.
@@ -117,9 +129,10 @@ struct d3d_engine {
   void free_lat_scratch() {
     for (auto& p : lat_scratch) { if (p) (void)hipFree(p); p = nullptr; }
   }
-  // BF16 mode: whether the most recent forward ran the fused qkv + attention kernel (kernels_qkv_attn_bf16.hip) in its spatial / temporal
-  // blocks ("fused_spatial" / "fused_temporal" and the shape predicates): d3d_engine_get_info "bf16_fused_spatial_last" / "..temporal_last"
-  int bf16_fused_sp_last = 0, bf16_fused_tp_last = 0;
+  // the plan of the most recent forward (of a two-stream sampling: of the first half-batch, the one that holds sequence 0); all zero
+  // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
+  // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks
+  BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int device = -1;                // ordinal of the device the weights were committed on
@@ -383,46 +396,73 @@ int attention(d3d_engine* e, const float* qkv, float* out, void* out_x3, int B, 
   return D3D_OK;
 }
 
-// whether a forward of this engine takes the plane-resident, LayerNorm-folded F16X3 flow (run_blocks_fold)
-bool fold_flow(const d3d_engine* e) {
-  return e->cfg.precision == D3D_PREC_F16X3 && attn_temporal_x3_ok(e->T, e->D, e->H) && attn_temporal_x3_ok(e->J, e->D, e->H) &&
-         e->D % 32 == 0 && e->opt_fold_layernorm;
-}
-// "latency_mode": the k-split of fc2 + post-norm in a B-sequence forward, 0 = today's whole-row kernel.  Depends on (M, D, Dm, CU
-// count) only, so an eager run, a capture and a replay agree.
-int fc2_split_for(const d3d_engine* e, int B) {
-  if (!e->opt_latency_mode || !e->opt_fused_postnorm || !fold_flow(e)) return 0;
-  return fc2_splitk_choose(B * e->T * e->J, e->D, e->Dm, device_cu_count());
+// The plan of a forward of B sequences.  A pure function of the options, the shapes, B and the CU count, so an eager run, a capture
+// and a replay agree.
+BlockPlan plan_blocks(const d3d_engine* e, int B) {
+  const int T = e->T, J = e->J, D = e->D, Dm = e->Dm, H = e->H, M = B * T * J, cus = device_cu_count();
+  const bool x3 = e->cfg.precision == D3D_PREC_F16X3;
+  BlockPlan p;
+  if (x3 && attn_temporal_x3_ok(T, D, H) && attn_temporal_x3_ok(J, D, H) && D % 32 == 0 && e->opt_fold_layernorm) {
+    p.flow = BlockPlan::FOLD;
+    p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
+    p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
+    // the dedicated fc1 kernel runs whole 256-row tiles without guards (a launch of at least two rounds of tiles; smaller ones keep the
+    // template's 256 x 128 / sliced forms); the proj kernel whole 192-row tiles (the rows behind the last whole tile stay with the template)
+    p.fc1_own = e->opt_fc1_kernel && fc1_x3_ok(Dm, D) && (size_t)((M + 255) / 256) * (size_t)(Dm / 256) >= 512;
+    p.proj_own = e->opt_proj_kernel && proj_x3_ok(D, D) && (size_t)(M / 192) * (size_t)(D / 256) >= 512;
+    // post-norm inside the fc2 epilogue (X3PostNorm) where the tile shape for it exists; else fp32 + the row kernel
+    p.pn = e->opt_fused_postnorm && x3q_postnorm_ok(D, Dm);
+    if (e->opt_latency_mode) {
+      // fc2 + post-norm as a split-K GEMM + the ordered reduce / post-norm row kernel: d3d_kernels.h fc2_splitk_choose
+      if (p.pn) p.fc2_split = fc2_splitk_choose(M, D, Dm, cus);
+      // proj and fc1: the forced S of "proj_split" / "fc1_split" where the call fits the kernel pair, else the rule
+      if (D == 512) {
+        const int ps = e->opt_proj_split, fs = e->opt_fc1_split;
+        p.proj_split = ps < 0 ? proj_splitk_choose(M, D, D, cus) : (ps && proj_splitk_ok(D, D, ps) && proj_splitk_fits(M, D, ps, cus) ? ps : 0);
+        p.fc1_split = fs < 0 ? fc1_splitk_choose(M, Dm, D, cus) : (fs && fc1_splitk_ok(Dm, D, fs) && fc1_splitk_fits(M, Dm, fs, cus) ? fs : 0);
+      }
+    }
+  } else if (e->cfg.precision == D3D_PREC_BF16) {
+    p.flow = BlockPlan::BF16;
+    p.fused_sp = e->opt_fused_spatial && qkv_sattn_bf16_ok(T, J, D, H, B);
+    p.fused_tp = e->opt_fused_temporal && qkv_tattn_bf16_ok(T, J, D, H, B);
+    p.rows = e->opt_fused_postnorm && bf16_rows_ok(D, D) && bf16_rows_ok(D, Dm);
+    auto own = [&](int N) {   // from two rounds of 256 x 256 tiles on
+      return e->opt_bf16_gemm_kernel && gemm_bf16q_ok(N, D) && (long long)((M + 255) / 256) * (N / 256) >= 2LL * cus;
+    };
+    p.bf16q_qkv = own(3 * D);
+    p.bf16q_fc1 = own(Dm);
+  } else if (x3) {
+    p.attn_x3_sp = attn_temporal_x3_ok(J, D, H);
+    p.attn_x3_tp = attn_temporal_x3_ok(T, D, H);
+  }
+  return p;
 }
 
-// the same for proj and fc1: the forced S of "proj_split" / "fc1_split" where the call fits, else the rule
-int proj_split_for(const d3d_engine* e, int B) {
-  if (!e->opt_latency_mode || !fold_flow(e) || e->D != 512) return 0;
-  const int M = B * e->T * e->J, cus = device_cu_count();
-  if (e->opt_proj_split < 0) return proj_splitk_choose(M, e->D, e->D, cus);
-  const int S = e->opt_proj_split;
-  return S && proj_splitk_ok(e->D, e->D, S) && proj_splitk_fits(M, e->D, S, cus) ? S : 0;
+// The post-norm of block k (S2S:111-135): Spatial_norm / Temporal_norm by parity; Temporal_pos_embed behind block 0 only (row r takes
+// entry (r / J) % T); the NEXT block's time vector unless k is the last block.
+X3PostNorm block_postnorm(const d3d_engine* e, int k, const float* tvec, int64_t tvec_stride) {
+  const bool temporal = (k & 1) != 0;
+  X3PostNorm q{};
+  q.g = temporal ? e->tn_g : e->sn_g; q.b = temporal ? e->tn_b : e->sn_b; q.eps = e->ln_eps;
+  q.pos_div = 1; q.pos_mod = 1; q.rows_per_batch = e->T * e->J;
+  if (k == 0) { q.pos = e->tpos; q.pos_div = e->J; q.pos_mod = e->T; }
+  if (k + 1 < e->nblk && tvec) { q.tvec = tvec + (size_t)(k + 1) * e->D; q.tvec_stride = tvec_stride; }
+  return q;
 }
-int fc1_split_for(const d3d_engine* e, int B) {
-  if (!e->opt_latency_mode || !fold_flow(e) || e->D != 512) return 0;
-  const int M = B * e->T * e->J, cus = device_cu_count();
-  if (e->opt_fc1_split < 0) return fc1_splitk_choose(M, e->Dm, e->D, cus);
-  const int S = e->opt_fc1_split;
-  return S && fc1_splitk_ok(e->Dm, e->D, S) && fc1_splitk_fits(M, e->Dm, S, cus) ? S : 0;
+// the same as the arguments of the row kernel, over M rows
+LnArgs ln_postnorm(const d3d_engine* e, int M, const X3PostNorm& q) {
+  LnArgs a = ln_rows(M, e->D, q.rows_per_batch);
+  a.g1 = q.g; a.b1 = q.b; a.eps1 = q.eps;
+  a.pos = q.pos; a.pos_div = q.pos_div; a.pos_mod = q.pos_mod;
+  a.tvec = q.tvec; a.tvec_stride = q.tvec_stride;
+  return a;
 }
+
 // the scratch slot a forward with fc1 split needs, allocated outside any capture (the eager pass of a graph call comes first)
 int ensure_lat_scratch(d3d_engine* e, int slot) {
   if (!e->lat_scratch[slot]) HIP_TRY(hipMalloc(&e->lat_scratch[slot], FC1_SPLITK_SCRATCH_FLOATS * sizeof(float)));
   return D3D_OK;
-}
-
-// BF16 mode: which block types of a forward of B sequences run the fused qkv + attention kernel.  A pure function of the options and
-// the shape -- the same for eager and captured runs.
-bool bf16_fused_sp_for(const d3d_engine* e, int B) {
-  return e->cfg.precision == D3D_PREC_BF16 && e->opt_fused_spatial && qkv_sattn_bf16_ok(e->T, e->J, e->D, e->H, B);
-}
-bool bf16_fused_tp_for(const d3d_engine* e, int B) {
-  return e->cfg.precision == D3D_PREC_BF16 && e->opt_fused_temporal && qkv_tattn_bf16_ok(e->T, e->J, e->D, e->H, B);
 }
 
 // F16X3 production flow ("plane-resident, LayerNorm-folded"): the residual stream lives in the GEMM operand (pair) layout
@@ -432,8 +472,8 @@ bool bf16_fused_tp_for(const d3d_engine* e, int B) {
 // D == 512); for other widths the fc2 output goes to w.HN as fp32 and one stand-alone row kernel per block applies it.
 // The hidden activation (w.HID) is in "accumulator order" (pair_col_acc), matched by the fc2 weight split at commit.
 // Same op sequence as run_blocks (S2S:222-247, 111-135); leaves the final Temporal_norm output as fp32 in w.X.
-int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast, const float* tvec, int64_t tvec_stride,
-                    int B, const Workspace& w, hipStream_t s) {
+int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float* y, int y_bcast, const float* tvec,
+                    int64_t tvec_stride, int B, const Workspace& w, hipStream_t s) {
   const int T = e->T, J = e->J, D = e->D;
   const int M = B * T * J;
   const double MD4 = (double)M * D * 4.0;
@@ -457,35 +497,27 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
     }
     TRACE(0, 0, 0, w.HN, MDb);
     {  // stream entry: planes + row statistics of x (no normalisation)
-      LnArgs a{};
+      LnArgs a = ln_rows(M, D, T * J);
       a.x = w.HN; a.skip_ln1 = 1; a.y_x3 = XP; a.stats = w.ST1;
-      a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
       HIP_TRY(rowk(a, 1));
     }
   }
   TRACE(0, 1, 0, XP, MDb);
   TRACE(0, 1, 1, w.ST1, (size_t)M * 8);
-  const bool fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, e->H, D) && e->blk[0].qkv_f3h != nullptr;
-  // the dedicated fc1 kernel runs whole 256-row tiles without guards (a launch of at least two rounds of tiles; smaller ones keep the
-  // template's 256 x 128 / sliced forms)
-  const bool fc1_own = e->opt_fc1_kernel && fc1_x3_ok(e->Dm, D) && (size_t)((M + 255) / 256) * (size_t)(e->Dm / 256) >= 512;
-  if (fused_sp || fc1_own) {   // the fused spatial kernel / the fc1 kernel stage (and multiply) rows beyond the matrix: finite values there
+  if (pl.fused_sp || pl.fc1_own) {   // the fused spatial kernel / the fc1 kernel stage (and multiply) rows beyond the matrix: finite values there
     const size_t Mp = (size_t)((reinterpret_cast<char*>(w.HN) - reinterpret_cast<char*>(w.X)) / ((size_t)D * 4));   // rows of w.X as carved
     if (Mp > (size_t)M) HIP_TRY(hipMemsetAsync(XP + (size_t)M * 2 * D, 0, (Mp - (size_t)M) * 2 * D * sizeof(uint16_t), s));
   }
-  const bool fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, e->H, D);
   const int np2 = x3q_ntiles(M, D);                     // statistics partials per row written by a GEMM epilogue
   int np1 = 1;                                          // ... per row in w.ST1 (1 after a row kernel)
-  // post-norm inside the fc2 epilogue (X3PostNorm) where the tile shape for it exists; else fp32 + the row kernel
-  const bool pn = e->opt_fused_postnorm && x3q_postnorm_ok(D, e->Dm);
   // latency mode: S k-ranges of fc2 as fp32 partials + the ordered reduce / post-norm row kernel.  The partials take w.HN (the attention
   // output, dead since proj) and on into w.QKV (q / k / v planes, dead since attention): (Mp + 3 M) D floats >= 4 M D, contiguous.
-  const int ksplit = pn ? fc2_split_for(e, B) : 0;
+  const int ksplit = pl.fc2_split;
   float* const PART = w.HN;
   // ... and proj / fc1 (kernels_splitk_reduce.hip).  proj's partials take w.QKV (dead since attention) and on into w.HID (dead until
   // fc1): 3 M D + Mp Dm floats >= 4 M D, contiguous -- not w.HN, which holds proj's own A operand.  fc1's take the engine's scratch
   // buffer, the second half-batch of a two-stream sampling its own slot.
-  const int psplit = proj_split_for(e, B), fsplit = fc1_split_for(e, B);
+  const int psplit = pl.proj_split, fsplit = pl.fc1_split;
   float* const PPART = w.QKV;
   const int fslot = (e->side_stream && s == e->side_stream) ? 1 : 0;
   if (fsplit) {
@@ -502,12 +534,12 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N * (f.Rp ? 2 : 1)), s, sub);
       return launch_linear_x3p(A, W, bias, nullptr, C, Ch, Cl, M, N, K, epi, outsplit, qcols, 0, s, &f, wexp);
     };
-    if (temporal && fused_tp && bw.qkv_f3h) {
+    if (temporal && pl.fused_tp) {
       // temporal block: q, k, v of one (batch, joint) group stay in LDS and feed the T-key attention in the same kernel (kernels_qkv_tattn.hip)
       Prof p(e, D3D_KC_QKV_TATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)T * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_tattn(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, B, T, J, D, D, e->H, s));
       TRACE(k, 3, 0, AOx, MDb);
-    } else if (!temporal && fused_sp) {
+    } else if (!temporal && pl.fused_sp) {
       // spatial block: q, k, v of a frame group stay in LDS and feed the 17-key attention in the same kernel (kernels_qkv_sattn.hip)
       Prof p(e, D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)J * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_sattn(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, M, D, J, D, e->H, s));
@@ -539,7 +571,7 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
         TRACE(k, 4, 2, PPART, (size_t)psplit * MDb);
         Prof p(e, D3D_KC_LAYERNORM, 2.0 * M * D * (1 + psplit), MD4 * (2 + psplit), s);
         HIP_TRY(launch_splitk_residual(PPART, psplit, XP, bw.projb, XP, w.ST2, M, D, s));
-      } else if (e->opt_proj_kernel && proj_x3_ok(D, D) && (size_t)(Mw / 192) * (size_t)(D / 256) >= 512) {
+      } else if (pl.proj_own) {
         Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)D * D, 4.0 * ((double)M * D + (double)D * D + 2.0 * M * D), s, D3D_KC_LINEAR_PROJ);
         HIP_TRY(launch_proj_x3(AOx, bw.proj_x3, bw.projb, XP, w.ST2, bw.proj_e, Mw, D, D, s));
         if (M > Mw) {   // the ragged rest: the template's checked forms, on the sub-matrix behind the whole tiles
@@ -565,7 +597,7 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
         TRACE(k, 5, 2, FPART, (size_t)fsplit * M * e->Dm * 4);
         Prof p(e, D3D_KC_LAYERNORM, 12.0 * M * e->Dm, 4.0 * (double)M * e->Dm * (1 + fsplit), s);
         HIP_TRY(launch_splitk_gelu(FPART, fsplit, w.ST2, np2, bw.fc1_cs, bw.fc1_fb, e->ln_eps, HIDx, M, e->Dm, D, s));
-      } else if (fc1_own) {
+      } else if (pl.fc1_own) {
         Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)e->Dm * D, 4.0 * ((double)M * D + (double)e->Dm * D + (double)M * e->Dm), s, D3D_KC_LINEAR_FC1);
         HIP_TRY(launch_fc1_x3(XP, bw.fc1_f3, bw.fc1_fb, bw.fc1_cs, w.ST2, np2, e->ln_eps, bw.fc1_fe, HIDx, M, e->Dm, D, s));
       } else {
@@ -573,8 +605,8 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       }
     }
     TRACE(k, 5, 0, HIDx, (size_t)M * e->Dm * 4);
-    const float* pn_g = temporal ? e->tn_g : e->sn_g;
-    const float* pn_b = temporal ? e->tn_b : e->sn_b;
+    // x = post_norm(x + hidden W2^T + b2) [+ Temporal_pos_embed before TTE0] [+ next block's time vector]
+    const X3PostNorm q = block_postnorm(e, k, tvec, tvec_stride);
     const bool last = k + 1 == e->nblk;
     if (ksplit) {
       {
@@ -583,10 +615,6 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
         HIP_TRY(launch_linear_x3p_splitk(HIDx, bw.fc2_x3, PART, M, D, e->Dm, ksplit, s, bw.fc2_e));
       }
       TRACE(k, 6, 0, PART, (size_t)ksplit * MDb);
-      X3PostNorm q{};
-      q.g = pn_g; q.b = pn_b; q.eps = e->ln_eps; q.pos_div = 1; q.pos_mod = 1; q.rows_per_batch = T * J;
-      if (k == 0) { q.pos = e->tpos; q.pos_div = J; q.pos_mod = T; }
-      if (!last && tvec) { q.tvec = tvec + (size_t)(k + 1) * D; q.tvec_stride = tvec_stride; }
       {
         Prof p(e, D3D_KC_LAYERNORM, 8.0 * M * D, MD4 * (2 + ksplit), s);
         HIP_TRY(launch_splitk_postnorm(PART, ksplit, XP, bw.fc2b, q, last ? w.X : nullptr, last ? nullptr : XP, last ? nullptr : w.ST1, M, D, s));
@@ -596,12 +624,10 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       if (!last) TRACE(k, 7, 1, w.ST1, (size_t)M * 8);
       continue;
     }
-    if (pn) {  // x = post_norm(x + hidden W2^T + b2) [+ Temporal_pos_embed] [+ next block's time vector], all in the fc2 epilogue
+    if (pl.pn) {  // all in the fc2 epilogue
       X3Fold f{};
       f.Rp = XP;
-      f.pn.g = pn_g; f.pn.b = pn_b; f.pn.eps = e->ln_eps; f.pn.pos_div = 1; f.pn.pos_mod = 1; f.pn.rows_per_batch = T * J;
-      if (k == 0) { f.pn.pos = e->tpos; f.pn.pos_div = J; f.pn.pos_mod = T; }
-      if (!last && tvec) { f.pn.tvec = tvec + (size_t)(k + 1) * D; f.pn.tvec_stride = tvec_stride; }
+      f.pn = q;
       auto fc2 = [&](float* C, uint16_t* Ch, int outsplit) -> hipError_t {
         return gemm(HIDx, bw.fc2_x3, bw.fc2_e, bw.fc2b, C, Ch, nullptr, outsplit, D, e->Dm, EPI_RESIDUAL, 0, f);
       };
@@ -622,18 +648,11 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       HIP_TRY(gemm(HIDx, bw.fc2_x3, bw.fc2_e, bw.fc2b, w.HN, nullptr, nullptr, 0, D, e->Dm, EPI_RESIDUAL, 0, f));
     }
     TRACE(k, 6, 0, w.HN, MDb);
-    {  // x = post_norm(x) [+ Temporal_pos_embed before TTE0] [+ next block's time vector] -> planes + statistics (or fp32 at the end)
-      LnArgs a{};
+    {  // the post-norm as a row kernel -> planes + statistics (or fp32 at the end)
+      LnArgs a = ln_postnorm(e, M, q);
       a.x = w.HN;
-      a.g1 = pn_g; a.b1 = pn_b; a.eps1 = e->ln_eps;
-      a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
-      if (k == 0) { a.pos = e->tpos; a.pos_div = J; a.pos_mod = T; }
-      if (!last) {
-        if (tvec) { a.tvec = tvec + (size_t)(k + 1) * D; a.tvec_stride = tvec_stride; }
-        a.y_x3 = XP; a.stats = w.ST1;
-      } else {
-        a.y = w.X;
-      }
+      if (!last) { a.y_x3 = XP; a.stats = w.ST1; }
+      else a.y = w.X;
       HIP_TRY(rowk(a, 1));
     }
     TRACE(k, 7, 0, w.X, MDb);
@@ -649,8 +668,8 @@ int run_blocks_fold(d3d_engine* e, const float* x2d, const float* y, int y_bcast
 // bf16 (fc1 epilogue), weights -> bf16 (commit).  Same op sequence as run_blocks (S2S:222-247, 111-135); leaves the final
 // Temporal_norm output as fp32 in w.X.  Measured first with three LayerNorm row kernels per block, then
 // given the whole-row proj / fc2 forms below; the row-kernel flow stays behind "fused_postnorm" = 0.
-int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast, const float* tvec, int64_t tvec_stride, int B,
-                    const Workspace& w, hipStream_t s) {
+int run_blocks_bf16(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float* y, int y_bcast, const float* tvec,
+                    int64_t tvec_stride, int B, const Workspace& w, hipStream_t s) {
   const int T = e->T, J = e->J, D = e->D;
   const int M = B * T * J;
   const double MD4 = (double)M * D * 4.0, MD2 = (double)M * D * 2.0;
@@ -664,7 +683,7 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
   auto linear = [&](const uint16_t* A, const uint16_t* W, const float* bias, const float* R, float* C, uint16_t* Cb, int N, int K, int epi,
                     int qcols, int sub) -> hipError_t {
     Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)N * K, 2.0 * ((double)M * K + (double)N * K) + (double)M * N * (R ? 8.0 : 2.0), s, sub);
-    if (e->opt_bf16_gemm_kernel && !R && Cb && gemm_bf16q_ok(N, K) && (long long)((M + 255) / 256) * (N / 256) >= 2LL * device_cu_count())
+    if (sub == D3D_KC_LINEAR_QKV ? pl.bf16q_qkv : sub == D3D_KC_LINEAR_FC1 && pl.bf16q_fc1)
       return launch_gemm_bf16q(A, W, bias, Cb, M, N, K, epi, qcols, s);
     return launch_linear_bf16(A, W, bias, R, C, Cb, M, N, K, epi, qcols, s);
   };
@@ -673,15 +692,13 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
     return launch_layernorm(a, s);
   };
   {  // h = bf16(norm1_0(x))
-    LnArgs a{};
+    LnArgs a = ln_rows(M, D, T * J);
     a.x = w.X; a.h_bf16 = HNb; a.g1 = e->blk[0].n1g; a.b1 = e->blk[0].n1b; a.eps1 = e->ln_eps;
-    a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
     HIP_TRY(lnorm(a));
   }
   // Whole-row tiles for proj and fc2 (launch_linear_bf16_rows; "fused_postnorm" option, D == 512): the LayerNorm behind each of
   // them -- norm2, resp. post-norm + next norm1 -- runs in the GEMM epilogue and the three row kernels per block are gone
   // (measured first un-fused, as planned: 59 of 323 ms per sampling were LayerNorm kernels at 5 TB/s).
-  const bool rows = e->opt_fused_postnorm && bf16_rows_ok(D, D) && bf16_rows_ok(D, e->Dm);
   auto linear_rows = [&](const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* Hb, int K, const X3PostNorm& pn, int sub) -> hipError_t {
     Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)D * K, 2.0 * ((double)M * K + (double)D * K) + (double)M * D * (Hb ? 10.0 : 8.0), s, sub);
     return launch_linear_bf16_rows(A, W, bias, w.X, Hb, M, D, K, pn, s);
@@ -689,12 +706,11 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
   // qkv GEMM + attention of a block in ONE kernel (kernels_qkv_attn_bf16.hip; "fused_spatial" / "fused_temporal"): q / k / v never reach
   // HBM.  Every head's tile reads whole rows of HNb, so the attention output cannot go there: it takes w.QKV, dead in such a block.
   // Bit-identical to the two launches it replaces.
-  const bool fused_sp = bf16_fused_sp_for(e, B), fused_tp = bf16_fused_tp_for(e, B);
   for (int k = 0; k < e->nblk; ++k) {
     const BlockW& bw = e->blk[k];
     const bool temporal = (k & 1) != 0;
     const uint16_t* AOb = HNb;                             // the attention output: proj's operand
-    if (temporal ? fused_tp : fused_sp) {
+    if (temporal ? pl.fused_tp : pl.fused_sp) {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_QKV_TATTN : D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)N * D, 2.0 * MD2 + 2.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_attn_bf16(HNb, bw.qkv_x3, bw.qkvb, QKVb, temporal ? B * J : B * T, N, temporal ? J : 1, D, e->H, temporal ? 1 : 0, s));
@@ -708,46 +724,31 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
       else HIP_TRY(launch_attn_bf16(QKVb, HNb, B * T, J, 1, D, e->H, s));
     }
     }
-    if (rows) {
+    // x = post_norm(x + hidden W2^T + b2) [+ Temporal_pos_embed before TTE0] [+ next block's time vector]; h = bf16(next.norm1(x))
+    X3PostNorm post = block_postnorm(e, k, tvec, tvec_stride);
+    if (k + 1 < e->nblk) { post.g2 = e->blk[k + 1].n1g; post.b2 = e->blk[k + 1].n1b; post.eps2 = e->ln_eps; }
+    if (pl.rows) {
       {  // x += attn Wproj^T + b (fp32 stream in place); h = bf16(norm2(x)) over the attention output's rows (same tile rows: in place)
         X3PostNorm pn{};
         pn.g2 = bw.n2g; pn.b2 = bw.n2b; pn.eps2 = e->ln_eps; pn.pos_div = 1; pn.pos_mod = 1; pn.rows_per_batch = T * J;
         HIP_TRY(linear_rows(AOb, bw.proj_x3, bw.projb, HNb, D, pn, D3D_KC_LINEAR_PROJ));
       }
       HIP_TRY(linear(HNb, bw.fc1_x3, bw.fc1b, nullptr, nullptr, HIDb, e->Dm, D, EPI_GELU, 0, D3D_KC_LINEAR_FC1));
-      {  // x = post_norm(x + hidden W2^T + b2) [+ Temporal_pos_embed] [+ next block's time vector]; h = bf16(next.norm1(x))
-        X3PostNorm pn{};
-        pn.g = temporal ? e->tn_g : e->sn_g; pn.b = temporal ? e->tn_b : e->sn_b; pn.eps = e->ln_eps;
-        pn.pos_div = 1; pn.pos_mod = 1; pn.rows_per_batch = T * J;
-        if (k == 0) { pn.pos = e->tpos; pn.pos_div = J; pn.pos_mod = T; }
-        const bool last = k + 1 == e->nblk;
-        if (!last) {
-          if (tvec) { pn.tvec = tvec + (size_t)(k + 1) * D; pn.tvec_stride = tvec_stride; }
-          pn.g2 = e->blk[k + 1].n1g; pn.b2 = e->blk[k + 1].n1b; pn.eps2 = e->ln_eps;
-        }
-        HIP_TRY(linear_rows(HIDb, bw.fc2_x3, bw.fc2b, last ? nullptr : HNb, e->Dm, pn, D3D_KC_LINEAR_FC2));
-      }
+      HIP_TRY(linear_rows(HIDb, bw.fc2_x3, bw.fc2b, k + 1 < e->nblk ? HNb : nullptr, e->Dm, post, D3D_KC_LINEAR_FC2));
       continue;
     }
     HIP_TRY(linear(AOb, bw.proj_x3, bw.projb, w.X, w.X, nullptr, D, D, EPI_RESIDUAL, 0, D3D_KC_LINEAR_PROJ));
     {  // h = bf16(norm2(x))
-      LnArgs a{};
+      LnArgs a = ln_rows(M, D, T * J);
       a.x = w.X; a.h_bf16 = HNb; a.g1 = bw.n2g; a.b1 = bw.n2b; a.eps1 = e->ln_eps;
-      a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
       HIP_TRY(lnorm(a));
     }
     HIP_TRY(linear(HNb, bw.fc1_x3, bw.fc1b, nullptr, nullptr, HIDb, e->Dm, D, EPI_GELU, 0, D3D_KC_LINEAR_FC1));
     HIP_TRY(linear(HIDb, bw.fc2_x3, bw.fc2b, w.X, w.X, nullptr, D, e->Dm, EPI_RESIDUAL, 0, D3D_KC_LINEAR_FC2));
-    {  // x = post_norm(x) [+ Temporal_pos_embed before TTE0] [+ next block's time vector]; h = bf16(next.norm1(x))
-      LnArgs a{};
+    {  // the post-norm and the next norm1 as a row kernel
+      LnArgs a = ln_postnorm(e, M, post);
       a.x = w.X; a.y = w.X;
-      a.g1 = temporal ? e->tn_g : e->sn_g; a.b1 = temporal ? e->tn_b : e->sn_b; a.eps1 = e->ln_eps;
-      a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
-      if (k == 0) { a.pos = e->tpos; a.pos_div = J; a.pos_mod = T; }
-      if (k + 1 < e->nblk) {
-        if (tvec) { a.tvec = tvec + (size_t)(k + 1) * D; a.tvec_stride = tvec_stride; }
-        a.h_bf16 = HNb; a.g2 = e->blk[k + 1].n1g; a.b2 = e->blk[k + 1].n1b; a.eps2 = e->ln_eps;
-      }
+      if (k + 1 < e->nblk) { a.h_bf16 = HNb; a.g2 = post.g2; a.b2 = post.b2; a.eps2 = post.eps2; }
       HIP_TRY(lnorm(a));
     }
   }
@@ -756,14 +757,13 @@ int run_blocks_bf16(d3d_engine* e, const float* x2d, const float* y, int y_bcast
 
 // One denoiser forward up to (not including) the head: leaves the final Temporal_norm output in w.X.
 // tvec: (n, nblk, D) time-embedding table slice or nullptr; tvec_stride = 0 (all rows share entry 0) or nblk*D.
-int run_blocks(d3d_engine* e, const float* x2d, const float* y, int y_bcast, const float* tvec, int64_t tvec_stride,
+int run_blocks(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float* y, int y_bcast, const float* tvec, int64_t tvec_stride,
                int B, const Workspace& w, hipStream_t s) {
   const int T = e->T, J = e->J, D = e->D;
   const int M = B * T * J;
   const double MD4 = (double)M * D * 4.0;
-  if (fold_flow(e))
-    return run_blocks_fold(e, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
-  if (e->cfg.precision == D3D_PREC_BF16) return run_blocks_bf16(e, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
+  if (pl.flow == BlockPlan::FOLD) return run_blocks_fold(e, pl, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
+  if (pl.flow == BlockPlan::BF16) return run_blocks_bf16(e, pl, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
   {
     Prof p(e, D3D_KC_EMBED, 2.0 * M * D * e->cin, MD4 + (double)M * e->cin * 4.0, s);
     HIP_TRY(launch_embed(x2d, y, e->fus_w, e->fus_b, e->spos, tvec, tvec_stride, w.X, B, T, J, D, e->cfg.in_chans,
@@ -790,9 +790,8 @@ int run_blocks(d3d_engine* e, const float* x2d, const float* y, int y_bcast, con
     return launch_layernorm(a, s);
   };
   {  // h = norm1_0(x)
-    LnArgs a{};
-    a.x = w.X; a.y = nullptr; a.h = w.HN; a.g1 = e->blk[0].n1g; a.b1 = e->blk[0].n1b; a.eps1 = e->ln_eps;
-    a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
+    LnArgs a = ln_rows(M, D, T * J);
+    a.x = w.X; a.h = w.HN; a.g1 = e->blk[0].n1g; a.b1 = e->blk[0].n1b; a.eps1 = e->ln_eps;
     HIP_TRY(lnorm(a));
   }
   for (int k = 0; k < e->nblk; ++k) {
@@ -800,7 +799,7 @@ int run_blocks(d3d_engine* e, const float* x2d, const float* y, int y_bcast, con
     const bool temporal = (k & 1) != 0;
     // F16X3: the qkv GEMM hands q/k/v to the fp16-MFMA attention kernel as hi/lo planes.  A spatial block is the same
     // kernel over groups of J consecutive tokens (one "joint", "frames" = the J tokens of a frame, B*T "batches").
-    const bool attn_x3 = x3 && attn_temporal_x3_ok(temporal ? T : J, D, e->H);
+    const bool attn_x3 = temporal ? pl.attn_x3_tp : pl.attn_x3_sp;
     uint16_t* QKVh = reinterpret_cast<uint16_t*>(w.QKV);
     uint16_t* QKVl = QKVh + (size_t)M * 3 * D;
     qcols_ = attn_x3 ? D : 0;
@@ -820,24 +819,17 @@ int run_blocks(d3d_engine* e, const float* x2d, const float* y, int y_bcast, con
     }
     HIP_TRY(linear(w.HN, HNx, bw.projw, bw.proj_x3, bw.proj_e, bw.projb, w.X, w.X, nullptr, nullptr, 0, D, D, EPI_RESIDUAL));
     {  // h = norm2(x)
-      LnArgs a{};
-      a.x = w.X; a.y = nullptr; a.h = w.HN; a.g1 = bw.n2g; a.b1 = bw.n2b; a.eps1 = e->ln_eps;
-      a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
+      LnArgs a = ln_rows(M, D, T * J);
+      a.x = w.X; a.h = w.HN; a.g1 = bw.n2g; a.b1 = bw.n2b; a.eps1 = e->ln_eps;
       HIP_TRY(lnorm(a));
     }
     HIP_TRY(linear(w.HN, HNx, bw.fc1w, bw.fc1_x3, bw.fc1_e, bw.fc1b, nullptr, w.HID, x3 ? HIDx : nullptr, nullptr, x3 ? 2 : 0, e->Dm, D,
                    EPI_GELU));
     HIP_TRY(linear(w.HID, HIDx, bw.fc2w, bw.fc2_x3, bw.fc2_e, bw.fc2b, w.X, w.X, nullptr, nullptr, 0, D, e->Dm, EPI_RESIDUAL));
     {  // x = post_norm(x) [+ Temporal_pos_embed before TTE0] [+ next block's time vector]; h = next.norm1(x)
-      LnArgs a{};
+      LnArgs a = ln_postnorm(e, M, block_postnorm(e, k, tvec, tvec_stride));
       a.x = w.X; a.y = w.X;
-      a.g1 = temporal ? e->tn_g : e->sn_g; a.b1 = temporal ? e->tn_b : e->sn_b; a.eps1 = e->ln_eps;
-      a.rows = M; a.D = D; a.rows_per_batch = T * J; a.pos_div = 1; a.pos_mod = 1;
-      if (k == 0) { a.pos = e->tpos; a.pos_div = J; a.pos_mod = T; }
-      if (k + 1 < e->nblk) {
-        if (tvec) { a.tvec = tvec + (size_t)(k + 1) * D; a.tvec_stride = tvec_stride; }
-        a.h = w.HN; a.g2 = e->blk[k + 1].n1g; a.b2 = e->blk[k + 1].n1b; a.eps2 = e->ln_eps;
-      }
+      if (k + 1 < e->nblk) { a.h = w.HN; a.g2 = e->blk[k + 1].n1g; a.b2 = e->blk[k + 1].n1b; a.eps2 = e->ln_eps; }
       HIP_TRY(lnorm(a));
     }
   }
@@ -1258,11 +1250,7 @@ int d3d_denoise(d3d_engine* e, const float* x2d, const float* y, int32_t y_frame
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   RangeScope range_scope(e);
   Workspace w = carve(e, B, ws);
-  e->fc2_split_last = fc2_split_for(e, B);
-  e->proj_split_last = proj_split_for(e, B);
-  e->fc1_split_last = fc1_split_for(e, B);
-  e->bf16_fused_sp_last = bf16_fused_sp_for(e, B) ? 1 : 0;
-  e->bf16_fused_tp_last = bf16_fused_tp_for(e, B) ? 1 : 0;
+  const BlockPlan plan = e->last_plan = plan_blocks(e, B);
   const float* tvec = nullptr;
   int64_t stride = 0;
   if (e->Dt) {
@@ -1273,7 +1261,7 @@ int d3d_denoise(d3d_engine* e, const float* x2d, const float* y, int32_t y_frame
     tvec = w.TEMB;
     stride = (n_times == 1) ? 0 : (int64_t)e->nblk * e->D;
   }
-  rc = run_blocks(e, x2d, y, (y_frames == 1 && e->T != 1) ? 1 : 0, tvec, stride, B, w, s);
+  rc = run_blocks(e, plan, x2d, y, (y_frames == 1 && e->T != 1) ? 1 : 0, tvec, stride, B, w, s);
   if (rc) return rc;
   HeadArgs h{};
   rc = prep_head(e, h, B, w, s);
@@ -1294,12 +1282,13 @@ int ddim_loop(d3d_engine* e, const float* x2d, const float* init_noise, const fl
   const int S = e->S;
   const size_t yel = (size_t)head_rows(e, B) * 3;
   if (!step_stride) step_stride = yel;
+  const BlockPlan plan = plan_blocks(e, B);
   for (int i = 0; i < S; ++i) {
     const int t = e->times[i], tn = e->times[i + 1];
     const float* y_cur = (i == 0) ? init_noise : ((i & 1) ? w.Y0 : w.Y1);
     float* y_next = (i == S - 1) ? out : ((i & 1) ? w.Y1 : w.Y0);
     const float* tvec = e->Dt ? e->temb_sched + (size_t)i * e->nblk * e->D : nullptr;
-    int rc = run_blocks(e, x2d, y_cur, e->cfg.seq2frame ? 1 : 0, tvec, 0, B, w, s);
+    int rc = run_blocks(e, plan, x2d, y_cur, e->cfg.seq2frame ? 1 : 0, tvec, 0, B, w, s);
     if (rc) return rc;
     HeadArgs h{};
     rc = prep_head(e, h, B, w, s);
@@ -1388,11 +1377,7 @@ int d3d_ddim_sample(d3d_engine* e, const float* x2d, const float* init_noise, co
   const size_t xin_row = (size_t)e->T * e->J * e->cfg.in_chans;                 // x2d elements per sequence
   SplitWs sw{};
   if (split) sw = carve_split(e, B, ws);
-  e->fc2_split_last = fc2_split_for(e, split ? sw.B0 : B);   // (two half-batches: the first half's -- the one that holds sequence 0)
-  e->proj_split_last = proj_split_for(e, split ? sw.B0 : B);
-  e->fc1_split_last = fc1_split_for(e, split ? sw.B0 : B);
-  e->bf16_fused_sp_last = bf16_fused_sp_for(e, split ? sw.B0 : B) ? 1 : 0;
-  e->bf16_fused_tp_last = bf16_fused_tp_for(e, split ? sw.B0 : B) ? 1 : 0;
+  e->last_plan = plan_blocks(e, split ? sw.B0 : B);   // what ddim_loop runs (two half-batches: the first half's, see last_plan)
   const size_t xin0 = split ? (size_t)sw.B0 * xin_row : 0, y0 = split ? (size_t)head_rows(e, sw.B0) * 3 : 0;
   if (!use_graph) {
     if (split)
@@ -1559,13 +1544,13 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "device") *value = e->device;
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
-  else if (k == "fc2_split_last") *value = e->fc2_split_last;
-  else if (k == "proj_split_last") *value = e->proj_split_last;
-  else if (k == "fc1_split_last") *value = e->fc1_split_last;
+  else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
+  else if (k == "proj_split_last") *value = e->last_plan.proj_split;
+  else if (k == "fc1_split_last") *value = e->last_plan.fc1_split;
   else if (k == "proj_split") *value = e->opt_proj_split;
   else if (k == "fc1_split") *value = e->opt_fc1_split;
-  else if (k == "bf16_fused_spatial_last") *value = e->bf16_fused_sp_last;
-  else if (k == "bf16_fused_temporal_last") *value = e->bf16_fused_tp_last;
+  else if (k == "bf16_fused_spatial_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_sp;
+  else if (k == "bf16_fused_temporal_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_tp;
   else return fail(D3D_EINVAL, "unknown info key: " + k);
   return D3D_OK;
 }
@@ -1787,350 +1772,13 @@ const char* d3d_kernel_class_name(int32_t cls) {
   return (cls >= 0 && cls < D3D_KC_COUNT) ? names[cls] : "?";
 }
 
-// ---- single-op hooks ----------------------------------------------------------------------------------------------
+// ---- single-op hooks that read engine fields (the others: engine_ops.hip) -----------------------------------------------
 int d3d_op_time_embedding(d3d_engine* e, const float* times_dev, int32_t n, float* out, float* scratch, void* stream) {
   if (!e || !times_dev || !out || !scratch || n <= 0) return fail(D3D_EINVAL, "bad argument");
   if (!e->committed) return fail(D3D_ESTATE, "weights not committed");
   if (!e->Dt) return fail(D3D_ESTATE, "engine was built with with_time_emb = 0");
   RangeScope range_scope(e);
   return compute_temb(e, times_dev, n, out, scratch, reinterpret_cast<hipStream_t>(stream));
-}
-
-namespace {
-// test/bench helper: F16X3 pair buffer of an fp32 device matrix (rows padded to 256, zero rows).  Weights are split on
-// the host with the same routine the engine uses at commit; activations on the device with the producers' split.
-struct TmpPair {
-  uint16_t* dev = nullptr;
-  int wexp = 12;
-  ~TmpPair() { (void)hipFree(dev); }
-};
-int make_pair(TmpPair& t, const float* src_dev, int rows, int cols, bool weight, hipStream_t s) {
-  const size_t rp = ((size_t)rows + 255) / 256 * 256;
-  const size_t n16 = 2 * rp * cols;
-  HIP_TRY(hipMalloc(&t.dev, n16 * sizeof(uint16_t)));
-  HIP_TRY(hipMemsetAsync(t.dev, 0, n16 * sizeof(uint16_t), s));
-  if (weight) {
-    std::vector<float> h((size_t)rows * cols);
-    std::vector<uint16_t> pr(2 * h.size());
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(h.data(), src_dev, h.size() * sizeof(float), hipMemcpyDeviceToHost));
-    t.wexp = split_weight_f16x3(h.data(), rows, cols, pr.data());
-    HIP_TRY(hipMemcpy(t.dev, pr.data(), pr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(launch_split_x3(src_dev, t.dev, (size_t)rows, cols, s));
-  }
-  return D3D_OK;
-}
-}  // namespace
-
-int d3d_probe_machine(int32_t what, float ms_target, float* result, void* stream) {
-  if (!result || (what != 0 && what != 1) || !(ms_target > 0.f) || ms_target > 2000.f) return fail(D3D_EINVAL, "bad argument");
-  HIP_TRY(launch_probe_machine(what, ms_target, result, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
-}
-
-int d3d_op_linear(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
-                  int32_t K, int32_t epi, int32_t precision, void* stream) {
-  return d3d_op_linear_bench(A, W, bias, R, C, M, N, K, epi, precision, 0, 1, nullptr, stream);
-}
-
-int d3d_op_linear_bench(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
-                        int32_t K, int32_t epi, int32_t precision, int32_t variant, int32_t reps, float* avg_ms, void* stream) {
-  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16) return fail(D3D_EUNSUP, "precision not implemented");
-  if (!A || !W || !C || reps < 1) return fail(D3D_EINVAL, "bad argument");
-  if (K % 32) return fail(D3D_EUNSUP, "K must be a multiple of 32");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (precision == D3D_PREC_BF16) {
-    // test / bench hook of the bf16 operand mode: operands rounded to bf16 on the device (rows padded to 256, zero), the product
-    // through launch_linear_bf16; EPI_NONE / EPI_GELU results come back through the kernel's bf16 output (rounded once more)
-    if (K % 64 || N % 8) return fail(D3D_EUNSUP, "bf16 mode: K % 64 == 0 and N % 8 == 0");
-    if (epi == EPI_RESIDUAL && !R) return fail(D3D_EINVAL, "residual required");
-    const size_t mp = ((size_t)M + 255) / 256 * 256, np = ((size_t)N + 255) / 256 * 256;
-    struct DevBuf {   // (freed on every return path: HIP_TRY leaves early)
-      uint16_t* p = nullptr;
-      ~DevBuf() { (void)hipFree(p); }
-    } ab_, wb_, cb_;
-    HIP_TRY(hipMalloc(&ab_.p, mp * K * 2));
-    HIP_TRY(hipMalloc(&wb_.p, np * K * 2));
-    HIP_TRY(hipMalloc(&cb_.p, (size_t)M * N * 2));
-    uint16_t *ab = ab_.p, *wb = wb_.p, *cb = cb_.p;
-    hipError_t le = hipMemsetAsync(ab, 0, mp * K * 2, s);
-    if (le == hipSuccess) le = hipMemsetAsync(wb, 0, np * K * 2, s);
-    if (le == hipSuccess) le = launch_f32_to_bf16(A, ab, (size_t)M * K, s);
-    if (le == hipSuccess) le = launch_f32_to_bf16(W, wb, (size_t)N * K, s);
-    auto once = [&]() -> hipError_t { return launch_linear_bf16(ab, wb, bias, R, C, cb, M, N, K, epi, 0, s); };
-    if (le == hipSuccess) le = once();
-    if (le == hipSuccess && avg_ms) {
-      hipEvent_t e0, e1;
-      (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-      for (int i = 0; i < 3 && le == hipSuccess; ++i) le = once();          // warm clocks
-      (void)hipEventRecord(e0, s);
-      for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
-      (void)hipEventRecord(e1, s);
-      (void)hipEventSynchronize(e1);
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-      *avg_ms = ms / reps;
-    }
-    if (le == hipSuccess && epi != EPI_RESIDUAL) le = launch_bf16_to_f32(cb, C, (size_t)M * N, s);
-    hipError_t se = hipStreamSynchronize(s);
-    HIP_TRY(le);
-    HIP_TRY(se);
-    return D3D_OK;
-  }
-  TmpPair ap, wp;
-  if (precision == D3D_PREC_F16X3 && (N % 4) != 0) variant = 9;   // the plane kernel stores 4 columns at a time
-  if (precision == D3D_PREC_F16X3) {
-    int rc = make_pair(wp, W, N, K, true, s);
-    if (rc) return rc;
-    if (variant != 9) {
-      rc = make_pair(ap, A, M, K, false, s);
-      if (rc) return rc;
-    }
-  }
-  auto once = [&]() -> hipError_t {
-    if (precision == D3D_PREC_FP32) return launch_linear_f32(A, W, bias, R, C, M, N, K, epi, s);
-    if (variant == 9) return wp.wexp == 12 ? launch_linear_f16x3(A, wp.dev, bias, R, C, M, N, K, epi, s) : hipErrorInvalidValue;   // on-the-fly A split
-    return launch_linear_x3p(ap.dev, wp.dev, bias, R, C, nullptr, nullptr, M, N, K, epi, 0, 0, variant, s, nullptr, wp.wexp);
-  };
-  HIP_TRY(once());
-  if (avg_ms) {
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, s));
-    hipError_t le = hipSuccess;
-    for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
-    HIP_TRY(hipEventRecord(e1, s));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(le);
-    *avg_ms = ms / reps;
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return D3D_OK;
-}
-
-int d3d_op_linear_postnorm(const float* A, const float* W, const float* bias, const float* R, const float* gamma,
-                           const float* beta, float eps, const float* pos, int32_t pos_div, int32_t pos_mod, const float* tvec,
-                           int64_t tvec_stride, int32_t rows_per_batch, float* Y, float* stats, int32_t M, int32_t N, int32_t K,
-                           int32_t reps, float* avg_ms, void* stream) {
-  if (!A || !W || !bias || !R || !gamma || !beta || !Y || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
-  if (!x3q_postnorm_ok(N, K)) return fail(D3D_EUNSUP, "the post-norm GEMM form exists for N == 512, K % 32 == 0");
-  if ((pos && (pos_div < 1 || pos_mod < 1)) || (tvec && tvec_stride != 0 && rows_per_batch < 1))
-    return fail(D3D_EINVAL, "bad row-class arguments");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  TmpPair ap, wp, rp, yp;
-  int rc = make_pair(wp, W, N, K, true, s);
-  if (!rc) rc = make_pair(ap, A, M, K, false, s);
-  if (!rc) rc = make_pair(rp, R, M, N, false, s);
-  if (!rc && stats) rc = make_pair(yp, R, M, N, false, s);   // (any initialised pair buffer of the output's size)
-  if (rc) return rc;
-  const int np = x3q_ntiles(M, N);
-  float* part = nullptr;
-  if (stats) HIP_TRY(hipMalloc(&part, (size_t)M * np * 2 * sizeof(float)));
-  X3Fold f{};
-  f.Rp = rp.dev;
-  f.pn.g = gamma; f.pn.b = beta; f.pn.eps = eps;
-  f.pn.pos = pos; f.pn.pos_div = pos ? pos_div : 1; f.pn.pos_mod = pos ? pos_mod : 1;
-  f.pn.tvec = tvec; f.pn.tvec_stride = tvec_stride; f.pn.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-  f.st_out = part;
-  auto once = [&]() -> hipError_t {
-    if (stats) return launch_linear_x3p(ap.dev, wp.dev, bias, nullptr, nullptr, yp.dev, nullptr, M, N, K, EPI_RESIDUAL, 2, 0, 0, s, &f, wp.wexp);
-    return launch_linear_x3p(ap.dev, wp.dev, bias, nullptr, Y, nullptr, nullptr, M, N, K, EPI_RESIDUAL, 0, 0, 0, s, &f, wp.wexp);
-  };
-  hipError_t le = once();
-  if (le == hipSuccess && avg_ms) {
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, s);
-    for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *avg_ms = ms / reps;
-  }
-  if (le == hipSuccess && stats) le = launch_unsplit_x3(yp.dev, Y, (size_t)M, N, part, np, stats, s);
-  hipError_t se = hipStreamSynchronize(s);
-  if (part) (void)hipFree(part);
-  HIP_TRY(le);
-  HIP_TRY(se);
-  return D3D_OK;
-}
-
-int d3d_op_linear_splitk_postnorm(const float* A, const float* W, const float* bias, const float* R, const float* gamma,
-                                  const float* beta, float eps, const float* pos, int32_t pos_div, int32_t pos_mod, const float* tvec,
-                                  int64_t tvec_stride, int32_t rows_per_batch, float* Y, float* stats, int32_t M, int32_t N, int32_t K,
-                                  int32_t S, float* partials, int32_t reps, float* avg_ms, void* stream) {
-  if (!A || !W || !bias || !R || !gamma || !beta || !Y || !partials || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
-  if (!fc2_splitk_ok(N, K, S)) return fail(D3D_EUNSUP, "the split-K fc2 + post-norm pair exists for N == 512, S in {2, 4}, (K / 32) % S == 0");
-  if ((pos && (pos_div < 1 || pos_mod < 1)) || (tvec && tvec_stride != 0 && rows_per_batch < 1))
-    return fail(D3D_EINVAL, "bad row-class arguments");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  TmpPair ap, wp, rp, yp;
-  int rc = make_pair(wp, W, N, K, true, s);
-  if (!rc) rc = make_pair(ap, A, M, K, false, s);
-  if (!rc) rc = make_pair(rp, R, M, N, false, s);
-  if (!rc && stats) rc = make_pair(yp, R, M, N, false, s);   // (any initialised pair buffer of the output's size)
-  if (rc) return rc;
-  float* st1 = nullptr;
-  if (stats) HIP_TRY(hipMalloc(&st1, (size_t)M * 2 * sizeof(float)));
-  X3PostNorm q{};
-  q.g = gamma; q.b = beta; q.eps = eps;
-  q.pos = pos; q.pos_div = pos ? pos_div : 1; q.pos_mod = pos ? pos_mod : 1;
-  q.tvec = tvec; q.tvec_stride = tvec_stride; q.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-  auto gemm = [&]() -> hipError_t { return launch_linear_x3p_splitk(ap.dev, wp.dev, partials, M, N, K, S, s, wp.wexp); };
-  auto rowk = [&]() -> hipError_t {
-    return launch_splitk_postnorm(partials, S, rp.dev, bias, q, stats ? nullptr : Y, stats ? yp.dev : nullptr, st1, M, N, s);
-  };
-  auto once = [&]() -> hipError_t {   // (the row kernel reads rp and writes yp / Y: repeats see the same input)
-    const hipError_t ge = gemm();
-    return ge == hipSuccess ? rowk() : ge;
-  };
-  hipError_t le = once();
-  if (le == hipSuccess && avg_ms) {
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, s);
-    for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *avg_ms = ms / reps;
-  }
-  if (le == hipSuccess && stats) le = launch_unsplit_x3(yp.dev, Y, (size_t)M, N, st1, 1, stats, s);
-  hipError_t se = hipStreamSynchronize(s);
-  if (st1) (void)hipFree(st1);
-  HIP_TRY(le);
-  HIP_TRY(se);
-  return D3D_OK;
-}
-
-namespace {
-// mean time of `once` over reps launches on s (the op hooks' avg_ms)
-hipError_t time_reps(const std::function<hipError_t()>& once, int reps, float* avg_ms, hipStream_t s) {
-  hipError_t le = hipSuccess;
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, s);
-  for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
-  (void)hipEventRecord(e1, s);
-  (void)hipEventSynchronize(e1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *avg_ms = ms / reps;
-  return le;
-}
-struct DevF32 {   // (freed on every return path)
-  float* p = nullptr;
-  ~DevF32() { (void)hipFree(p); }
-};
-}  // namespace
-
-int d3d_op_linear_splitk_residual(const float* A, const float* W, const float* bias, const float* R, float* Y, float* stats, int32_t M,
-                                  int32_t N, int32_t K, int32_t S, float* partials, int32_t reps, float* avg_ms, void* stream) {
-  if (!A || !W || !bias || !R || !Y || (S != 0 && !partials) || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
-  if (S == 0 ? !(N == 512 && K > 0 && K % 32 == 0) : !proj_splitk_ok(N, K, S))
-    return fail(D3D_EUNSUP, "the split-K proj pair exists for N == 512, S in {2, 4}, K / 32 / S >= 4 whole k-tiles (S == 0: the default kernel)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  TmpPair ap, wp, rp, yp;
-  int rc = make_pair(wp, W, N, K, true, s);
-  if (!rc) rc = make_pair(ap, A, M, K, false, s);
-  if (!rc) rc = make_pair(rp, R, M, N, false, s);
-  if (!rc) rc = make_pair(yp, R, M, N, false, s);   // (the output planes: the residual is read from rp, so repeats see the same input)
-  if (rc) return rc;
-  const int np = x3q_ntiles(M, N);
-  DevF32 part;   // (whole 256-row tiles, as the engine's statistics buffers)
-  HIP_TRY(hipMalloc(&part.p, ((size_t)M + 255) / 256 * 256 * np * 2 * sizeof(float)));
-  X3Fold f{};
-  f.Rp = rp.dev; f.st_out = part.p;
-  auto once = [&]() -> hipError_t {
-    if (S == 0) return launch_linear_x3p(ap.dev, wp.dev, bias, nullptr, nullptr, yp.dev, nullptr, M, N, K, EPI_RESIDUAL, 2, 0, 0, s, &f, wp.wexp);
-    const hipError_t ge = launch_linear_x3p_splitk(ap.dev, wp.dev, partials, M, N, K, S, s, wp.wexp);
-    return ge == hipSuccess ? launch_splitk_residual(partials, S, rp.dev, bias, yp.dev, part.p, M, N, s) : ge;
-  };
-  hipError_t le = once();
-  if (le == hipSuccess && avg_ms) le = time_reps(once, reps, avg_ms, s);
-  if (le == hipSuccess) le = launch_unsplit_x3(yp.dev, Y, (size_t)M, N, nullptr, 0, nullptr, s);
-  if (le == hipSuccess && stats) le = hipMemcpyAsync(stats, part.p, (size_t)M * np * 2 * sizeof(float), hipMemcpyDeviceToDevice, s);
-  hipError_t se = hipStreamSynchronize(s);
-  HIP_TRY(le);
-  HIP_TRY(se);
-  return D3D_OK;
-}
-
-int d3d_op_linear_splitk_gelu(const float* X, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
-                              float* H, int32_t M, int32_t N, int32_t K, int32_t S, float* partials, int32_t reps, float* avg_ms,
-                              void* stream) {
-  if (!X || !W || !bias || !gamma || !beta || !H || (S != 0 && !partials) || M < 1 || reps < 1 || !(eps > 0.f))
-    return fail(D3D_EINVAL, "bad argument");
-  if (S == 0 ? !(N > 0 && N % 512 == 0 && K > 0 && K % 64 == 0) : !fc1_splitk_ok(N, K, S))
-    return fail(D3D_EUNSUP, "the split-K fc1 pair exists for N % 512 == 0, K % 64 == 0, S in {2, 4}, K / 32 / S >= 4 whole k-tiles (S == 0: the default kernel)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // the LayerNorm fold of the weight commit: W diag(gamma) as planes, csum, b + W beta
-  const size_t nk = (size_t)N * K;
-  std::vector<float> hw(nk), hg(K), hb(K), hbias(N), wg(nk), fold(2 * (size_t)N);
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(hw.data(), W, nk * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hg.data(), gamma, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hb.data(), beta, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hbias.data(), bias, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < (size_t)N; ++r) {
-    double c = 0.0, bsum = (double)hbias[r];
-    for (size_t q = 0; q < (size_t)K; ++q) {
-      const float wv = hw[r * K + q] * hg[q];
-      wg[r * K + q] = wv;
-      c += (double)wv;
-      bsum += (double)hw[r * K + q] * (double)hb[q];
-    }
-    fold[r] = (float)c;
-    fold[N + r] = (float)bsum;
-  }
-  TmpPair wp, xp, hp;
-  const size_t npad = ((size_t)N + 255) / 256 * 256, mpad = ((size_t)M + 255) / 256 * 256;
-  {
-    std::vector<uint16_t> pr(2 * npad * K, 0);
-    wp.wexp = split_weight_f16x3(wg.data(), N, K, pr.data());
-    HIP_TRY(hipMalloc(&wp.dev, pr.size() * sizeof(uint16_t)));
-    HIP_TRY(hipMemcpy(wp.dev, pr.data(), pr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMalloc(&xp.dev, 2 * mpad * K * sizeof(uint16_t)));
-  HIP_TRY(hipMemsetAsync(xp.dev, 0, 2 * mpad * K * sizeof(uint16_t), s));
-  HIP_TRY(hipMalloc(&hp.dev, 2 * mpad * N * sizeof(uint16_t)));
-  HIP_TRY(hipMemsetAsync(hp.dev, 0, 2 * mpad * N * sizeof(uint16_t), s));
-  DevF32 fd, st;
-  HIP_TRY(hipMalloc(&fd.p, fold.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(fd.p, fold.data(), fold.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&st.p, mpad * 2 * sizeof(float)));
-  HIP_TRY(hipMemsetAsync(st.p, 0, mpad * 2 * sizeof(float), s));
-  {  // the stream entry row kernel: planes of 8 x + one (sum, sum of squares) per row
-    LnArgs a{};
-    a.x = X; a.skip_ln1 = 1; a.y_x3 = xp.dev; a.stats = st.p;
-    a.rows = M; a.D = K; a.rows_per_batch = M; a.pos_div = 1; a.pos_mod = 1;
-    HIP_TRY(launch_layernorm(a, s));
-  }
-  X3Fold f{};
-  f.st_in = st.p; f.st_np = 1; f.csum = fd.p; f.eps = eps;
-  auto once = [&]() -> hipError_t {
-    if (S == 0) return launch_linear_x3p(xp.dev, wp.dev, fd.p + N, nullptr, nullptr, hp.dev, nullptr, M, N, K, EPI_GELU, 2, 0, 0, s, &f, wp.wexp);
-    const hipError_t ge = launch_linear_x3p_splitk(xp.dev, wp.dev, partials, M, N, K, S, s, wp.wexp);
-    return ge == hipSuccess ? launch_splitk_gelu(partials, S, st.p, 1, fd.p, fd.p + N, eps, hp.dev, M, N, K, s) : ge;
-  };
-  hipError_t le = once();
-  if (le == hipSuccess && avg_ms) le = time_reps(once, reps, avg_ms, s);
-  if (le == hipSuccess) le = launch_unsplit_acc(hp.dev, H, (size_t)M, N, s);
-  hipError_t se = hipStreamSynchronize(s);
-  HIP_TRY(le);
-  HIP_TRY(se);
-  return D3D_OK;
 }
 
 int d3d_op_head(d3d_engine* e, const float* X, float* x0, int32_t rows, void* stream) {
@@ -2140,93 +1788,6 @@ int d3d_op_head(d3d_engine* e, const float* X, float* x0, int32_t rows, void* st
   h.g = e->hd_g; h.b = e->hd_b; h.eps = 1e-5f; h.Wh = e->hd_w; h.bh = e->hd_bias; h.D = e->D;
   h.X = X; h.rows = rows; h.x0_raw = x0; h.mode = 0;
   HIP_TRY(launch_head(h, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
-}
-
-int d3d_op_qkv_attn_bf16(const float* A, const float* Wqkv, const float* bias, int32_t groups, int32_t N, int32_t stride, int32_t D,
-                         int32_t H, int32_t temporal, float* out, void* stream) {
-  if (!A || !Wqkv || !bias || !out || groups <= 0 || N <= 0 || stride <= 0 || D <= 0 || H <= 0 || groups % stride) return fail(D3D_EINVAL, "bad argument");
-  const int T = temporal ? N : groups / stride, J = temporal ? stride : N, B = temporal ? groups / stride : 1;
-  if (!(temporal ? qkv_tattn_bf16_ok(T, J, D, H, B) : qkv_sattn_bf16_ok(T, J, D, H, B)))
-    return fail(D3D_EUNSUP, "fused bf16 qkv + attention: head_dim 64, D % 128 == 0, D >= 256, groups of <= 255 tokens (spatial: <= 32)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // test hook: operands rounded to bf16 on the device into buffers of EXACTLY the operand sizes (the kernel reads no pad rows), the fused
-  // kernel alone, its bf16 output widened to fp32
-  const size_t rows = (size_t)groups * N, na = rows * D, nw = (size_t)3 * D * D;
-  struct DevBuf {
-    uint16_t* p = nullptr;
-    ~DevBuf() { (void)hipFree(p); }
-  } ab, wb, ob;
-  HIP_TRY(hipMalloc(&ab.p, na * 2));
-  HIP_TRY(hipMalloc(&wb.p, nw * 2));
-  HIP_TRY(hipMalloc(&ob.p, na * 2));
-  hipError_t le = launch_f32_to_bf16(A, ab.p, na, s);
-  if (le == hipSuccess) le = launch_f32_to_bf16(Wqkv, wb.p, nw, s);
-  if (le == hipSuccess) le = hipMemsetAsync(ob.p, 0xff, na * 2, s);   // (NaN: a row the kernel skipped shows)
-  if (le == hipSuccess) le = launch_qkv_attn_bf16(ab.p, wb.p, bias, ob.p, groups, N, stride, D, H, temporal ? 1 : 0, s);
-  if (le == hipSuccess) le = launch_bf16_to_f32(ob.p, out, na, s);
-  hipError_t se = hipStreamSynchronize(s);
-  HIP_TRY(le);
-  HIP_TRY(se);
-  return D3D_OK;
-}
-
-int d3d_op_layernorm(const float* x, const float* gamma, const float* beta, float* out, int32_t rows, int32_t D, float eps,
-                     void* stream) {
-  if (!x || !gamma || !beta || !out) return fail(D3D_EINVAL, "null tensor");
-  LnArgs a{};
-  a.x = x; a.y = out; a.g1 = gamma; a.b1 = beta; a.eps1 = eps; a.rows = rows; a.D = D; a.rows_per_batch = 1;
-  a.pos_div = 1; a.pos_mod = 1;
-  HIP_TRY(launch_layernorm(a, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
-}
-
-int d3d_op_attention(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
-                     int32_t precision, int32_t force_generic, void* stream) {
-  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16) return fail(D3D_EUNSUP, "precision not implemented");
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (precision == D3D_PREC_BF16) {
-    // test hook: fp32 qkv -> bf16 (q third scaled by 2^-3, as the qkv GEMM epilogue writes it) -> bf16-MFMA attention -> fp32
-    const int N = temporal ? T : J;
-    if (!attn_bf16_ok(N, D, H)) return fail(D3D_EUNSUP, "bf16 attention: head_dim 64, group length <= 256");
-    const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-    float* qs = nullptr;
-    uint16_t* tmp = nullptr;
-    HIP_TRY(hipMalloc(&qs, nq * sizeof(float)));
-    HIP_TRY(hipMalloc(&tmp, (nq + no) * sizeof(uint16_t)));
-    hipError_t le = hipMemcpyAsync(qs, qkv, nq * sizeof(float), hipMemcpyDeviceToDevice, s);
-    if (le == hipSuccess) le = launch_scale_cols(qs, rows, 3 * D, D, 0.125f, s);
-    if (le == hipSuccess) le = launch_f32_to_bf16(qs, tmp, nq, s);
-    if (le == hipSuccess) le = temporal ? launch_attn_bf16(tmp, tmp + nq, B, T, J, D, H, s) : launch_attn_bf16(tmp, tmp + nq, B * T, J, 1, D, H, s);
-    if (le == hipSuccess) le = launch_bf16_to_f32(tmp + nq, out, no, s);
-    hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(qs); (void)hipFree(tmp);
-    HIP_TRY(le);
-    HIP_TRY(se);
-    return D3D_OK;
-  }
-  if (precision == D3D_PREC_F16X3 && temporal && !force_generic && attn_temporal_x3_ok(T, D, H)) {
-    // test hook: fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> fp16-MFMA attention -> pair layout -> fp32
-    const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-    uint16_t* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, (2 * nq + 2 * no) * sizeof(uint16_t)));
-    hipError_t e1 = launch_split_qkv(qkv, tmp, tmp + nq, rows, D, s);
-    hipError_t e2 = (e1 == hipSuccess) ? launch_attn_temporal_x3(tmp, tmp + nq, tmp + 2 * nq, B, T, J, D, H, s) : e1;
-    hipError_t e3 = (e2 == hipSuccess) ? launch_unsplit_pair(tmp + 2 * nq, out, rows, D, s) : e2;
-    hipError_t e4 = hipStreamSynchronize(s);
-    (void)hipFree(tmp);
-    HIP_TRY(e3);
-    HIP_TRY(e4);
-    return D3D_OK;
-  }
-  if (!force_generic && !temporal && attn_spatial_fast_ok(J, D, H)) {
-    HIP_TRY(launch_attn_spatial_f32(qkv, out, nullptr, B, T, J, D, H, s));
-  } else if (!force_generic && temporal && attn_temporal_fast_ok(T, D, H)) {
-    HIP_TRY(launch_attn_temporal_f32(qkv, out, nullptr, B, T, J, D, H, s));
-  } else {
-    HIP_TRY(launch_attn_generic(qkv, out, nullptr, B, T, J, D, H, temporal, s));
-  }
   return D3D_OK;
 }
 

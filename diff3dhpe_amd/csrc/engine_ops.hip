@@ -1,0 +1,369 @@
+// Single-op test / bench hooks of the C ABI that need no engine: each allocates its temporaries, brings the fp32 operands into the
+// kernel's operand form, runs the launch sequence once (`once`), optionally times `reps` more, converts the result back to fp32 and
+// synchronises the caller's stream.  d3d_op_time_embedding and d3d_op_head read engine fields and live in engine.hip.
+#include <hip/hip_runtime.h>
+
+#include <functional>
+#include <vector>
+
+#include "d3d_kernels.h"
+#include "engine_internal.h"
+
+using namespace d3d;
+
+namespace {
+
+// device memory of n elements, freed on every return path (HIP_TRY leaves early)
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { (void)hipFree(p); }
+  hipError_t alloc(size_t n) { return hipMalloc(&p, n * sizeof(T)); }
+};
+
+size_t pad256(size_t n) { return (n + 255) / 256 * 256; }
+
+// F16X3 pair buffer of an fp32 device matrix (rows padded to 256, zero rows).  Weights are split on the host with the same routine the
+// engine uses at commit; activations on the device with the producers' split.
+struct TmpPair : DevBuf<uint16_t> {
+  int wexp = 12;
+};
+int make_pair(TmpPair& t, const float* src_dev, int rows, int cols, bool weight, hipStream_t s) {
+  const size_t n16 = 2 * pad256(rows) * cols;
+  HIP_TRY(t.alloc(n16));
+  HIP_TRY(hipMemsetAsync(t.p, 0, n16 * sizeof(uint16_t), s));
+  if (weight) {
+    std::vector<float> h((size_t)rows * cols);
+    std::vector<uint16_t> pr(2 * h.size());
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(h.data(), src_dev, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+    t.wexp = split_weight_f16x3(h.data(), rows, cols, pr.data());
+    HIP_TRY(hipMemcpy(t.p, pr.data(), pr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(launch_split_x3(src_dev, t.p, (size_t)rows, cols, s));
+  }
+  return D3D_OK;
+}
+
+// The operand pairs of C = A W^T [+ R]: W [N][K], then A [M][K] and R [M][N] where given, then (with_y) the output planes [M][N] -- any
+// initialised pair buffer of that size; a hook reads its residual from r, so repeats see the same input.
+struct X3Operands { TmpPair a, w, r, y; };
+int make_operands(X3Operands& o, const float* A, const float* W, const float* R, int M, int N, int K, bool with_y, hipStream_t s) {
+  int rc = make_pair(o.w, W, N, K, true, s);
+  if (!rc && A) rc = make_pair(o.a, A, M, K, false, s);
+  if (!rc && R) rc = make_pair(o.r, R, M, N, false, s);
+  if (!rc && with_y) rc = make_pair(o.y, R, M, N, false, s);
+  return rc;
+}
+
+// mean time of `once` over reps launches on s, behind `warm` untimed ones (the op hooks' avg_ms)
+hipError_t time_reps(const std::function<hipError_t()>& once, int reps, float* avg_ms, hipStream_t s, int warm = 0) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t le = hipEventCreate(&e0);
+  if (le == hipSuccess) le = hipEventCreate(&e1);
+  for (int i = 0; i < warm && le == hipSuccess; ++i) le = once();
+  if (le == hipSuccess) le = hipEventRecord(e0, s);
+  for (int i = 0; i < reps && le == hipSuccess; ++i) le = once();
+  if (le == hipSuccess) le = hipEventRecord(e1, s);
+  if (le == hipSuccess) le = hipEventSynchronize(e1);
+  float ms = 0.f;
+  if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (le == hipSuccess) *avg_ms = ms / reps;
+  return le;
+}
+
+// `once`, then the timed repeats where the caller asked for them
+hipError_t run_timed(const std::function<hipError_t()>& once, int reps, float* avg_ms, hipStream_t s, int warm = 0) {
+  const hipError_t le = once();
+  return le == hipSuccess && avg_ms ? time_reps(once, reps, avg_ms, s, warm) : le;
+}
+
+// the post-norm row arguments of the two post-norm hooks, from the caller's
+bool row_class_args_ok(const float* pos, int pos_div, int pos_mod, const float* tvec, int64_t tvec_stride, int rows_per_batch) {
+  return !(pos && (pos_div < 1 || pos_mod < 1)) && !(tvec && tvec_stride != 0 && rows_per_batch < 1);
+}
+X3PostNorm hook_postnorm(const float* gamma, const float* beta, float eps, const float* pos, int pos_div, int pos_mod, const float* tvec,
+                         int64_t tvec_stride, int rows_per_batch) {
+  X3PostNorm q{};
+  q.g = gamma; q.b = beta; q.eps = eps;
+  q.pos = pos; q.pos_div = pos ? pos_div : 1; q.pos_mod = pos ? pos_mod : 1;
+  q.tvec = tvec; q.tvec_stride = tvec_stride; q.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
+  return q;
+}
+
+// the hooks' common tail: the launch status first, then the stream's
+int finish(hipError_t le, hipStream_t s) {
+  const hipError_t se = hipStreamSynchronize(s);
+  HIP_TRY(le);
+  HIP_TRY(se);
+  return D3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int d3d_probe_machine(int32_t what, float ms_target, float* result, void* stream) {
+  if (!result || (what != 0 && what != 1) || !(ms_target > 0.f) || ms_target > 2000.f) return fail(D3D_EINVAL, "bad argument");
+  HIP_TRY(launch_probe_machine(what, ms_target, result, reinterpret_cast<hipStream_t>(stream)));
+  return D3D_OK;
+}
+
+int d3d_op_linear(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
+                  int32_t K, int32_t epi, int32_t precision, void* stream) {
+  return d3d_op_linear_bench(A, W, bias, R, C, M, N, K, epi, precision, 0, 1, nullptr, stream);
+}
+
+int d3d_op_linear_bench(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
+                        int32_t K, int32_t epi, int32_t precision, int32_t variant, int32_t reps, float* avg_ms, void* stream) {
+  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16) return fail(D3D_EUNSUP, "precision not implemented");
+  if (!A || !W || !C || reps < 1) return fail(D3D_EINVAL, "bad argument");
+  if (K % 32) return fail(D3D_EUNSUP, "K must be a multiple of 32");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (precision == D3D_PREC_BF16) {
+    // the bf16 operand mode: operands rounded to bf16 on the device (rows padded to 256, zero), the product through launch_linear_bf16;
+    // EPI_NONE / EPI_GELU results come back through the kernel's bf16 output (rounded once more)
+    if (K % 64 || N % 8) return fail(D3D_EUNSUP, "bf16 mode: K % 64 == 0 and N % 8 == 0");
+    if (epi == EPI_RESIDUAL && !R) return fail(D3D_EINVAL, "residual required");
+    const size_t mp = pad256(M), np = pad256(N);
+    DevBuf<uint16_t> ab, wb, cb;
+    HIP_TRY(ab.alloc(mp * K));
+    HIP_TRY(wb.alloc(np * K));
+    HIP_TRY(cb.alloc((size_t)M * N));
+    hipError_t le = hipMemsetAsync(ab.p, 0, mp * K * 2, s);
+    if (le == hipSuccess) le = hipMemsetAsync(wb.p, 0, np * K * 2, s);
+    if (le == hipSuccess) le = launch_f32_to_bf16(A, ab.p, (size_t)M * K, s);
+    if (le == hipSuccess) le = launch_f32_to_bf16(W, wb.p, (size_t)N * K, s);
+    auto once = [&]() -> hipError_t { return launch_linear_bf16(ab.p, wb.p, bias, R, C, cb.p, M, N, K, epi, 0, s); };
+    if (le == hipSuccess) le = run_timed(once, reps, avg_ms, s, /*warm clocks*/ 3);
+    if (le == hipSuccess && epi != EPI_RESIDUAL) le = launch_bf16_to_f32(cb.p, C, (size_t)M * N, s);
+    return finish(le, s);
+  }
+  X3Operands o;
+  if (precision == D3D_PREC_F16X3 && (N % 4) != 0) variant = 9;   // the plane kernel stores 4 columns at a time
+  if (precision == D3D_PREC_F16X3) {
+    const int rc = make_operands(o, variant != 9 ? A : nullptr, W, nullptr, M, N, K, false, s);
+    if (rc) return rc;
+  }
+  auto once = [&]() -> hipError_t {
+    if (precision == D3D_PREC_FP32) return launch_linear_f32(A, W, bias, R, C, M, N, K, epi, s);
+    if (variant == 9) return o.w.wexp == 12 ? launch_linear_f16x3(A, o.w.p, bias, R, C, M, N, K, epi, s) : hipErrorInvalidValue;   // on-the-fly A split
+    return launch_linear_x3p(o.a.p, o.w.p, bias, R, C, nullptr, nullptr, M, N, K, epi, 0, 0, variant, s, nullptr, o.w.wexp);
+  };
+  return finish(run_timed(once, reps, avg_ms, s), s);
+}
+
+int d3d_op_linear_postnorm(const float* A, const float* W, const float* bias, const float* R, const float* gamma,
+                           const float* beta, float eps, const float* pos, int32_t pos_div, int32_t pos_mod, const float* tvec,
+                           int64_t tvec_stride, int32_t rows_per_batch, float* Y, float* stats, int32_t M, int32_t N, int32_t K,
+                           int32_t reps, float* avg_ms, void* stream) {
+  if (!A || !W || !bias || !R || !gamma || !beta || !Y || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
+  if (!x3q_postnorm_ok(N, K)) return fail(D3D_EUNSUP, "the post-norm GEMM form exists for N == 512, K % 32 == 0");
+  if (!row_class_args_ok(pos, pos_div, pos_mod, tvec, tvec_stride, rows_per_batch)) return fail(D3D_EINVAL, "bad row-class arguments");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  X3Operands o;
+  const int rc = make_operands(o, A, W, R, M, N, K, stats != nullptr, s);
+  if (rc) return rc;
+  const int np = x3q_ntiles(M, N);
+  DevBuf<float> part;
+  if (stats) HIP_TRY(part.alloc((size_t)M * np * 2));
+  X3Fold f{};
+  f.Rp = o.r.p;
+  f.pn = hook_postnorm(gamma, beta, eps, pos, pos_div, pos_mod, tvec, tvec_stride, rows_per_batch);
+  f.st_out = part.p;
+  auto once = [&]() -> hipError_t {
+    if (stats) return launch_linear_x3p(o.a.p, o.w.p, bias, nullptr, nullptr, o.y.p, nullptr, M, N, K, EPI_RESIDUAL, 2, 0, 0, s, &f, o.w.wexp);
+    return launch_linear_x3p(o.a.p, o.w.p, bias, nullptr, Y, nullptr, nullptr, M, N, K, EPI_RESIDUAL, 0, 0, 0, s, &f, o.w.wexp);
+  };
+  hipError_t le = run_timed(once, reps, avg_ms, s);
+  if (le == hipSuccess && stats) le = launch_unsplit_x3(o.y.p, Y, (size_t)M, N, part.p, np, stats, s);
+  return finish(le, s);
+}
+
+int d3d_op_linear_splitk_postnorm(const float* A, const float* W, const float* bias, const float* R, const float* gamma,
+                                  const float* beta, float eps, const float* pos, int32_t pos_div, int32_t pos_mod, const float* tvec,
+                                  int64_t tvec_stride, int32_t rows_per_batch, float* Y, float* stats, int32_t M, int32_t N, int32_t K,
+                                  int32_t S, float* partials, int32_t reps, float* avg_ms, void* stream) {
+  if (!A || !W || !bias || !R || !gamma || !beta || !Y || !partials || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
+  if (!fc2_splitk_ok(N, K, S)) return fail(D3D_EUNSUP, "the split-K fc2 + post-norm pair exists for N == 512, S in {2, 4}, (K / 32) % S == 0");
+  if (!row_class_args_ok(pos, pos_div, pos_mod, tvec, tvec_stride, rows_per_batch)) return fail(D3D_EINVAL, "bad row-class arguments");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  X3Operands o;
+  const int rc = make_operands(o, A, W, R, M, N, K, stats != nullptr, s);
+  if (rc) return rc;
+  DevBuf<float> st1;
+  if (stats) HIP_TRY(st1.alloc((size_t)M * 2));
+  const X3PostNorm q = hook_postnorm(gamma, beta, eps, pos, pos_div, pos_mod, tvec, tvec_stride, rows_per_batch);
+  auto once = [&]() -> hipError_t {   // (the row kernel reads o.r and writes o.y / Y: repeats see the same input)
+    const hipError_t ge = launch_linear_x3p_splitk(o.a.p, o.w.p, partials, M, N, K, S, s, o.w.wexp);
+    if (ge != hipSuccess) return ge;
+    return launch_splitk_postnorm(partials, S, o.r.p, bias, q, stats ? nullptr : Y, stats ? o.y.p : nullptr, st1.p, M, N, s);
+  };
+  hipError_t le = run_timed(once, reps, avg_ms, s);
+  if (le == hipSuccess && stats) le = launch_unsplit_x3(o.y.p, Y, (size_t)M, N, st1.p, 1, stats, s);
+  return finish(le, s);
+}
+
+int d3d_op_linear_splitk_residual(const float* A, const float* W, const float* bias, const float* R, float* Y, float* stats, int32_t M,
+                                  int32_t N, int32_t K, int32_t S, float* partials, int32_t reps, float* avg_ms, void* stream) {
+  if (!A || !W || !bias || !R || !Y || (S != 0 && !partials) || M < 1 || reps < 1) return fail(D3D_EINVAL, "bad argument");
+  if (S == 0 ? !(N == 512 && K > 0 && K % 32 == 0) : !proj_splitk_ok(N, K, S))
+    return fail(D3D_EUNSUP, "the split-K proj pair exists for N == 512, S in {2, 4}, K / 32 / S >= 4 whole k-tiles (S == 0: the default kernel)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  X3Operands o;
+  const int rc = make_operands(o, A, W, R, M, N, K, true, s);
+  if (rc) return rc;
+  const int np = x3q_ntiles(M, N);
+  DevBuf<float> part;   // (whole 256-row tiles, as the engine's statistics buffers)
+  HIP_TRY(part.alloc(pad256(M) * np * 2));
+  X3Fold f{};
+  f.Rp = o.r.p; f.st_out = part.p;
+  auto once = [&]() -> hipError_t {
+    if (S == 0) return launch_linear_x3p(o.a.p, o.w.p, bias, nullptr, nullptr, o.y.p, nullptr, M, N, K, EPI_RESIDUAL, 2, 0, 0, s, &f, o.w.wexp);
+    const hipError_t ge = launch_linear_x3p_splitk(o.a.p, o.w.p, partials, M, N, K, S, s, o.w.wexp);
+    return ge == hipSuccess ? launch_splitk_residual(partials, S, o.r.p, bias, o.y.p, part.p, M, N, s) : ge;
+  };
+  hipError_t le = run_timed(once, reps, avg_ms, s);
+  if (le == hipSuccess) le = launch_unsplit_x3(o.y.p, Y, (size_t)M, N, nullptr, 0, nullptr, s);
+  if (le == hipSuccess && stats) le = hipMemcpyAsync(stats, part.p, (size_t)M * np * 2 * sizeof(float), hipMemcpyDeviceToDevice, s);
+  return finish(le, s);
+}
+
+int d3d_op_linear_splitk_gelu(const float* X, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
+                              float* H, int32_t M, int32_t N, int32_t K, int32_t S, float* partials, int32_t reps, float* avg_ms,
+                              void* stream) {
+  if (!X || !W || !bias || !gamma || !beta || !H || (S != 0 && !partials) || M < 1 || reps < 1 || !(eps > 0.f))
+    return fail(D3D_EINVAL, "bad argument");
+  if (S == 0 ? !(N > 0 && N % 512 == 0 && K > 0 && K % 64 == 0) : !fc1_splitk_ok(N, K, S))
+    return fail(D3D_EUNSUP, "the split-K fc1 pair exists for N % 512 == 0, K % 64 == 0, S in {2, 4}, K / 32 / S >= 4 whole k-tiles (S == 0: the default kernel)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // the LayerNorm fold of the weight commit: W diag(gamma) as planes, csum, b + W beta
+  const size_t nk = (size_t)N * K;
+  std::vector<float> hw(nk), hg(K), hb(K), hbias(N), wg(nk), fold(2 * (size_t)N);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(hw.data(), W, nk * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hg.data(), gamma, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hb.data(), beta, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hbias.data(), bias, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < (size_t)N; ++r) {
+    double c = 0.0, bsum = (double)hbias[r];
+    for (size_t q = 0; q < (size_t)K; ++q) {
+      const float wv = hw[r * K + q] * hg[q];
+      wg[r * K + q] = wv;
+      c += (double)wv;
+      bsum += (double)hw[r * K + q] * (double)hb[q];
+    }
+    fold[r] = (float)c;
+    fold[N + r] = (float)bsum;
+  }
+  TmpPair wp, xp, hp;
+  const size_t npad = pad256(N), mpad = pad256(M);
+  {
+    std::vector<uint16_t> pr(2 * npad * K, 0);
+    wp.wexp = split_weight_f16x3(wg.data(), N, K, pr.data());
+    HIP_TRY(wp.alloc(pr.size()));
+    HIP_TRY(hipMemcpy(wp.p, pr.data(), pr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(xp.alloc(2 * mpad * K));
+  HIP_TRY(hipMemsetAsync(xp.p, 0, 2 * mpad * K * sizeof(uint16_t), s));
+  HIP_TRY(hp.alloc(2 * mpad * N));
+  HIP_TRY(hipMemsetAsync(hp.p, 0, 2 * mpad * N * sizeof(uint16_t), s));
+  DevBuf<float> fd, st;
+  HIP_TRY(fd.alloc(fold.size()));
+  HIP_TRY(hipMemcpy(fd.p, fold.data(), fold.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(st.alloc(mpad * 2));
+  HIP_TRY(hipMemsetAsync(st.p, 0, mpad * 2 * sizeof(float), s));
+  {  // the stream entry row kernel: planes of 8 x + one (sum, sum of squares) per row
+    LnArgs a = ln_rows(M, K, M);
+    a.x = X; a.skip_ln1 = 1; a.y_x3 = xp.p; a.stats = st.p;
+    HIP_TRY(launch_layernorm(a, s));
+  }
+  X3Fold f{};
+  f.st_in = st.p; f.st_np = 1; f.csum = fd.p; f.eps = eps;
+  auto once = [&]() -> hipError_t {
+    if (S == 0) return launch_linear_x3p(xp.p, wp.p, fd.p + N, nullptr, nullptr, hp.p, nullptr, M, N, K, EPI_GELU, 2, 0, 0, s, &f, wp.wexp);
+    const hipError_t ge = launch_linear_x3p_splitk(xp.p, wp.p, partials, M, N, K, S, s, wp.wexp);
+    return ge == hipSuccess ? launch_splitk_gelu(partials, S, st.p, 1, fd.p, fd.p + N, eps, hp.p, M, N, K, s) : ge;
+  };
+  hipError_t le = run_timed(once, reps, avg_ms, s);
+  if (le == hipSuccess) le = launch_unsplit_acc(hp.p, H, (size_t)M, N, s);
+  return finish(le, s);
+}
+
+int d3d_op_qkv_attn_bf16(const float* A, const float* Wqkv, const float* bias, int32_t groups, int32_t N, int32_t stride, int32_t D,
+                         int32_t H, int32_t temporal, float* out, void* stream) {
+  if (!A || !Wqkv || !bias || !out || groups <= 0 || N <= 0 || stride <= 0 || D <= 0 || H <= 0 || groups % stride) return fail(D3D_EINVAL, "bad argument");
+  const int T = temporal ? N : groups / stride, J = temporal ? stride : N, B = temporal ? groups / stride : 1;
+  if (!(temporal ? qkv_tattn_bf16_ok(T, J, D, H, B) : qkv_sattn_bf16_ok(T, J, D, H, B)))
+    return fail(D3D_EUNSUP, "fused bf16 qkv + attention: head_dim 64, D % 128 == 0, D >= 256, groups of <= 255 tokens (spatial: <= 32)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // operands rounded to bf16 on the device into buffers of EXACTLY the operand sizes (the kernel reads no pad rows), the fused kernel
+  // alone, its bf16 output widened to fp32
+  const size_t rows = (size_t)groups * N, na = rows * D, nw = (size_t)3 * D * D;
+  DevBuf<uint16_t> ab, wb, ob;
+  HIP_TRY(ab.alloc(na));
+  HIP_TRY(wb.alloc(nw));
+  HIP_TRY(ob.alloc(na));
+  hipError_t le = launch_f32_to_bf16(A, ab.p, na, s);
+  if (le == hipSuccess) le = launch_f32_to_bf16(Wqkv, wb.p, nw, s);
+  if (le == hipSuccess) le = hipMemsetAsync(ob.p, 0xff, na * 2, s);   // (NaN: a row the kernel skipped shows)
+  if (le == hipSuccess) le = launch_qkv_attn_bf16(ab.p, wb.p, bias, ob.p, groups, N, stride, D, H, temporal ? 1 : 0, s);
+  if (le == hipSuccess) le = launch_bf16_to_f32(ob.p, out, na, s);
+  return finish(le, s);
+}
+
+int d3d_op_layernorm(const float* x, const float* gamma, const float* beta, float* out, int32_t rows, int32_t D, float eps,
+                     void* stream) {
+  if (!x || !gamma || !beta || !out) return fail(D3D_EINVAL, "null tensor");
+  LnArgs a = ln_rows(rows, D, 1);
+  a.x = x; a.y = out; a.g1 = gamma; a.b1 = beta; a.eps1 = eps;
+  HIP_TRY(launch_layernorm(a, reinterpret_cast<hipStream_t>(stream)));
+  return D3D_OK;
+}
+
+int d3d_op_attention(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                     int32_t precision, int32_t force_generic, void* stream) {
+  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16) return fail(D3D_EUNSUP, "precision not implemented");
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
+  if (precision == D3D_PREC_BF16) {
+    // fp32 qkv -> bf16 (q third scaled by 2^-3, as the qkv GEMM epilogue writes it) -> bf16-MFMA attention -> fp32
+    const int N = temporal ? T : J;
+    if (!attn_bf16_ok(N, D, H)) return fail(D3D_EUNSUP, "bf16 attention: head_dim 64, group length <= 256");
+    DevBuf<float> qs;
+    DevBuf<uint16_t> tmp;
+    HIP_TRY(qs.alloc(nq));
+    HIP_TRY(tmp.alloc(nq + no));
+    hipError_t le = hipMemcpyAsync(qs.p, qkv, nq * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (le == hipSuccess) le = launch_scale_cols(qs.p, rows, 3 * D, D, 0.125f, s);
+    if (le == hipSuccess) le = launch_f32_to_bf16(qs.p, tmp.p, nq, s);
+    if (le == hipSuccess) le = temporal ? launch_attn_bf16(tmp.p, tmp.p + nq, B, T, J, D, H, s) : launch_attn_bf16(tmp.p, tmp.p + nq, B * T, J, 1, D, H, s);
+    if (le == hipSuccess) le = launch_bf16_to_f32(tmp.p + nq, out, no, s);
+    return finish(le, s);
+  }
+  if (precision == D3D_PREC_F16X3 && temporal && !force_generic && attn_temporal_x3_ok(T, D, H)) {
+    // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> fp16-MFMA attention -> pair layout -> fp32
+    DevBuf<uint16_t> tmp;
+    HIP_TRY(tmp.alloc(2 * nq + 2 * no));
+    hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
+    if (le == hipSuccess) le = launch_attn_temporal_x3(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s);
+    if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
+    return finish(le, s);
+  }
+  if (!force_generic && !temporal && attn_spatial_fast_ok(J, D, H)) {
+    HIP_TRY(launch_attn_spatial_f32(qkv, out, nullptr, B, T, J, D, H, s));
+  } else if (!force_generic && temporal && attn_temporal_fast_ok(T, D, H)) {
+    HIP_TRY(launch_attn_temporal_f32(qkv, out, nullptr, B, T, J, D, H, s));
+  } else {
+    HIP_TRY(launch_attn_generic(qkv, out, nullptr, B, T, J, D, H, temporal, s));
+  }
+  return D3D_OK;
+}
+
+}  // extern "C"
