@@ -324,9 +324,10 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3p(const _Floa
   // middle of unit u and awaited ONCE, at the top of unit u+1: with 4 planes a wave had one of K / V in flight at a time,
   // each hidden only by half a unit of arithmetic, and the launch ran at the latency x concurrency limit (3.9 TB/s)
   // -- and its planes hold T rows, not TP: a fragment read of the pad rows [T, TP) runs on into the next plane (the next
-  // wave's slice, a zeroed tail behind the last one).  That is harmless: whatever finite fp16 values stand there, the
-  // scores of keys >= T are overwritten with -inf before the softmax and their E is an exact 0 in the PV product; the whole
-  // allocation is zeroed once so that nothing non-finite is ever read.  13 KiB per wave instead of 24.
+  // wave's slice, a zeroed tail behind the last one).  What stands there may be ANOTHER group's planes, NaN / Inf included: the
+  // scores of keys >= T are overwritten with -inf before the softmax, so K may hold any bits; their E is an exact 0 in the PV
+  // product, and the V fragments of those keys are masked to zeros in registers there (0 x NaN would be NaN).  The whole
+  // allocation is zeroed once (the tail behind the last wave stays zero).  13 KiB per wave instead of 24.
   constexpr int NPL = WAVEP ? 6 : 4;
   const int PL = WAVEP ? T * 128 : PLANE;         // plane stride in bytes
   unsigned char* const lds = lds_all + (WAVEP ? (int)(threadIdx.x >> 6) * NPL * PL : 0);
@@ -522,6 +523,19 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3p(const _Floa
         }
         const int k0 = kt * 32 + 16 * s2 + 4 * h;
         const int gi = lane & 15, tq_ = gi >> 2, tp_ = gi & 3;
+        // WAVEP: the planes hold T rows, so the V fragments of the pad keys [T, TP) are whatever follows the plane -- the wave's other V
+        // buffer (another unit's V) or the next wave's K -- and may be NaN / Inf planes of ANOTHER group (the GEMM epilogues store a NaN
+        // as a NaN): E is an exact 0 there, and 0 x NaN is NaN.  Their bits are masked to +0 in registers; element e of a fragment is
+        // key k0 + e (e < 4) / k0 + 4 + e (e >= 4).  Only the half-tile that holds keys >= T pays for it (wave-uniform branch).
+        const bool vpad = WAVEP && kt * 32 + 16 * s2 + 16 > T;
+        u32x4 vmask = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+        if (vpad) {
+#pragma unroll
+          for (int j2 = 0; j2 < 4; ++j2) {
+            const int ka = k0 + 8 * (j2 >> 1) + 2 * (j2 & 1);      // key of element 2 j2; element 2 j2 + 1 is the next key
+            vmask[j2] = (ka < T ? 0x0000ffffu : 0u) | (ka + 1 < T ? 0xffff0000u : 0u);
+          }
+        }
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           const int d0 = dt * 32 + 16 * ((lane >> 4) & 1);
@@ -537,6 +551,10 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3p(const _Floa
             const h4 c0h = __builtin_bit_cast(h4, c0), c1h = __builtin_bit_cast(h4, c1);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { vh[e] = a0h[e]; vh[4 + e] = a1h[e]; vl[e] = c0h[e]; vl[4 + e] = c1h[e]; }
+          }
+          if (vpad) {
+            vh = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vh) & vmask);
+            vl = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vl) & vmask);
           }
           oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, eh, oacc[dt], 0, 0, 0);
           oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, el, oacc[dt], 0, 0, 0);

@@ -46,3 +46,64 @@ def build_product(cfg, seed, sampling=9, eta=0.0, clip=True, device="cuda", prec
 
 def maxabs(a, b):
     return (a.detach().cpu().double() - torch.as_tensor(b).double()).abs().max().item()
+
+
+# ------------------------------------------------------------------------------------------------ row isolation / guard bands
+BAND_BYTES = 4096
+BAND_PATTERN = 0x7FC5A5A5      # a quiet NaN as fp32; as int32 it is positive, so fill_ takes it
+
+
+def _pattern_bytes(lo, hi, device):
+    """The bytes lo .. hi-1 of a buffer filled with the little-endian int32 BAND_PATTERN from byte 0 on."""
+    pat = torch.tensor([(BAND_PATTERN >> (8 * i)) & 0xFF for i in range(4)], dtype=torch.uint8, device=device)
+    return pat[torch.arange(lo, hi, device=device) % 4]
+
+
+def banded(shape, dtype=torch.float32, device="cuda"):
+    """(view, check): a tensor of `shape` that starts BAND_BYTES into one uint8 buffer of BAND_BYTES + its bytes rounded up to BAND_BYTES +
+    BAND_BYTES, every 32-bit word of which -- the view's own included -- holds BAND_PATTERN.  check() asserts that every byte in front of
+    the view and behind it still does (the back band starts at the first byte behind the view: the padding up to the next multiple of
+    BAND_BYTES is part of it); untouched(view) counts the words of the view itself that do."""
+    nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+    inner = (nbytes + BAND_BYTES - 1) // BAND_BYTES * BAND_BYTES
+    total = BAND_BYTES + inner + BAND_BYTES
+    buf = torch.empty(total, dtype=torch.uint8, device=device)
+    buf.view(torch.int32).fill_(BAND_PATTERN)
+    view = buf[BAND_BYTES:BAND_BYTES + nbytes].view(dtype).view(shape)
+
+    def check():
+        for name, lo, hi in (("front", 0, BAND_BYTES), ("back", BAND_BYTES + nbytes, total)):
+            bad = (buf[lo:hi] != _pattern_bytes(lo, hi, buf.device)).nonzero()
+            assert bad.numel() == 0, (f"{name} band: {bad.numel()} bytes changed, the first {int(bad[0]) + lo - BAND_BYTES} bytes from the "
+                                      f"view's start (the view holds {nbytes})")
+    return view, check
+
+
+def untouched(view):
+    """How many whole 32-bit words of a banded view still hold BAND_PATTERN."""
+    assert view.is_contiguous(), "untouched() counts the words of the memory the launch wrote: a contiguous view"
+    b = view.reshape(-1).view(torch.uint8)
+    return int((b[:b.numel() // 4 * 4].view(torch.int32) == BAND_PATTERN).sum())
+
+
+def group_index(B, T, J, temporal):
+    """The attention group of every token row m = (b T + t) J + j: temporal groups are (b, j) -> b J + j, spatial ones (b, t) -> b T + t."""
+    m = torch.arange(B * T * J)
+    return (m // (T * J)) * J + m % J if temporal else m // J
+
+
+def poison_groups(x, group_index, kinds=("nan", "inf"), cols=None):
+    """(poisoned copy of x, keep mask over its rows).  Every row of an odd-numbered group becomes non-finite -- kinds[0] for groups = 1
+    mod 4, kinds[1] for groups = 3 mod 4 -- in all its columns, or in `cols` (a slice) only; even groups are untouched, so in any tile
+    packing every clean group has poisoned neighbours on both sides."""
+    value = {"nan": float("nan"), "inf": float("inf"), "-inf": float("-inf")}
+    g = torch.as_tensor(group_index).to(x.device).long()
+    assert g.shape == (x.shape[0],), (g.shape, x.shape)
+    bad = x.clone()
+    sl = slice(None) if cols is None else cols
+    for rem, kind in ((1, kinds[0]), (3, kinds[1])):
+        rows = (g % 4 == rem).nonzero().flatten()
+        sub = bad[rows]
+        sub[:, sl] = value[kind]
+        bad[rows] = sub
+    return bad, g % 2 == 0
