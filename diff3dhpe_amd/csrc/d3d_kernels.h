@@ -34,6 +34,16 @@ inline int device_cu_count() {
   cache[dev & 63].store(n, std::memory_order_release);
   return n;
 }
+// launch tail of the persistent kernels that hold a CU each: opts `fn` in to `lds_bytes` of dynamic LDS on the current device and sets
+// `grid` to one workgroup per CU, at most one per tile
+inline hipError_t persistent_grid(const void* fn, size_t lds_bytes, std::atomic<unsigned long long>& done, long long tiles, int& grid) {
+  if (hipError_t ae = lds_optin(fn, lds_bytes, done)) return ae;
+  const int n_cu = device_cu_count();
+  if (n_cu <= 0) return hipErrorUnknown;
+  if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+  grid = tiles < n_cu ? (int)tiles : n_cu;
+  return hipSuccess;
+}
 // workgroups of `fn` (block threads, dyn_lds bytes of dynamic LDS) that one CU holds at a time -- registers AND LDS, as the runtime
 // computes it; a persistent kernel sized beyond this runs its surplus workgroups as a second, thinner wave of work.  0 on error.
 inline int resident_workgroups_per_cu(const void* fn, int block, size_t dyn_lds) {

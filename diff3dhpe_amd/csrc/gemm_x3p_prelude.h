@@ -1,10 +1,9 @@
-// What the epilogues of the F16X3 token GEMM need from their includer (kernels_gemm_x3p.hip, kernels_proj_x3.hip), inside namespace d3d:
-// the operand typedefs, the scales, the range guard, the 4-column split store and the patch fence.
+// What the epilogues of the F16X3 token GEMM need from their includer (kernels_gemm_x3p.hip and the plain GEMMs on the two-phase k-loop),
+// inside namespace d3d: the scales, the range guard, the 4-column split store and the patch fence, behind the operand typedefs of
+// kloop_common.h.
 #pragma once
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+#include "kloop_common.h"   // f32x4 / h8 / h4
 
 constexpr int PBK = 32;                          // k-tile depth (fp16 elements)
 constexpr float P_A_SCALE = 8.0f;

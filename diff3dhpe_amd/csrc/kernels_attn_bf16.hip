@@ -21,17 +21,13 @@
 
 namespace d3d {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "attn_lds.h"   // f32x16 / s4v, kswz / vkey / vswz
+
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef short s4v __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int BDH = 64;
-__device__ __forceinline__ int kswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-// V rows: the four key rows of one transposing read must land in four different 64-byte bank groups (kernels_attn_x3.hip)
-__device__ __forceinline__ int vkey(int row) { return (((row >> 1) & 1) << 2) ^ ((row >> 2) & 3); }
-__device__ __forceinline__ int vswz(int row, int chunk) { return row * 128 + ((chunk ^ vkey(row)) << 4); }
 }  // namespace
 
 // QT: 32-query tiles per wave (1 or 2).  QT = 2 halves the workgroup (NKT / 2 waves, each taking query tiles w and w + NKT / 2 one

@@ -34,40 +34,17 @@
 
 namespace d3d {
 
-#include "gemm_x3p_prelude.h"   // f32x4 / h8 / h4, PBK, P_A_SCALE, range_note*, store_split4, D3D_PATCH_FENCE
+#include "kloop_common.h"       // f32x4 / h8 / h4, sgpr_ptr, KL_GLDS, KL_DMA_PLAN, KL_XCD_TILE_ORDER
+#include "gemm_x3p_prelude.h"   // PBK, P_A_SCALE, range_note*, store_split4, D3D_PATCH_FENCE
 
 // Operand tile in LDS: rows of 128 B = 8 chunks of 16 B (0-3 hi, 4-7 lo of the k-tile); physical chunk = c ^ ((row>>1)&7).
 // A 16-lane ds_read_b128 group reads 16 consecutive rows at one logical chunk: row parity picks the half of the 256-byte
 // bank row, (row>>1)&7 permutes the 8 chunks of that half -> 16 distinct 4-bank slots.  The lo chunk of a fragment is
 // the hi chunk's offset XOR 64.
 
-// ---- DMA plan (branch-free): the k-tile of a BM x BN tile is (BM + BN)/8 pieces of 8 rows x
-// 128 B; wave w moves pieces w, w + NW, ... of A, then of W.  A lane serves row (8 piece + lane/8), LDS slot lane%8,
-// and fetches the source chunk the swizzle assigns to that slot (constant per lane: NW is even, so (row>>1)&7 =
-// 4 (w&1) + lane/16).  Contract: the A buffer holds >= mtiles*BM rows and the W buffer >= ntiles*BN rows
-// (padding rows are staged and multiplied but never stored).
-// Source addresses are formed as (wave-uniform byte base: SGPR pair, advanced by scalar adds) + (one 32-bit per-lane byte
-// offset, the same for every piece and k-tile), so that the DMA takes the saddr form and needs no per-piece 64-bit VALU
-// address arithmetic.
-#define D3D_DMA_PLAN(NW_, BM_)                                                                                          \
-  const int lr_ = lane >> 3;                                                                                            \
-  const int csrc_ = (lane & 7) ^ (((wave & 1) << 2) | (lr_ >> 1));                                                      \
-  const size_t K2_ = 2 * (size_t)K;                                                                                     \
-  const char* ubA = reinterpret_cast<const char*>(Ap) + (size_t)(m0 + wave * 8) * K2_ * 2;                             \
-  const char* ubB = reinterpret_cast<const char*>(Wp) + (size_t)(n0 + wave * 8) * K2_ * 2;                             \
-  unsigned lofs_ = (unsigned)(lr_ * (int)K2_ + csrc_ * 8) * 2u;                                                   \
-  const size_t it_stride = (size_t)((NW_) * 8) * K2_ * 2;                 /* bytes */                                   \
-  const int dstA = wave * 1024 + lane * 16, dstB = (BM_) * 128 + wave * 1024 + lane * 16
-
-#define D3D_GLDS(SRC, DSTOFF)                                                                                           \
-  __builtin_amdgcn_global_load_lds((SRC), (__attribute__((address_space(3))) void*)(uintptr_t)(lds + (DSTOFF)), 16, 0, 0)
-// wave-uniform pointer pinned into an SGPR pair
-__device__ __forceinline__ const char* sgpr_ptr(const char* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
-}
-
+// The DMA plan of a k-tile (which wave moves which piece, the swizzle on the source address, the saddr form) is KL_DMA_PLAN of
+// kloop_common.h; here for the operands Ap / Wp of K columns and the tile at (m0, n0), all in scope.
+#define D3D_DMA_PLAN(NW_, BM_) KL_DMA_PLAN(Ap, Wp, 2 * (size_t)K, m0, n0, NW_, (BM_) * 128)
 
 // Launch-time dispatch over (epilogue, output form): the five combinations the engine and the op hooks use.
 #define D3D_X3_DISPATCH(LAUNCH)                                                                                          \
@@ -222,9 +199,9 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
   do {                                                                                                                  \
     if ((IT) < A_IT) {                                                                                                  \
       if ((amask >> (IT)) & 1u)                                                                                         \
-        D3D_GLDS(sgpr_ptr(ubA + ((size_t)(KT) * 128 + (IT) * it_stride)) + lofs_, (ST) * STAGE + dstA + (IT) * NW * 1024); \
+        KL_GLDS(sgpr_ptr(ubA + ((size_t)(KT) * 128 + (IT) * it_stride)) + lofs_, (ST) * STAGE + dstA + (IT) * NW * 1024); \
     } else                                                                                                              \
-      D3D_GLDS(sgpr_ptr(ubB + ((size_t)(KT) * 128 + ((IT) - A_IT) * it_stride)) + lofs_,                               \
+      KL_GLDS(sgpr_ptr(ubB + ((size_t)(KT) * 128 + ((IT) - A_IT) * it_stride)) + lofs_,                               \
                (ST) * STAGE + dstB + ((IT) - A_IT) * NW * 1024);                                                        \
   } while (0)
 
@@ -253,8 +230,8 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
   const char* ubBn = reinterpret_cast<const char*>(Wp) + (size_t)(n0n + wave * 8) * K2_ * 2;
 #define D3D_QSTAGE_NEXT(IT)                                                                                             \
   do {                                                                                                                  \
-    if ((IT) < A_IT) D3D_GLDS(sgpr_ptr(ubAn + (IT) * it_stride) + lofs_, dstA + (IT) * NW * 1024);                       \
-    else D3D_GLDS(sgpr_ptr(ubBn + ((IT) - A_IT) * it_stride) + lofs_, dstB + ((IT) - A_IT) * NW * 1024);                 \
+    if ((IT) < A_IT) KL_GLDS(sgpr_ptr(ubAn + (IT) * it_stride) + lofs_, dstA + (IT) * NW * 1024);                       \
+    else KL_GLDS(sgpr_ptr(ubBn + ((IT) - A_IT) * it_stride) + lofs_, dstB + ((IT) - A_IT) * NW * 1024);                 \
   } while (0)
 
   [[maybe_unused]] auto qk_wait_vm = [](int n) {   // s_waitcnt vmcnt(n), n wave-uniform
@@ -414,11 +391,11 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
       if ((IT) < A_IT) {                                                                                                 \
         if ((amask >> (IT)) & 1u) {                                                                                      \
           const char* b_ = nxt_ ? ubAn + (IT) * it_stride : ubA + ((size_t)(KTT) * 128 + (IT) * it_stride);              \
-          D3D_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstA + (IT) * NW * 1024);                                                 \
+          KL_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstA + (IT) * NW * 1024);                                                 \
         }                                                                                                                \
       } else {                                                                                                           \
         const char* b_ = nxt_ ? ubBn + ((IT) - A_IT) * it_stride : ubB + ((size_t)(KTT) * 128 + ((IT) - A_IT) * it_stride); \
-        D3D_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstB + ((IT) - A_IT) * NW * 1024);                                          \
+        KL_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstB + ((IT) - A_IT) * NW * 1024);                                          \
       }                                                                                                                  \
     } while (0)
     // one phase: H = 0 / 1.  Even phase (H = 0) of k-tile KT: A(KT+1) if DO_A (and all of W(1) in a tile's first phase, W_FULL1);
@@ -724,19 +701,8 @@ __global__ __launch_bounds__(512) void k_linear_x3q_persist(const _Float16* __re
   static_assert(TM % 2 == 0 && (WM == 1 || WM == 2), "tail slices");   // (four-way slices need TM % 4 == 0: x3q_walk)
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int G = (int)gridDim.x, b = (int)blockIdx.x;
-  const int vfull = (mtiles / 8) * 8 * ntiles, mrem = mtiles % 8;
   // valid-tile ordinal -> tile: the uniform launch's blockIdx order without its padding slots
-  auto tile_of = [&](int o, int& mt, int& nt) {
-    if (o < vfull) {
-      const int xcd = o & 7, slot = o >> 3;
-      mt = (slot / ntiles) * 8 + xcd;
-      nt = slot % ntiles;
-    } else {
-      const int o2 = o - vfull;
-      mt = (mtiles / 8) * 8 + o2 % mrem;
-      nt = o2 / mrem;
-    }
-  };
+  KL_XCD_TILE_ORDER(mtiles, ntiles);
   const int nitems = wk.nfull + (b < wk.split * wk.rem ? 1 : 0);
   if (nitems == 0) return;
   // item k of this workgroup: a whole tile (k < nfull) or a slice of a tail tile
@@ -765,8 +731,8 @@ __global__ __launch_bounds__(512) void k_linear_x3q_persist(const _Float16* __re
     D3D_DMA_PLAN(NW, BM);
 #pragma unroll
     for (int it = 0; it < N_IT; ++it) {
-      if (it < A_IT) D3D_GLDS(sgpr_ptr(ubA + it * it_stride) + lofs_, dstA + it * NW * 1024);
-      else D3D_GLDS(sgpr_ptr(ubB + (it - A_IT) * it_stride) + lofs_, dstB + (it - A_IT) * NW * 1024);
+      if (it < A_IT) KL_GLDS(sgpr_ptr(ubA + it * it_stride) + lofs_, dstA + it * NW * 1024);
+      else KL_GLDS(sgpr_ptr(ubB + (it - A_IT) * it_stride) + lofs_, dstB + (it - A_IT) * NW * 1024);
     }
   }
   int tid_o = (int)threadIdx.x;

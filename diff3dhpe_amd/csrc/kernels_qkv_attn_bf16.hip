@@ -37,32 +37,18 @@ typedef __bf16 qa_bf8 __attribute__((ext_vector_type(8)));
 namespace d3d {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+#include "kloop_common.h"
+#include "attn_lds.h"
+
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef short s4v __attribute__((ext_vector_type(4)));
 
-constexpr int QA_BM = 256, QA_BN = 192, QA_TM = 8, QA_NJ = 3;
-constexpr int QA_AREG = QA_BM * 128, QA_STAGE = (QA_BM + QA_BN) * 128;   // 57344
-constexpr int QA_AIT = 4, QA_BIT = 3;                                    // 1-KiB DMA pieces per wave per k-tile
+QF_SHAPE(8, 3, 256, 192, 4, 3);                                          // 256 x 192 stage of 57344 bytes, 64-deep bf16 k-tiles
 constexpr int QA_ROWS = 255;                                             // token rows of a tile at most
-constexpr int QA_PQ = QA_STAGE, QA_PK = QA_PQ + 256 * 128, QA_PV = QA_PK + 256 * 128;
+constexpr int QA_PQ = QF_STAGE, QA_PK = QA_PQ + 256 * 128, QA_PV = QA_PK + 256 * 128;
 constexpr int QA_VROWS = 288;
 constexpr int QA_LDS = QA_PV + QA_VROWS * 128;                           // 159744
 static_assert(QA_LDS <= 160 * 1024, "LDS map");
-
-// swizzles of kernels_attn_bf16.hip, on the tile's row index
-__device__ __forceinline__ int kswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int vkey(int row) { return (((row >> 1) & 1) << 2) ^ ((row >> 2) & 3); }
-__device__ __forceinline__ int vswz(int row, int chunk) { return row * 128 + ((chunk ^ vkey(row)) << 4); }
-
-__device__ __forceinline__ const char* sgpr_ptr(const char* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
-}
 
 struct QaArgs {
   const char* A;        // bf16 operand rows [M][D] (norm1(x))
@@ -73,22 +59,6 @@ struct QaArgs {
   int N, udiv;          // tokens of a group, token stride: token t of group u is row (u / udiv) * N * udiv + u % udiv + t * udiv
   int g, units, mtiles; // groups per tile, groups of the launch, ceil(units / g)
 };
-
-#define QA_GLDS(SRC, DSTOFF)                                                                                            \
-  __builtin_amdgcn_global_load_lds((SRC), (__attribute__((address_space(3))) void*)(uintptr_t)(lds + (DSTOFF)), 16, 0, 0)
-
-__device__ __forceinline__ void wait_vm(int n) {   // s_waitcnt vmcnt(n), n wave-uniform
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-  }
-}
 
 // first row of group `unit` (clamped to the launch's last group)
 __device__ __forceinline__ unsigned qa_unit_row(const QaArgs& a, int unit) {
@@ -234,19 +204,8 @@ __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
   const int tiles = a.mtiles * H;
   if (b >= tiles) return;
   const int nitems = (tiles - b + G - 1) / G;
-  const int vfull = (a.mtiles / 8) * 8 * H, mrem = a.mtiles % 8;
-  // tile ordinal -> (M-tile, head): all heads of an M-tile on one XCD, as the GEMMs walk (kernels_qkv_sattn.hip)
-  auto tile_of = [&](int o, int& mt, int& hd) {
-    if (o < vfull) {
-      const int xcd = o & 7, slot = o >> 3;
-      mt = (slot / H) * 8 + xcd;
-      hd = slot % H;
-    } else {
-      const int o2 = o - vfull;
-      mt = (a.mtiles / 8) * 8 + o2 % mrem;
-      hd = o2 / mrem;
-    }
-  };
+  // tile ordinal -> (M-tile, head): all heads of an M-tile on one XCD, as the GEMMs walk
+  KL_XCD_TILE_ORDER(a.mtiles, H);
 
   const int K = a.D;
   const unsigned rowB = 2u * (unsigned)K;         // bytes of an operand / weight row
@@ -258,21 +217,16 @@ __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int lr = lane >> 3, csrc = (lane & 7) ^ (((wave & 1) << 2) | (lr >> 1));
 #pragma unroll
-    for (int it = 0; it < QA_AIT; ++it)
-      QA_GLDS(sgpr_ptr(a.A) + (qa_row(a, mt, it * 64 + wave * 8 + lr) * rowB + (unsigned)csrc * 16u), wave * 1024 + lane * 16 + it * 8192);
+    for (int it = 0; it < QF_AIT; ++it)
+      KL_GLDS(sgpr_ptr(a.A) + (qa_row(a, mt, it * 64 + wave * 8 + lr) * rowB + (unsigned)csrc * 16u), wave * 1024 + lane * 16 + it * 8192);
     const unsigned lofs = (unsigned)lr * rowB + (unsigned)csrc * 16u;
 #pragma unroll
-    for (int it = 0; it < QA_BIT; ++it)
-      QA_GLDS(sgpr_ptr(a.W + (size_t)qa_wrow(a, it * 64 + wave * 8, hd) * rowB) + lofs, QA_AREG + wave * 1024 + lane * 16 + it * 8192);
+    for (int it = 0; it < QF_BIT; ++it)
+      KL_GLDS(sgpr_ptr(a.W + (size_t)qa_wrow(a, it * 64 + wave * 8, hd) * rowB) + lofs, QF_AREG + wave * 1024 + lane * 16 + it * 8192);
   }
   int tid_o = (int)threadIdx.x;
   for (int item = 0; item < nitems; ++item) {
-    asm volatile("" : "+v"(tid_o));   // per-lane offsets are re-derived in every tile instead of being hoisted (and spilled)
-    const int tid = tid_o;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int r16 = lane & 15, q = lane >> 4;
+    QF_TILE_LANES;
     const bool has_next = item + 1 < nitems;
     int mtn = mt, hdn = hd;
     if (has_next) tile_of((item + 1) * G + b, mtn, hdn);
@@ -281,54 +235,31 @@ __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
     const int lr_ = lane >> 3;
     const int csrc_ = (lane & 7) ^ (((wave & 1) << 2) | (lr_ >> 1));
     unsigned lofs_ = (unsigned)lr_ * rowB + (unsigned)csrc_ * 16u;
-    unsigned offA[QA_AIT], offAn[QA_AIT];
+    unsigned offA[QF_AIT], offAn[QF_AIT];
 #pragma unroll
-    for (int it = 0; it < QA_AIT; ++it) {
+    for (int it = 0; it < QF_AIT; ++it) {
       offA[it] = qa_row(a, mt, it * 64 + wave * 8 + lr_) * rowB + (unsigned)csrc_ * 16u;
       offAn[it] = qa_row(a, mtn, it * 64 + wave * 8 + lr_) * rowB + (unsigned)csrc_ * 16u;
     }
-    const int dstA = wave * 1024 + lane * 16, dstB = QA_AREG + wave * 1024 + lane * 16;
+    const int dstA = wave * 1024 + lane * 16, dstB = QF_AREG + wave * 1024 + lane * 16;
     // piece IT (A: 0..3, W: 4..6) of k-tile KTT of this tile, or (KTT == nk) of k-tile 0 of the next one
 #define QA_PIECE(KTT, IT)                                                                                               \
     do {                                                                                                                \
       const bool nxt_ = (KTT) >= nk;                                                                                    \
-      const int st_ = ((KTT) & 1) * QA_STAGE;                                                                           \
+      const int st_ = ((KTT) & 1) * QF_STAGE;                                                                           \
       const size_t kofs_ = nxt_ ? (size_t)0 : (size_t)(KTT) * 128;                                                      \
-      if ((IT) < QA_AIT) {                                                                                              \
-        QA_GLDS(sgpr_ptr(a.A + kofs_) + (nxt_ ? offAn[(IT) % QA_AIT] : offA[(IT) % QA_AIT]), st_ + dstA + (IT) * 8192);  \
+      if ((IT) < QF_AIT) {                                                                                              \
+        KL_GLDS(sgpr_ptr(a.A + kofs_) + (nxt_ ? offAn[(IT) % QF_AIT] : offA[(IT) % QF_AIT]), st_ + dstA + (IT) * 8192);  \
       } else {                                                                                                          \
-        const char* b_ = a.W + (size_t)qa_wrow(a, ((IT) - QA_AIT) * 64 + wave * 8, nxt_ ? hdn : hd) * rowB + kofs_;     \
-        QA_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstB + ((IT) - QA_AIT) * 8192);                                             \
+        const char* b_ = a.W + (size_t)qa_wrow(a, ((IT) - QF_AIT) * 64 + wave * 8, nxt_ ? hdn : hd) * rowB + kofs_;     \
+        KL_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstB + ((IT) - QF_AIT) * 8192);                                             \
       }                                                                                                                 \
     } while (0)
 
-    f32x4 acc[QA_TM][QA_NJ];
-#pragma unroll
-    for (int i = 0; i < QA_TM; ++i)
-#pragma unroll
-      for (int j = 0; j < QA_NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
-
-    const int foff = (q ^ (r16 >> 1)) << 4;
-    const int aoff = (wm * 128 + r16) * 128 + foff, boff = QA_AREG + (wn * 48 + r16) * 128 + foff;
-    h8 bh[QA_NJ], bl[QA_NJ], ah[2], al[2];
+    QF_TILE_ACC;
     int issued_prev = 0;
-#define QF_STAGE QA_STAGE
-#define QF_NJ QA_NJ
-#define QF_TM QA_TM
-#define QF_AIT QA_AIT
-#define QF_BIT QA_BIT
-#define QF_PIECE(KTT, IT) QA_PIECE(KTT, IT)
-    QF_KLOOP_HEAD
-    QF_KLOOP_TAIL
-#undef QF_STAGE
-#undef QF_NJ
-#undef QF_TM
-#undef QF_AIT
-#undef QF_BIT
-#undef QF_PIECE
-#undef QA_PIECE
+    QF_KLOOP_HEAD(QA_PIECE)
+    QF_KLOOP_TAIL(QA_PIECE)
     __builtin_amdgcn_s_setprio(0);
 
     __syncthreads();   // every wave is out of the k-loop: stage 1 and the LDS behind it become the q / k / v planes
@@ -336,17 +267,17 @@ __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
     // ---- q / k / v -> planes: fma(acc, 1, bias), the q third times 2^-3, round to nearest even (x3q_epilogue8<.., FX_BF16>)
     if (tid < 256) *reinterpret_cast<uint4*>(lds + QA_PV + 256 * 128 + tid * 16) = make_uint4(0, 0, 0, 0);
     {
-      float4 b4[QA_NJ];
+      float4 b4[QF_NJ];
 #pragma unroll
-      for (int j = 0; j < QA_NJ; ++j) b4[j] = *reinterpret_cast<const float4*>(a.bias + j * a.D + 64 * hd + 16 * wn + 4 * q);
+      for (int j = 0; j < QF_NJ; ++j) b4[j] = *reinterpret_cast<const float4*>(a.bias + j * a.D + 64 * hd + 16 * wn + 4 * q);
       const int chunk = 2 * wn + (q >> 1), half8 = (q & 1) << 3;          // this lane's 8 bytes: 16-byte chunk d / 8, half (d & 4)
 #pragma unroll
-      for (int i = 0; i < QA_TM; ++i) {
-        const int R = wm * 128 + 16 * i + r16;
+      for (int i = 0; i < QF_TM; ++i) {
+        const int R = wm * 16 * QF_TM + 16 * i + r16;
         unsigned char* const pkq = lds + kswz(R, chunk) + half8;
         unsigned char* const pv = lds + QA_PV + vswz(R, chunk) + half8;
 #pragma unroll
-        for (int j = 0; j < QA_NJ; ++j) {
+        for (int j = 0; j < QF_NJ; ++j) {
           const float osc = j == 0 ? 0.125f : 1.0f;
           const float bj[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
           bf4 o;
@@ -400,12 +331,8 @@ bool qkv_tattn_bf16_ok(int T, int J, int D, int H, int B) { return qkv_attn_bf16
 
 template <typename KF>
 static hipError_t qa_launch(KF kern, std::atomic<unsigned long long>& attr_done, const QaArgs& a, hipStream_t s) {
-  if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kern), QA_LDS, attr_done)) return ae;
-  int n_cu = device_cu_count();
-  if (n_cu <= 0) return hipErrorUnknown;
-  const long long tiles = (long long)a.mtiles * a.H;
-  if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-  const int grid = tiles < n_cu ? (int)tiles : n_cu;
+  int grid = 0;
+  if (hipError_t ge = persistent_grid(reinterpret_cast<const void*>(kern), QA_LDS, attr_done, (long long)a.mtiles * a.H, grid)) return ge;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), QA_LDS, s, a);
   return hipGetLastError();
 }

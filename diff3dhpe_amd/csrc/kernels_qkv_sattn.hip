@@ -29,78 +29,22 @@
 namespace d3d {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_alias __attribute__((ext_vector_type(4), may_alias));
-typedef unsigned u32x2_alias __attribute__((ext_vector_type(2), may_alias));
+#include "kloop_common.h"
+#include "attn_lds.h"
 
-constexpr int QS_BM = 256, QS_BN = 192, QS_TM = 8, QS_NJ = 3;
-constexpr int QS_AREG = QS_BM * 128, QS_STAGE = (QS_BM + QS_BN) * 128;   // 57344
-constexpr int QS_AIT = 4, QS_BIT = 3;                                    // 1-KiB DMA pieces per wave per k-tile
+QF_SHAPE(8, 3, 256, 192, 4, 3);                                          // 256 x 192 x 32 stage of 57344 bytes
 constexpr int QS_J = 17, QS_FPT = 15, QS_ROWS = QS_J * QS_FPT;           // 255 token rows per tile
 constexpr int QS_PLANE = QS_J * 128, QS_SLOT = 6 * QS_PLANE;             // 2176, 13056
-constexpr int QS_QKV = QS_STAGE;                                         // frame slots start behind stage 0
+constexpr int QS_QKV = QF_STAGE;                                         // frame slots start behind stage 0
 constexpr int QS_STX = QS_QKV + 8 * QS_SLOT;                             // 161792: (rstd', -mean rstd) of the tile's 256 rows, 2 KiB
-constexpr int QS_RAW = 2 * QS_STAGE;                                     // raw statistics partials while the k-loop runs (16 KiB)
+constexpr int QS_RAW = 2 * QF_STAGE;                                     // raw statistics partials while the k-loop runs (16 KiB)
 constexpr int QS_RAW_MAX = 16384;
-constexpr int QS_LDS = QS_STX + QS_BM * 8;                               // 163840
+constexpr int QS_LDS = QS_STX + QF_BM * 8;                               // 163840
 static_assert(QS_LDS <= 160 * 1024 && QS_RAW + QS_RAW_MAX <= QS_STX, "LDS map");
 // planes of a slot: V hi, V lo, K hi, K lo, Q hi, Q lo.  The fragment reads of the 15 pad rows of a plane run on into what follows
 // it: for V that must be FINITE (0 x NaN in the second product) -- V hi runs into V lo, V lo into K hi, both written in the same pass;
 // pad keys of K are overwritten with -inf scores and pad queries of Q are never stored: any bits will do there.
 constexpr int QS_PV = 0, QS_PK = 2 * QS_PLANE, QS_PQ = 4 * QS_PLANE;
-
-// swizzles of kernels_attn_x3.hip (K / Q rows: fragment reads of 16 consecutive rows at one logical chunk; V rows: transpose reads)
-__device__ __forceinline__ int kswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int vkey(int row) { return (((row >> 1) & 1) << 2) ^ ((row >> 2) & 3); }
-__device__ __forceinline__ int vswz(int row, int chunk) { return row * 128 + ((chunk ^ vkey(row)) << 4); }
-
-__device__ __forceinline__ const char* sgpr_ptr(const char* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
-}
-
-// (v0, v1) -> packed fp16 pairs hi = fp16(k v), lo = fp16(k v - hi): the split of split8_x3 / split_pair_f16 (same single roundings)
-__device__ __forceinline__ void split_pair(float v0, float v1, float k, unsigned& hi, unsigned& lo) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(k));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(k));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(v0), "v"(k), "v"(hi));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(k), "v"(hi));
-}
-__device__ __forceinline__ void split_pair_s(float e0, float e1, float k, unsigned& hi, unsigned& lo) {   // (scalar k: the E split)
-  asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(e0), "s"(k));
-  asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(e1), "s"(k));
-  asm volatile("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(e0), "s"(k), "v"(hi));
-  asm volatile("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(e1), "s"(k), "v"(hi));
-}
-__device__ __forceinline__ void split8_e(const float (&e)[8], h8& eh, h8& el) {
-  u32x4 hv, lv;
-#pragma unroll
-  for (int pr = 0; pr < 4; ++pr) {
-    unsigned a, b;
-    split_pair_s(e[2 * pr], e[2 * pr + 1], 1024.0f, a, b);
-    hv[pr] = a; lv[pr] = b;
-  }
-  eh = __builtin_bit_cast(h8, hv);
-  el = __builtin_bit_cast(h8, lv);
-}
-// output patch (kernels_attn_x3.hip): lanes < 32 end up owning the whole hi chunk of their row, lanes >= 32 the whole lo chunk
-__device__ __forceinline__ void patch_wr(unsigned char* patch, int r, int h, int g, h4 oh, h4 ol) {
-  const uint2 a = __builtin_bit_cast(uint2, oh), b = __builtin_bit_cast(uint2, ol);
-  const auto s0 = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-  const auto s1 = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-  u32x4_alias v;
-  v[0] = s0[0]; v[1] = s1[0]; v[2] = s0[1]; v[3] = s1[1];
-  *reinterpret_cast<u32x4_alias*>(patch + r * 128 + ((((h << 2) + g) ^ (r & 7)) << 4)) = v;
-}
-__device__ __forceinline__ u32x4 patch_rd(const unsigned char* patch, int row, int chunk) {
-  return *reinterpret_cast<const u32x4_alias*>(patch + row * 128 + ((chunk ^ (row & 7)) << 4));
-}
 
 // Diagnostic builds only (-DQS_ABL=n, wrong results; experiments/lds_conflict_attribution.sh): 1 no slot writes, 2 no attention units,
 // 4 no output patches -- which LDS accesses the bank-conflict counter belongs to.
@@ -121,22 +65,6 @@ struct QsArgs {
   int M, K, F, mtiles, D;  // tokens, GEMM depth, frames (M / 17), M-tiles (ceil(F / 15)), model width (8 heads x 64)
   unsigned* range;         // the engine's range-guard word
 };
-
-#define QS_GLDS(SRC, DSTOFF)                                                                                            \
-  __builtin_amdgcn_global_load_lds((SRC), (__attribute__((address_space(3))) void*)(uintptr_t)(lds + (DSTOFF)), 16, 0, 0)
-
-__device__ __forceinline__ void wait_vm(int n) {   // s_waitcnt vmcnt(n), n wave-uniform
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-  }
-}
 
 // One frame of one head from its LDS slot: the arithmetic of k_attn_temporal_x3p<1, 8, 3> (same MFMAs in the same order, same
 // softmax, same conversions), outputs through the wave-private patch (aliasing the slot's Q planes, dead once the query fragments
@@ -310,34 +238,15 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
   const int nk = K / 32;
   int mt = 0, hd = 0;
   tile_of(b, mt, hd);
-  {   // first k-tile of the first tile
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int lr = lane >> 3, csrc = (lane & 7) ^ (((wave & 1) << 2) | (lr >> 1));
-    const unsigned lofs = (unsigned)(lr * (int)K2 + csrc * 8) * 2u;
-    const char* ubA = reinterpret_cast<const char*>(a.Ap) + (size_t)(mt * QS_ROWS + wave * 8) * K2 * 2;
-    const char* ubB = reinterpret_cast<const char*>(a.Wp) + (size_t)(hd * QS_BN + wave * 8) * K2 * 2;
-    const size_t it_stride = (size_t)64 * K2 * 2;
-#pragma unroll
-    for (int it = 0; it < QS_AIT; ++it) QS_GLDS(sgpr_ptr(ubA + it * it_stride) + lofs, wave * 1024 + lane * 16 + it * 8192);
-#pragma unroll
-    for (int it = 0; it < QS_BIT; ++it) QS_GLDS(sgpr_ptr(ubB + it * it_stride) + lofs, QS_AREG + wave * 1024 + lane * 16 + it * 8192);
-  }
+  QF_STAGE_FIRST(a.Ap, a.Wp, mt * QS_ROWS, hd * QF_BN)
   int tid_o = (int)threadIdx.x;
   for (int item = 0; item < nitems; ++item) {
-    asm volatile("" : "+v"(tid_o));   // per-lane offsets are re-derived in every tile instead of being hoisted (and spilled)
-    const int tid = tid_o;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int r16 = lane & 15, q = lane >> 4;
-    const bool has_next = item + 1 < nitems;
-    int mtn = 0, hdn = 0;
-    if (has_next) tile_of((item + 1) * G + b, mtn, hdn);
-    const int m0 = mt * QS_ROWS, n0 = hd * QS_BN;
+    QF_TILE_LANES;
+    QF_TILE_NEXT(mtn, hdn);
+    const int m0 = mt * QS_ROWS, n0 = hd * QF_BN;
 
     // ---- row statistics of the folded LayerNorm: raw partials by LDS-DMA under the k-loop (16-byte aligned blocks), else read later
-    const int st_bytes = QS_BM * a.st_np * 8;
+    const int st_bytes = QF_BM * a.st_np * 8;
     const bool st_dma = st_bytes <= QS_RAW_MAX && (((size_t)m0 * a.st_np * 8) & 15) == 0;   // (uniform)
     int st_issued = 0;
     if (st_dma) {
@@ -346,57 +255,17 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
       for (int it = 0; it < QS_RAW_MAX / 1024 / 8; ++it) {
         const int pc = wave + it * 8;
         if (pc * 1024 < st_bytes) {
-          QS_GLDS(sgpr_ptr(src + pc * 1024) + lane * 16, QS_RAW + pc * 1024);
+          KL_GLDS(sgpr_ptr(src + pc * 1024) + lane * 16, QS_RAW + pc * 1024);
           ++st_issued;
         }
       }
     }
 
-    // ---- DMA plan (kernels_gemm_x3p.hip D3D_DMA_PLAN)
-    const int lr_ = lane >> 3;
-    const int csrc_ = (lane & 7) ^ (((wave & 1) << 2) | (lr_ >> 1));
-    const char* ubA = reinterpret_cast<const char*>(a.Ap) + (size_t)(m0 + wave * 8) * K2 * 2;
-    const char* ubB = reinterpret_cast<const char*>(a.Wp) + (size_t)(n0 + wave * 8) * K2 * 2;
-    unsigned lofs_ = (unsigned)(lr_ * (int)K2 + csrc_ * 8) * 2u;
-    const size_t it_stride = (size_t)64 * K2 * 2;
-    const int dstA = wave * 1024 + lane * 16, dstB = QS_AREG + wave * 1024 + lane * 16;
-    // next tile's operand bases: its first k-tile is issued by the last two phases of this tile's k-loop (stage 0 is free then)
-    const char* ubAn = reinterpret_cast<const char*>(a.Ap) + (size_t)(mtn * QS_ROWS + wave * 8) * K2 * 2;
-    const char* ubBn = reinterpret_cast<const char*>(a.Wp) + (size_t)(hdn * QS_BN + wave * 8) * K2 * 2;
-    // piece IT (A: 0..3, W: 4..6) of k-tile KTT of this tile, or (KTT == nk) of k-tile 0 of the next one
-#define QS_PIECE(KTT, IT)                                                                                               \
-    do {                                                                                                                \
-      const bool nxt_ = (KTT) >= nk;                                                                                    \
-      const int st_ = ((KTT) & 1) * QS_STAGE;                                                                           \
-      if ((IT) < QS_AIT) {                                                                                              \
-        const char* b_ = nxt_ ? ubAn + (IT) * it_stride : ubA + ((size_t)(KTT) * 128 + (IT) * it_stride);               \
-        QS_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstA + (IT) * 8192);                                                        \
-      } else {                                                                                                          \
-        const char* b_ = nxt_ ? ubBn + ((IT) - QS_AIT) * it_stride : ubB + ((size_t)(KTT) * 128 + ((IT) - QS_AIT) * it_stride); \
-        QS_GLDS(sgpr_ptr(b_) + lofs_, st_ + dstB + ((IT) - QS_AIT) * 8192);                                             \
-      }                                                                                                                 \
-    } while (0)
-
-    f32x4 acc[QS_TM][QS_NJ];
-#pragma unroll
-    for (int i = 0; i < QS_TM; ++i)
-#pragma unroll
-      for (int j = 0; j < QS_NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
-
-    const int foff = (q ^ (r16 >> 1)) << 4;
-    const int aoff = (wm * 128 + r16) * 128 + foff, boff = QS_AREG + (wn * 48 + r16) * 128 + foff;
-    h8 bh[QS_NJ], bl[QS_NJ], ah[2], al[2];
+    // ---- DMA plan (kloop_common.h KL_DMA_PLAN; a tile stages 256 rows from row 255 mt on), accumulators, fragment offsets
+    QF_TILE_PLAN(a.Ap, a.Wp, m0, n0, mtn * QS_ROWS, hdn * QF_BN);
+    QF_TILE_ACC;
     int issued_prev = st_issued;
-    // the k-loop: qkv_fused_kloop.h (shared with the other fused kernel), this kernel's constants and DMA pieces behind the QF_ names
-#define QF_STAGE QS_STAGE
-#define QF_NJ QS_NJ
-#define QF_TM QS_TM
-#define QF_AIT QS_AIT
-#define QF_BIT QS_BIT
-#define QF_PIECE(KTT, IT) QS_PIECE(KTT, IT)
-    QF_KLOOP_HEAD
+    QF_KLOOP_HEAD(QF_PIECE)
     // ---- row statistics -> (rstd * out_scale, -mean rstd) per tile row, in front of the last k-tile: every wave reduces 32 rows (lanes
     // 0-31) in the shadow of its SIMD partner's MFMAs -- behind the k-loop this step was 1.1 us of a 38 us tile with half the waves
     // idle.  The raw partials landed long ago (the first counted wait of the tile retired them; phase barriers since).
@@ -418,29 +287,22 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
         srow[t] = make_float2(rstd * a.out_scale, -mean * rstd);
       }
     }
-    QF_KLOOP_TAIL
-#undef QF_STAGE
-#undef QF_NJ
-#undef QF_TM
-#undef QF_AIT
-#undef QF_BIT
-#undef QF_PIECE
-#undef QS_PIECE
+    QF_KLOOP_TAIL(QF_PIECE)
     __builtin_amdgcn_s_setprio(0);
 
     __syncthreads();   // statistics visible; every wave is out of the k-loop: stage 1 and the LDS behind it become the frame slots
 
-    float2 st[QS_TM];
+    float2 st[QF_TM];
 #pragma unroll
-    for (int i = 0; i < QS_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + QS_STX)[wm * 128 + 16 * i + r16];
-    float4 cs4[QS_NJ], b4[QS_NJ];
+    for (int i = 0; i < QF_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + QS_STX)[wm * 16 * QF_TM + 16 * i + r16];
+    float4 cs4[QF_NJ], b4[QF_NJ];
 #pragma unroll
-    for (int j = 0; j < QS_NJ; ++j) {
+    for (int j = 0; j < QF_NJ; ++j) {
       const int n = n0 + wn * 48 + 16 * j + 4 * q;
       cs4[j] = *reinterpret_cast<const float4*>(a.csum + n);
       b4[j] = *reinterpret_cast<const float4*>(a.bias + n);
     }
-    float amaxj[QS_NJ] = {0.0f, 0.0f, 0.0f};   // max |value| per accumulator column tile j = q / k / v (plane scale applied at the end)
+    float amaxj[QF_NJ] = {0.0f, 0.0f, 0.0f};   // max |value| per accumulator column tile j = q / k / v (plane scale applied at the end)
     // q / k / v of this pass's frames -> frame slots (LayerNorm fold and hi / lo split of x3q_epilogue8).  Frame fr of the tile:
     // pass (fr >> 2) & 1, slot (fr & 3) + 4 (fr >> 3).  Column tile j of a wave IS part j (the weight rows are ordered that way at
     // commit): q columns 16 wn .. + 15 of the head in j = 0, the same k columns in j = 1, v in j = 2 -- plane and scale are
@@ -450,9 +312,9 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
     const int chunk = 2 * wn + (q >> 1), half8 = (q & 1) << 3;            // this lane's 8 bytes: 16-byte chunk d / 8, half (d & 4)
     auto write_pass = [&](int pass) {
 #pragma unroll
-      for (int i = 0; i < QS_TM; ++i) {
+      for (int i = 0; i < QF_TM; ++i) {
         if (pass == 0 ? (i > 4) : (i < 4 && !(wm == 1 && i == 0))) continue;   // (wave-uniform: m-tiles without rows of this pass)
-        const int R = wm * 128 + 16 * i + r16;
+        const int R = wm * 16 * QF_TM + 16 * i + r16;
         const int fr = (R * 241) >> 12, jr = R - fr * QS_J;               // R / 17 for R < 256
         if (((fr >> 2) & 1) != pass || fr >= QS_FPT) continue;
         unsigned char* const row = lds + QS_QKV + ((fr & 3) + 4 * (fr >> 3)) * QS_SLOT + jr * 128 + half8;
@@ -460,7 +322,7 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
         unsigned char* const pv = row + ((chunk ^ vkey(jr)) << 4);
         const f2 sx = (f2)(st[i].x), sy = (f2)(st[i].y);
 #pragma unroll
-        for (int j = 0; j < QS_NJ; ++j) {
+        for (int j = 0; j < QF_NJ; ++j) {
           const float osc = j == 0 ? 1.0f : 8.0f;
           f2 a01, a23, c01, c23, b01, b23;
           a01.x = acc[i][j][0]; a01.y = acc[i][j][1]; a23.x = acc[i][j][2]; a23.y = acc[i][j][3];
@@ -497,7 +359,7 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
     {
       float amax = 0.0f;
 #pragma unroll
-      for (int j = 0; j < QS_NJ; ++j) amax = fmaxf(amax, amaxj[j] * (j == 0 ? 1.0f : (j == 1 ? 8.0f : 16.015f)));   // v: flagged from |v| > 4090 on
+      for (int j = 0; j < QF_NJ; ++j) amax = fmaxf(amax, amaxj[j] * (j == 0 ? 1.0f : (j == 1 ? 8.0f : 16.015f)));   // v: flagged from |v| > 4090 on
       if (amax > X3_HALF_MAX) range_raise(a.range, RANGE_BIT_ACT);
     }
     __syncthreads();
@@ -523,11 +385,8 @@ hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, cons
   a.out = (_Float16*)out_x3; a.M = M; a.K = K; a.F = M / J; a.mtiles = (a.F + QS_FPT - 1) / QS_FPT; a.D = D;
   a.range = launch_range_word();
   static std::atomic<unsigned long long> attr_done{0};   // one bit per device
-  if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(k_qkv_sattn), QS_LDS, attr_done)) return ae;
-  int n_cu = device_cu_count();
-  if (n_cu <= 0) return hipErrorUnknown;
-  const int tiles = a.mtiles * 8;
-  const int grid = tiles < n_cu ? tiles : n_cu;
+  int grid = 0;
+  if (hipError_t ge = persistent_grid(reinterpret_cast<const void*>(k_qkv_sattn), QS_LDS, attr_done, (long long)a.mtiles * 8, grid)) return ge;
   hipLaunchKernelGGL(k_qkv_sattn, dim3(grid), dim3(512), QS_LDS, s, a);
   return hipGetLastError();
 }

@@ -33,73 +33,17 @@
 namespace d3d {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_alias __attribute__((ext_vector_type(4), may_alias));
-typedef unsigned u32x2_alias __attribute__((ext_vector_type(2), may_alias));
+#include "kloop_common.h"
+#include "attn_lds.h"
 
-constexpr int QT_BM = 256, QT_BN = 192, QT_TM = 8, QT_NJ = 3;
-constexpr int QT_AREG = QT_BM * 128, QT_STAGE = (QT_BM + QT_BN) * 128;   // 57344
-constexpr int QT_AIT = 4, QT_BIT = 3;                                    // 1-KiB DMA pieces per wave per k-tile
+QF_SHAPE(8, 3, 256, 192, 4, 3);                                          // 256 x 192 x 32 stage of 57344 bytes
 constexpr int QT_PLANE = 256 * 128;                                      // one fp16 plane of 256 key rows x 64 dims
 constexpr int QT_K = 0, QT_V = 2 * QT_PLANE, QT_Q = 4 * QT_PLANE;        // K hi | K lo | V hi | V lo | Q exchange, then output patches (32 KiB)
-constexpr int QT_RAW = 2 * QT_STAGE;                                     // raw statistics partials while the k-loop runs (16 KiB)
+constexpr int QT_RAW = 2 * QF_STAGE;                                     // raw statistics partials while the k-loop runs (16 KiB)
 constexpr int QT_RAW_MAX = 16384;
 constexpr int QT_STX = QT_Q + 30 * 1024;                                 // (rstd', -mean rstd) of the tile's 256 rows, 2 KiB, until the epilogue has read them
 constexpr int QT_LDS = QT_Q + 32 * 1024;                                 // 163840
-static_assert(QT_LDS <= 160 * 1024 && QT_RAW + QT_RAW_MAX <= QT_Q && QT_STX + QT_BM * 8 <= QT_LDS, "LDS map");
-
-// swizzles of kernels_attn_x3.hip (K / Q rows: fragment reads of 16 consecutive rows at one logical chunk; V rows: transpose reads)
-__device__ __forceinline__ int kswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int vkey(int row) { return (((row >> 1) & 1) << 2) ^ ((row >> 2) & 3); }
-__device__ __forceinline__ int vswz(int row, int chunk) { return row * 128 + ((chunk ^ vkey(row)) << 4); }
-
-__device__ __forceinline__ const char* sgpr_ptr(const char* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
-}
-
-// (v0, v1) -> packed fp16 pairs hi = fp16(k v), lo = fp16(k v - hi): the split of split8_x3 / split_pair_f16 (same single roundings)
-__device__ __forceinline__ void split_pair(float v0, float v1, float k, unsigned& hi, unsigned& lo) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(k));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(k));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(v0), "v"(k), "v"(hi));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(k), "v"(hi));
-}
-__device__ __forceinline__ void split_pair_s(float e0, float e1, float k, unsigned& hi, unsigned& lo) {   // (scalar k: the E split)
-  asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(e0), "s"(k));
-  asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(e1), "s"(k));
-  asm volatile("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(e0), "s"(k), "v"(hi));
-  asm volatile("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(e1), "s"(k), "v"(hi));
-}
-__device__ __forceinline__ void split8_e(const float (&e)[8], h8& eh, h8& el) {
-  u32x4 hv, lv;
-#pragma unroll
-  for (int pr = 0; pr < 4; ++pr) {
-    unsigned a, b;
-    split_pair_s(e[2 * pr], e[2 * pr + 1], 1024.0f, a, b);
-    hv[pr] = a; lv[pr] = b;
-  }
-  eh = __builtin_bit_cast(h8, hv);
-  el = __builtin_bit_cast(h8, lv);
-}
-// output patch (kernels_attn_x3.hip): lanes < 32 end up owning the whole hi chunk of their row, lanes >= 32 the whole lo chunk
-__device__ __forceinline__ void patch_wr(unsigned char* patch, int r, int h, int g, h4 oh, h4 ol) {
-  const uint2 a = __builtin_bit_cast(uint2, oh), b = __builtin_bit_cast(uint2, ol);
-  const auto s0 = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-  const auto s1 = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-  u32x4_alias v;
-  v[0] = s0[0]; v[1] = s1[0]; v[2] = s0[1]; v[3] = s1[1];
-  *reinterpret_cast<u32x4_alias*>(patch + r * 128 + ((((h << 2) + g) ^ (r & 7)) << 4)) = v;
-}
-__device__ __forceinline__ u32x4 patch_rd(const unsigned char* patch, int row, int chunk) {
-  return *reinterpret_cast<const u32x4_alias*>(patch + row * 128 + ((chunk ^ (row & 7)) << 4));
-}
+static_assert(QT_LDS <= 160 * 1024 && QT_RAW + QT_RAW_MAX <= QT_Q && QT_STX + QF_BM * 8 <= QT_LDS, "LDS map");
 
 struct QtArgs {
   const _Float16* Ap;      // residual stream, pair layout [M rows][2 K] of 8 x
@@ -117,23 +61,6 @@ struct QtArgs {
   unsigned* range;         // the engine's range-guard word
 };
 
-#define QT_GLDS(SRC, DSTOFF)                                                                                            \
-  __builtin_amdgcn_global_load_lds((SRC), (__attribute__((address_space(3))) void*)(uintptr_t)(lds + (DSTOFF)), 16, 0, 0)
-
-__device__ __forceinline__ void wait_vm(int n) {   // s_waitcnt vmcnt(n), n wave-uniform
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-  }
-}
-
-
 // LDS fragment reads as inline asm with hand-placed counted waits (kernels_attn_x3.hip: the compiler's own waits came out as
 // lgkmcnt(0) behind every pair of reads)
 template <int OFF>
@@ -150,12 +77,6 @@ template <int... Js, class F>
 __device__ __forceinline__ void static_for_(std::integer_sequence<int, Js...>, F&& f) { (f(std::integral_constant<int, Js>{}), ...); }
 template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_(std::make_integer_sequence<int, N>{}, f); }
-__device__ __forceinline__ void split_pair_v(float e0, float e1, float k, unsigned& hi, unsigned& lo) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(e0), "v"(k));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(e1), "v"(k));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(e0), "v"(k), "v"(hi));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(e1), "v"(k), "v"(hi));
-}
 
 constexpr int QT_NKT = 8;
 #ifndef QT_PB1
@@ -388,8 +309,8 @@ __device__ __forceinline__ void qt_products_outputs(unsigned char* const lds, in
         amax = fmaxf(fmaxf(amax, fabsf(o8[0])), fabsf(o8[1]));
         amax = fmaxf(fmaxf(amax, fabsf(o8[2])), fabsf(o8[3]));
         unsigned h0, l0, h1, l1;
-        split_pair_v(o8[0], o8[1], 1.0f, h0, l0);
-        split_pair_v(o8[2], o8[3], 1.0f, h1, l1);
+        split_pair(o8[0], o8[1], 1.0f, h0, l0);
+        split_pair(o8[2], o8[3], 1.0f, h1, l1);
         const h4 oh = __builtin_bit_cast(h4, make_uint2(h0, h1)), ol = __builtin_bit_cast(h4, make_uint2(l0, l1));
         if (!(QT_ABL & 8)) patch_wr(patch, r, h, g4, oh, ol);
         else asm volatile("" ::"v"(oh), "v"(ol));
@@ -468,10 +389,10 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
     const int lr = lane >> 3, csrc = (lane & 7) ^ (((wave & 1) << 2) | (lr >> 1));
     const size_t tok0_ = GRP ? (size_t)(bj_ / a.TPS) * T * J : (size_t)(bj_ / J) * T * J + (size_t)(bj_ % J);
     const char* tA = reinterpret_cast<const char*>(a.Ap) + tok0_ * K2 * 2;
-    const char* ubB = reinterpret_cast<const char*>(a.Wp) + (size_t)(hd_ * QT_BN + wave * 8) * K2 * 2;
+    const char* ubB = reinterpret_cast<const char*>(a.Wp) + (size_t)(hd_ * QF_BN + wave * 8) * K2 * 2;
     const unsigned lofsW = (unsigned)(lr * (int)K2 + csrc * 8) * 2u;
 #pragma unroll
-    for (int it = 0; it < QT_AIT; ++it) {
+    for (int it = 0; it < QF_AIT; ++it) {
       const int row = wave * 8 + 64 * it + lr;
       unsigned lo;
       if constexpr (GRP) {
@@ -480,28 +401,23 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
       } else {
         lo = (unsigned)(((size_t)(row < T ? row : T - 1) * J * K2 + csrc * 8) * 2);
       }
-      QT_GLDS(sgpr_ptr(tA) + lo, wave * 1024 + lane * 16 + it * 8192);
+      KL_GLDS(sgpr_ptr(tA) + lo, wave * 1024 + lane * 16 + it * 8192);
     }
     const size_t it_stride = (size_t)64 * K2 * 2;
 #pragma unroll
-    for (int it = 0; it < QT_BIT; ++it) QT_GLDS(sgpr_ptr(ubB + it * it_stride) + lofsW, QT_AREG + wave * 1024 + lane * 16 + it * 8192);
+    for (int it = 0; it < QF_BIT; ++it) KL_GLDS(sgpr_ptr(ubB + it * it_stride) + lofsW, QF_AREG + wave * 1024 + lane * 16 + it * 8192);
   };
   stage_first(bj, hd, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6));
   int tid_o = (int)threadIdx.x;
   for (int item = 0; item < nitems; ++item) {
-    asm volatile("" : "+v"(tid_o));   // per-lane offsets are re-derived in every tile instead of being hoisted (and spilled)
-    const int tid = tid_o;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int r16 = lane & 15, q = lane >> 4;
+    QF_TILE_LANES;
     const bool more = item + 1 < nitems;
     constexpr bool has_next = false;   // (the k-loop stages nothing of the next tile: the planes need the whole LDS)
     int bjn = 0, hdn = 0;
     if (more) tile_of((item + 1) * G + b, bjn, hdn);
     const size_t tok0 = GRP ? (size_t)(bj / a.TPS) * T * J : (size_t)(bj / J) * T * J + (size_t)(bj % J);   // GRP: the batch element's first token
     const int jt = GRP ? bj % a.TPS : 0;
-    const int n0 = hd * QT_BN;
+    const int n0 = hd * QF_BN;
 
     // ---- row statistics of the folded LayerNorm: raw partials gathered by LDS-DMA under the k-loop -- lane l of piece pc serves row
     // 16 pc + l / 4, 16-byte chunk l % 4 of its 64 bytes (8 partials) --, else read at the reduction
@@ -519,7 +435,7 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
         } else {
           lo = (unsigned)((size_t)(row < T ? row : T - 1) * J * 64 + (lane & 3) * 16);
         }
-        QT_GLDS(sgpr_ptr(src) + lo, QT_RAW + pc * 1024 + lane * 16);
+        KL_GLDS(sgpr_ptr(src) + lo, QT_RAW + pc * 1024 + lane * 16);
         ++st_issued;
       }
     }
@@ -537,51 +453,34 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
       const int row = wave * 8 + 192 + lr_;
       lofsA3_ = (unsigned)(((size_t)(row < T ? row : T - 1) * J * K2 + csrc_ * 8) * 2);
     }
-    unsigned lofsAg_[QT_AIT] = {0u, 0u, 0u, 0u};                                                // grouped form: A piece it, from the element's first token
+    unsigned lofsAg_[QF_AIT] = {0u, 0u, 0u, 0u};                                                // grouped form: A piece it, from the element's first token
     if constexpr (GRP) {
 #pragma unroll
-      for (int it = 0; it < QT_AIT; ++it) {
+      for (int it = 0; it < QF_AIT; ++it) {
         const int tr = grow(wave * 8 + 64 * it + lr_, jt);
         lofsAg_[it] = (unsigned)(((size_t)(tr >= 0 ? tr : jt * a.G) * K2 + csrc_ * 8) * 2);
       }
     }
     const size_t it_stride = (size_t)64 * K2 * 2, it_strideA = (size_t)64 * J * K2 * 2;
-    const int dstA = wave * 1024 + lane * 16, dstB = QT_AREG + wave * 1024 + lane * 16;
+    const int dstA = wave * 1024 + lane * 16, dstB = QF_AREG + wave * 1024 + lane * 16;
     // piece IT (A: 0..3, W: 4..6) of k-tile KTT of this tile
 #define QT_PIECE(KTT, IT)                                                                                               \
     do {                                                                                                                \
-      const int st_ = ((KTT) & 1) * QT_STAGE;                                                                           \
-      if (GRP && (IT) < QT_AIT) {                                                                                       \
-        QT_GLDS(sgpr_ptr(tA + (size_t)(KTT) * 128) + lofsAg_[(IT) < QT_AIT ? (IT) : 0], st_ + dstA + (IT) * 8192);      \
+      const int st_ = ((KTT) & 1) * QF_STAGE;                                                                           \
+      if (GRP && (IT) < QF_AIT) {                                                                                       \
+        KL_GLDS(sgpr_ptr(tA + (size_t)(KTT) * 128) + lofsAg_[(IT) < QF_AIT ? (IT) : 0], st_ + dstA + (IT) * 8192);      \
       } else if ((IT) < 3) {                                                                                            \
-        QT_GLDS(sgpr_ptr(ubA + ((size_t)(KTT) * 128 + (IT) * it_strideA)) + lofsA_, st_ + dstA + (IT) * 8192);          \
+        KL_GLDS(sgpr_ptr(ubA + ((size_t)(KTT) * 128 + (IT) * it_strideA)) + lofsA_, st_ + dstA + (IT) * 8192);          \
       } else if ((IT) == 3) {                                                                                           \
-        QT_GLDS(sgpr_ptr(tA + (size_t)(KTT) * 128) + lofsA3_, st_ + dstA + 3 * 8192);                                   \
+        KL_GLDS(sgpr_ptr(tA + (size_t)(KTT) * 128) + lofsA3_, st_ + dstA + 3 * 8192);                                   \
       } else {                                                                                                          \
-        QT_GLDS(sgpr_ptr(ubB + ((size_t)(KTT) * 128 + ((IT) - QT_AIT) * it_stride)) + lofs_, st_ + dstB + ((IT) - QT_AIT) * 8192); \
+        KL_GLDS(sgpr_ptr(ubB + ((size_t)(KTT) * 128 + ((IT) - QF_AIT) * it_stride)) + lofs_, st_ + dstB + ((IT) - QF_AIT) * 8192); \
       }                                                                                                                 \
     } while (0)
 
-    f32x4 acc[QT_TM][QT_NJ];
-#pragma unroll
-    for (int i = 0; i < QT_TM; ++i)
-#pragma unroll
-      for (int j = 0; j < QT_NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
-
-    const int foff = (q ^ (r16 >> 1)) << 4;
-    const int aoff = (wm * 128 + r16) * 128 + foff, boff = QT_AREG + (wn * 48 + r16) * 128 + foff;
-    h8 bh[QT_NJ], bl[QT_NJ], ah[2], al[2];
+    QF_TILE_ACC;
     int issued_prev = st_issued;
-    // the k-loop: qkv_fused_kloop.h (shared with the other fused kernel), this kernel's constants and DMA pieces behind the QF_ names
-#define QF_STAGE QT_STAGE
-#define QF_NJ QT_NJ
-#define QF_TM QT_TM
-#define QF_AIT QT_AIT
-#define QF_BIT QT_BIT
-#define QF_PIECE(KTT, IT) QT_PIECE(KTT, IT)
-    QF_KLOOP_HEAD
+    QF_KLOOP_HEAD(QT_PIECE)
     // ---- row statistics -> (rstd * out_scale, -mean rstd) per tile row, in front of the last k-tile: every wave reduces 32 rows (lanes
     // 0-31) in the shadow of its SIMD partner's MFMAs -- behind the k-loop this step was 1.1 us of a 38 us tile with half the waves
     // idle.  The raw partials landed long ago (the first counted wait of the tile retired them; phase barriers since).
@@ -610,25 +509,18 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
         srow[t] = make_float2(rstd * a.out_scale, -mean * rstd);
       }
     }
-    QF_KLOOP_TAIL
-#undef QF_STAGE
-#undef QF_NJ
-#undef QF_TM
-#undef QF_AIT
-#undef QF_BIT
-#undef QF_PIECE
-#undef QT_PIECE
+    QF_KLOOP_TAIL(QT_PIECE)
     __builtin_amdgcn_s_setprio(0);
     if constexpr (GRP) asm volatile("" : "+v"(lofsAg_[0]), "+v"(lofsAg_[1]), "+v"(lofsAg_[2]), "+v"(lofsAg_[3]));
     else asm volatile("" : "+v"(lofsA_), "+v"(lofsA3_));
 
     __syncthreads();   // statistics visible; every wave is out of the k-loop: the LDS becomes planes + exchange
-    float2 st[QT_TM];
+    float2 st[QF_TM];
 #pragma unroll
-    for (int i = 0; i < QT_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + QT_STX)[wm * 128 + 16 * i + r16];
-    float4 cs4[QT_NJ], b4[QT_NJ];
+    for (int i = 0; i < QF_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + QT_STX)[wm * 16 * QF_TM + 16 * i + r16];
+    float4 cs4[QF_NJ], b4[QF_NJ];
 #pragma unroll
-    for (int j = 0; j < QT_NJ; ++j) {
+    for (int j = 0; j < QF_NJ; ++j) {
       const int n = n0 + wn * 48 + 16 * j + 4 * q;
       cs4[j] = *reinterpret_cast<const float4*>(a.csum + n);
       b4[j] = *reinterpret_cast<const float4*>(a.bias + n);
@@ -638,15 +530,15 @@ __global__ __launch_bounds__(512) void k_qkv_tattn(QtArgs a) {
     // are compile-time per j).  Lane: rows 128 wm + 16 i + r16, head dims 16 wn + 4 q .. + 3 = 8 bytes of 16-byte chunk 2 wn + (q >> 1).
     typedef float f2 __attribute__((ext_vector_type(2)));
     const int chunk = 2 * wn + (q >> 1), half8 = (q & 1) << 3;
-    float amaxj[QT_NJ] = {0.0f, 0.0f, 0.0f};
+    float amaxj[QF_NJ] = {0.0f, 0.0f, 0.0f};
     auto write_rows = [&](bool want_q, bool want_kv) {
 #pragma unroll
-      for (int i = 0; i < QT_TM; ++i) {
-        const int R = wm * 128 + 16 * i + r16;                             // tile row = frame
+      for (int i = 0; i < QF_TM; ++i) {
+        const int R = wm * 16 * QF_TM + 16 * i + r16;                             // tile row = frame
         const int Rq = 16 * i + r16;                                       // row inside this half's exchange planes
         const f2 sx = (f2)(st[i].x), sy = (f2)(st[i].y);
 #pragma unroll
-        for (int j = 0; j < QT_NJ; ++j) {
+        for (int j = 0; j < QF_NJ; ++j) {
           if (j == 0 ? !want_q : !want_kv) continue;
           const float osc = j == 0 ? 1.0f : 8.0f;
           f2 a01, a23, c01, c23, b01, b23;
@@ -794,11 +686,8 @@ hipError_t launch_qkv_tattn(const void* Apair, const void* Wpair_tileorder, cons
   a.range = launch_range_word();
   const void* kfn = grp ? reinterpret_cast<const void*>(k_qkv_tattn<true>) : reinterpret_cast<const void*>(k_qkv_tattn<false>);
   static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};   // one bit per device
-  if (hipError_t ae = lds_optin(kfn, QT_LDS, attr_done[grp ? 1 : 0])) return ae;
-  int n_cu = device_cu_count();
-  if (n_cu <= 0) return hipErrorUnknown;
-  const int tiles = a.BJ * 8;
-  const int grid = tiles < n_cu ? tiles : n_cu;
+  int grid = 0;
+  if (hipError_t ge = persistent_grid(kfn, QT_LDS, attr_done[grp ? 1 : 0], (long long)a.BJ * 8, grid)) return ge;
   if (grp) hipLaunchKernelGGL(k_qkv_tattn<true>, dim3(grid), dim3(512), QT_LDS, s, a);
   else hipLaunchKernelGGL(k_qkv_tattn<false>, dim3(grid), dim3(512), QT_LDS, s, a);
   return hipGetLastError();
