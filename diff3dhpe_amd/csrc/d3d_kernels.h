@@ -13,6 +13,9 @@ namespace d3d {
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device's function object, and the CU count is a
 // property of a device: both are cached per device (one process may drive several GPUs -- nn.DataParallel, RUN:216-218 --
 // from several threads).  `done` holds one bit per device ordinal; racing threads at worst repeat the idempotent call.
+// Every kernel that takes dynamic LDS is launched through launch_lds<kernel>: the opt-in word must be one per kernel
+// instantiation, and the function-local static of a template keyed on the kernel itself is exactly that -- no launcher
+// declares a word of its own.
 inline hipError_t lds_optin(const void* fn, size_t bytes, std::atomic<unsigned long long>& done) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -34,10 +37,22 @@ inline int device_cu_count() {
   cache[dev & 63].store(n, std::memory_order_release);
   return n;
 }
-// launch tail of the persistent kernels that hold a CU each: opts `fn` in to `lds_bytes` of dynamic LDS on the current device and sets
-// `grid` to one workgroup per CU, at most one per tile
-inline hipError_t persistent_grid(const void* fn, size_t lds_bytes, std::atomic<unsigned long long>& done, long long tiles, int& grid) {
-  if (hipError_t ae = lds_optin(fn, lds_bytes, done)) return ae;
+// Launch of kernel Kfn with lds_bytes of dynamic LDS: opts Kfn in on the current device (once per device), launches, returns the
+// launch's error.  optin_bytes: the size opted in to where it is not the launch's own (a kernel whose LDS varies from call to call
+// opts in to its maximum once).
+template <auto Kfn, class... Args>
+hipError_t launch_lds_optin(size_t optin_bytes, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, Args... args) {
+  static std::atomic<unsigned long long> done{0};   // one word per Kfn, one bit per device
+  if (hipError_t e = lds_optin(reinterpret_cast<const void*>(Kfn), optin_bytes, done)) return e;
+  hipLaunchKernelGGL(Kfn, grid, block, lds_bytes, s, args...);
+  return hipGetLastError();
+}
+template <auto Kfn, class... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, Args... args) {
+  return launch_lds_optin<Kfn>(lds_bytes, grid, block, lds_bytes, s, args...);
+}
+// grid of the persistent kernels that hold a CU each: one workgroup per CU, at most one per tile
+inline hipError_t persistent_grid(long long tiles, int& grid) {
   const int n_cu = device_cu_count();
   if (n_cu <= 0) return hipErrorUnknown;
   if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;

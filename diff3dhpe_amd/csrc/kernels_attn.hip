@@ -314,13 +314,10 @@ template <int NKT>
 static hipError_t launch_temporal_nkt(const float* qkv, float* out, void* out_x3, int B, int T, int J, int D, int H,
                                       hipStream_t s) {
   const size_t lds_bytes = (size_t)32 * NKT * (K_LD + V_LD) * sizeof(float);
-  static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-  if (hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_attn_temporal_f32<NKT>), lds_bytes, attr_set)) return e;
   const long long grid = (long long)B * J * H;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_attn_temporal_f32<NKT>, dim3((unsigned)grid), dim3(64 * NKT), lds_bytes, s, qkv, out,
-                     (_Float16*)out_x3, T, J, H, D, launch_range_word());
-  return hipGetLastError();
+  return launch_lds<k_attn_temporal_f32<NKT>>(dim3((unsigned)grid), dim3(64 * NKT), lds_bytes, s, qkv, out, (_Float16*)out_x3, T, J, H, D,
+                                              launch_range_word());
 }
 
 hipError_t launch_attn_temporal_f32(const float* qkv, float* out, void* out_x3, int B, int T, int J, int D, int H,

@@ -222,13 +222,10 @@ bool attn_bf16_ok(int T, int D, int H) { return T >= 1 && T <= 256 && H > 0 && D
 template <int NKT, int MU = 1, int QT = 1>
 static hipError_t launch_nkt(const __bf16* qkv, __bf16* out, int B, int T, int J, int D, int H, hipStream_t s) {
   const size_t lds_bytes = (size_t)MU * 2 * 32 * NKT * 128;
-  static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-  if (hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_attn_bf16<NKT, MU, QT>), lds_bytes, attr_set)) return e;
   const long long units = (long long)B * J * H;
   if (units > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_attn_bf16<NKT, MU, QT>), dim3((unsigned)((units + MU - 1) / MU)), dim3(64 * ((NKT + QT - 1) / QT) * MU), lds_bytes, s,
-                     qkv, out, T, J, H, D, (int)units);
-  return hipGetLastError();
+  return launch_lds<k_attn_bf16<NKT, MU, QT>>(dim3((unsigned)((units + MU - 1) / MU)), dim3(64 * ((NKT + QT - 1) / QT) * MU), lds_bytes, s,
+                                              qkv, out, T, J, H, D, (int)units);
 }
 
 // qkv: bf16 [B*T*J][3D] (q third pre-scaled by dh^-0.5); out: bf16 [B*T*J][D].  Spatial blocks: call with (B*T, J, 1).

@@ -936,13 +936,10 @@ template <int NKT, int MU = 1>
 static hipError_t launch_x3_nkt(const _Float16* ph, const _Float16* pl, _Float16* ox, int B, int T, int J, int D,
                                 int H, hipStream_t s) {
   const size_t lds_bytes = (size_t)MU * 4 * 32 * NKT * 128;   // per unit: K_hi, K_lo, V_hi, V_lo planes of TP rows x 128 B
-  static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-  if (hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_attn_temporal_x3<NKT, MU>), lds_bytes, attr_set)) return e;
   const long long units = (long long)B * J * H;
   if (units > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_attn_temporal_x3<NKT, MU>), dim3((unsigned)((units + MU - 1) / MU)), dim3(64 * NKT * MU), lds_bytes, s, ph,
-                     pl, ox, T, J, H, D, (int)units, launch_range_word());
-  return hipGetLastError();
+  return launch_lds<k_attn_temporal_x3<NKT, MU>>(dim3((unsigned)((units + MU - 1) / MU)), dim3(64 * NKT * MU), lds_bytes, s, ph, pl, ox, T,
+                                                 J, H, D, (int)units, launch_range_word());
 }
 
 template <int NKT, int MU = 1, int WIT = 3>
@@ -950,10 +947,6 @@ static hipError_t launch_x3p_nkt(const _Float16* ph, const _Float16* pl, _Float1
                                  hipStream_t s) {
   // wave-private units (MU > 1, NKT == 1): 6 planes of T rows per wave (V double-buffered) + one zeroed pad behind the last
   const size_t lds_bytes = MU > 1 ? (size_t)MU * 6 * T * 128 + (size_t)(32 * NKT - T) * 128 + (size_t)MU * 4096 : (size_t)4 * 32 * NKT * 128 + (size_t)NKT * 4096;
-  static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-  if (hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_attn_temporal_x3p<NKT, MU, WIT>), MU > 1 ? (size_t)160 * 1024 : lds_bytes,
-                               attr_set))
-    return e;
   const int n_cu = device_cu_count();
   if (n_cu <= 0) return hipErrorUnknown;
   const long long units = (long long)B * J * H;
@@ -974,23 +967,21 @@ static hipError_t launch_x3p_nkt(const _Float16* ph, const _Float16* pl, _Float1
   }
   const long long wgs = (units + MU - 1) / MU;
   const long long grid = wgs < (long long)n_cu * per_cu ? wgs : (long long)n_cu * per_cu;
-  hipLaunchKernelGGL((k_attn_temporal_x3p<NKT, MU, WIT>), dim3((unsigned)grid), dim3(64 * NKT * MU), lds_bytes, s, ph, pl, ox, T, J, H,
-                     D, (int)units, launch_range_word());
-  return hipGetLastError();
+  // the wave-private form's LDS varies with T: it opts in to the whole 160 KiB once
+  return launch_lds_optin<k_attn_temporal_x3p<NKT, MU, WIT>>(MU > 1 ? (size_t)160 * 1024 : lds_bytes, dim3((unsigned)grid), dim3(64 * NKT * MU),
+                                                             lds_bytes, s, ph, pl, ox, T, J, H, D, (int)units, launch_range_word());
 }
 
 static hipError_t launch_x3s(const _Float16* ph, const _Float16* pl, _Float16* ox, int B, int T, int J, int D, int H, hipStream_t s) {
   constexpr int NKT = 8;
   const size_t lds_bytes = (size_t)4 * 32 * NKT * 128 + NKT * 4096;   // K / V planes + one 4 KiB output patch per wave = 160 KiB
-  static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-  if (hipError_t e = lds_optin(reinterpret_cast<const void*>(&k_attn_temporal_x3s<NKT>), lds_bytes, attr_set)) return e;
   const int n_cu = device_cu_count();
   if (n_cu <= 0) return hipErrorUnknown;
   const long long units = (long long)B * J * H;
   if (units > 0x7fffffffLL / 4) return hipErrorInvalidValue;
   const long long grid = units < n_cu ? units : n_cu;
-  hipLaunchKernelGGL((k_attn_temporal_x3s<NKT>), dim3((unsigned)grid), dim3(64 * NKT), lds_bytes, s, ph, pl, ox, T, J, H, D, (int)units, launch_range_word());
-  return hipGetLastError();
+  return launch_lds<k_attn_temporal_x3s<NKT>>(dim3((unsigned)grid), dim3(64 * NKT), lds_bytes, s, ph, pl, ox, T, J, H, D, (int)units,
+                                              launch_range_word());
 }
 
 hipError_t launch_attn_temporal_x3(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J,

@@ -78,17 +78,10 @@ hipError_t launch_gemm_bf16q(const void* A, const void* W, const float* bias, vo
   a.Ap = (const _Float16*)A; a.Wp = (const _Float16*)W; a.bias = bias; a.out = (_Float16*)Cb;
   a.M = M; a.N = N; a.Kp = K / 2; a.mtiles = (M + QF_BM - 1) / QF_BM; a.ntiles = N / QF_BN; a.qcols = qcols;
   a.range = launch_range_word();
-  static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};   // one bit per device
-  const long long tiles = (long long)a.mtiles * a.ntiles;
   int grid = 0;
-  if (epi == EPI_GELU) {
-    if (hipError_t ge = persistent_grid(reinterpret_cast<const void*>(k_gemm_bf16q<EPI_GELU>), BQ_LDS, attr_done[1], tiles, grid)) return ge;
-    hipLaunchKernelGGL(k_gemm_bf16q<EPI_GELU>, dim3(grid), dim3(512), BQ_LDS, s, a);
-  } else {
-    if (hipError_t ge = persistent_grid(reinterpret_cast<const void*>(k_gemm_bf16q<EPI_NONE>), BQ_LDS, attr_done[0], tiles, grid)) return ge;
-    hipLaunchKernelGGL(k_gemm_bf16q<EPI_NONE>, dim3(grid), dim3(512), BQ_LDS, s, a);
-  }
-  return hipGetLastError();
+  if (hipError_t ge = persistent_grid((long long)a.mtiles * a.ntiles, grid)) return ge;
+  return epi == EPI_GELU ? launch_lds<k_gemm_bf16q<EPI_GELU>>(dim3(grid), dim3(512), BQ_LDS, s, a)
+                         : launch_lds<k_gemm_bf16q<EPI_NONE>>(dim3(grid), dim3(512), BQ_LDS, s, a);
 }
 
 }  // namespace d3d

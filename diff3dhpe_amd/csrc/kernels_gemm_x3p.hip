@@ -46,24 +46,6 @@ namespace d3d {
 // kloop_common.h; here for the operands Ap / Wp of K columns and the tile at (m0, n0), all in scope.
 #define D3D_DMA_PLAN(NW_, BM_) KL_DMA_PLAN(Ap, Wp, 2 * (size_t)K, m0, n0, NW_, (BM_) * 128)
 
-// Launch-time dispatch over (epilogue, output form): the five combinations the engine and the op hooks use.
-#define D3D_X3_DISPATCH(LAUNCH)                                                                                          \
-  do {                                                                                                                   \
-    if (outsplit == 0) {                                                                                                 \
-      if (epi == EPI_NONE) LAUNCH(EPI_NONE, 0);                                                                          \
-      else if (epi == EPI_GELU) LAUNCH(EPI_GELU, 0);                                                                     \
-      else if (epi == EPI_RESIDUAL) LAUNCH(EPI_RESIDUAL, 0);                                                             \
-      else return hipErrorInvalidValue;                                                                                  \
-    } else if (outsplit == 1) {                                                                                          \
-      if (epi == EPI_NONE) LAUNCH(EPI_NONE, 1);                                                                          \
-      else return hipErrorInvalidValue;                                                                                  \
-    } else {                                                                                                             \
-      if (epi == EPI_GELU) LAUNCH(EPI_GELU, 2);                                                                          \
-      else if (epi == EPI_NONE) LAUNCH(EPI_NONE, 2);                                                                     \
-      else return hipErrorInvalidValue;                                                                                  \
-    }                                                                                                                    \
-  } while (0)
-
 #include "gemm_x3p_epilogue.h"
 
 // The products of one (m-tile, n-tile) pair for one staged 128-byte line of each operand row.  F16X3: the line holds the 32 hi
@@ -769,6 +751,37 @@ static X3Walk x3q_walk(int tiles, int grid, bool four_way = true) {
   return w;
 }
 
+// The forms of the tile template that exist, X(FX, EPI, OUTSPLIT) -- listed once; launch_x3q (one workgroup per tile) and
+// launch_x3q_persist (the walk) instantiate their kernels from this list, under their own compile-time conditions.  (The list's
+// order is the kernels' order in the code object.)
+#define D3D_X3_FORMS(X)                                                                                                  \
+  /* bf16 operand mode: the three forms its block flow uses (launch_linear_bf16) */                                      \
+  X(FX_BF16, EPI_NONE, 3) X(FX_BF16, EPI_GELU, 3) X(FX_BF16, EPI_RESIDUAL, 0)                                            \
+  /* plain: the fp32-stream flow and the op hooks */                                                                     \
+  X(0, EPI_NONE, 0) X(0, EPI_GELU, 0) X(0, EPI_RESIDUAL, 0) X(0, EPI_NONE, 1) X(0, EPI_GELU, 2) X(0, EPI_NONE, 2)        \
+  /* folded forms of the engine's plane-resident block (engine.hip run_blocks): qkv, proj, fc1, fc2 */                   \
+  X(FX_LNF, EPI_NONE, 1) X(FX_RP | FX_SO, EPI_RESIDUAL, 2) X(FX_LNF, EPI_GELU, 2) X(FX_RP, EPI_RESIDUAL, 0)
+// whether the call in scope (fx, epi, outsplit) asks for a form; a plain call with an outsplit other than 0 and 1 means the pair layout
+#define D3D_X3_FORM_IS(FX_, EPI_, OS_) \
+  (fx == (FX_) && epi == EPI_ && ((FX_) == 0 && OS_ == 2 ? outsplit != 0 && outsplit != 1 : outsplit == OS_))
+
+// fold -> (fx bits, device tail) of a launch; -1 for a folded LayerNorm without its column sums / partial count.  The LDS the
+// statistics take beyond the operand stages differs between the launchers and stays with them.
+static int x3q_fold_tail(const X3Fold* fold, int w_exp, bool bf16, X3Tail& tail) {
+  tail.out_scale = bf16 ? 1.0f : ldexpf(1.0f, -(3 + w_exp));
+  tail.range = launch_range_word();
+  int fx = bf16 ? FX_BF16 : 0;
+  if (fold) {
+    if (fold->st_in) fx |= FX_LNF;
+    if (fold->Rp) fx |= FX_RP;
+    if (fold->st_out) fx |= FX_SO;
+    tail.st_in = fold->st_in; tail.st_np = fold->st_np; tail.csum = fold->csum; tail.eps = fold->eps;
+    tail.Rp = (const _Float16*)fold->Rp; tail.st_out = fold->st_out;
+    if ((fx & FX_LNF) && (!fold->csum || fold->st_np < 1)) return -1;
+  }
+  return fx;
+}
+
 template <int TM, int WM, int WN, int NST = 2>
 static hipError_t launch_x3q(const _Float16* Ap, const _Float16* Wp, const float* bias, const float* R, float* C, _Float16* Ch,
                              _Float16* Cl, int M, int N, int K, int epi, int outsplit, int qcols, hipStream_t s,
@@ -778,53 +791,18 @@ static hipError_t launch_x3q(const _Float16* Ap, const _Float16* Wp, const float
   const int grid = ((mtiles + 7) / 8) * 8 * ntiles;
   size_t lds_bytes = NST * (size_t)((BM + BN) * 128);
   X3Tail tail{};
-  tail.out_scale = ldexpf(1.0f, -(3 + w_exp));
-  tail.range = launch_range_word();
-  int fx = 0;
-  if (fold) {
-    if (fold->st_in) fx |= FX_LNF;
-    if (fold->Rp) fx |= FX_RP;
-    if (fold->st_out) fx |= FX_SO;
-    tail.st_in = fold->st_in; tail.st_np = fold->st_np; tail.csum = fold->csum; tail.eps = fold->eps;
-    tail.Rp = (const _Float16*)fold->Rp; tail.st_out = fold->st_out;
-    if (fx & FX_LNF) lds_bytes += (size_t)BM * 8;   // row statistics beyond the operand stages
-    else if (fx & FX_SO) lds_bytes += 8 * 1024;     // a kilobyte per wave for the rows' statistics (x3q_epilogue8)
-    if ((fx & FX_LNF) && (!fold->csum || fold->st_np < 1)) return hipErrorInvalidValue;
-  }
-#define D3D_X3Q_LAUNCH_FX(EPI_, OS_, FX_)                                                                                 \
-  do {                                                                                                                    \
-    auto kfn = k_linear_x3q<TM, WM, WN, EPI_, OS_, FX_, NST>;                                                             \
-    static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                       \
-    if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;                   \
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * WM * WN), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles,    \
-                       ntiles, qcols, tail);                                                                              \
-  } while (0)
-#define D3D_X3Q_LAUNCH(EPI_, OS_) D3D_X3Q_LAUNCH_FX(EPI_, OS_, 0)
-  if (bf16) {   // bf16 operand mode: the three forms its block flow uses (launch_linear_bf16)
-    tail.out_scale = 1.0f;
-    if constexpr (WM * WN == 8) {
-      if (fx == 0 && epi == EPI_NONE && outsplit == 3) D3D_X3Q_LAUNCH_FX(EPI_NONE, 3, FX_BF16);
-      else if (fx == 0 && epi == EPI_GELU && outsplit == 3) D3D_X3Q_LAUNCH_FX(EPI_GELU, 3, FX_BF16);
-      else if (fx == 0 && epi == EPI_RESIDUAL && outsplit == 0) D3D_X3Q_LAUNCH_FX(EPI_RESIDUAL, 0, FX_BF16);
-      else return hipErrorInvalidValue;
-    } else {
-      return hipErrorInvalidValue;
-    }
-  } else if (fx == 0) {
-    D3D_X3_DISPATCH(D3D_X3Q_LAUNCH);
-  } else if constexpr (WM * WN == 8) {   // folded forms exist for the production (8-wave) shapes only
-    // the four folded forms of the engine's plane-resident block (engine.hip run_blocks)
-    if (fx == FX_LNF && epi == EPI_NONE && outsplit == 1) D3D_X3Q_LAUNCH_FX(EPI_NONE, 1, FX_LNF);                        // qkv
-    else if (fx == (FX_RP | FX_SO) && epi == EPI_RESIDUAL && outsplit == 2) D3D_X3Q_LAUNCH_FX(EPI_RESIDUAL, 2, FX_RP | FX_SO);  // proj
-    else if (fx == FX_LNF && epi == EPI_GELU && outsplit == 2) D3D_X3Q_LAUNCH_FX(EPI_GELU, 2, FX_LNF);                   // fc1
-    else if (fx == FX_RP && epi == EPI_RESIDUAL && outsplit == 0) D3D_X3Q_LAUNCH_FX(EPI_RESIDUAL, 0, FX_RP);             // fc2
-    else return hipErrorInvalidValue;
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef D3D_X3Q_LAUNCH
-#undef D3D_X3Q_LAUNCH_FX
-  return hipGetLastError();
+  const int fx = x3q_fold_tail(fold, w_exp, bf16, tail);
+  if (fx < 0) return hipErrorInvalidValue;
+  if (fx & FX_LNF) lds_bytes += (size_t)BM * 8;   // row statistics beyond the operand stages
+  else if (fx & FX_SO) lds_bytes += 8 * 1024;     // a kilobyte per wave for the rows' statistics (x3q_epilogue8)
+#define D3D_X3Q_FORM(FX_, EPI_, OS_)                                                                                      \
+  if constexpr ((FX_) == 0 || WM * WN == 8)   /* bf16 and folded forms exist for the production (8-wave) shapes only */   \
+    if (D3D_X3_FORM_IS(FX_, EPI_, OS_))                                                                                   \
+      return launch_lds<k_linear_x3q<TM, WM, WN, EPI_, OS_, FX_, NST>>(dim3(grid), dim3(64 * WM * WN), lds_bytes, s, Ap, Wp, bias, R, C, \
+                                                                       Ch, Cl, M, N, K, mtiles, ntiles, qcols, tail);
+  D3D_X3_FORMS(D3D_X3Q_FORM)
+#undef D3D_X3Q_FORM
+  return hipErrorInvalidValue;
 }
 
 // Tile choice: 256x256 -- as a persistent walk, one workgroup per CU (k_linear_x3q_persist: +1 % over one workgroup per tile:
@@ -850,49 +828,18 @@ static hipError_t launch_x3q_persist(const _Float16* Ap, const _Float16* Wp, con
   constexpr size_t STAGE = (size_t)(BM + 256) * 128;
   size_t lds_bytes = std::max(2 * STAGE, STAGE + 65536);     // two operand stages; the epilogue patches (64 KiB) start at stage 1
   X3Tail tail{};
-  tail.out_scale = ldexpf(1.0f, -(3 + w_exp));
-  tail.range = launch_range_word();
-  int fx = 0;
-  if (fold) {
-    if (fold->st_in) fx |= FX_LNF;
-    if (fold->Rp) fx |= FX_RP;
-    if (fold->st_out) fx |= FX_SO;
-    tail.st_in = fold->st_in; tail.st_np = fold->st_np; tail.csum = fold->csum; tail.eps = fold->eps;
-    tail.Rp = (const _Float16*)fold->Rp; tail.st_out = fold->st_out;
-    if (fx & FX_LNF) lds_bytes += (size_t)BM * 8 + 16384;   // (rstd, -mean rstd) per row + the raw partials staged by LDS-DMA
-    else if (fx & FX_SO) lds_bytes += 8 * 1024;              // a kilobyte per wave for the rows' statistics (x3q_epilogue8)
-    if ((fx & FX_LNF) && (!fold->csum || fold->st_np < 1)) return hipErrorInvalidValue;
-  }
-#define D3D_X3P_LAUNCH_FX(EPI_, OS_, FX_)                                                                                 \
-  do {                                                                                                                    \
-    auto kfn = k_linear_x3q_persist<TM, 2, 4, EPI_, OS_, FX_>;                                                                     \
-    static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                       \
-    if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;                   \
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles, ntiles,     \
-                       qcols, wk, tail);                                                                                  \
-  } while (0)
-#define D3D_X3P_LAUNCH(EPI_, OS_) D3D_X3P_LAUNCH_FX(EPI_, OS_, 0)
-  if constexpr (TM != 8) {   // the 192-row walk exists for the proj form only
-    if (!bf16 && fx == (FX_RP | FX_SO) && epi == EPI_RESIDUAL && outsplit == 2) D3D_X3P_LAUNCH_FX(EPI_RESIDUAL, 2, FX_RP | FX_SO);
-    else return hipErrorInvalidValue;
-  } else if (bf16) {
-    tail.out_scale = 1.0f;
-    if (fx == 0 && epi == EPI_NONE && outsplit == 3) D3D_X3P_LAUNCH_FX(EPI_NONE, 3, FX_BF16);
-    else if (fx == 0 && epi == EPI_GELU && outsplit == 3) D3D_X3P_LAUNCH_FX(EPI_GELU, 3, FX_BF16);
-    else if (fx == 0 && epi == EPI_RESIDUAL && outsplit == 0) D3D_X3P_LAUNCH_FX(EPI_RESIDUAL, 0, FX_BF16);
-    else return hipErrorInvalidValue;
-  } else if (fx == 0) {
-    D3D_X3_DISPATCH(D3D_X3P_LAUNCH);
-  } else {
-    if (fx == FX_LNF && epi == EPI_NONE && outsplit == 1) D3D_X3P_LAUNCH_FX(EPI_NONE, 1, FX_LNF);
-    else if (fx == (FX_RP | FX_SO) && epi == EPI_RESIDUAL && outsplit == 2) D3D_X3P_LAUNCH_FX(EPI_RESIDUAL, 2, FX_RP | FX_SO);
-    else if (fx == FX_LNF && epi == EPI_GELU && outsplit == 2) D3D_X3P_LAUNCH_FX(EPI_GELU, 2, FX_LNF);
-    else if (fx == FX_RP && epi == EPI_RESIDUAL && outsplit == 0) D3D_X3P_LAUNCH_FX(EPI_RESIDUAL, 0, FX_RP);
-    else return hipErrorInvalidValue;
-  }
-#undef D3D_X3P_LAUNCH
-#undef D3D_X3P_LAUNCH_FX
-  return hipGetLastError();
+  const int fx = x3q_fold_tail(fold, w_exp, bf16, tail);
+  if (fx < 0) return hipErrorInvalidValue;
+  if (fx & FX_LNF) lds_bytes += (size_t)BM * 8 + 16384;   // (rstd, -mean rstd) per row + the raw partials staged by LDS-DMA
+  else if (fx & FX_SO) lds_bytes += 8 * 1024;              // a kilobyte per wave for the rows' statistics (x3q_epilogue8)
+#define D3D_X3P_FORM(FX_, EPI_, OS_)                                                                                      \
+  if constexpr (TM == 8 || (FX_) == (FX_RP | FX_SO))   /* the 192-row walk exists for the proj form only */               \
+    if (D3D_X3_FORM_IS(FX_, EPI_, OS_))                                                                                   \
+      return launch_lds<k_linear_x3q_persist<TM, 2, 4, EPI_, OS_, FX_>>(dim3(grid), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, \
+                                                                        K, mtiles, ntiles, qcols, wk, tail);
+  D3D_X3_FORMS(D3D_X3P_FORM)
+#undef D3D_X3P_FORM
+  return hipErrorInvalidValue;
 }
 
 // Post-norm form (X3Fold::pn): 128 x 512 tiles (<8,1,8>: eight waves of 128 x 64 side by side, 2 x 80 KiB of LDS -- the whole
@@ -902,6 +849,28 @@ static hipError_t launch_x3q_persist(const _Float16* Ap, const _Float16* Wp, con
 // otherwise), so the result stays batch-size independent bitwise.
 bool x3q_postnorm_ok(int N, int K) { return N == 512 && K % PBK == 0; }
 
+// The launch ladder of the whole-row tiles, for the F16X3 post-norm form (FX_RP | FX_PN, K pair columns) and the bf16 whole-row form
+// (FX_PN | FX_BF16, K / 2 pair columns): the persistent walk where the 128-row tiles fill the chip for a few rounds (and the k-tile
+// count is even), 64-row tiles where there are fewer 128-row tiles than CUs (same values: rows are independent), else one 128-row
+// tile per workgroup.
+template <int OS, int FX>
+static hipError_t launch_x3q_rows(const _Float16* Ap, const _Float16* Wp, const float* bias, float* C, _Float16* Ch, int M, int N, int K,
+                                  const X3Tail& tail, hipStream_t s) {
+  int n_cu = device_cu_count() / 8 * 8;   // (per device)
+  if (n_cu < 8) n_cu = 8;
+  const float* R = nullptr;
+  _Float16* Cl = nullptr;
+  const int mtiles = (M + 127) / 128, mtiles64 = (M + 63) / 64, ntiles = 1, qcols = 0;
+  const size_t lds_bytes = 2 * (size_t)((128 + 512) * 128), lds_small = 2 * (size_t)((64 + 512) * 128);
+  if (mtiles >= 4 * n_cu && (K / PBK) % 2 == 0)
+    return launch_lds<k_linear_x3q_persist<8, 1, 8, EPI_RESIDUAL, OS, FX>>(dim3(n_cu), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles, ntiles, qcols,
+                                                                           x3q_walk(mtiles, n_cu), tail);
+  if (mtiles < n_cu)
+    return launch_lds<k_linear_x3q<4, 1, 8, EPI_RESIDUAL, OS, FX>>(dim3((mtiles64 + 7) / 8 * 8), dim3(512), lds_small, s, Ap, Wp, bias, R, C,
+                                                                   Ch, Cl, M, N, K, mtiles64, ntiles, qcols, tail);
+  return launch_lds<k_linear_x3q<8, 1, 8, EPI_RESIDUAL, OS, FX>>(dim3((mtiles + 7) / 8 * 8), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles, ntiles, qcols, tail);
+}
+
 static hipError_t launch_x3q_pn(const _Float16* Ap, const _Float16* Wp, const float* bias, float* C, _Float16* Ch, int M, int N,
                                 int K, int outsplit, hipStream_t s, const X3Fold* fold, int w_exp) {
   if (!x3q_postnorm_ok(N, K) || !fold->Rp || !fold->pn.b || !bias || (outsplit == 2 ? (!Ch || !fold->st_out) : !C))
@@ -909,49 +878,12 @@ static hipError_t launch_x3q_pn(const _Float16* Ap, const _Float16* Wp, const fl
   if (outsplit != 0 && outsplit != 2) return hipErrorInvalidValue;
   if (fold->pn.pos && (fold->pn.pos_div < 1 || fold->pn.pos_mod < 1)) return hipErrorInvalidValue;
   if (fold->pn.tvec && fold->pn.tvec_stride != 0 && fold->pn.rows_per_batch < 1) return hipErrorInvalidValue;
-  const int mtiles = (M + 127) / 128, ntiles = 1;
-  const int vtiles = ((mtiles + 7) / 8) * 8;
-  int n_cu = device_cu_count() / 8 * 8;   // (per device)
-  if (n_cu < 8) n_cu = 8;
-  const bool persist = mtiles >= 4 * n_cu && (K / PBK) % 2 == 0;
-  const X3Walk wk = x3q_walk(mtiles * ntiles, n_cu);
-  const size_t lds_bytes = 2 * (size_t)((128 + 512) * 128);
-  const bool small = mtiles < n_cu;
-  const int mtiles64 = (M + 63) / 64, vtiles64 = ((mtiles64 + 7) / 8) * 8;
-  const size_t lds_small = 2 * (size_t)((64 + 512) * 128);
   X3Tail tail{};
   tail.out_scale = ldexpf(1.0f, -(3 + w_exp));
   tail.range = launch_range_word();
   tail.Rp = (const _Float16*)fold->Rp; tail.st_out = fold->st_out; tail.pn = fold->pn;
-  const int qcols = 0;
-  _Float16* Cl = nullptr;
-  const float* R = nullptr;
-#define D3D_X3PN_LAUNCH(OS_)                                                                                              \
-  do {                                                                                                                    \
-    if (persist) {                                                                                                        \
-      auto kfn = k_linear_x3q_persist<8, 1, 8, EPI_RESIDUAL, OS_, FX_RP | FX_PN>;                                         \
-      static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                     \
-      if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;                 \
-      hipLaunchKernelGGL(kfn, dim3(n_cu), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles, ntiles,   \
-                         qcols, wk, tail);                                                                                \
-    } else if (small) {   /* fewer 128-row tiles than CUs: 64-row tiles (same values: rows are independent) */            \
-      auto kfn = k_linear_x3q<4, 1, 8, EPI_RESIDUAL, OS_, FX_RP | FX_PN>;                                                 \
-      static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                     \
-      if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_small, attr_done)) return ae;                 \
-      hipLaunchKernelGGL(kfn, dim3(vtiles64), dim3(512), lds_small, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles64, ntiles, \
-                         qcols, tail);                                                                                    \
-    } else {                                                                                                              \
-      auto kfn = k_linear_x3q<8, 1, 8, EPI_RESIDUAL, OS_, FX_RP | FX_PN>;                                                 \
-      static std::atomic<unsigned long long> attr_done{0};   /* one bit per device */                                     \
-      if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;                 \
-      hipLaunchKernelGGL(kfn, dim3(vtiles), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K, mtiles, ntiles, \
-                         qcols, tail);                                                                                    \
-    }                                                                                                                     \
-  } while (0)
-  if (outsplit == 2) D3D_X3PN_LAUNCH(2);
-  else D3D_X3PN_LAUNCH(0);
-#undef D3D_X3PN_LAUNCH
-  return hipGetLastError();
+  return outsplit == 2 ? launch_x3q_rows<2, FX_RP | FX_PN>(Ap, Wp, bias, C, Ch, M, N, K, tail, s)
+                       : launch_x3q_rows<0, FX_RP | FX_PN>(Ap, Wp, bias, C, Ch, M, N, K, tail, s);
 }
 
 // d3d_kernels.h: the split-K x split-N partial GEMM behind launch_fc2_splitk_postnorm.  A rows padded to 256 as everywhere.
@@ -965,11 +897,8 @@ hipError_t launch_linear_x3p_splitk(const void* Apair, const void* Wpair, float*
   X3Tail tail{};
   tail.out_scale = ldexpf(1.0f, -(3 + w_exp));
   tail.range = launch_range_word();
-  static std::atomic<unsigned long long> attr_done{0};   // one bit per device
-  if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(k_linear_x3q_splitk), lds_bytes, attr_done)) return ae;
-  hipLaunchKernelGGL(k_linear_x3q_splitk, dim3(grid), dim3(512), lds_bytes, s, (const _Float16*)Apair, (const _Float16*)Wpair, P, M, N, K,
-                     mtiles, ntiles, S, K / PBK / S, tail);
-  return hipGetLastError();
+  return launch_lds<k_linear_x3q_splitk>(dim3(grid), dim3(512), lds_bytes, s, (const _Float16*)Apair, (const _Float16*)Wpair, P, M, N, K, mtiles,
+                                         ntiles, S, K / PBK / S, tail);
 }
 
 // bf16 mode, whole-row form (d3d_kernels.h launch_linear_bf16_rows): the 128 x 512 tile shape of the post-norm form, bf16 MFMAs,
@@ -983,45 +912,11 @@ hipError_t launch_linear_bf16_rows(const void* A, const void* W, const float* bi
   if (pn.g && !pn.b) return hipErrorInvalidValue;
   if (pn.pos && (pn.pos_div < 1 || pn.pos_mod < 1)) return hipErrorInvalidValue;
   if (pn.tvec && pn.tvec_stride != 0 && pn.rows_per_batch < 1) return hipErrorInvalidValue;
-  const _Float16 *Ap = (const _Float16*)A, *Wp = (const _Float16*)W;
-  _Float16* Ch = (_Float16*)Hb;
-  _Float16* Cl = nullptr;
-  const float* R = nullptr;
-  float* C = X;
-  const int K2 = K / 2;
-  const int mtiles = (M + 127) / 128, ntiles = 1;
-  const int vtiles = ((mtiles + 7) / 8) * 8;
-  int n_cu = device_cu_count() / 8 * 8;   // (per device)
-  if (n_cu < 8) n_cu = 8;
-  const bool persist = mtiles >= 4 * n_cu && (K2 / PBK) % 2 == 0;
-  const X3Walk wk = x3q_walk(mtiles * ntiles, n_cu);
-  const size_t lds_bytes = 2 * (size_t)((128 + 512) * 128);
-  const bool small = mtiles < n_cu;
-  const int mtiles64 = (M + 63) / 64, vtiles64 = ((mtiles64 + 7) / 8) * 8;
-  const size_t lds_small = 2 * (size_t)((64 + 512) * 128);
   X3Tail tail{};
   tail.out_scale = 1.0f;
   tail.range = launch_range_word();
   tail.pn = pn;
-  const int qcols = 0;
-  constexpr int FXB = FX_PN | FX_BF16;
-  if (persist) {
-    auto kfn = k_linear_x3q_persist<8, 1, 8, EPI_RESIDUAL, 0, FXB>;
-    static std::atomic<unsigned long long> attr_done{0};   // one bit per device
-    if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;
-    hipLaunchKernelGGL(kfn, dim3(n_cu), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K2, mtiles, ntiles, qcols, wk, tail);
-  } else if (small) {   // fewer 128-row tiles than CUs: 64-row tiles (same values: rows are independent)
-    auto kfn = k_linear_x3q<4, 1, 8, EPI_RESIDUAL, 0, FXB>;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_small, attr_done)) return ae;
-    hipLaunchKernelGGL(kfn, dim3(vtiles64), dim3(512), lds_small, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K2, mtiles64, ntiles, qcols, tail);
-  } else {
-    auto kfn = k_linear_x3q<8, 1, 8, EPI_RESIDUAL, 0, FXB>;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (hipError_t ae = lds_optin(reinterpret_cast<const void*>(kfn), lds_bytes, attr_done)) return ae;
-    hipLaunchKernelGGL(kfn, dim3(vtiles), dim3(512), lds_bytes, s, Ap, Wp, bias, R, C, Ch, Cl, M, N, K2, mtiles, ntiles, qcols, tail);
-  }
-  return hipGetLastError();
+  return launch_x3q_rows<0, FX_PN | FX_BF16>((const _Float16*)A, (const _Float16*)W, bias, X, (_Float16*)Hb, M, N, K / 2, tail, s);
 }
 
 static bool x3q_big(int M, int N) {

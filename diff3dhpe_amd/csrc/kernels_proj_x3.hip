@@ -72,11 +72,9 @@ hipError_t launch_proj_x3(const void* Apair, const void* Wpair, const float* bia
   a.out_scale = ldexpf(1.0f, -(3 + w_exp));
   a.M = M; a.N = N; a.K = K; a.mtiles = M / QF_BM; a.ntiles = N / QF_BN;
   a.range = launch_range_word();
-  static std::atomic<unsigned long long> attr_done{0};   // one bit per device
   int grid = 0;
-  if (hipError_t ge = persistent_grid(reinterpret_cast<const void*>(k_proj_x3), PJ_LDS, attr_done, (long long)a.mtiles * a.ntiles, grid)) return ge;
-  hipLaunchKernelGGL(k_proj_x3, dim3(grid), dim3(512), PJ_LDS, s, a);
-  return hipGetLastError();
+  if (hipError_t ge = persistent_grid((long long)a.mtiles * a.ntiles, grid)) return ge;
+  return launch_lds<k_proj_x3>(dim3(grid), dim3(512), PJ_LDS, s, a);
 }
 
 }  // namespace d3d

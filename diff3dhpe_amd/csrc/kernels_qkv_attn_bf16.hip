@@ -329,12 +329,11 @@ static bool qkv_attn_bf16_shape_ok(long long groups, int N, int D, int H) {
 bool qkv_sattn_bf16_ok(int T, int J, int D, int H, int B) { return J <= 32 && qkv_attn_bf16_shape_ok((long long)B * T, J, D, H); }
 bool qkv_tattn_bf16_ok(int T, int J, int D, int H, int B) { return qkv_attn_bf16_shape_ok((long long)B * J, T, D, H); }
 
-template <typename KF>
-static hipError_t qa_launch(KF kern, std::atomic<unsigned long long>& attr_done, const QaArgs& a, hipStream_t s) {
+template <auto Kfn>
+static hipError_t qa_launch(const QaArgs& a, hipStream_t s) {
   int grid = 0;
-  if (hipError_t ge = persistent_grid(reinterpret_cast<const void*>(kern), QA_LDS, attr_done, (long long)a.mtiles * a.H, grid)) return ge;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), QA_LDS, s, a);
-  return hipGetLastError();
+  if (hipError_t ge = persistent_grid((long long)a.mtiles * a.H, grid)) return ge;
+  return launch_lds<Kfn>(dim3(grid), dim3(512), QA_LDS, s, a);
 }
 
 // A: bf16 [groups * N][D]; W: bf16 [3 D][D]; bias: [3 D]; out: bf16 [groups * N][D] (not A: every head reads whole rows of A).
@@ -347,17 +346,16 @@ hipError_t launch_qkv_attn_bf16(const void* A, const void* W, const float* bias,
   a.A = (const char*)A; a.W = (const char*)W; a.bias = bias; a.out = (__bf16*)out;
   a.D = D; a.H = H; a.N = N; a.udiv = stride;
   a.g = QA_ROWS / N; a.units = groups; a.mtiles = (groups + a.g - 1) / a.g;
-  static std::atomic<unsigned long long> attr_done[9] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // one bit per device
-  if (!temporal) return qa_launch(k_qkv_sattn_bf16, attr_done[0], a, s);
+  if (!temporal) return qa_launch<k_qkv_sattn_bf16>(a, s);
   switch ((N + 31) / 32) {
-    case 1: return qa_launch(k_qkv_tattn_bf16<1>, attr_done[1], a, s);
-    case 2: return qa_launch(k_qkv_tattn_bf16<2>, attr_done[2], a, s);
-    case 3: return qa_launch(k_qkv_tattn_bf16<3>, attr_done[3], a, s);
-    case 4: return qa_launch(k_qkv_tattn_bf16<4>, attr_done[4], a, s);
-    case 5: return qa_launch(k_qkv_tattn_bf16<5>, attr_done[5], a, s);
-    case 6: return qa_launch(k_qkv_tattn_bf16<6>, attr_done[6], a, s);
-    case 7: return qa_launch(k_qkv_tattn_bf16<7>, attr_done[7], a, s);
-    default: return qa_launch(k_qkv_tattn_bf16<8>, attr_done[8], a, s);
+    case 1: return qa_launch<k_qkv_tattn_bf16<1>>(a, s);
+    case 2: return qa_launch<k_qkv_tattn_bf16<2>>(a, s);
+    case 3: return qa_launch<k_qkv_tattn_bf16<3>>(a, s);
+    case 4: return qa_launch<k_qkv_tattn_bf16<4>>(a, s);
+    case 5: return qa_launch<k_qkv_tattn_bf16<5>>(a, s);
+    case 6: return qa_launch<k_qkv_tattn_bf16<6>>(a, s);
+    case 7: return qa_launch<k_qkv_tattn_bf16<7>>(a, s);
+    default: return qa_launch<k_qkv_tattn_bf16<8>>(a, s);
   }
 }
 

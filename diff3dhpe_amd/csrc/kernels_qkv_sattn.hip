@@ -384,11 +384,9 @@ hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, cons
   a.st_np = st_np; a.eps = eps; a.out_scale = ldexpf(1.0f, -(3 + w_exp));
   a.out = (_Float16*)out_x3; a.M = M; a.K = K; a.F = M / J; a.mtiles = (a.F + QS_FPT - 1) / QS_FPT; a.D = D;
   a.range = launch_range_word();
-  static std::atomic<unsigned long long> attr_done{0};   // one bit per device
   int grid = 0;
-  if (hipError_t ge = persistent_grid(reinterpret_cast<const void*>(k_qkv_sattn), QS_LDS, attr_done, (long long)a.mtiles * 8, grid)) return ge;
-  hipLaunchKernelGGL(k_qkv_sattn, dim3(grid), dim3(512), QS_LDS, s, a);
-  return hipGetLastError();
+  if (hipError_t ge = persistent_grid((long long)a.mtiles * 8, grid)) return ge;
+  return launch_lds<k_qkv_sattn>(dim3(grid), dim3(512), QS_LDS, s, a);
 }
 
 }  // namespace d3d

@@ -684,13 +684,10 @@ hipError_t launch_qkv_tattn(const void* Apair, const void* Wpair_tileorder, cons
     if ((size_t)T * J * 2 * K * 2 > 0xffffffffull) return hipErrorInvalidValue;
   }
   a.range = launch_range_word();
-  const void* kfn = grp ? reinterpret_cast<const void*>(k_qkv_tattn<true>) : reinterpret_cast<const void*>(k_qkv_tattn<false>);
-  static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};   // one bit per device
   int grid = 0;
-  if (hipError_t ge = persistent_grid(kfn, QT_LDS, attr_done[grp ? 1 : 0], (long long)a.BJ * 8, grid)) return ge;
-  if (grp) hipLaunchKernelGGL(k_qkv_tattn<true>, dim3(grid), dim3(512), QT_LDS, s, a);
-  else hipLaunchKernelGGL(k_qkv_tattn<false>, dim3(grid), dim3(512), QT_LDS, s, a);
-  return hipGetLastError();
+  if (hipError_t ge = persistent_grid((long long)a.BJ * 8, grid)) return ge;
+  return grp ? launch_lds<k_qkv_tattn<true>>(dim3(grid), dim3(512), QT_LDS, s, a)
+             : launch_lds<k_qkv_tattn<false>>(dim3(grid), dim3(512), QT_LDS, s, a);
 }
 
 }  // namespace d3d

@@ -148,8 +148,6 @@ hipError_t launch_probe_machine(int what, float ms_target, float* result, hipStr
     }
     *result = (float)((double)n_cu * 8 * iters * 96.0 * 16384.0 / ((double)ms * 1e9));
   } else {
-    static std::atomic<unsigned long long> attr_set{0};
-    PROBE_TRY(lds_optin(reinterpret_cast<const void*>(&k_probe_stage), 2 * PS_STAGE, attr_set));
     PROBE_TRY(hipMalloc(&din, (size_t)PS_ROWS * PS_PITCH));
     PROBE_TRY(hipMalloc(&dout, (size_t)n_cu * 4));
     PROBE_TRY(hipMemsetAsync(din, 0x3c, (size_t)PS_ROWS * PS_PITCH, s));
@@ -157,8 +155,7 @@ hipError_t launch_probe_machine(int what, float ms_target, float* result, hipStr
     const int tiles = (int)fmaxf(4.f, ms_target * 1000.f / 20.f);
     for (int rep = 0; rep < 2; ++rep) {
       PROBE_TRY(hipEventRecord(e0, s));
-      hipLaunchKernelGGL(k_probe_stage, dim3(n_cu), dim3(512), 2 * PS_STAGE, s, (const char*)din, (unsigned*)dout, tiles);
-      PROBE_TRY(hipGetLastError());
+      PROBE_TRY(launch_lds<k_probe_stage>(dim3(n_cu), dim3(512), 2 * PS_STAGE, s, (const char*)din, (unsigned*)dout, tiles));
       PROBE_TRY(hipEventRecord(e1, s));
       PROBE_TRY(hipEventSynchronize(e1));
       PROBE_TRY(hipEventElapsedTime(&ms, e0, e1));

@@ -17,12 +17,30 @@ def _eng():
     return engine
 
 
-@pytest.mark.parametrize("prec", ["fp32", "f16x3"])
-@pytest.mark.parametrize("M,N,K", [(128, 128, 32), (300, 96, 32), (1000, 1536, 512), (2066, 512, 1024), (17, 64, 64),
-                                   (4131, 1024, 512), (129, 130, 96)])
+def _cus():
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
+# Row counts that put a launcher on a given branch of its ladder depend on the device's CU count: named here, resolved inside the test
+# (collection does not touch the GPU).
+_ROWS = {"walk256": lambda cu: 256 * 2 * cu + 100,    # 256 x 256 tiles: the persistent walk (>= 4 rounds) with a ragged last round
+         "rows128": lambda cu: 128 * cu + 77,         # whole-row tiles: more 128-row tiles than CUs, one tile per workgroup
+         "rowswalk": lambda cu: 128 * 4 * cu + 77}    # whole-row tiles: the persistent walk
+
+
+def _rows(M):
+    return _ROWS[M](_cus()) if isinstance(M, str) else M
+
+
+_LINEAR_SHAPES = [(128, 128, 32), (300, 96, 32), (1000, 1536, 512), (2066, 512, 1024), (17, 64, 64), (4131, 1024, 512), (129, 130, 96)]
+
+
+@pytest.mark.parametrize("M,N,K,prec", [(M, N, K, prec) for prec in ("fp32", "f16x3") for (M, N, K) in _LINEAR_SHAPES]
+                         + [("walk256", 512, 512, "f16x3")])
 def test_linear_matches_fp64(M, N, K, prec):
     """Both GEMM paths must sit at fp32-rounding distance from the fp64 product (F16X3 = 3 fp16 MFMAs on hi/lo splits)."""
     E = _eng()
+    M = _rows(M)
     A = hashed(f"A{M}", (M, K), 11, 2.0).cuda()
     W = hashed(f"W{N}", (N, K), 12, 1.0 / np.sqrt(K)).cuda()
     b = hashed(f"b{N}", (N,), 13, 0.5).cuda()
@@ -78,13 +96,16 @@ def test_linear_bit_reproducible_and_row_independent(prec):
 
 
 @pytest.mark.parametrize("M,K,mode", [(128, 2048, "plain"), (300, 512, "pos"), (4131, 2048, "tvec1"), (1000, 64, "tvecrows"),
-                                      (17, 32, "all"), (140000, 512, "big")])
+                                      (17, 32, "all"), (140000, 512, "big"), ("rows128", 512, "plain"), ("rows128", 512, "tvecrows"),
+                                      ("rowswalk", 512, "plain"), ("rowswalk", 512, "tvecrows")])
 def test_linear_postnorm_matches_fp64(M, K, mode):
     """fc2 + post-norm in one GEMM (whole-row 128x512 tiles, LayerNorm in the epilogue; S2S:131-135 + 236/245 with the
     additions of S2S:238-242 / 113-116): both output forms against fp64 math, the row statistics handed to the next folded
-    GEMM, and bitwise independence of a row from the tile position / launch form (M = 140000 takes the persistent walk)."""
+    GEMM, and bitwise independence of a row from the tile position / launch form (M = 140000 takes the persistent walk).
+    "rows128" / "rowswalk": the 128-row one-tile-per-workgroup form and the persistent walk of the launcher at the engine's depth."""
     E = _eng()
     N = 512
+    M = _rows(M)
     A = hashed(f"pnA{M}", (M, K), 21, 2.0).cuda()
     W = hashed(f"pnW{K}", (N, K), 22, 1.0 / np.sqrt(K)).cuda()
     b = hashed("pnb", (N,), 23, 0.5).cuda()
