@@ -239,6 +239,14 @@ hipError_t launch_scale_cols(float* x, size_t rows, int cols, int ncols_scaled, 
 bool qkv_sattn_ok(int J, int D, int H, int K);
 hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, const float* bias_hm, const float* csum_hm, const float* st_in,
                             int st_np, float eps, int w_exp, void* out_x3, int M, int K, int J, int D, int H, hipStream_t s);
+// Block 0 without the K = D GEMM (k_qkv_sattn_direct): its input rows are W_e u + b_e + spos[j] + tv[b] with u the in_chans + 3 raw channels
+// of a token, so Wg x = G u + P[j] + Q[b] (fp32; G [3 D][in_chans + 3] and P [J][3 D] in the head-major order of bias_hm / csum_hm, Q [1 or B][3 D]
+// in the original column order; Q nullptr without time embedding, q_stride 0 or 3 D floats between batch elements).  in_chans 1 .. 3.  x2d / y / y_bcast_T as launch_embed_planes.  out_x3: the fused form;
+// out_x3 == nullptr: the [M][3 D] hi / lo planes launch_attn_temporal_x3 reads, bit for bit the values the fused form keeps in LDS.
+bool qkv_sattn_direct_ok(int J, int D, int H, int in_chans);
+hipError_t launch_qkv_sattn_direct(const float* x2d, const float* y, int y_bcast_T, int in_chans, const float* G, const float* P, const float* Q,
+                                   int q_stride, const float* bias_hm, const float* csum_hm, const float* st_in, int st_np, float eps, void* out_x3,
+                                   void* planes_hi, void* planes_lo, int M, int T, int J, int D, int H, hipStream_t s);
 // kernels_qkv_tattn.hip: the temporal counterpart -- the LayerNorm-folded qkv GEMM of one (batch, joint) group (T in 193..255 frames; T <= 127:
 // of 255 / T joints of one batch element, per-joint key windows) x one head with the T-key attention of k_attn_temporal_x3s run from LDS; the same tile-ordered weight / bias / csum as launch_qkv_sattn.
 // kernels_fc1_x3.hip: fc1 (LayerNorm-folded, GELU, accumulator-order pair output) on the hand-specialised k-loop of the fused kernels,
@@ -295,9 +303,10 @@ hipError_t launch_embed_planes(const float* x2d, const float* y, const float* Wf
 
 // sinusoid + trunk + per-block projections: out (n, nblk, D)
 hipError_t launch_sinusoid(const float* times, const float* freqs, float* out, int n, int D, hipStream_t s);
-// out[n,N] = post(act_pre(in[n,K]) @ W[N,K]^T + b); act: 0 none, 1 gelu(post), 2 silu(pre)
+// out[n,N] = post(act_pre(in[n,K]) @ W[N,K]^T + b); act: 0 none, 1 gelu(post), 2 silu(pre); b may be nullptr; in_stride: floats between
+// input rows (0 = K)
 hipError_t launch_small_linear(const float* in, const float* W, const float* b, float* out, int n, int N, int K,
-                               int act, hipStream_t s);
+                               int act, hipStream_t s, int64_t in_stride = 0);
 
 // seq2frame frame reduce (S2F:261-263): out[b,j,:] = sum_t w[t] X[b,t,j,:] + bias
 hipError_t launch_frame_reduce(const float* X, const float* w, const float* bias, float* out, int B, int T, int J, int D,

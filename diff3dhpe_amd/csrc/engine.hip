@@ -63,6 +63,8 @@ struct BlockPlan {
   Flow flow = PLAIN;          // run_blocks / run_blocks_fold / run_blocks_bf16
   // FOLD, BF16: the qkv GEMM and the attention of the spatial / temporal blocks as one kernel
   bool fused_sp = false, fused_tp = false;
+  // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
+  bool b0_direct = false;
   // PLAIN in F16X3: q / k / v go to the fp16-MFMA attention kernel as planes
   bool attn_x3_sp = false, attn_x3_tp = false;
   // FOLD: fc1 / proj on their own kernels; the post-norm inside the fc2 epilogue
@@ -93,6 +95,13 @@ struct d3d_engine {
   // per tile: kernels_qkv_tattn.hip)
   // BF16 mode: both keys select the bf16 qkv GEMM + attention kernels (kernels_qkv_attn_bf16.hip) for their block type, every T <= 255
   bool opt_fused_temporal = true;
+  // "block0_direct": block 0 of the F16X3 fold flow computes Wg x0 as G u + P[j] + Q[b] from the CIN raw channels of a token (the input
+  // rows are an affine map of them: kernels_qkv_sattn.hip k_qkv_sattn_direct) -- no qkv GEMM in that block; 0 = the GEMM, for A/B runs
+  bool opt_block0_direct = true;
+  // its tables, resident like the weights (one allocation): Wg = W_qkv diag(gamma1) of block 0 as fp32 [3 D][D] (the weight of the per-forward
+  // small linear that makes Q from the time vector, original row order), G = Wg W_e [3 D][CIN] and P[j] = Wg (b_e + spos[j]) [J][3 D] in the
+  // head-major tile order of qkv_f3h / qkv_csh / qkv_fbh, so a tile's slices are contiguous
+  float *b0_tab = nullptr, *b0_wg = nullptr, *b0_G = nullptr, *b0_P = nullptr;
   // "fc1_kernel": fc1 on its own kernel (kernels_fc1_x3.hip) where the launch fills the chip for a few rounds; bit-identical
   bool opt_fc1_kernel = true;
   // "proj_kernel": the same for proj (kernels_proj_x3.hip: whole 192-row tiles; the rows behind the last whole tile stay with the template)
@@ -209,6 +218,7 @@ struct d3d_engine {
     if (ev_join) (void)hipEventDestroy(ev_join);
     for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto ev : ev_pool) (void)hipEventDestroy(ev);
+    (void)hipFree(b0_tab);
     (void)hipFree(arena); (void)hipFree(arena16); (void)hipFree(arena_fold); (void)hipFree(tblk_w); (void)hipFree(tblk_b); (void)hipFree(freqs_dev);
     (void)hipFree(ac_dev); (void)hipFree(somac_dev); (void)hipFree(sqrt_ac_dev); (void)hipFree(temb_sched);
   }
@@ -338,7 +348,7 @@ int trace(d3d_engine* e, int blk, int kernel, int buf, const void* p, size_t byt
 
 // Workspace carve-up (float offsets).  AO (attention output) aliases HN: norm1(x) is dead once the qkv GEMM has run.
 struct Workspace {
-  float *X, *HN, *QKV, *HID, *Y0, *Y1, *TEMB, *TSCR, *RED, *TIMES, *XIN, *NIN, *OUTB, *ST1, *ST2;
+  float *X, *HN, *QKV, *HID, *Y0, *Y1, *TEMB, *TSCR, *RED, *TIMES, *XIN, *NIN, *OUTB, *ST1, *ST2, *QT;
   size_t total_bytes;
 };
 
@@ -364,10 +374,13 @@ Workspace carve(const d3d_engine* e, int B, void* base) {
   size_t oXI = take(M * e->cfg.in_chans), oNI = take(M * 3), oOB = take(M * 3);   // graph-mode staging copies
   // row statistics of the LN-folded GEMMs; whole 256-row tiles, the persistent walk stages a tile's block of them by LDS-DMA
   size_t oS1 = take(Mp * 2 * (size_t)((D + 63) / 64)), oS2 = take(Mp * 2 * (size_t)((D + 63) / 64));
+  // "block0_direct": the time rows Q[b] = Wg tv[b] of this forward, (B, 3 D) -- in the caller's workspace, so the two half-batches of a
+  // two-stream sampling and concurrent engines never share them
+  size_t oQT = take((size_t)B * 3 * D);
   if (b) {   // (d3d_workspace_bytes asks for the size alone: no arithmetic on a null base -- UBSan, experiments/asan_host.sh)
     w.X = b + oX; w.HN = b + oHN; w.QKV = b + oQKV; w.HID = b + oHID; w.Y0 = b + oY0; w.Y1 = b + oY1;
     w.TEMB = b + oTE; w.TSCR = b + oTS; w.RED = b + oRED; w.TIMES = b + oTI;
-    w.XIN = b + oXI; w.NIN = b + oNI; w.OUTB = b + oOB; w.ST1 = b + oS1; w.ST2 = b + oS2;
+    w.XIN = b + oXI; w.NIN = b + oNI; w.OUTB = b + oOB; w.ST1 = b + oS1; w.ST2 = b + oS2; w.QT = b + oQT;
   }
   w.total_bytes = off * sizeof(float);
   return w;
@@ -396,6 +409,44 @@ int attention(d3d_engine* e, const float* qkv, float* out, void* out_x3, int B, 
   return D3D_OK;
 }
 
+// "block0_direct": the commit-time tables of block 0 (d3d_engine::b0_tab).  wg: W_qkv diag(gamma1) [3 D][D], the fp32 values the commit
+// splits block 0's qkv planes from (q rows as handed over: qk_scale and qkv_bias = False arrive as derived tensors, the LayerNorm's gamma /
+// beta / eps live in wg, the folded bias and the kernel argument).  G and P are summed in fp64 and stored as fp32.  Built where block 0 can
+// take the direct form at all: a spatial F16X3 block on the fused kernel's tile geometry, embedding straight into the planes.
+void block0_tables_host(const float* wg, const float* We, const float* be, const float* spos, int D, int H, int cin, int J, float* G, float* P) {
+  const size_t N = 3 * (size_t)D, dh = (size_t)D / H;
+  std::vector<double> v((size_t)J * D);
+  for (int j = 0; j < J; ++j)
+    for (int k = 0; k < D; ++k) v[(size_t)j * D + k] = (double)be[k] + (double)spos[(size_t)j * D + k];
+  for (size_t n = 0; n < N; ++n) {   // head-major row n <- original row src, as the commit orders qkv_f3h
+    const size_t hd_ = n / (3 * dh), cc = n % (3 * dh), src = ((cc % 48) / 16) * D + hd_ * dh + 16 * (cc / 48) + cc % 16;
+    const float* wr = wg + src * D;
+    for (int c = 0; c < cin; ++c) {
+      double a = 0.0;
+      for (int k = 0; k < D; ++k) a += (double)wr[k] * (double)We[(size_t)k * cin + c];
+      G[n * cin + c] = (float)a;
+    }
+    for (int j = 0; j < J; ++j) {
+      double a = 0.0;
+      for (int k = 0; k < D; ++k) a += (double)wr[k] * v[(size_t)j * D + k];
+      P[(size_t)j * N + n] = (float)a;
+    }
+  }
+}
+int build_block0_tables(d3d_engine* e, const std::vector<float>& wg) {
+  const int D = e->D, J = e->J, cin = e->cin;
+  if (!embed_planes_ok(D, e->cfg.in_chans) || !qkv_sattn_direct_ok(J, D, e->H, e->cfg.in_chans)) return D3D_OK;
+  const size_t N = 3 * (size_t)D, n_wg = N * D, n_G = align_up(N * cin, 64), n_P = (size_t)J * N;
+  std::vector<float> tab(n_G + n_P);
+  block0_tables_host(wg.data(), e->slots[e->index["fusion_layer.weight"]].host.data(), e->slots[e->index["fusion_layer.bias"]].host.data(),
+                     e->slots[e->index["Spatial_pos_embed"]].host.data(), D, e->H, cin, J, tab.data(), tab.data() + n_G);
+  HIP_TRY(hipMalloc(&e->b0_tab, (n_wg + tab.size()) * sizeof(float)));
+  HIP_TRY(hipMemcpy(e->b0_tab, wg.data(), n_wg * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->b0_tab + n_wg, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+  e->b0_wg = e->b0_tab; e->b0_G = e->b0_tab + n_wg; e->b0_P = e->b0_G + n_G;   // (set last: a failed copy leaves the direct form off)
+  return D3D_OK;
+}
+
 // The plan of a forward of B sequences.  A pure function of the options, the shapes, B and the CU count, so an eager run, a capture
 // and a replay agree.
 BlockPlan plan_blocks(const d3d_engine* e, int B) {
@@ -406,6 +457,9 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
     p.flow = BlockPlan::FOLD;
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
+    // block 0 from the raw channels: every forward of this flow whose block 0 has the tables (fused or not, any B, any time rows)
+    p.b0_direct = e->opt_block0_direct && e->b0_G != nullptr && e->blk[0].qkv_csh != nullptr && embed_planes_ok(D, e->cfg.in_chans) &&
+                  qkv_sattn_direct_ok(J, D, H, e->cfg.in_chans);
     // the dedicated fc1 kernel runs whole 256-row tiles without guards (a launch of at least two rounds of tiles; smaller ones keep the
     // template's 256 x 128 / sliced forms); the proj kernel whole 192-row tiles (the rows behind the last whole tile stay with the template)
     p.fc1_own = e->opt_fc1_kernel && fc1_x3_ok(Dm, D) && (size_t)((M + 255) / 256) * (size_t)(Dm / 256) >= 512;
@@ -508,6 +562,20 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
     const size_t Mp = (size_t)((reinterpret_cast<char*>(w.HN) - reinterpret_cast<char*>(w.X)) / ((size_t)D * 4));   // rows of w.X as carved
     if (Mp > (size_t)M) HIP_TRY(hipMemsetAsync(XP + (size_t)M * 2 * D, 0, (Mp - (size_t)M) * 2 * D * sizeof(uint16_t), s));
   }
+  // block 0 direct: the time rows Q[b] = Wg tv[b] (block 0's slice of the time vector), one row when every batch element shares t
+  const float* b0_Q = nullptr;
+  const int b0_qstride = tvec_stride ? 3 * D : 0;
+  if (pl.b0_direct && tvec) {
+    HIP_TRY(launch_small_linear(tvec, e->b0_wg, nullptr, w.QT, tvec_stride ? B : 1, 3 * D, D, 0, s, tvec_stride));
+    b0_Q = w.QT;
+  }
+  auto qkv_direct = [&](void* out_x3, void* ph, void* plo) -> hipError_t {
+    const BlockW& b0 = e->blk[0];
+    return launch_qkv_sattn_direct(x2d, y, y_bcast, e->cfg.in_chans, e->b0_G, e->b0_P, b0_Q, b0_qstride, b0.qkv_fbh, b0.qkv_csh, w.ST1, 1, e->ln_eps,
+                                   out_x3, ph, plo, M, T, J, D, e->H, s);
+  };
+  // its work: the CIN-deep fill (+ 2 adds) per q / k / v value; M input rows, the tables and the statistics in
+  const double b0_flops = 2.0 * M * 3.0 * D * (e->cin + 1), b0_in = (double)M * (e->cin + 2) * 4.0 + 4.0 * 3.0 * D * (e->cin + J + 1);
   const int np2 = x3q_ntiles(M, D);                     // statistics partials per row written by a GEMM epilogue
   int np1 = 1;                                          // ... per row in w.ST1 (1 after a row kernel)
   // latency mode: S k-ranges of fc2 as fp32 partials + the ordered reduce / post-norm row kernel.  The partials take w.HN (the attention
@@ -539,13 +607,21 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
       Prof p(e, D3D_KC_QKV_TATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)T * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_tattn(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, B, T, J, D, D, e->H, s));
       TRACE(k, 3, 0, AOx, MDb);
+    } else if (k == 0 && pl.b0_direct && pl.fused_sp) {
+      // block 0: the same kernel with the fill from the raw channels in place of the k-loop
+      Prof p(e, D3D_KC_QKV_SATTN, b0_flops + 4.0 * M * (double)J * D, b0_in + MD4, s);
+      HIP_TRY(qkv_direct(AOx, nullptr, nullptr));
+      TRACE(k, 3, 0, AOx, MDb);
     } else if (!temporal && pl.fused_sp) {
       // spatial block: q, k, v of a frame group stay in LDS and feed the 17-key attention in the same kernel (kernels_qkv_sattn.hip)
       Prof p(e, D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)J * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_sattn(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, M, D, J, D, e->H, s));
       TRACE(k, 3, 0, AOx, MDb);
     } else {
-    {  // q, k, v planes = norm1(x) Wqkv^T + b   (LayerNorm folded; q third pre-scaled by dh^-0.5)
+    if (k == 0 && pl.b0_direct) {   // block 0: the planes from the raw channels, the values the fused form keeps in LDS
+      Prof p(e, D3D_KC_LINEAR, b0_flops, b0_in + 3.0 * MD4, s, D3D_KC_LINEAR_QKV);
+      HIP_TRY(qkv_direct(nullptr, QKVh, QKVl));
+    } else {  // q, k, v planes = norm1(x) Wqkv^T + b   (LayerNorm folded; q third pre-scaled by dh^-0.5)
       X3Fold f{};
       f.st_in = w.ST1; f.st_np = np1; f.csum = bw.qkv_cs; f.eps = e->ln_eps;
       HIP_TRY(gemm(XP, bw.qkv_f3, bw.qkv_fe, bw.qkv_fb, nullptr, QKVh, QKVl, 1, 3 * D, D, EPI_NONE, D, f));
@@ -1017,6 +1093,7 @@ int d3d_engine_commit_weights(d3d_engine* e) {
     e->blk.push_back(blockw("TTEblocks." + std::to_string(i)));
   }
   e->weights_clamped = false;
+  if (e->b0_tab) { (void)hipFree(e->b0_tab); e->b0_tab = e->b0_wg = e->b0_G = e->b0_P = nullptr; }
   HIP_TRY(hipGetDevice(&e->device));
   if (!e->range_dev) {
     HIP_TRY(hipMalloc(&e->range_dev, 256));
@@ -1108,6 +1185,10 @@ int d3d_engine_commit_weights(d3d_engine* e) {
         b.qkv_csh = e->arena_fold + fo;
         b.qkv_fbh = e->arena_fold + fo + rows;
         fo += 2 * rows;
+      }
+      if (k == 0) {   // wg still holds W diag(gamma) of block 0's qkv: the fp32 values its planes are split from
+        const int rc = build_block0_tables(e, wg);
+        if (rc) return rc;
       }
       folded(p + ".mlp.fc1.weight", p + ".mlp.fc1.bias", p + ".norm2", Dm, D, b.fc1_f3, b.fc1_cs, b.fc1_fb, b.fc1_fe);
     }
@@ -1458,6 +1539,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "fold_layernorm") e->opt_fold_layernorm = value != 0;
   else if (k == "fused_spatial") e->opt_fused_spatial = value != 0;
   else if (k == "fused_temporal") e->opt_fused_temporal = value != 0;
+  else if (k == "block0_direct") e->opt_block0_direct = value != 0;
   else if (k == "fc1_kernel") e->opt_fc1_kernel = value != 0;
   else if (k == "proj_kernel") e->opt_proj_kernel = value != 0;
   else if (k == "head_inject") e->opt_head_inject = value != 0;
@@ -1547,6 +1629,7 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;
   else if (k == "fc1_split_last") *value = e->last_plan.fc1_split;
+  else if (k == "block0_direct_last") *value = e->last_plan.b0_direct ? 1 : 0;
   else if (k == "proj_split") *value = e->opt_proj_split;
   else if (k == "fc1_split") *value = e->opt_fc1_split;
   else if (k == "bf16_fused_spatial_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_sp;

@@ -388,12 +388,12 @@ hipError_t launch_sinusoid(const float* times, const float* freqs, float* out, i
 // act: 0 none, 1 GELU on the output (time_mlp.2, S2S:172), 2 SiLU on the input (Block.time_mlp.0, S2S:105)
 __global__ __launch_bounds__(256) void k_small_linear(const float* __restrict__ in, const float* __restrict__ W,
                                                       const float* __restrict__ b, float* __restrict__ out, int n, int N,
-                                                      int K, int act) {
+                                                      int K, int act, int64_t in_stride) {
   const int lane = threadIdx.x & 63;
   const size_t w = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= (size_t)n * N) return;
   const int i = (int)(w / N), o = (int)(w % N);
-  const float* x = in + (size_t)i * K;
+  const float* x = in + (size_t)i * in_stride;
   const float* wr = W + (size_t)o * K;
   float acc = 0.f;
   for (int k = lane; k < K; k += 64) {
@@ -403,16 +403,17 @@ __global__ __launch_bounds__(256) void k_small_linear(const float* __restrict__ 
   }
   acc = wave_sum(acc);
   if (lane == 0) {
-    acc += b[o];
+    if (b) acc += b[o];
     if (act == 1) acc = gelu_erf(acc);
     out[w] = acc;
   }
 }
 
 hipError_t launch_small_linear(const float* in, const float* W, const float* b, float* out, int n, int N, int K,
-                               int act, hipStream_t s) {
+                               int act, hipStream_t s, int64_t in_stride) {
   const size_t waves = (size_t)n * N;
-  hipLaunchKernelGGL(k_small_linear, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, in, W, b, out, n, N, K, act);
+  hipLaunchKernelGGL(k_small_linear, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, in, W, b, out, n, N, K, act,
+                     in_stride ? in_stride : (int64_t)K);
   return hipGetLastError();
 }
 

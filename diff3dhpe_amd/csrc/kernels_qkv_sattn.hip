@@ -21,6 +21,8 @@
 // of a 40.5 us tile, in-kernel stamps; the epilogue steps are VALU-issue-bound with two waves per SIMD)
 // LDS map (160 KiB): [0, 56 K) stage 0 | [56 K, 158 K) stage 1, then the frame slots (+ the raw row-statistics block during the
 // k-loop) | 2 KiB of per-row LayerNorm statistics.
+// Block 0 runs k_qkv_sattn_direct (below): the same tile and the same code behind the accumulators, which it fills from the raw input
+// channels of the tokens and commit-time tables instead of a k-loop ("block0_direct" engine option).
 #include "d3d_kernels.h"
 #include "qkv_fused_kloop.h"
 
@@ -64,6 +66,7 @@ struct QsArgs {
   _Float16* out;           // attention output, pair layout [M][2 D] of 8 o
   int M, K, F, mtiles, D;  // tokens, GEMM depth, frames (M / 17), M-tiles (ceil(F / 15)), model width (8 heads x 64)
   unsigned* range;         // the engine's range-guard word
+  _Float16 *ph, *pl;       // plane-writing form only: q / k / v hi / lo planes [M][3 D]
 };
 
 // One frame of one head from its LDS slot: the arithmetic of k_attn_temporal_x3p<1, 8, 3> (same MFMAs in the same order, same
@@ -213,6 +216,137 @@ __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Flo
     }
 }
 
+// What both forms of the kernel run around their accumulators (k_qkv_sattn: the k-loop; k_qkv_sattn_direct: the block-0 fill) ---------
+typedef float qs_f2 __attribute__((ext_vector_type(2)));
+
+// Row statistics -> (rstd * out_scale, -mean rstd) per tile row: every wave reduces 32 rows (lanes 0-31)
+__device__ __forceinline__ void qs_row_stats(unsigned char* lds, const QsArgs& a, int m0, int wave, int lane, bool st_dma) {
+  float2* const srow = reinterpret_cast<float2*>(lds + QS_STX);
+  const int K = a.K;
+  if (lane < 32) {
+    const int t = wave * 32 + lane, row = m0 + t;
+    float sm = 0.f, sq = 0.f;
+    if (row < a.M) {
+      const float2* raw = st_dma ? reinterpret_cast<const float2*>(lds + QS_RAW) + t * a.st_np
+                                 : reinterpret_cast<const float2*>(a.st_in) + (size_t)row * a.st_np;
+      for (int p = 0; p < a.st_np; ++p) { sm += raw[p].x; sq += raw[p].y; }
+    }
+    if (sq >= (X3_HALF_MAX * 0.125f) * (X3_HALF_MAX * 0.125f)) range_raise(a.range, RANGE_BIT_ACT);   // (producer's planes, as x3q_tile)
+    const float mean = sm / (float)K;
+    const float var = fmaxf(sq / (float)K - mean * mean, 0.0f);
+    if (row < a.M && mean * mean > 256.0f * var) range_raise(a.range, RANGE_BIT_STATS);
+    const float rstd = 1.0f / sqrtf(var + a.eps);
+    srow[t] = make_float2(rstd * a.out_scale, -mean * rstd);
+  }
+}
+
+// Four accumulator columns of one row -> q / k / v values (LayerNorm fold of x3q_epilogue8) and their hi / lo fp16 pairs of osc v
+__device__ __forceinline__ void qs_fold_split(const f32x4& ac, qs_f2 sx, qs_f2 sy, const float4& cs, const float4& bb, float osc, float& amax,
+                                              u32x2_alias& hv, u32x2_alias& lv) {
+  typedef qs_f2 f2;
+  f2 a01, a23, c01, c23, b01, b23;
+  a01.x = ac[0]; a01.y = ac[1]; a23.x = ac[2]; a23.y = ac[3];
+  c01.x = cs.x; c01.y = cs.y; c23.x = cs.z; c23.y = cs.w;
+  b01.x = bb.x; b01.y = bb.y; b23.x = bb.z; b23.y = bb.w;
+  const f2 v01 = __builtin_elementwise_fma(sx, a01, __builtin_elementwise_fma(sy, c01, b01));
+  const f2 v23 = __builtin_elementwise_fma(sx, a23, __builtin_elementwise_fma(sy, c23, b23));
+  amax = fmaxf(fmaxf(amax, fabsf(v01.x)), fabsf(v01.y));
+  amax = fmaxf(fmaxf(amax, fabsf(v23.x)), fabsf(v23.y));
+  unsigned h0, l0, h1, l1;
+  split_pair(v01.x, v01.y, osc, h0, l0);
+  split_pair(v23.x, v23.y, osc, h1, l1);
+  hv[0] = h0; hv[1] = h1; lv[0] = l0; lv[1] = l1;
+}
+
+// Everything behind the accumulators of tile (mt, hd), statistics in LDS and visible.  PLANES = false: the two passes of slot writes and
+// attention units.  PLANES = true (block 0 of the two-kernel flow): the same values as [M][3 D] hi / lo planes in HBM, what
+// launch_attn_temporal_x3 reads -- column 512 part + 64 hd + 16 wn + x of the original weight order.
+template <bool PLANES>
+__device__ __forceinline__ void qs_tail(f32x4 (&acc)[QF_TM][QF_NJ], unsigned char* lds, const QsArgs& a, int mt, int hd, int m0, int n0,
+                                        int wave, int lane, int wm, int wn, int r16, int q) {
+  float2 st[QF_TM];
+#pragma unroll
+  for (int i = 0; i < QF_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + QS_STX)[wm * 16 * QF_TM + 16 * i + r16];
+  float4 cs4[QF_NJ], b4[QF_NJ];
+#pragma unroll
+  for (int j = 0; j < QF_NJ; ++j) {
+    const int n = n0 + wn * 48 + 16 * j + 4 * q;
+    cs4[j] = *reinterpret_cast<const float4*>(a.csum + n);
+    b4[j] = *reinterpret_cast<const float4*>(a.bias + n);
+  }
+  float amaxj[QF_NJ] = {0.0f, 0.0f, 0.0f};   // max |value| per accumulator column tile j = q / k / v (plane scale applied at the end)
+  // q / k / v of this pass's frames -> frame slots (LayerNorm fold and hi / lo split of x3q_epilogue8).  Frame fr of the tile:
+  // pass (fr >> 2) & 1, slot (fr & 3) + 4 (fr >> 3).  Column tile j of a wave IS part j (the weight rows are ordered that way at
+  // commit): q columns 16 wn .. + 15 of the head in j = 0, the same k columns in j = 1, v in j = 2 -- plane and scale are
+  // compile-time per j, and one address serves q and k (same row swizzle), one v.  Rows beyond the matrix hold finite values
+  // (the engine zeroes the pad rows of the stream; the direct form fills them from zero inputs): nothing non-finite can reach a slot.
+  typedef qs_f2 f2;
+  const int chunk = 2 * wn + (q >> 1), half8 = (q & 1) << 3;            // this lane's 8 bytes: 16-byte chunk d / 8, half (d & 4)
+  auto write_pass = [&](int pass) {
+#pragma unroll
+    for (int i = 0; i < QF_TM; ++i) {
+      if (pass == 0 ? (i > 4) : (i < 4 && !(wm == 1 && i == 0))) continue;   // (wave-uniform: m-tiles without rows of this pass)
+      const int R = wm * 16 * QF_TM + 16 * i + r16;
+      const int fr = (R * 241) >> 12, jr = R - fr * QS_J;               // R / 17 for R < 256
+      if (((fr >> 2) & 1) != pass || fr >= QS_FPT) continue;
+      unsigned char* const row = lds + QS_QKV + ((fr & 3) + 4 * (fr >> 3)) * QS_SLOT + jr * 128 + half8;
+      unsigned char* const pkq = row + ((chunk ^ ((jr >> 1) & 7)) << 4);
+      unsigned char* const pv = row + ((chunk ^ vkey(jr)) << 4);
+      const f2 sx = (f2)(st[i].x), sy = (f2)(st[i].y);
+#pragma unroll
+      for (int j = 0; j < QF_NJ; ++j) {
+        const float osc = j == 0 ? 1.0f : 8.0f;
+        u32x2_alias hv, lv;
+        qs_fold_split(acc[i][j], sx, sy, cs4[j], b4[j], osc, amaxj[j], hv, lv);
+        unsigned char* const ph = j == 0 ? pkq + QS_PQ : (j == 1 ? pkq + QS_PK : pv + QS_PV);
+        if (!(QS_ABL & 1)) {
+          *reinterpret_cast<u32x2_alias*>(ph) = hv;
+          *reinterpret_cast<u32x2_alias*>(ph + QS_PLANE) = lv;
+        }
+      }
+    }
+  };
+  auto attend = [&](int pass) {
+    const int fr = (wave & 3) + 4 * pass + 8 * (wave >> 2);             // frame of the tile this wave takes: slot = wave
+    const long long gf = (long long)mt * QS_FPT + fr;
+    if (!(QS_ABL & 2) && fr < QS_FPT && gf < a.F)
+      qs_attention(lds + QS_QKV + wave * QS_SLOT, lane, a.out + ((size_t)gf * QS_J) * 2 * a.D + hd * 128, a.D);
+  };
+  auto range_check = [&]() {
+    float amax = 0.0f;
+#pragma unroll
+    for (int j = 0; j < QF_NJ; ++j) amax = fmaxf(amax, amaxj[j] * (j == 0 ? 1.0f : (j == 1 ? 8.0f : 16.015f)));   // v: flagged from |v| > 4090 on
+    if (amax > X3_HALF_MAX) range_raise(a.range, RANGE_BIT_ACT);
+  };
+  if (PLANES) {
+#pragma unroll
+    for (int i = 0; i < QF_TM; ++i) {
+      const int R = wm * 16 * QF_TM + 16 * i + r16, m = m0 + R;
+      if (R >= QS_ROWS || m >= a.M) continue;                            // (row 255 is the next tile's first)
+      const f2 sx = (f2)(st[i].x), sy = (f2)(st[i].y);
+      const size_t o = (size_t)m * 3 * a.D + hd * 64 + 16 * wn + 4 * q;
+#pragma unroll
+      for (int j = 0; j < QF_NJ; ++j) {
+        const float osc = j == 0 ? 1.0f : 8.0f;
+        u32x2_alias hv, lv;
+        qs_fold_split(acc[i][j], sx, sy, cs4[j], b4[j], osc, amaxj[j], hv, lv);
+        *reinterpret_cast<u32x2_alias*>(a.ph + o + j * a.D) = hv;
+        *reinterpret_cast<u32x2_alias*>(a.pl + o + j * a.D) = lv;
+      }
+    }
+    range_check();
+    return;
+  }
+  write_pass(0);
+  __syncthreads();
+  attend(0);
+  __syncthreads();
+  write_pass(1);
+  range_check();
+  __syncthreads();
+  attend(1);
+}
+
 __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int G = (int)gridDim.x, b = (int)blockIdx.x;
@@ -269,103 +403,156 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
     // ---- row statistics -> (rstd * out_scale, -mean rstd) per tile row, in front of the last k-tile: every wave reduces 32 rows (lanes
     // 0-31) in the shadow of its SIMD partner's MFMAs -- behind the k-loop this step was 1.1 us of a 38 us tile with half the waves
     // idle.  The raw partials landed long ago (the first counted wait of the tile retired them; phase barriers since).
-    {
-      float2* const srow = reinterpret_cast<float2*>(lds + QS_STX);
-      if (lane < 32) {
-        const int t = wave * 32 + lane, row = m0 + t;
-        float sm = 0.f, sq = 0.f;
-        if (row < a.M) {
-          const float2* raw = st_dma ? reinterpret_cast<const float2*>(lds + QS_RAW) + t * a.st_np
-                                     : reinterpret_cast<const float2*>(a.st_in) + (size_t)row * a.st_np;
-          for (int p = 0; p < a.st_np; ++p) { sm += raw[p].x; sq += raw[p].y; }
-        }
-        if (sq >= (X3_HALF_MAX * 0.125f) * (X3_HALF_MAX * 0.125f)) range_raise(a.range, RANGE_BIT_ACT);   // (producer's planes, as x3q_tile)
-        const float mean = sm / (float)K;
-        const float var = fmaxf(sq / (float)K - mean * mean, 0.0f);
-        if (row < a.M && mean * mean > 256.0f * var) range_raise(a.range, RANGE_BIT_STATS);
-        const float rstd = 1.0f / sqrtf(var + a.eps);
-        srow[t] = make_float2(rstd * a.out_scale, -mean * rstd);
-      }
-    }
+    qs_row_stats(lds, a, m0, wave, lane, st_dma);
     QF_KLOOP_TAIL(QF_PIECE)
     __builtin_amdgcn_s_setprio(0);
 
     __syncthreads();   // statistics visible; every wave is out of the k-loop: stage 1 and the LDS behind it become the frame slots
 
-    float2 st[QF_TM];
-#pragma unroll
-    for (int i = 0; i < QF_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + QS_STX)[wm * 16 * QF_TM + 16 * i + r16];
-    float4 cs4[QF_NJ], b4[QF_NJ];
-#pragma unroll
-    for (int j = 0; j < QF_NJ; ++j) {
-      const int n = n0 + wn * 48 + 16 * j + 4 * q;
-      cs4[j] = *reinterpret_cast<const float4*>(a.csum + n);
-      b4[j] = *reinterpret_cast<const float4*>(a.bias + n);
-    }
-    float amaxj[QF_NJ] = {0.0f, 0.0f, 0.0f};   // max |value| per accumulator column tile j = q / k / v (plane scale applied at the end)
-    // q / k / v of this pass's frames -> frame slots (LayerNorm fold and hi / lo split of x3q_epilogue8).  Frame fr of the tile:
-    // pass (fr >> 2) & 1, slot (fr & 3) + 4 (fr >> 3).  Column tile j of a wave IS part j (the weight rows are ordered that way at
-    // commit): q columns 16 wn .. + 15 of the head in j = 0, the same k columns in j = 1, v in j = 2 -- plane and scale are
-    // compile-time per j, and one address serves q and k (same row swizzle), one v.  Rows beyond the matrix hold finite values
-    // (the engine zeroes the pad rows of the stream): nothing non-finite can reach a slot.
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const int chunk = 2 * wn + (q >> 1), half8 = (q & 1) << 3;            // this lane's 8 bytes: 16-byte chunk d / 8, half (d & 4)
-    auto write_pass = [&](int pass) {
-#pragma unroll
-      for (int i = 0; i < QF_TM; ++i) {
-        if (pass == 0 ? (i > 4) : (i < 4 && !(wm == 1 && i == 0))) continue;   // (wave-uniform: m-tiles without rows of this pass)
-        const int R = wm * 16 * QF_TM + 16 * i + r16;
-        const int fr = (R * 241) >> 12, jr = R - fr * QS_J;               // R / 17 for R < 256
-        if (((fr >> 2) & 1) != pass || fr >= QS_FPT) continue;
-        unsigned char* const row = lds + QS_QKV + ((fr & 3) + 4 * (fr >> 3)) * QS_SLOT + jr * 128 + half8;
-        unsigned char* const pkq = row + ((chunk ^ ((jr >> 1) & 7)) << 4);
-        unsigned char* const pv = row + ((chunk ^ vkey(jr)) << 4);
-        const f2 sx = (f2)(st[i].x), sy = (f2)(st[i].y);
-#pragma unroll
-        for (int j = 0; j < QF_NJ; ++j) {
-          const float osc = j == 0 ? 1.0f : 8.0f;
-          f2 a01, a23, c01, c23, b01, b23;
-          a01.x = acc[i][j][0]; a01.y = acc[i][j][1]; a23.x = acc[i][j][2]; a23.y = acc[i][j][3];
-          c01.x = cs4[j].x; c01.y = cs4[j].y; c23.x = cs4[j].z; c23.y = cs4[j].w;
-          b01.x = b4[j].x; b01.y = b4[j].y; b23.x = b4[j].z; b23.y = b4[j].w;
-          const f2 v01 = __builtin_elementwise_fma(sx, a01, __builtin_elementwise_fma(sy, c01, b01));
-          const f2 v23 = __builtin_elementwise_fma(sx, a23, __builtin_elementwise_fma(sy, c23, b23));
-          amaxj[j] = fmaxf(fmaxf(amaxj[j], fabsf(v01.x)), fabsf(v01.y));
-          amaxj[j] = fmaxf(fmaxf(amaxj[j], fabsf(v23.x)), fabsf(v23.y));
-          unsigned h0, l0, h1, l1;
-          split_pair(v01.x, v01.y, osc, h0, l0);
-          split_pair(v23.x, v23.y, osc, h1, l1);
-          unsigned char* const ph = j == 0 ? pkq + QS_PQ : (j == 1 ? pkq + QS_PK : pv + QS_PV);
-          u32x2_alias hv, lv;
-          hv[0] = h0; hv[1] = h1; lv[0] = l0; lv[1] = l1;
-          if (!(QS_ABL & 1)) {
-            *reinterpret_cast<u32x2_alias*>(ph) = hv;
-            *reinterpret_cast<u32x2_alias*>(ph + QS_PLANE) = lv;
-          }
-        }
-      }
-    };
-    auto attend = [&](int pass) {
-      const int fr = (wave & 3) + 4 * pass + 8 * (wave >> 2);             // frame of the tile this wave takes: slot = wave
-      const long long gf = (long long)mt * QS_FPT + fr;
-      if (!(QS_ABL & 2) && fr < QS_FPT && gf < a.F)
-        qs_attention(lds + QS_QKV + wave * QS_SLOT, lane, a.out + ((size_t)gf * QS_J) * 2 * a.D + hd * 128, a.D);
-    };
-    write_pass(0);
-    __syncthreads();
-    attend(0);
-    __syncthreads();
-    write_pass(1);
-    {
-      float amax = 0.0f;
-#pragma unroll
-      for (int j = 0; j < QF_NJ; ++j) amax = fmaxf(amax, amaxj[j] * (j == 0 ? 1.0f : (j == 1 ? 8.0f : 16.015f)));   // v: flagged from |v| > 4090 on
-      if (amax > X3_HALF_MAX) range_raise(a.range, RANGE_BIT_ACT);
-    }
-    __syncthreads();
-    attend(1);
+    qs_tail<false>(acc, lds, a, mt, hd, m0, n0, wave, lane, wm, wn, r16, q);
     mt = mtn; hd = hdn;
     __syncthreads();   // the slots are read before the next tile's statistics block and second k-tile are staged over them
+  }
+}
+
+// ---- block 0, direct form ------------------------------------------------------------------------------------------------------------
+// The residual stream that enters block 0 is x0[m, :] = W_e u_m + b_e + spos[j(m)] + tv[b(m)] with u_m the CIN <= 8 raw input channels of
+// token m (k_embed_planes), so the inner product of the fold identity collapses to
+//   Wg[n, :] x0[m, :] = G[n, :] u_m + P[j(m), n] + Q[b(m), n],   G = Wg W_e,  P[j] = Wg (b_e + spos[j]),  Q[b] = Wg tv[b]
+// (G, P: fp64 at commit, stored fp32; Q: one small linear per forward).  Same tile, same eight waves, same accumulator ownership as
+// k_qkv_sattn, but no operand staging and no k-loop: every lane fills its 8 x 3 x 4 accumulators in true units (out_scale = 1) by
+//   acc = 0;  acc = fmaf(u[c], G[n][c], acc) for c = 0 .. CIN - 1;  acc += P[j][n];  acc += Q[b][n]
+// in exactly that order, and qs_tail does the rest.  G and P are stored in the HEAD-MAJOR tile order of the folded weight / csum / bias
+// (row 192 hd + 48 wn + 16 part + x), so a tile's slices are contiguous; Q comes from the small linear in the ORIGINAL column order
+// (512 part + 64 hd + 16 wn + x: the four columns of an accumulator are adjacent there too).
+struct QdSrc {
+  const float *x2d, *y;    // the inputs of k_embed_planes: [M][CIN2], [M or B J][3]
+  const float *G, *P, *Q;  // head-major [3 D][CIN] and [J][3 D]; original order [1 or B][3 D] (Q: nullptr without time embedding)
+  int q_stride;            // floats between the Q rows of consecutive batch elements: 0 (all share one) or 3 D
+  int TJ, y_bcast_T;       // rows per batch element; y holds one frame per batch element (seq2frame)
+};
+// LDS, in the stage area the k-loop form fills with operands: the head's 192 columns of G, P and of the Q rows of the tile's batch elements
+constexpr int QD_GROW = 8;                                               // G: 192 rows of 8 floats (CIN used)
+constexpr int QD_QSLOTS = 16;                                            // 256 rows hold at most 16 frames, so at most 16 batch elements
+constexpr int QD_G = 0, QD_P = QD_G + QF_BN * QD_GROW * 4, QD_Q = QD_P + QS_J * QF_BN * 4;
+static_assert(QD_Q + QD_QSLOTS * QF_BN * 4 <= QS_QKV, "the direct form's tables fit the unused stage area");
+static_assert(QF_BM <= QD_QSLOTS * QS_J, "a tile's rows span at most QD_QSLOTS frames, so at most QD_QSLOTS batch elements");
+
+// tile column c = 48 wn + 16 part + x of head hd in the original column order of the qkv weight
+__device__ __forceinline__ int qd_col(int c, int hd) { return 512 * ((c % 48) >> 4) + 64 * hd + 16 * (c / 48) + (c & 15); }
+
+template <int CIN2>
+__device__ __forceinline__ void qd_stage(unsigned char* lds, const QdSrc& d, int M, int m0, int hd, int tid) {
+  constexpr int CIN = CIN2 + 3;
+  float* const sG = reinterpret_cast<float*>(lds + QD_G);
+  float* const sP = reinterpret_cast<float*>(lds + QD_P);
+  float* const sQ = reinterpret_cast<float*>(lds + QD_Q);
+  for (int idx = tid; idx < QF_BN * CIN; idx += 512) {                  // (the head's rows of G are one contiguous block)
+    const int c = idx / CIN, k = idx - c * CIN;
+    sG[c * QD_GROW + k] = d.G[QF_BN * CIN * hd + idx];
+  }
+  for (int idx = tid; idx < QS_J * QF_BN; idx += 512) {
+    const int j = idx / QF_BN, c = idx - j * QF_BN;
+    sP[idx] = d.P[j * 1536 + QF_BN * hd + c];
+  }
+  if (d.Q) {   // slot s: batch element m0 / TJ + s (one slot when all share a row)
+    const int b_lo = m0 / d.TJ, nb = d.q_stride ? min(QD_QSLOTS, M / d.TJ - b_lo) : 1;
+    for (int idx = tid; idx < nb * QF_BN; idx += 512) {
+      const int sl = idx / QF_BN, c = idx - sl * QF_BN;
+      sQ[idx] = d.Q[(size_t)(b_lo + sl) * d.q_stride + qd_col(c, hd)];
+    }
+  }
+}
+
+// The accumulators of tile row m0 .. and head hd, tables staged and visible.  The scheduling fences keep one column's G row / one row's P
+// and Q values in flight at a time: hoisted together they would not fit the registers beside 96 accumulators and the 8 x CIN inputs.
+template <int CIN2>
+__device__ __forceinline__ void qd_fill(f32x4 (&acc)[QF_TM][QF_NJ], const unsigned char* lds, const QdSrc& d, int M, int m0, int wm, int wn,
+                                        int r16, int q) {
+  constexpr int CIN = CIN2 + 3;
+  const int c0 = wn * 48 + 4 * q;                                        // first of this lane's four tile columns of part 0
+  const int b_lo = m0 / d.TJ;
+  const float* const sG = reinterpret_cast<const float*>(lds + QD_G);
+  const float* const sP = reinterpret_cast<const float*>(lds + QD_P);
+  const float* const sQ = reinterpret_cast<const float*>(lds + QD_Q);
+  float u[QF_TM][CIN];
+#pragma unroll
+  for (int ii = 0; ii < QF_TM; ++ii) {
+    const int R = wm * 16 * QF_TM + 16 * ii + r16, m = m0 + R;
+    const int fr = (R * 241) >> 12, jr = R - fr * QS_J;                // R / 17 for R < 256; jr = m % 17: a tile starts on a frame
+#pragma unroll
+    for (int k = 0; k < CIN; ++k) u[ii][k] = 0.0f;                     // rows beyond the matrix: zero inputs
+    if (m < M) {
+#pragma unroll
+      for (int k = 0; k < CIN2; ++k) u[ii][k] = d.x2d[(size_t)m * CIN2 + k];
+      const size_t my = d.y_bcast_T ? ((size_t)(m / d.TJ) * QS_J + jr) : (size_t)m;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) u[ii][CIN2 + k] = d.y[my * 3 + k];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < QF_NJ; ++j) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float g[CIN];
+#pragma unroll
+      for (int k = 0; k < CIN; ++k) g[k] = sG[(c0 + 16 * j + e) * QD_GROW + k];
+#pragma unroll
+      for (int ii = 0; ii < QF_TM; ++ii) {
+        float v = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CIN; ++k) v = fmaf(u[ii][k], g[k], v);
+        acc[ii][j][e] = v;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < QF_TM; ++i) {   // (the row's offsets are formed again here: kept from the loop above they cost 16 registers)
+    const int R = wm * 16 * QF_TM + 16 * i + r16, m = m0 + R;
+    const int po = (R - ((R * 241) >> 12) * QS_J) * QF_BN + c0;
+    const int qo = c0 + (d.q_stride ? min(m / d.TJ - b_lo, QD_QSLOTS - 1) * QF_BN : 0);
+    if (m < M) {   // rows beyond the matrix keep 0, what the k-loop form makes of the zeroed pad rows of the stream
+#pragma unroll
+      for (int j = 0; j < QF_NJ; ++j) {
+        const float4 p4 = *reinterpret_cast<const float4*>(sP + po + 16 * j);
+        acc[i][j][0] += p4.x; acc[i][j][1] += p4.y; acc[i][j][2] += p4.z; acc[i][j][3] += p4.w;
+      }
+      if (d.Q) {
+#pragma unroll
+        for (int j = 0; j < QF_NJ; ++j) {
+          const float4 q4 = *reinterpret_cast<const float4*>(sQ + qo + 16 * j);
+          acc[i][j][0] += q4.x; acc[i][j][1] += q4.y; acc[i][j][2] += q4.z; acc[i][j][3] += q4.w;
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <int CIN2, bool PLANES>
+__global__ __launch_bounds__(512) void k_qkv_sattn_direct(QsArgs a, QdSrc d) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int G = (int)gridDim.x, b = (int)blockIdx.x;
+  const int tiles = a.mtiles * 8;
+  if (b >= tiles) return;
+  const int nitems = (tiles - b + G - 1) / G;
+  KL_XCD_TILE_ORDER(a.mtiles, 8);                                        // the walk of k_qkv_sattn
+  int tid_o = (int)threadIdx.x;
+  for (int item = 0; item < nitems; ++item) {
+    QF_TILE_LANES;                                                       // (per-lane offsets re-derived per tile, not hoisted and spilled)
+    int mt = 0, hd = 0;
+    tile_of(item * G + b, mt, hd);
+    const int m0 = mt * QS_ROWS, n0 = hd * QF_BN;
+    // the head's columns of G, P and Q into the (otherwise unused) stage area, the row statistics from HBM
+    qd_stage<CIN2>(lds, d, a.M, m0, hd, tid);
+    qs_row_stats(lds, a, m0, wave, lane, false);
+    __syncthreads();
+    f32x4 acc[QF_TM][QF_NJ];
+    qd_fill<CIN2>(acc, lds, d, a.M, m0, wm, wn, r16, q);
+    __builtin_amdgcn_sched_barrier(0);
+    qs_tail<PLANES>(acc, lds, a, mt, hd, m0, n0, wave, lane, wm, wn, r16, q);
+    __syncthreads();   // the slots, the tables and the statistics are read before the next tile's are staged over them
   }
 }
 
@@ -387,6 +574,38 @@ hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, cons
   int grid = 0;
   if (hipError_t ge = persistent_grid((long long)a.mtiles * 8, grid)) return ge;
   return launch_lds<k_qkv_sattn>(dim3(grid), dim3(512), QS_LDS, s, a);
+}
+
+// in_chans 4 and 5 (8 x 7 / 8 x 8 input registers beside the 96 accumulators) do not fit the 256 VGPRs of two waves per SIMD without
+// spilling: such models keep the GEMM in block 0 ("block0_direct_last" reads 0)
+bool qkv_sattn_direct_ok(int J, int D, int H, int in_chans) { return qkv_sattn_ok(J, D, H, D) && in_chans >= 1 && in_chans <= 3; }
+
+// Block 0 of the F16X3 flow from the raw input channels (k_qkv_sattn_direct).  out_x3 != nullptr: the fused form, attention output in the
+// pair layout; else planes_hi / planes_lo: the q / k / v planes of the two-kernel flow, the same bits the fused form puts into LDS.
+hipError_t launch_qkv_sattn_direct(const float* x2d, const float* y, int y_bcast_T, int in_chans, const float* G, const float* P, const float* Q,
+                                   int q_stride, const float* bias_hm, const float* csum_hm, const float* st_in, int st_np, float eps, void* out_x3,
+                                   void* planes_hi, void* planes_lo, int M, int T, int J, int D, int H, hipStream_t s) {
+  if (!qkv_sattn_direct_ok(J, D, H, in_chans) || M <= 0 || T <= 0 || M % (T * J) != 0 || st_np < 1 || !x2d || !y || !G || !P || !bias_hm || !csum_hm ||
+      !st_in || (q_stride != 0 && q_stride != 3 * D) || (!out_x3 && (!planes_hi || !planes_lo)))
+    return hipErrorInvalidValue;
+  QsArgs a{};
+  a.bias = bias_hm; a.csum = csum_hm; a.st_in = st_in; a.st_np = st_np; a.eps = eps; a.out_scale = 1.0f;
+  a.out = (_Float16*)out_x3; a.M = M; a.K = D; a.F = M / J; a.mtiles = (a.F + QS_FPT - 1) / QS_FPT; a.D = D;
+  a.ph = (_Float16*)planes_hi; a.pl = (_Float16*)planes_lo;
+  a.range = launch_range_word();
+  QdSrc d{};
+  d.x2d = x2d; d.y = y; d.G = G; d.P = P; d.Q = Q; d.q_stride = q_stride; d.TJ = T * J; d.y_bcast_T = y_bcast_T;
+  int grid = 0;
+  if (hipError_t ge = persistent_grid((long long)a.mtiles * 8, grid)) return ge;
+#define D3D_QD(C2)                                                                                                      \
+  case C2:                                                                                                              \
+    return out_x3 ? launch_lds<k_qkv_sattn_direct<C2, false>>(dim3(grid), dim3(512), QS_LDS, s, a, d)                   \
+                  : launch_lds<k_qkv_sattn_direct<C2, true>>(dim3(grid), dim3(512), QS_LDS, s, a, d);
+  switch (in_chans) {
+    D3D_QD(1) D3D_QD(2) D3D_QD(3)
+  }
+#undef D3D_QD
+  return hipErrorInvalidValue;
 }
 
 }  // namespace d3d

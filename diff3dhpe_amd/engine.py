@@ -212,14 +212,15 @@ class Engine:
     @_locked
     def set_option(self, key: str, value: int) -> None:
         """Explicit engine switch (include/d3d.h: "fused_postnorm", "fold_layernorm", "streams", "latency_mode", "proj_split",
-        "fc1_split"); the library reads no environment."""
+        "fc1_split", "block0_direct"); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
     def info(self, key: str) -> int:
         """Read-only engine facts (include/d3d.h d3d_engine_get_info): "graphs_cached", "graphs_captured", "streams", "device",
         "latency_mode", "fc2_split_last", "proj_split_last", "fc1_split_last", "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the most recent forward of a
-        bf16 engine ran the fused qkv + attention kernel in its spatial / temporal blocks)."""
+        bf16 engine ran the fused qkv + attention kernel in its spatial / temporal blocks), "block0_direct_last" (1 when block 0 of the most recent
+        forward computed q / k / v from the raw input channels instead of the qkv GEMM)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)

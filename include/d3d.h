@@ -162,6 +162,12 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     the keys say.  Bit-identical either way, for every T, non-finite activations included (a group's pad keys are
  *                     masked to zeros in registers: a sequence's result depends on its own rows only).  "bf16_fused_spatial_last" / "bf16_fused_temporal_last"
  *                     (d3d_engine_get_info) report what the latest forward ran.
+ *   "block0_direct"   1 (default) / 0: F16X3 folded flow, block 0 (D = 512, 17 joints, 8 heads, in_chans <= 3): its input rows are W_e u + b_e + spos[j] + tv[b]
+ *                     with u the in_chans + 3 raw channels of a token, so q / k / v follow from commit-time tables (G = Wg W_e, P[j] =
+ *                     Wg (b_e + spos[j]), fp64 sums stored as fp32) and one time row per forward (Q = Wg tv, in the caller's workspace) with
+ *                     in_chans + 3 fmas and two adds per value: block 0 runs no qkv GEMM / 0: the K = 512 GEMM like every other block.
+ *                     Both "fused_spatial" settings take the same fill function: bit-identical to each other; against 0 the results move
+ *                     in the last bits (inside the parity gate).  "block0_direct_last" (d3d_engine_get_info) reports what ran.
  *   "fc1_kernel"      1 (default) / 0: fc1 (LayerNorm-folded, GELU) on its own kernel -- the hand-specialised k-loop of the fused kernels
  *                     with the token GEMM's own epilogue function, from two rounds of 256 x 256 tiles on -- / as a form of the token GEMM.
  *                     Bit-identical.
@@ -239,7 +245,8 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * "proj_split_last" / "fc1_split_last" (the same for proj and fc1), "proj_split" / "fc1_split" (the option values),
  * "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the spatial / temporal blocks of the most recent d3d_denoise /
  * d3d_ddim_sample call of a D3D_PREC_BF16 engine ran the fused qkv + attention kernel, else 0; 0 before the first call and in the
- * other precisions).
+ * other precisions), "block0_direct_last" (1 when block 0 of the most recent d3d_denoise / d3d_ddim_sample call computed q / k / v from
+ * the raw input channels -- option "block0_direct" --, else 0: option off, another precision, or a shape without the tables).
  * Unknown key: D3D_EINVAL. */
 int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value);
 
