@@ -1,4 +1,4 @@
-// LDS layout helpers of the attention kernels (kernels_attn_x3.hip, kernels_attn_bf16.hip and the attention steps of the fused
+// LDS layout helpers of the attention kernels (kernels_attn_x3.hip, kernels_attn_x3_long.hip, kernels_attn_bf16.hip and the attention steps of the fused
 // kernels_qkv_sattn.hip, kernels_qkv_tattn.hip, kernels_qkv_attn_bf16.hip), included inside namespace d3d: the row swizzles of the
 // K / Q and V planes, the hi / lo fp16 splits, the output patch.
 #pragma once

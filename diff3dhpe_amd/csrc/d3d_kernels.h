@@ -373,6 +373,12 @@ hipError_t launch_attn_generic(const float* qkv, float* out, void* out_x3, int B
 hipError_t launch_attn_temporal_x3(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                    hipStream_t s);
 bool attn_temporal_x3_ok(int T, int D, int H);
+// ---- kernels_attn_x3_long.hip: the same attention for windows of any length (the keys stream through LDS in chunks of 256 frames;
+// the scores are computed twice, for the exact maximum and for the numerators).  Same planes in, same pair layout out; bit-identical to
+// launch_attn_temporal_x3 wherever that runs (T <= 256).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_temporal_x3_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
+                                        hipStream_t s);
+bool attn_temporal_x3_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

@@ -63,6 +63,8 @@ struct BlockPlan {
   Flow flow = PLAIN;          // run_blocks / run_blocks_fold / run_blocks_bf16
   // FOLD, BF16: the qkv GEMM and the attention of the spatial / temporal blocks as one kernel
   bool fused_sp = false, fused_tp = false;
+  // FOLD: the temporal blocks' attention on the key-streaming kernel (kernels_attn_x3_long.hip: windows of more than 256 frames)
+  bool tp_long = false;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
   // PLAIN in F16X3: q / k / v go to the fp16-MFMA attention kernel as planes
@@ -125,6 +127,9 @@ struct d3d_engine {
   // tiles runs as a split-K x split-N GEMM + an ordered reduce / post-norm row kernel (d3d_kernels.h fc2_splitk_choose).  Changes the
   // order of additions: results stay inside the parity gate but are no longer bit-identical to the default path's.
   bool opt_latency_mode = false;
+  // "long_temporal" (on by default): an F16X3 engine whose window is longer than 256 frames keeps the folded flow, its temporal blocks on
+  // the key-streaming attention kernel (kernels_attn_x3_long.hip); 0 = the plain row-kernel flow with the generic fp32 attention
+  bool opt_long_temporal = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -140,7 +145,8 @@ struct d3d_engine {
   }
   // the plan of the most recent forward (of a two-stream sampling: of the first half-batch, the one that holds sequence 0); all zero
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
-  // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks
+  // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
+  // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -453,8 +459,11 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   const int T = e->T, J = e->J, D = e->D, Dm = e->Dm, H = e->H, M = B * T * J, cus = device_cu_count();
   const bool x3 = e->cfg.precision == D3D_PREC_F16X3;
   BlockPlan p;
-  if (x3 && attn_temporal_x3_ok(T, D, H) && attn_temporal_x3_ok(J, D, H) && D % 32 == 0 && e->opt_fold_layernorm) {
+  // windows of more than 256 frames: no F16X3 attention kernel holds their keys in LDS; the long kernel streams them
+  const bool tp_long = e->opt_long_temporal && T > 256 && attn_temporal_x3_long_ok(T, D, H);
+  if (x3 && (attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H) && D % 32 == 0 && e->opt_fold_layernorm) {
     p.flow = BlockPlan::FOLD;
+    p.tp_long = tp_long;      // (qkv_tattn_ok refuses T > 255: such temporal blocks take the two-kernel branch)
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
     // block 0 from the raw channels: every forward of this flow whose block 0 has the tables (fused or not, any B, any time rows)
@@ -630,7 +639,8 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
     {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD4, s);
-      if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
+      if (temporal && pl.tp_long) HIP_TRY(launch_attn_temporal_x3_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
+      else if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
     }
     TRACE(k, 3, 0, AOx, MDb);
@@ -972,7 +982,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 134; }   // 134: latency mode covers proj and fc1 ("proj_split" / "fc1_split", d3d_op_linear_splitk_residual / _gelu)
+int d3d_version(void) { return 135; }   // 135: F16X3 windows of more than 256 frames keep the folded flow ("long_temporal", d3d_op_attention_long)
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1562,6 +1572,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
       if (rc) { e->opt_latency_mode = false; return rc; }
     }
   }
+  else if (k == "long_temporal") e->opt_long_temporal = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1625,6 +1636,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "streams") *value = e->opt_streams;
   else if (k == "device") *value = e->device;
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
+  else if (k == "long_temporal") *value = e->opt_long_temporal ? 1 : 0;
+  else if (k == "long_temporal_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.tp_long;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

@@ -206,6 +206,14 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     folded LayerNorm, GELU, hidden planes).  Each has its own rule, a function of (M, N, K, CU count) alone that
  *                     compares the split against the launch it replaces; "proj_split_last" / "fc1_split_last" report what ran.  A
  *                     sequence's result is bit-identical across calls that get the same three S.
+ *   "long_temporal"   1 (default) / 0: F16X3 engines with num_frame > 256.  No F16X3 attention kernel holds the keys of such a window in
+ *                     LDS; with the key on, the engine keeps its folded flow (LayerNorm-folded GEMMs, plane-resident residual stream, fused
+ *                     spatial qkv + attention, block 0 direct, fc2 + post-norm) and the temporal blocks run the folded qkv GEMM followed by
+ *                     the key-streaming attention kernel (keys pass through LDS in chunks of 256 frames, the scores are computed twice: the
+ *                     exact two-pass softmax of every other form) / 0: the plain row-kernel flow with the generic fp32 attention kernel,
+ *                     as before version 135.  The two differ in the last bits, both inside the parity gate.  num_frame <= 256, FP32 and
+ *                     BF16 engines: no effect.  d3d_workspace_bytes does not change.  "long_temporal_last" (d3d_engine_get_info) reports
+ *                     what the latest forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -246,7 +254,9 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the spatial / temporal blocks of the most recent d3d_denoise /
  * d3d_ddim_sample call of a D3D_PREC_BF16 engine ran the fused qkv + attention kernel, else 0; 0 before the first call and in the
  * other precisions), "block0_direct_last" (1 when block 0 of the most recent d3d_denoise / d3d_ddim_sample call computed q / k / v from
- * the raw input channels -- option "block0_direct" --, else 0: option off, another precision, or a shape without the tables).
+ * the raw input channels -- option "block0_direct" --, else 0: option off, another precision, or a shape without the tables),
+ * "long_temporal" (the option value), "long_temporal_last" (1 when the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample
+ * call ran the key-streaming F16X3 attention kernel, else 0: num_frame <= 256, option off, another precision, or before any forward).
  * Unknown key: D3D_EINVAL. */
 int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value);
 
@@ -452,6 +462,10 @@ int d3d_op_layernorm(const float* x_dev, const float* gamma_dev, const float* be
  * force_generic != 0 selects the slow any-shape kernel (cross-check). */
 int d3d_op_attention(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
                      int32_t temporal, int32_t precision, int32_t force_generic, void* stream);
+/* The temporal core of the F16X3 mode from the key-streaming kernel alone (option "long_temporal"): fp32 qkv in, fp32 out, split into /
+ * merged from the hi / lo fp16 planes on the device as in d3d_op_attention (D3D_PREC_F16X3).  Any T >= 1, head width D / H == 64 (else
+ * D3D_EUNSUP); for T <= 256 bit for bit the result of d3d_op_attention (temporal = 1, D3D_PREC_F16X3). */
+int d3d_op_attention_long(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
 /* The fused qkv GEMM + attention kernel of the BF16 mode alone: out = attention(bf16(A) bf16(Wqkv)^T + bias) with q / k / v rounded to
  * bf16 (q third times dh^-1/2) and kept on chip -- bit for bit d3d_op_linear (D3D_PREC_BF16) followed by d3d_op_attention (D3D_PREC_BF16)
  * on the same tensors.  A: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias: (3 D); out: (groups * N, D) fp32.  Group u holds the N
