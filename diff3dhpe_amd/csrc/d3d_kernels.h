@@ -379,6 +379,12 @@ bool attn_temporal_x3_ok(int T, int D, int H);
 hipError_t launch_attn_temporal_x3_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                         hipStream_t s);
 bool attn_temporal_x3_long_ok(int T, int D, int H);
+// ---- kernels_attn_f32_long.hip: launch_attn_temporal_f32's attention (exact fp32, v_mfma_f32_32x32x2_f32) for windows of any length:
+// the keys stream through LDS in chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out, no
+// pair-layout form; bit-identical to launch_attn_temporal_f32 wherever that runs (T <= 256).  The launch also refuses
+// B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_temporal_f32_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_temporal_f32_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

@@ -65,6 +65,9 @@ struct BlockPlan {
   bool fused_sp = false, fused_tp = false;
   // FOLD: the temporal blocks' attention on the key-streaming kernel (kernels_attn_x3_long.hip: windows of more than 256 frames)
   bool tp_long = false;
+  // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel (kernels_attn_f32_long.hip: windows of more than 256
+  // frames, which k_attn_temporal_f32 cannot hold in LDS); false = k_attn_generic there
+  bool tp_long_f32 = false;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
   // PLAIN in F16X3: q / k / v go to the fp16-MFMA attention kernel as planes
@@ -130,6 +133,9 @@ struct d3d_engine {
   // "long_temporal" (on by default): an F16X3 engine whose window is longer than 256 frames keeps the folded flow, its temporal blocks on
   // the key-streaming attention kernel (kernels_attn_x3_long.hip); 0 = the plain row-kernel flow with the generic fp32 attention
   bool opt_long_temporal = true;
+  // "long_temporal_f32" (on by default): an FP32 engine whose window is longer than 256 frames runs its temporal blocks' attention on the
+  // key-streaming fp32 MFMA kernel (kernels_attn_f32_long.hip); 0 = the generic one-thread-per-row kernel.  F16X3 / BF16 engines: no effect
+  bool opt_long_temporal_f32 = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -146,7 +152,8 @@ struct d3d_engine {
   // the plan of the most recent forward (of a two-stream sampling: of the first half-batch, the one that holds sequence 0); all zero
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
-  // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip
+  // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip, "long_temporal_f32_last" = the same for
+  // kernels_attn_f32_long.hip
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -404,12 +411,13 @@ int compute_temb(d3d_engine* e, const float* times_dev, int n, float* out, float
   return D3D_OK;
 }
 
-int attention(d3d_engine* e, const float* qkv, float* out, void* out_x3, int B, bool temporal, hipStream_t s) {
+int attention(d3d_engine* e, const BlockPlan& pl, const float* qkv, float* out, void* out_x3, int B, bool temporal, hipStream_t s) {
   if (!temporal) {
     if (attn_spatial_fast_ok(e->J, e->D, e->H)) HIP_TRY(launch_attn_spatial_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
     else HIP_TRY(launch_attn_generic(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, 0, s));
   } else {
-    if (attn_temporal_fast_ok(e->T, e->D, e->H)) HIP_TRY(launch_attn_temporal_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
+    if (pl.tp_long_f32) HIP_TRY(launch_attn_temporal_f32_long(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (FP32 engines only: no out_x3)
+    else if (attn_temporal_fast_ok(e->T, e->D, e->H)) HIP_TRY(launch_attn_temporal_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
     else HIP_TRY(launch_attn_generic(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, 1, s));
   }
   return D3D_OK;
@@ -498,6 +506,9 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   } else if (x3) {
     p.attn_x3_sp = attn_temporal_x3_ok(J, D, H);
     p.attn_x3_tp = attn_temporal_x3_ok(T, D, H);
+  } else if (e->cfg.precision == D3D_PREC_FP32) {
+    // windows of more than 256 frames: the resident fp32 MFMA kernel cannot hold their keys; the long kernel streams them
+    p.tp_long_f32 = e->opt_long_temporal_f32 && T > 256 && attn_temporal_f32_long_ok(T, D, H);
   }
   return p;
 }
@@ -899,7 +910,7 @@ int run_blocks(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float
         if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, HNx, B, T, J, D, e->H, s));
         else HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, HNx, B * T, J, 1, D, e->H, s));
       } else {
-        int rc = attention(e, w.QKV, w.HN, x3 ? HNx : nullptr, B, temporal, s);
+        int rc = attention(e, pl, w.QKV, w.HN, x3 ? HNx : nullptr, B, temporal, s);
         if (rc) return rc;
       }
     }
@@ -982,7 +993,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 135; }   // 135: F16X3 windows of more than 256 frames keep the folded flow ("long_temporal", d3d_op_attention_long)
+int d3d_version(void) { return 136; }   // 136: FP32 windows of more than 256 frames on an MFMA attention kernel ("long_temporal_f32", d3d_op_attention_long_f32)
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1573,6 +1584,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
     }
   }
   else if (k == "long_temporal") e->opt_long_temporal = value != 0;
+  else if (k == "long_temporal_f32") e->opt_long_temporal_f32 = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1638,6 +1650,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
   else if (k == "long_temporal") *value = e->opt_long_temporal ? 1 : 0;
   else if (k == "long_temporal_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.tp_long;
+  else if (k == "long_temporal_f32") *value = e->opt_long_temporal_f32 ? 1 : 0;
+  else if (k == "long_temporal_f32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

@@ -380,4 +380,11 @@ int d3d_op_attention_long(const float* qkv, float* out, int32_t B, int32_t T, in
   return finish(le, s);
 }
 
+int d3d_op_attention_long_f32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_temporal_f32_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 64");
+  HIP_TRY(launch_attn_temporal_f32_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
+  return D3D_OK;
+}
+
 }  // extern "C"

@@ -213,8 +213,9 @@ class Engine:
     def set_option(self, key: str, value: int) -> None:
         """Explicit engine switch (include/d3d.h: "fused_postnorm", "fold_layernorm", "streams", "latency_mode", "proj_split",
         "fc1_split", "block0_direct", "long_temporal": 1 (default) keeps an F16X3 engine with num_frame > 256 on the folded flow, its
-        temporal blocks on the key-streaming attention kernel; 0 gives such an engine the plain row-kernel flow); the library reads no
-        environment."""
+        temporal blocks on the key-streaming attention kernel; 0 gives such an engine the plain row-kernel flow, "long_temporal_f32": 1 (default)
+        runs the temporal blocks of an FP32 engine with num_frame > 256 on the key-streaming fp32 MFMA attention kernel; 0 keeps the generic
+        one-thread-per-row kernel there); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
@@ -224,7 +225,8 @@ class Engine:
         bf16 engine ran the fused qkv + attention kernel in its spatial / temporal blocks), "block0_direct_last" (1 when block 0 of the most recent
         forward computed q / k / v from the raw input channels instead of the qkv GEMM), "long_temporal" (the option), "long_temporal_last"
         (1 when the temporal blocks of the most recent forward ran the key-streaming F16X3 attention kernel: num_frame > 256 with the
-        option on; else 0)."""
+        option on; else 0), "long_temporal_f32" (the option), "long_temporal_f32_last" (the same for an FP32 engine and the key-streaming
+        fp32 attention kernel; "long_temporal_last" stays 0 there)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -580,6 +582,19 @@ def op_attention_long(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torc
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib().d3d_op_attention_long(_ptr(q), _ptr(out), B, T, J, D, H, st))
+    return out
+
+
+def op_attention_long_f32(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming fp32 temporal attention kernel alone (include/d3d.h d3d_op_attention_long_f32): qkv (B*T*J, 3*D) -> (B*T*J, D),
+    any T >= 1; for T <= 256 bit for bit op_attention(..., temporal=True, precision="fp32")."""
+    dev = qkv.device
+    D = qkv.shape[-1] // 3
+    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
+    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_attention_long_f32(_ptr(q), _ptr(out), B, T, J, D, H, st))
     return out
 
 

@@ -10,7 +10,11 @@ spread in every alternation (the condition for shipping the option on by default
 events around every kernel) gives the per-launch time of the temporal attention in both modes.  Writes profiles/long_temporal.json (or
 the path given with --out).
 
-    python experiments/long_temporal.py [--out FILE] [--samples 5] [--repeats 5]
+--fp32: the same legs on two FP32 engines, "long_temporal_f32" = 1 (the key-streaming fp32 MFMA attention kernel, kernels_attn_f32_long.hip)
+against 0 (the generic one-thread-per-row kernel in the temporal blocks); every other launch is the same in both legs.  Writes
+profiles/long_temporal_f32.json.
+
+    python experiments/long_temporal.py [--fp32] [--out FILE] [--samples 5] [--repeats 5]
 """
 import argparse
 import json
@@ -29,13 +33,13 @@ from diff3dhpe_amd.synth import synth_state_dict, synth_inputs  # noqa: E402
 STEPS = 9
 
 
-def product(T, sd, long_temporal):
+def product(T, sd, long_temporal, prec="f16x3", key="long_temporal"):
     net = d3d.HPE_model(d3d.S2S_NAME)(num_frame=T, embed_dim=512, depth=8)
     net.load_state_dict(sd)
-    net.precision = "f16x3"
+    net.precision = prec
     diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=STEPS, loss_type="l2", clip_denoised=True).eval().cuda()
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
-    eng.set_option("long_temporal", int(long_temporal))
+    eng.set_option(key, int(long_temporal))
     return eng, net, diff   # (the engine lives as long as its model)
 
 
@@ -69,21 +73,25 @@ def per_launch(eng, x2d, nz):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "long_temporal.json"))
+    ap.add_argument("--fp32", action="store_true", help='FP32 engines, "long_temporal_f32" 1 / 0')
+    ap.add_argument("--out", default=None)
     ap.add_argument("--samples", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--frames", type=int, nargs="*", default=[351, 513])
     ap.add_argument("--batches", type=int, nargs="*", default=[1, 8])
     a = ap.parse_args()
+    prec, key = ("fp32", "long_temporal_f32") if a.fp32 else ("f16x3", "long_temporal")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", key + ".json")
     assert torch.cuda.is_available(), "needs the GPU"
-    res = {"what": f"{STEPS}-step DDIM sampling, F16X3, depth 8, D = 512, hipGraph replay, long_temporal 1 (on) vs 0 (off: the launches of the "
+    res = {"what": f"{STEPS}-step DDIM sampling, {prec.upper()}, depth 8, D = 512, hipGraph replay, {key} 1 (on) vs 0 (off: the launches of the "
                    f"tree before the option), two engines with the same weights alternating in one process; ms are medians of {a.repeats} round "
                    f"medians of {a.samples} samplings; spread = max - min of the off leg's round medians",
            "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count, "cells": []}
     for T in a.frames:
         cfg = DenoiserConfig(num_frame=T, embed_dim=512, depth=8)
         sd = {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, 0).items()}
-        legs = {"on": product(T, sd, True), "off": product(T, sd, False)}
+        legs = {"on": product(T, sd, True, prec, key), "off": product(T, sd, False, prec, key)}
         for B in a.batches:
             inp = synth_inputs(B, T, seed=1)
             x2d, nz = torch.from_numpy(inp["x2d"]).cuda(), torch.from_numpy(inp["noise"]).cuda()
@@ -92,7 +100,7 @@ def main():
                 eng.set_graph_mode(True)
                 for _ in range(2):
                     outs[name] = eng.ddim_sample(x2d, nz).clone()
-                ran[name] = eng.info("long_temporal_last")
+                ran[name] = eng.info(key + "_last")
             torch.cuda.synchronize()
             assert ran == {"on": 1, "off": 0}, ran
             med = {"on": [], "off": []}

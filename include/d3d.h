@@ -214,6 +214,13 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     as before version 135.  The two differ in the last bits, both inside the parity gate.  num_frame <= 256, FP32 and
  *                     BF16 engines: no effect.  d3d_workspace_bytes does not change.  "long_temporal_last" (d3d_engine_get_info) reports
  *                     what the latest forward ran.
+ *   "long_temporal_f32"  1 (default) / 0: FP32 engines with num_frame > 256 (the engine a precision-"auto" model falls back to, and the exact
+ *                     reference arithmetic).  The resident fp32 MFMA attention kernel holds K and V of at most 256 frames in LDS; with the key
+ *                     on, the temporal blocks of such an engine run the key-streaming fp32 kernel (v_mfma_f32_32x32x2_f32, keys pass
+ *                     through LDS in chunks of 256 frames, three passes: maximum, sum, normalised product -- the resident kernel's
+ *                     arithmetic in its order) / 0: the generic one-thread-per-row kernel, as before version 136.  The two differ in the
+ *                     last bits, both inside the parity gate.  num_frame <= 256, F16X3 and BF16 engines: no effect.  d3d_workspace_bytes
+ *                     does not change.  "long_temporal_f32_last" (d3d_engine_get_info) reports what the latest forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -256,7 +263,9 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * other precisions), "block0_direct_last" (1 when block 0 of the most recent d3d_denoise / d3d_ddim_sample call computed q / k / v from
  * the raw input channels -- option "block0_direct" --, else 0: option off, another precision, or a shape without the tables),
  * "long_temporal" (the option value), "long_temporal_last" (1 when the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample
- * call ran the key-streaming F16X3 attention kernel, else 0: num_frame <= 256, option off, another precision, or before any forward).
+ * call ran the key-streaming F16X3 attention kernel, else 0: num_frame <= 256, option off, another precision, or before any forward),
+ * "long_temporal_f32" (the option value), "long_temporal_f32_last" (the same for a D3D_PREC_FP32 engine and the key-streaming fp32
+ * attention kernel; "long_temporal_last" stays 0 on such an engine).
  * Unknown key: D3D_EINVAL. */
 int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value);
 
@@ -466,6 +475,10 @@ int d3d_op_attention(const float* qkv_dev, float* out_dev, int32_t B, int32_t T,
  * merged from the hi / lo fp16 planes on the device as in d3d_op_attention (D3D_PREC_F16X3).  Any T >= 1, head width D / H == 64 (else
  * D3D_EUNSUP); for T <= 256 bit for bit the result of d3d_op_attention (temporal = 1, D3D_PREC_F16X3). */
 int d3d_op_attention_long(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
+/* The temporal core of the FP32 mode from the key-streaming fp32 kernel alone (option "long_temporal_f32"): fp32 qkv in, fp32 out.  Any
+ * T >= 1, head width D / H == 64 (else D3D_EUNSUP); for T <= 256 bit for bit the result of d3d_op_attention (temporal = 1,
+ * D3D_PREC_FP32, force_generic = 0). */
+int d3d_op_attention_long_f32(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
 /* The fused qkv GEMM + attention kernel of the BF16 mode alone: out = attention(bf16(A) bf16(Wqkv)^T + bias) with q / k / v rounded to
  * bf16 (q third times dh^-1/2) and kept on chip -- bit for bit d3d_op_linear (D3D_PREC_BF16) followed by d3d_op_attention (D3D_PREC_BF16)
  * on the same tensors.  A: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias: (3 D); out: (groups * N, D) fp32.  Group u holds the N
