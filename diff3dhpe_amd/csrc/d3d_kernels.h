@@ -233,8 +233,8 @@ hipError_t launch_f32_to_bf16(const float* x, void* y, size_t n, hipStream_t s);
 hipError_t launch_bf16_to_f32(const void* x, float* y, size_t n, hipStream_t s);
 hipError_t launch_scale_cols(float* x, size_t rows, int cols, int ncols_scaled, float f, hipStream_t s);   // op hooks only
 
-// ---- kernels_qkv_sattn.hip: spatial blocks, qkv GEMM (LayerNorm-folded) + 17-key attention in one kernel --------------------
-// Apair: the residual stream planes (rows up to 255 * ceil(frames / 15) + 1 are staged); W / bias / csum HEAD-MAJOR (row 192 h +
+// ---- kernels_qkv_sattn.hip: spatial blocks, qkv GEMM (LayerNorm-folded) + J-key attention in one kernel, J = 15, 16, 17 --------------------
+// Apair: the residual stream planes (rows up to 255 * ceil(frames / 15) + 1 are staged at 17 joints, never more at 15 / 16); W / bias / csum HEAD-MAJOR (row 192 h +
 // 64 part + d); st_in / st_np / eps as X3Fold; out_x3: attention output in the pair layout.  M = frames * J tokens.
 bool qkv_sattn_ok(int J, int D, int H, int K);
 hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, const float* bias_hm, const float* csum_hm, const float* st_in,

@@ -377,7 +377,9 @@ Workspace carve(const d3d_engine* e, int B, void* base) {
   float* b = reinterpret_cast<float*>(base);
   Workspace w{};
   // F16X3 operand planes are read in whole 256-row tiles; the fused spatial kernel's tiles start every 255 rows (15 frames) and
-  // stage 256, so the last one may reach 255 * ceil(frames / 15) + 1 rows
+  // stage 256, so the last one may reach 255 * ceil(frames / 15) + 1 rows.  Sized that way whatever J is: the 16-frame tiles of 15 and
+  // 16 joints need 240 * ceil(frames / 16) + 16 rows (never more than the above: 15 c >= 15 for every tile count c >= 1) and
+  // 256 * ceil(frames / 16) = M rounded up to 256 (what Mp is rounded to anyway), so d3d_workspace_bytes does not depend on the form
   const size_t fr = M / (size_t)e->J, qs_rows = 255 * ((fr + 14) / 15) + 1;
   const size_t Mp = (std::max(std::max(M, qs_rows), (M + 191) / 192 * 192) + 255) / 256 * 256;   // (and whole 192-row tiles)
   size_t oX = take(Mp * D), oHN = take(Mp * D), oQKV = take(M * 3 * D), oHID = take(Mp * e->Dm);
@@ -633,7 +635,7 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
       HIP_TRY(qkv_direct(AOx, nullptr, nullptr));
       TRACE(k, 3, 0, AOx, MDb);
     } else if (!temporal && pl.fused_sp) {
-      // spatial block: q, k, v of a frame group stay in LDS and feed the 17-key attention in the same kernel (kernels_qkv_sattn.hip)
+      // spatial block: q, k, v of a frame group stay in LDS and feed the J-key attention in the same kernel (kernels_qkv_sattn.hip)
       Prof p(e, D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)J * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_sattn(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, M, D, J, D, e->H, s));
       TRACE(k, 3, 0, AOx, MDb);
@@ -993,7 +995,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 136; }   // 136: FP32 windows of more than 256 frames on an MFMA attention kernel ("long_temporal_f32", d3d_op_attention_long_f32)
+int d3d_version(void) { return 137; }   // 137: skeletons of 15 and 16 joints on the fused spatial kernels and the fp32 spatial kernel; info key "fused_spatial_last"
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1659,6 +1661,7 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "block0_direct_last") *value = e->last_plan.b0_direct ? 1 : 0;
   else if (k == "proj_split") *value = e->opt_proj_split;
   else if (k == "fc1_split") *value = e->opt_fc1_split;
+  else if (k == "fused_spatial_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.fused_sp;
   else if (k == "bf16_fused_spatial_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_sp;
   else if (k == "bf16_fused_temporal_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_tp;
   else return fail(D3D_EINVAL, "unknown info key: " + k);

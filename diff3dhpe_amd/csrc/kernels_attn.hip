@@ -169,17 +169,28 @@ __global__ __launch_bounds__(256) void k_attn_spatial_f32(const float* __restric
   }
 }
 
-bool attn_spatial_fast_ok(int J, int D, int H) { return J == 17 && H > 0 && D == H * SP_DH; }
+// 15, 16 and 17 joints: the skeletons the reference's datasets produce (other counts take k_attn_generic)
+bool attn_spatial_fast_ok(int J, int D, int H) { return J >= 15 && J <= 17 && H > 0 && D == H * SP_DH; }
+
+template <int NJ>
+static hipError_t launch_attn_spatial_f32_nj(const float* qkv, float* out, void* out_x3, long long units, int D, int H, hipStream_t s) {
+  constexpr int UPB = 4 * (64 / NJ);             // units per block: four waves of 64 / NJ
+  const long long grid = (units + UPB - 1) / UPB;
+  if (units > 0x7fffffffLL || grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_attn_spatial_f32<NJ>, dim3((unsigned)grid), dim3(256), 0, s, qkv, out, (_Float16*)out_x3, (int)units, H, D, launch_range_word());
+  return hipGetLastError();
+}
 
 hipError_t launch_attn_spatial_f32(const float* qkv, float* out, void* out_x3, int B, int T, int J, int D, int H,
                                    hipStream_t s) {
   if (!attn_spatial_fast_ok(J, D, H)) return hipErrorInvalidValue;
   const long long units = (long long)B * T * H;
-  constexpr int UPB = 4 * (64 / 17);
-  const long long grid = (units + UPB - 1) / UPB;
-  if (units > 0x7fffffffLL || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_attn_spatial_f32<17>, dim3((unsigned)grid), dim3(256), 0, s, qkv, out, (_Float16*)out_x3, (int)units, H, D, launch_range_word());
-  return hipGetLastError();
+  switch (J) {
+    case 15: return launch_attn_spatial_f32_nj<15>(qkv, out, out_x3, units, D, H, s);
+    case 16: return launch_attn_spatial_f32_nj<16>(qkv, out, out_x3, units, D, H, s);
+    case 17: return launch_attn_spatial_f32_nj<17>(qkv, out, out_x3, units, D, H, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 // =============================================================================================== temporal (MFMA f32)

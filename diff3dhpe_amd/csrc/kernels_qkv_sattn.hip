@@ -1,8 +1,10 @@
-// Spatial blocks of the F16X3 flow, fused: the LayerNorm-folded qkv GEMM of a frame group with the 17-key GRAND attention of its
+// Spatial blocks of the F16X3 flow, fused: the LayerNorm-folded qkv GEMM of a frame group with the 17-key (15, 16) GRAND attention of its
 // frames run from LDS (S2S:67 + 73-83 for the per-frame groups of S2S:119).  What it removes from the unfused flow
 // (k_linear_x3q_persist<qkv form> + k_attn_temporal_x3p<1,8,3>): the q / k / v planes never exist in HBM -- 1.62 GB written and
 // 1.62 GB read back per launch pair at the bench shape -- and one kernel launch per spatial block.
 //
+// (What follows describes the 17-joint form.  15 and 16 joints run the same code on a tile of 16 whole frames -- 240 / 256 rows, slots
+// of 6 x J rows, both passes with eight slots: see QsGeo below for what changes with the joint count.)
 // Tile = 15 whole frames (255 token rows; 256 are staged and multiplied) x ONE head's q, k, v (192 output columns: the folded weight
 // is stored HEAD-MAJOR at commit, rows [192 h, 192 h + 192) = q_h, k_h, v_h, so an N-tile is contiguous).  Eight waves (2 x 4), a
 // wave owns 128 rows x 48 columns = 8 x 3 accumulator tiles of 16x16 (96 VGPRs).  The k-loop is the two-phase persistent loop of
@@ -21,6 +23,8 @@
 // of a 40.5 us tile, in-kernel stamps; the epilogue steps are VALU-issue-bound with two waves per SIMD)
 // LDS map (160 KiB): [0, 56 K) stage 0 | [56 K, 158 K) stage 1, then the frame slots (+ the raw row-statistics block during the
 // k-loop) | 2 KiB of per-row LayerNorm statistics.
+// Skeletons of 15 and 16 joints (the reference's --dataset humaneva* branch, 16-joint H36M variants) take the same kernels on a tile of
+// 16 frames: QsGeo below.  The joint count is a compile-time parameter; the 17-joint instantiations are the code they were before it was.
 // Block 0 runs k_qkv_sattn_direct (below): the same tile and the same code behind the accumulators, which it fills from the raw input
 // channels of the tokens and commit-time tables instead of a k-loop ("block0_direct" engine option).
 #include "d3d_kernels.h"
@@ -35,18 +39,59 @@ namespace {
 #include "attn_lds.h"
 
 QF_SHAPE(8, 3, 256, 192, 4, 3);                                          // 256 x 192 x 32 stage of 57344 bytes
-constexpr int QS_J = 17, QS_FPT = 15, QS_ROWS = QS_J * QS_FPT;           // 255 token rows per tile
-constexpr int QS_PLANE = QS_J * 128, QS_SLOT = 6 * QS_PLANE;             // 2176, 13056
 constexpr int QS_QKV = QF_STAGE;                                         // frame slots start behind stage 0
-constexpr int QS_STX = QS_QKV + 8 * QS_SLOT;                             // 161792: (rstd', -mean rstd) of the tile's 256 rows, 2 KiB
 constexpr int QS_RAW = 2 * QF_STAGE;                                     // raw statistics partials while the k-loop runs (16 KiB)
 constexpr int QS_RAW_MAX = 16384;
-constexpr int QS_LDS = QS_STX + QF_BM * 8;                               // 163840
-static_assert(QS_LDS <= 160 * 1024 && QS_RAW + QS_RAW_MAX <= QS_STX, "LDS map");
-// planes of a slot: V hi, V lo, K hi, K lo, Q hi, Q lo.  The fragment reads of the 15 pad rows of a plane run on into what follows
-// it: for V that must be FINITE (0 x NaN in the second product) -- V hi runs into V lo, V lo into K hi, both written in the same pass;
-// pad keys of K are overwritten with -inf scores and pad queries of Q are never stored: any bits will do there.
-constexpr int QS_PV = 0, QS_PK = 2 * QS_PLANE, QS_PQ = 4 * QS_PLANE;
+// The tile geometry of a joint count J (a compile-time parameter of the whole kernel family; J = 17 is the form described above):
+//   J = 17: 15 frames, 255 rows (row 255 is the next tile's first)      J = 16: 16 frames, 256 rows, a frame is one 16-row m-tile
+//   J = 15: 16 frames, 240 rows; the 16 trailing rows (the next tile's first frame and the first joint of its second) are staged and
+//           multiplied like row 255 of the 17-joint form and never written to a slot, attended, stored or counted
+// With 16 frames both passes fill all eight slots (same rule: frame fr -> pass (fr >> 2) & 1, slot (fr & 3) + 4 (fr >> 3)).
+template <int J>
+struct QsGeo {
+  static_assert(J == 15 || J == 16 || J == 17, "joint counts with a tile geometry");
+  static constexpr int FPT = J == 17 ? 15 : 16, ROWS = J * FPT;          // whole frames / token rows per tile
+  static constexpr int PLANE = J * 128;                                  // 1920, 2048, 2176
+  // a slot: six planes; its last two (Q hi, Q lo) double as the wave's 4 KiB output patch, which at J = 15 is 256 bytes more than they hold
+  static constexpr int SLOT = 4 * PLANE + (2 * PLANE > 4096 ? 2 * PLANE : 4096);   // 11776, 12288, 13056
+  static constexpr int STX = QS_QKV + 8 * SLOT;                          // (rstd', -mean rstd) of the tile's 256 rows, 2 KiB (J = 17: 161792)
+  static constexpr int LDS = STX + QF_BM * 8;                            // 153600, 157696, 163840
+  static_assert(LDS <= 160 * 1024 && QS_RAW + QS_RAW_MAX <= STX, "LDS map");
+  // planes of a slot: V hi, V lo, K hi, K lo, Q hi, Q lo.  A fragment read takes 32 rows (K, Q) or the key rows of the 16-key steps it
+  // runs (V), so the rows behind a plane's J are whatever follows it.  For V that must be FINITE (0 x NaN in the second product):
+  //   J = 17: 15 pad rows; V hi runs into V lo, V lo into K hi, both written in the same pass
+  //   J = 16: one 16-key step, all of its rows real: no V read leaves its plane
+  //   J = 15: one 16-key step with ONE pad row, key 15: row 0 of V lo behind V hi, row 0 of K hi behind V lo -- the same frame's own
+  //           values, written in the same pass
+  // Pad keys of K never reach the softmax (-inf scores, or accumulator registers nothing reads) and pad queries of Q are never stored:
+  // any bits will do there.  The last slot's Q reads end 32 - J rows behind it, inside the statistics block.
+  static constexpr int PV = 0, PK = 2 * PLANE, PQ = 4 * PLANE;
+  static_assert(PQ + PLANE + 32 * 128 <= SLOT + QF_BM * 8, "the 32-row reads of the last slot's Q lo plane stay inside the allocation");
+};
+// tile row R -> its frame R / J: a multiply-shift (a shift at 16), checked against the division for every row of a tile
+template <int J>
+__host__ __device__ constexpr int qs_frame(int R) { return J == 17 ? (R * 241) >> 12 : (J == 16 ? R >> 4 : (R * 137) >> 11); }
+template <int J>
+constexpr bool qs_frame_exact() {
+  for (int R = 0; R < QF_BM; ++R)
+    if (qs_frame<J>(R) != R / J) return false;
+  return true;
+}
+static_assert(qs_frame_exact<15>() && qs_frame_exact<16>() && qs_frame_exact<17>(), "R / J for R < 256");
+// m-tiles (bit i: rows 128 wm + 16 i .. + 15) of wave row wm that hold a row of a frame of `pass`: the wave-uniform skip of write_pass
+// -- derived from the rule, the per-row test stays the authority (J = 17: m-tiles 0-4 of both wave rows in pass 0, 4-7 and, in wave
+// row 1, m-tile 0 in pass 1; J = 16: m-tiles 0-3, then 4-7)
+template <int J>
+constexpr unsigned qs_mtiles(int wm, int pass) {
+  unsigned mk = 0;
+  for (int R = 128 * wm; R < 128 * wm + 128; ++R) {
+    const int fr = R / J;
+    if (fr < QsGeo<J>::FPT && ((fr >> 2) & 1) == pass) mk |= 1u << ((R >> 4) & 7);
+  }
+  return mk;
+}
+static_assert(qs_mtiles<17>(0, 0) == 0x1f && qs_mtiles<17>(1, 0) == 0x1f && qs_mtiles<17>(0, 1) == 0xf0 && qs_mtiles<17>(1, 1) == 0xf1, "");
+static_assert(qs_mtiles<16>(0, 0) == 0x0f && qs_mtiles<16>(1, 0) == 0x0f && qs_mtiles<16>(0, 1) == 0xf0 && qs_mtiles<16>(1, 1) == 0xf0, "");
 
 // Diagnostic builds only (-DQS_ABL=n, wrong results; experiments/lds_conflict_attribution.sh): 1 no slot writes, 2 no attention units,
 // 4 no output patches -- which LDS accesses the bank-conflict counter belongs to.
@@ -64,7 +109,7 @@ struct QsArgs {
   int st_np;
   float eps, out_scale;    // LayerNorm eps; 2^-(3 + k)
   _Float16* out;           // attention output, pair layout [M][2 D] of 8 o
-  int M, K, F, mtiles, D;  // tokens, GEMM depth, frames (M / 17), M-tiles (ceil(F / 15)), model width (8 heads x 64)
+  int M, K, F, mtiles, D;  // tokens, GEMM depth, frames (M / J), M-tiles (ceil(F / frames per tile)), model width (8 heads x 64)
   unsigned* range;         // the engine's range-guard word
   _Float16 *ph, *pl;       // plane-writing form only: q / k / v hi / lo planes [M][3 D]
 };
@@ -72,19 +117,27 @@ struct QsArgs {
 // One frame of one head from its LDS slot: the arithmetic of k_attn_temporal_x3p<1, 8, 3> (same MFMAs in the same order, same
 // softmax, same conversions), outputs through the wave-private patch (aliasing the slot's Q planes, dead once the query fragments
 // are in registers) as whole 128-byte lines.
+// J <= 16: every key sits in accumulator registers 0..7 (one 16-key step); registers 8..15 are pad keys in both lane halves, so the base
+// kernel's second step of O^T += V^T E carries exact zeros only (its E is exp2(-inf) = 0, its V fragments are masked to zero) and is
+// dropped, as are the zero terms of its max and its sum.  J = 15: key 15 is register 7 of lane half 1 and scores -inf.
+template <int J>
 __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Float16* out_row0, int D) {
-  constexpr int T = QS_J;
-  unsigned char* const sVh = slot + QS_PV;
-  unsigned char* const sVl = slot + QS_PV + QS_PLANE;
-  unsigned char* const sKh = slot + QS_PK;
-  unsigned char* const sKl = slot + QS_PK + QS_PLANE;
-  unsigned char* const sQh = slot + QS_PQ;
-  unsigned char* const sQl = slot + QS_PQ + QS_PLANE;
-  unsigned char* const patch = slot + QS_PQ;      // 4 KiB over the Q planes (4352 B)
+  typedef QsGeo<J> Geo;
+  constexpr int T = J;
+  constexpr int NQ = J > 16 ? 9 : 8;              // accumulator registers that hold a real key in some lane half
+  constexpr int NS2 = J > 16 ? 2 : 1;             // 16-key steps of the second product
+  constexpr int NIT = (J + 7) / 8;                // 8-row passes of the output patch that carry rows < J
+  unsigned char* const sVh = slot + Geo::PV;
+  unsigned char* const sVl = slot + Geo::PV + Geo::PLANE;
+  unsigned char* const sKh = slot + Geo::PK;
+  unsigned char* const sKl = slot + Geo::PK + Geo::PLANE;
+  unsigned char* const sQh = slot + Geo::PQ;
+  unsigned char* const sQl = slot + Geo::PQ + Geo::PLANE;
+  unsigned char* const patch = slot + Geo::PQ;    // 4 KiB over the Q planes (and, at J = 15, the slot's 256 spare bytes behind them)
   const int r = lane & 31, h = lane >> 5;
   h8 qh[4], ql[4];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {                // rows >= 17 read the planes behind: their query columns are never stored
+  for (int ks = 0; ks < 4; ++ks) {                // rows >= J read the planes behind: their query columns are never stored
     const int qo = kswz(r, 2 * ks + h);
     qh[ks] = *reinterpret_cast<const h8*>(sQh + qo);
     ql[ks] = *reinterpret_cast<const h8*>(sQl + qo);
@@ -103,10 +156,12 @@ __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Flo
   }
   // keys of accumulator register q in lane half h: (q & 3) + 8 (q >> 2) + 4 h.  With 17 keys, registers 9..15 hold pad keys in both
   // halves and register 8 (key 16 / 20) a real one in half 0 only: their numerators are exact zeros -- no exponentials, no sums
+  // (J <= 16: registers 8..15 are pad in both halves; at J = 15 register 7 of half 1 is key 15)
   float m = -INFINITY;
-  if (h != 0) sacc[8] = -INFINITY;
+  if (J == 17 && h != 0) sacc[8] = -INFINITY;
+  if (J == 15 && h != 0) sacc[7] = -INFINITY;
 #pragma unroll
-  for (int q = 0; q < 9; ++q) m = fmaxf(m, sacc[q]);
+  for (int q = 0; q < NQ; ++q) m = fmaxf(m, sacc[q]);
   m = fmaxf(m, __shfl_xor(m, 32, 64));
   constexpr float C_EXP = 1.4426950408889634f / 64.0f;
   const float mb = m * C_EXP;
@@ -114,7 +169,7 @@ __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Flo
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     float e = 0.0f;
-    if (q < 9) {
+    if (q < NQ) {
       e = __builtin_amdgcn_exp2f(fmaf(sacc[q], C_EXP, -mb));
       l += e;
     }
@@ -125,7 +180,7 @@ __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Flo
 #pragma unroll
   for (int q = 0; q < 16; ++q) { oacc[0][q] = 0.f; oacc[1][q] = 0.f; }
 #pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2) {
+  for (int s2 = 0; s2 < NS2; ++s2) {
     h8 eh, el;
     {
       if (s2 == 0) {
@@ -170,7 +225,7 @@ __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Flo
   const int tqc = r < T ? r : 0;
   // (no range tracking here: |o| = |(P - I) V| <= 2.0001 max |v|, and the slot writer raises the guard when a |v| exceeds 4090 --
   // half the plane range --, so an un-flagged run cannot overflow the output planes; 28 VALU instructions per unit less)
-  u32x4 pw[6];
+  u32x4 pw[2 * NIT];
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt) {
 #pragma unroll
@@ -203,16 +258,16 @@ __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Flo
     }
     asm volatile("" ::: "memory");     // (the rows read back were written by other lanes)
 #pragma unroll
-    for (int it = 0; it < 3; ++it) pw[dt * 3 + it] = (QS_ABL & 4) ? u32x4{0u, 0u, 0u, 0u} : patch_rd(patch, 8 * it + (lane >> 3), lane & 7);
+    for (int it = 0; it < NIT; ++it) pw[dt * NIT + it] = (QS_ABL & 4) ? u32x4{0u, 0u, 0u, 0u} : patch_rd(patch, 8 * it + (lane >> 3), lane & 7);
     asm volatile("" ::: "memory");
   }
   _Float16* const pw_ptr = out_row0 + (size_t)(lane >> 3) * 2 * D + 8 * (lane & 7);
   const size_t pw_stride = (size_t)8 * 2 * D;
 #pragma unroll
-  for (int it = 0; it < 3; ++it)
+  for (int it = 0; it < NIT; ++it)
     if (8 * it + (lane >> 3) < T) {
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt) *reinterpret_cast<u32x4*>(pw_ptr + it * pw_stride + dt * 64) = pw[dt * 3 + it];
+      for (int dt = 0; dt < 2; ++dt) *reinterpret_cast<u32x4*>(pw_ptr + it * pw_stride + dt * 64) = pw[dt * NIT + it];
     }
 }
 
@@ -220,8 +275,9 @@ __device__ __forceinline__ void qs_attention(unsigned char* slot, int lane, _Flo
 typedef float qs_f2 __attribute__((ext_vector_type(2)));
 
 // Row statistics -> (rstd * out_scale, -mean rstd) per tile row: every wave reduces 32 rows (lanes 0-31)
+template <int J>
 __device__ __forceinline__ void qs_row_stats(unsigned char* lds, const QsArgs& a, int m0, int wave, int lane, bool st_dma) {
-  float2* const srow = reinterpret_cast<float2*>(lds + QS_STX);
+  float2* const srow = reinterpret_cast<float2*>(lds + QsGeo<J>::STX);
   const int K = a.K;
   if (lane < 32) {
     const int t = wave * 32 + lane, row = m0 + t;
@@ -261,12 +317,13 @@ __device__ __forceinline__ void qs_fold_split(const f32x4& ac, qs_f2 sx, qs_f2 s
 // Everything behind the accumulators of tile (mt, hd), statistics in LDS and visible.  PLANES = false: the two passes of slot writes and
 // attention units.  PLANES = true (block 0 of the two-kernel flow): the same values as [M][3 D] hi / lo planes in HBM, what
 // launch_attn_temporal_x3 reads -- column 512 part + 64 hd + 16 wn + x of the original weight order.
-template <bool PLANES>
+template <int J, bool PLANES>
 __device__ __forceinline__ void qs_tail(f32x4 (&acc)[QF_TM][QF_NJ], unsigned char* lds, const QsArgs& a, int mt, int hd, int m0, int n0,
                                         int wave, int lane, int wm, int wn, int r16, int q) {
+  typedef QsGeo<J> Geo;
   float2 st[QF_TM];
 #pragma unroll
-  for (int i = 0; i < QF_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + QS_STX)[wm * 16 * QF_TM + 16 * i + r16];
+  for (int i = 0; i < QF_TM; ++i) st[i] = reinterpret_cast<const float2*>(lds + Geo::STX)[wm * 16 * QF_TM + 16 * i + r16];
   float4 cs4[QF_NJ], b4[QF_NJ];
 #pragma unroll
   for (int j = 0; j < QF_NJ; ++j) {
@@ -282,14 +339,23 @@ __device__ __forceinline__ void qs_tail(f32x4 (&acc)[QF_TM][QF_NJ], unsigned cha
   // (the engine zeroes the pad rows of the stream; the direct form fills them from zero inputs): nothing non-finite can reach a slot.
   typedef qs_f2 f2;
   const int chunk = 2 * wn + (q >> 1), half8 = (q & 1) << 3;            // this lane's 8 bytes: 16-byte chunk d / 8, half (d & 4)
+  constexpr unsigned MT00 = qs_mtiles<J>(0, 0), MT10 = qs_mtiles<J>(1, 0), MT01 = qs_mtiles<J>(0, 1), MT11 = qs_mtiles<J>(1, 1);   // [wm][pass]
   auto write_pass = [&](int pass) {
 #pragma unroll
     for (int i = 0; i < QF_TM; ++i) {
-      if (pass == 0 ? (i > 4) : (i < 4 && !(wm == 1 && i == 0))) continue;   // (wave-uniform: m-tiles without rows of this pass)
+      // Wave-uniform: m-tiles without rows of this pass.  Two forms of ONE rule, on purpose: the 17-joint condition is kept as it was written
+      // (qs_mtiles<17> is static_assert-ed equal to it above) because the mask form, tried at 17, moves the register allocation of the four
+      // fused 17-joint kernels (943 changed lines in the assembly of k_qkv_sattn<17>), and those kernels are to stay the code they were.
+      if (J == 17) {
+        if (pass == 0 ? (i > 4) : (i < 4 && !(wm == 1 && i == 0))) continue;
+      } else if (!(((pass == 0 ? (wm ? MT10 : MT00) : (wm ? MT11 : MT01)) >> i) & 1)) {
+        continue;
+      }
       const int R = wm * 16 * QF_TM + 16 * i + r16;
-      const int fr = (R * 241) >> 12, jr = R - fr * QS_J;               // R / 17 for R < 256
-      if (((fr >> 2) & 1) != pass || fr >= QS_FPT) continue;
-      unsigned char* const row = lds + QS_QKV + ((fr & 3) + 4 * (fr >> 3)) * QS_SLOT + jr * 128 + half8;
+      // R / J for R < 256 (qs_frame; written out at 17, where the compiler takes the pass bit straight from the product)
+      const int fr = J == 17 ? (R * 241) >> 12 : qs_frame<J>(R), jr = R - fr * J;
+      if (((fr >> 2) & 1) != pass || fr >= Geo::FPT) continue;          // (J = 15: the 16 trailing rows are frames 16 and 17)
+      unsigned char* const row = lds + QS_QKV + ((fr & 3) + 4 * (fr >> 3)) * Geo::SLOT + jr * 128 + half8;
       unsigned char* const pkq = row + ((chunk ^ ((jr >> 1) & 7)) << 4);
       unsigned char* const pv = row + ((chunk ^ vkey(jr)) << 4);
       const f2 sx = (f2)(st[i].x), sy = (f2)(st[i].y);
@@ -298,19 +364,19 @@ __device__ __forceinline__ void qs_tail(f32x4 (&acc)[QF_TM][QF_NJ], unsigned cha
         const float osc = j == 0 ? 1.0f : 8.0f;
         u32x2_alias hv, lv;
         qs_fold_split(acc[i][j], sx, sy, cs4[j], b4[j], osc, amaxj[j], hv, lv);
-        unsigned char* const ph = j == 0 ? pkq + QS_PQ : (j == 1 ? pkq + QS_PK : pv + QS_PV);
+        unsigned char* const ph = j == 0 ? pkq + Geo::PQ : (j == 1 ? pkq + Geo::PK : pv + Geo::PV);
         if (!(QS_ABL & 1)) {
           *reinterpret_cast<u32x2_alias*>(ph) = hv;
-          *reinterpret_cast<u32x2_alias*>(ph + QS_PLANE) = lv;
+          *reinterpret_cast<u32x2_alias*>(ph + Geo::PLANE) = lv;
         }
       }
     }
   };
   auto attend = [&](int pass) {
     const int fr = (wave & 3) + 4 * pass + 8 * (wave >> 2);             // frame of the tile this wave takes: slot = wave
-    const long long gf = (long long)mt * QS_FPT + fr;
-    if (!(QS_ABL & 2) && fr < QS_FPT && gf < a.F)
-      qs_attention(lds + QS_QKV + wave * QS_SLOT, lane, a.out + ((size_t)gf * QS_J) * 2 * a.D + hd * 128, a.D);
+    const long long gf = (long long)mt * Geo::FPT + fr;
+    if (!(QS_ABL & 2) && fr < Geo::FPT && gf < a.F)
+      qs_attention<J>(lds + QS_QKV + wave * Geo::SLOT, lane, a.out + ((size_t)gf * J) * 2 * a.D + hd * 128, a.D);
   };
   auto range_check = [&]() {
     float amax = 0.0f;
@@ -322,7 +388,7 @@ __device__ __forceinline__ void qs_tail(f32x4 (&acc)[QF_TM][QF_NJ], unsigned cha
 #pragma unroll
     for (int i = 0; i < QF_TM; ++i) {
       const int R = wm * 16 * QF_TM + 16 * i + r16, m = m0 + R;
-      if (R >= QS_ROWS || m >= a.M) continue;                            // (row 255 is the next tile's first)
+      if (R >= Geo::ROWS || m >= a.M) continue;                          // (rows from Geo::ROWS on are the next tile's)
       const f2 sx = (f2)(st[i].x), sy = (f2)(st[i].y);
       const size_t o = (size_t)m * 3 * a.D + hd * 64 + 16 * wn + 4 * q;
 #pragma unroll
@@ -347,7 +413,9 @@ __device__ __forceinline__ void qs_tail(f32x4 (&acc)[QF_TM][QF_NJ], unsigned cha
   attend(1);
 }
 
+template <int J>
 __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
+  constexpr int QS_ROWS = QsGeo<J>::ROWS;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int G = (int)gridDim.x, b = (int)blockIdx.x;
   const int tiles = a.mtiles * 8;
@@ -395,7 +463,7 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
       }
     }
 
-    // ---- DMA plan (kloop_common.h KL_DMA_PLAN; a tile stages 256 rows from row 255 mt on), accumulators, fragment offsets
+    // ---- DMA plan (kloop_common.h KL_DMA_PLAN; a tile stages 256 rows from row QS_ROWS mt on), accumulators, fragment offsets
     QF_TILE_PLAN(a.Ap, a.Wp, m0, n0, mtn * QS_ROWS, hdn * QF_BN);
     QF_TILE_ACC;
     int issued_prev = st_issued;
@@ -403,13 +471,13 @@ __global__ __launch_bounds__(512) void k_qkv_sattn(QsArgs a) {
     // ---- row statistics -> (rstd * out_scale, -mean rstd) per tile row, in front of the last k-tile: every wave reduces 32 rows (lanes
     // 0-31) in the shadow of its SIMD partner's MFMAs -- behind the k-loop this step was 1.1 us of a 38 us tile with half the waves
     // idle.  The raw partials landed long ago (the first counted wait of the tile retired them; phase barriers since).
-    qs_row_stats(lds, a, m0, wave, lane, st_dma);
+    qs_row_stats<J>(lds, a, m0, wave, lane, st_dma);
     QF_KLOOP_TAIL(QF_PIECE)
     __builtin_amdgcn_s_setprio(0);
 
     __syncthreads();   // statistics visible; every wave is out of the k-loop: stage 1 and the LDS behind it become the frame slots
 
-    qs_tail<false>(acc, lds, a, mt, hd, m0, n0, wave, lane, wm, wn, r16, q);
+    qs_tail<J, false>(acc, lds, a, mt, hd, m0, n0, wave, lane, wm, wn, r16, q);
     mt = mtn; hd = hdn;
     __syncthreads();   // the slots are read before the next tile's statistics block and second k-tile are staged over them
   }
@@ -433,25 +501,31 @@ struct QdSrc {
 };
 // LDS, in the stage area the k-loop form fills with operands: the head's 192 columns of G, P and of the Q rows of the tile's batch elements
 constexpr int QD_GROW = 8;                                               // G: 192 rows of 8 floats (CIN used)
-constexpr int QD_QSLOTS = 16;                                            // 256 rows hold at most 16 frames, so at most 16 batch elements
-constexpr int QD_G = 0, QD_P = QD_G + QF_BN * QD_GROW * 4, QD_Q = QD_P + QS_J * QF_BN * 4;
-static_assert(QD_Q + QD_QSLOTS * QF_BN * 4 <= QS_QKV, "the direct form's tables fit the unused stage area");
-static_assert(QF_BM <= QD_QSLOTS * QS_J, "a tile's rows span at most QD_QSLOTS frames, so at most QD_QSLOTS batch elements");
+// A tile's REAL rows (QsGeo::ROWS = 16 J at most) span at most 16 frames, so at most 16 batch elements: one Q slot each.  (At J = 15 the
+// 16 trailing rows may belong to a seventeenth batch element: it has no slot, qd_fill clamps their lookup and nothing reads the result.)
+constexpr int QD_QSLOTS = 16;
+constexpr int QD_G = 0, QD_P = QD_G + QF_BN * QD_GROW * 4;               // P: J x 192 floats, then the Q slots
+template <int J>
+struct QdGeo {
+  static constexpr int Q = QD_P + J * QF_BN * 4;
+  static_assert(Q + QD_QSLOTS * QF_BN * 4 <= QS_QKV, "the direct form's tables fit the unused stage area");
+  static_assert(QsGeo<J>::ROWS <= QD_QSLOTS * J, "a tile's real rows span at most QD_QSLOTS frames, so at most QD_QSLOTS batch elements");
+};
 
 // tile column c = 48 wn + 16 part + x of head hd in the original column order of the qkv weight
 __device__ __forceinline__ int qd_col(int c, int hd) { return 512 * ((c % 48) >> 4) + 64 * hd + 16 * (c / 48) + (c & 15); }
 
-template <int CIN2>
+template <int J, int CIN2>
 __device__ __forceinline__ void qd_stage(unsigned char* lds, const QdSrc& d, int M, int m0, int hd, int tid) {
   constexpr int CIN = CIN2 + 3;
   float* const sG = reinterpret_cast<float*>(lds + QD_G);
   float* const sP = reinterpret_cast<float*>(lds + QD_P);
-  float* const sQ = reinterpret_cast<float*>(lds + QD_Q);
+  float* const sQ = reinterpret_cast<float*>(lds + QdGeo<J>::Q);
   for (int idx = tid; idx < QF_BN * CIN; idx += 512) {                  // (the head's rows of G are one contiguous block)
     const int c = idx / CIN, k = idx - c * CIN;
     sG[c * QD_GROW + k] = d.G[QF_BN * CIN * hd + idx];
   }
-  for (int idx = tid; idx < QS_J * QF_BN; idx += 512) {
+  for (int idx = tid; idx < J * QF_BN; idx += 512) {
     const int j = idx / QF_BN, c = idx - j * QF_BN;
     sP[idx] = d.P[j * 1536 + QF_BN * hd + c];
   }
@@ -466,7 +540,7 @@ __device__ __forceinline__ void qd_stage(unsigned char* lds, const QdSrc& d, int
 
 // The accumulators of tile row m0 .. and head hd, tables staged and visible.  The scheduling fences keep one column's G row / one row's P
 // and Q values in flight at a time: hoisted together they would not fit the registers beside 96 accumulators and the 8 x CIN inputs.
-template <int CIN2>
+template <int J, int CIN2>
 __device__ __forceinline__ void qd_fill(f32x4 (&acc)[QF_TM][QF_NJ], const unsigned char* lds, const QdSrc& d, int M, int m0, int wm, int wn,
                                         int r16, int q) {
   constexpr int CIN = CIN2 + 3;
@@ -474,18 +548,18 @@ __device__ __forceinline__ void qd_fill(f32x4 (&acc)[QF_TM][QF_NJ], const unsign
   const int b_lo = m0 / d.TJ;
   const float* const sG = reinterpret_cast<const float*>(lds + QD_G);
   const float* const sP = reinterpret_cast<const float*>(lds + QD_P);
-  const float* const sQ = reinterpret_cast<const float*>(lds + QD_Q);
+  const float* const sQ = reinterpret_cast<const float*>(lds + QdGeo<J>::Q);
   float u[QF_TM][CIN];
 #pragma unroll
   for (int ii = 0; ii < QF_TM; ++ii) {
     const int R = wm * 16 * QF_TM + 16 * ii + r16, m = m0 + R;
-    const int fr = (R * 241) >> 12, jr = R - fr * QS_J;                // R / 17 for R < 256; jr = m % 17: a tile starts on a frame
+    const int fr = qs_frame<J>(R), jr = R - fr * J;                    // R / J for R < 256; jr = m % J: a tile starts on a frame
 #pragma unroll
     for (int k = 0; k < CIN; ++k) u[ii][k] = 0.0f;                     // rows beyond the matrix: zero inputs
     if (m < M) {
 #pragma unroll
       for (int k = 0; k < CIN2; ++k) u[ii][k] = d.x2d[(size_t)m * CIN2 + k];
-      const size_t my = d.y_bcast_T ? ((size_t)(m / d.TJ) * QS_J + jr) : (size_t)m;
+      const size_t my = d.y_bcast_T ? ((size_t)(m / d.TJ) * J + jr) : (size_t)m;
 #pragma unroll
       for (int k = 0; k < 3; ++k) u[ii][CIN2 + k] = d.y[my * 3 + k];
     }
@@ -510,7 +584,7 @@ __device__ __forceinline__ void qd_fill(f32x4 (&acc)[QF_TM][QF_NJ], const unsign
 #pragma unroll
   for (int i = 0; i < QF_TM; ++i) {   // (the row's offsets are formed again here: kept from the loop above they cost 16 registers)
     const int R = wm * 16 * QF_TM + 16 * i + r16, m = m0 + R;
-    const int po = (R - ((R * 241) >> 12) * QS_J) * QF_BN + c0;
+    const int po = (R - qs_frame<J>(R) * J) * QF_BN + c0;
     const int qo = c0 + (d.q_stride ? min(m / d.TJ - b_lo, QD_QSLOTS - 1) * QF_BN : 0);
     if (m < M) {   // rows beyond the matrix keep 0, what the k-loop form makes of the zeroed pad rows of the stream
 #pragma unroll
@@ -530,8 +604,9 @@ __device__ __forceinline__ void qd_fill(f32x4 (&acc)[QF_TM][QF_NJ], const unsign
   }
 }
 
-template <int CIN2, bool PLANES>
+template <int J, int CIN2, bool PLANES>
 __global__ __launch_bounds__(512) void k_qkv_sattn_direct(QsArgs a, QdSrc d) {
+  constexpr int QS_ROWS = QsGeo<J>::ROWS;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int G = (int)gridDim.x, b = (int)blockIdx.x;
   const int tiles = a.mtiles * 8;
@@ -545,22 +620,26 @@ __global__ __launch_bounds__(512) void k_qkv_sattn_direct(QsArgs a, QdSrc d) {
     tile_of(item * G + b, mt, hd);
     const int m0 = mt * QS_ROWS, n0 = hd * QF_BN;
     // the head's columns of G, P and Q into the (otherwise unused) stage area, the row statistics from HBM
-    qd_stage<CIN2>(lds, d, a.M, m0, hd, tid);
-    qs_row_stats(lds, a, m0, wave, lane, false);
+    qd_stage<J, CIN2>(lds, d, a.M, m0, hd, tid);
+    qs_row_stats<J>(lds, a, m0, wave, lane, false);
     __syncthreads();
     f32x4 acc[QF_TM][QF_NJ];
-    qd_fill<CIN2>(acc, lds, d, a.M, m0, wm, wn, r16, q);
+    qd_fill<J, CIN2>(acc, lds, d, a.M, m0, wm, wn, r16, q);
     __builtin_amdgcn_sched_barrier(0);
-    qs_tail<PLANES>(acc, lds, a, mt, hd, m0, n0, wave, lane, wm, wn, r16, q);
+    qs_tail<J, PLANES>(acc, lds, a, mt, hd, m0, n0, wave, lane, wm, wn, r16, q);
     __syncthreads();   // the slots, the tables and the statistics are read before the next tile's are staged over them
   }
 }
 
+// whole frames per tile of joint count J (qkv_sattn_ok holds)
+int qs_frames_per_tile(int J) { return J == 17 ? QsGeo<17>::FPT : QsGeo<16>::FPT; }
+
 }  // namespace
 
-bool qkv_sattn_ok(int J, int D, int H, int K) { return J == QS_J && H == 8 && D == 512 && K % 64 == 0 && K >= 128; }
+bool qkv_sattn_ok(int J, int D, int H, int K) { return J >= 15 && J <= 17 && H == 8 && D == 512 && K % 64 == 0 && K >= 128; }
 
-// Tokens M = frames * 17; A / st_in must span 255 * ceil(frames / 15) + 1 rows (the engine's workspace does).
+// Tokens M = frames * J; A / st_in must span the rows the last tile stages -- 255 ceil(frames / 15) + 1 at J = 17, 240 ceil(frames / 16)
+// + 16 at J = 15, 256 ceil(frames / 16) at J = 16 (the engine's workspace does).
 hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, const float* bias_hm, const float* csum_hm, const float* st_in,
                             int st_np, float eps, int w_exp, void* out_x3, int M, int K, int J, int D, int H, hipStream_t s) {
   if (!qkv_sattn_ok(J, D, H, K) || M <= 0 || M % J != 0 || st_np < 1 || !Apair || !Wpair_headmajor || !bias_hm || !csum_hm || !st_in || !out_x3)
@@ -569,11 +648,17 @@ hipError_t launch_qkv_sattn(const void* Apair, const void* Wpair_headmajor, cons
   QsArgs a{};
   a.Ap = (const _Float16*)Apair; a.Wp = (const _Float16*)Wpair_headmajor; a.bias = bias_hm; a.csum = csum_hm; a.st_in = st_in;
   a.st_np = st_np; a.eps = eps; a.out_scale = ldexpf(1.0f, -(3 + w_exp));
-  a.out = (_Float16*)out_x3; a.M = M; a.K = K; a.F = M / J; a.mtiles = (a.F + QS_FPT - 1) / QS_FPT; a.D = D;
+  const int fpt = qs_frames_per_tile(J);
+  a.out = (_Float16*)out_x3; a.M = M; a.K = K; a.F = M / J; a.mtiles = (a.F + fpt - 1) / fpt; a.D = D;
   a.range = launch_range_word();
   int grid = 0;
   if (hipError_t ge = persistent_grid((long long)a.mtiles * 8, grid)) return ge;
-  return launch_lds<k_qkv_sattn>(dim3(grid), dim3(512), QS_LDS, s, a);
+  switch (J) {
+    case 15: return launch_lds<k_qkv_sattn<15>>(dim3(grid), dim3(512), QsGeo<15>::LDS, s, a);
+    case 16: return launch_lds<k_qkv_sattn<16>>(dim3(grid), dim3(512), QsGeo<16>::LDS, s, a);
+    case 17: return launch_lds<k_qkv_sattn<17>>(dim3(grid), dim3(512), QsGeo<17>::LDS, s, a);
+  }
+  return hipErrorInvalidValue;
 }
 
 // in_chans 4 and 5 (8 x 7 / 8 x 8 input registers beside the 96 accumulators) do not fit the 256 VGPRs of two waves per SIMD without
@@ -590,19 +675,22 @@ hipError_t launch_qkv_sattn_direct(const float* x2d, const float* y, int y_bcast
     return hipErrorInvalidValue;
   QsArgs a{};
   a.bias = bias_hm; a.csum = csum_hm; a.st_in = st_in; a.st_np = st_np; a.eps = eps; a.out_scale = 1.0f;
-  a.out = (_Float16*)out_x3; a.M = M; a.K = D; a.F = M / J; a.mtiles = (a.F + QS_FPT - 1) / QS_FPT; a.D = D;
+  const int fpt = qs_frames_per_tile(J);
+  a.out = (_Float16*)out_x3; a.M = M; a.K = D; a.F = M / J; a.mtiles = (a.F + fpt - 1) / fpt; a.D = D;
   a.ph = (_Float16*)planes_hi; a.pl = (_Float16*)planes_lo;
   a.range = launch_range_word();
   QdSrc d{};
   d.x2d = x2d; d.y = y; d.G = G; d.P = P; d.Q = Q; d.q_stride = q_stride; d.TJ = T * J; d.y_bcast_T = y_bcast_T;
   int grid = 0;
   if (hipError_t ge = persistent_grid((long long)a.mtiles * 8, grid)) return ge;
-#define D3D_QD(C2)                                                                                                      \
-  case C2:                                                                                                              \
-    return out_x3 ? launch_lds<k_qkv_sattn_direct<C2, false>>(dim3(grid), dim3(512), QS_LDS, s, a, d)                   \
-                  : launch_lds<k_qkv_sattn_direct<C2, true>>(dim3(grid), dim3(512), QS_LDS, s, a, d);
-  switch (in_chans) {
-    D3D_QD(1) D3D_QD(2) D3D_QD(3)
+#define D3D_QD(JJ, C2)                                                                                                  \
+  case 4 * JJ + C2:                                                                                                     \
+    return out_x3 ? launch_lds<k_qkv_sattn_direct<JJ, C2, false>>(dim3(grid), dim3(512), QsGeo<JJ>::LDS, s, a, d)       \
+                  : launch_lds<k_qkv_sattn_direct<JJ, C2, true>>(dim3(grid), dim3(512), QsGeo<JJ>::LDS, s, a, d);
+  switch (4 * J + in_chans) {
+    D3D_QD(15, 1) D3D_QD(15, 2) D3D_QD(15, 3)
+    D3D_QD(16, 1) D3D_QD(16, 2) D3D_QD(16, 3)
+    D3D_QD(17, 1) D3D_QD(17, 2) D3D_QD(17, 3)
   }
 #undef D3D_QD
   return hipErrorInvalidValue;

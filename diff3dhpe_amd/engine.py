@@ -221,7 +221,8 @@ class Engine:
     @_locked
     def info(self, key: str) -> int:
         """Read-only engine facts (include/d3d.h d3d_engine_get_info): "graphs_cached", "graphs_captured", "streams", "device",
-        "latency_mode", "fc2_split_last", "proj_split_last", "fc1_split_last", "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the most recent forward of a
+        "latency_mode", "fc2_split_last", "proj_split_last", "fc1_split_last", "fused_spatial_last" (1 when the spatial blocks of the most recent forward of an
+        F16X3 engine ran the fused qkv + attention kernel: 15, 16 or 17 joints with the option on), "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the most recent forward of a
         bf16 engine ran the fused qkv + attention kernel in its spatial / temporal blocks), "block0_direct_last" (1 when block 0 of the most recent
         forward computed q / k / v from the raw input channels instead of the qkv GEMM), "long_temporal" (the option), "long_temporal_last"
         (1 when the temporal blocks of the most recent forward ran the key-streaming F16X3 attention kernel: num_frame > 256 with the

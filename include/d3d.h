@@ -146,9 +146,11 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  * used by the A/B scripts under experiments/ and by tests that exercise the alternative flows):
  *   "fused_postnorm"  1 (default) / 0: F16X3 block flow with the block's post-norm inside the fc2 GEMM epilogue / as a row kernel
  *   "fold_layernorm"  1 (default) / 0: F16X3 flow with norm1 / norm2 folded into the qkv / fc1 GEMMs / as row kernels
- *   "fused_spatial"   1 (default) / 0: F16X3 flow, spatial blocks (17 joints of a frame, D = 512, 8 heads): the qkv GEMM of a group
- *                     of 15 frames keeps q / k / v in LDS and runs the frames' attention in the same kernel (S2S:67 + 73-83; the
- *                     q / k / v planes never go to HBM) / qkv GEMM and attention as two kernels.  Bit-identical either way.
+ *   "fused_spatial"   1 (default) / 0: F16X3 flow, spatial blocks (15, 16 or 17 joints of a frame, D = 512, 8 heads): the qkv GEMM of a
+ *                     group of 15 frames (17 joints; 16 frames of 15 or 16 joints) keeps q / k / v in LDS and runs the frames' attention in
+ *                     the same kernel (S2S:67 + 73-83; the q / k / v planes never go to HBM) / qkv GEMM and attention as two kernels.
+ *                     Bit-identical either way.  Other joint counts keep the two kernels whatever the key says.  "fused_spatial_last"
+ *                     (d3d_engine_get_info) reports what the latest forward ran.
  *   "fused_temporal"  1 (default) / 0: the same for the temporal blocks where the frames of a joint fit one 256-row tile (193 <= T <= 255,
  *                     D = 512, 8 heads): the qkv GEMM of one (batch, joint) group keeps K / V in LDS, exchanges the queries there and runs
  *                     the group's T-key attention in the same kernel (S2S:67 + 73-83 for the per-joint groups) / two kernels.  Bit-identical.
@@ -162,7 +164,7 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     the keys say.  Bit-identical either way, for every T, non-finite activations included (a group's pad keys are
  *                     masked to zeros in registers: a sequence's result depends on its own rows only).  "bf16_fused_spatial_last" / "bf16_fused_temporal_last"
  *                     (d3d_engine_get_info) report what the latest forward ran.
- *   "block0_direct"   1 (default) / 0: F16X3 folded flow, block 0 (D = 512, 17 joints, 8 heads, in_chans <= 3): its input rows are W_e u + b_e + spos[j] + tv[b]
+ *   "block0_direct"   1 (default) / 0: F16X3 folded flow, block 0 (D = 512, 15, 16 or 17 joints, 8 heads, in_chans <= 3): its input rows are W_e u + b_e + spos[j] + tv[b]
  *                     with u the in_chans + 3 raw channels of a token, so q / k / v follow from commit-time tables (G = Wg W_e, P[j] =
  *                     Wg (b_e + spos[j]), fp64 sums stored as fp32) and one time row per forward (Q = Wg tv, in the caller's workspace) with
  *                     in_chans + 3 fmas and two adds per value: block 0 runs no qkv GEMM / 0: the K = 512 GEMM like every other block.
@@ -258,6 +260,9 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * "streams", "device", "latency_mode", "fc2_split_last" (the k-split S of fc2 + post-norm in the most recent d3d_denoise /
  * d3d_ddim_sample call, 0 when the default whole-row kernel ran; a sampling run as two half-batches reports the first half's),
  * "proj_split_last" / "fc1_split_last" (the same for proj and fc1), "proj_split" / "fc1_split" (the option values),
+ * "fused_spatial_last" (1 when the spatial blocks of the most recent d3d_denoise / d3d_ddim_sample call of a D3D_PREC_F16X3 engine ran
+ * the fused qkv + attention kernel -- option "fused_spatial", 15, 16 or 17 joints --, else 0: option off, another joint count, another
+ * precision, or before any forward),
  * "bf16_fused_spatial_last" / "bf16_fused_temporal_last" (1 when the spatial / temporal blocks of the most recent d3d_denoise /
  * d3d_ddim_sample call of a D3D_PREC_BF16 engine ran the fused qkv + attention kernel, else 0; 0 before the first call and in the
  * other precisions), "block0_direct_last" (1 when block 0 of the most recent d3d_denoise / d3d_ddim_sample call computed q / k / v from
@@ -336,7 +341,7 @@ int d3d_window_gather_s2f(const float* seq_dev, int32_t n_frames, int32_t T, int
 #define D3D_KC_LINEAR_PROJ 8
 #define D3D_KC_LINEAR_FC1 9
 #define D3D_KC_LINEAR_FC2 10
-/* spatial blocks of the F16X3 flow: the LayerNorm-folded qkv GEMM and the 17-key attention as ONE kernel ("fused_spatial"); its
+/* spatial blocks of the F16X3 flow: the LayerNorm-folded qkv GEMM and the 15- / 16- / 17-key attention as ONE kernel ("fused_spatial"); its
  * launches are counted here only (neither under D3D_KC_LINEAR nor D3D_KC_ATTN_SPATIAL) */
 #define D3D_KC_QKV_SATTN 11
 /* temporal blocks likewise ("fused_temporal": the qkv GEMM of one (batch, joint) group and its T-key attention as ONE kernel); counted
