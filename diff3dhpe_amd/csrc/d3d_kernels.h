@@ -7,6 +7,8 @@
 
 #include <atomic>
 
+#include "weight_pack.h"   // split_weight_f16x3() and the rest of the host-side weight packing
+
 namespace d3d {
 
 // ---- per-device launch state ----------------------------------------------------------------------------------------
@@ -125,9 +127,6 @@ hipError_t launch_linear_f32(const float* A, const float* W, const float* bias, 
 // split_weight_f16x3() ([rows][2*cols] fp16 of 4096*w: this form takes k = 12 only).
 hipError_t launch_linear_f16x3(const float* A, const void* Wpair, const float* bias, const float* R, float* C, int M, int N,
                                int K, int epi, hipStream_t s);
-// Planes of 2^k * w, k chosen per matrix: 12 whenever |w| <= 15.99 everywhere, smaller for larger weights (LayerNorm-folded
-// weights of checkpoints with big gains).  Returns k (the GEMM's w_exp argument); *clamped is set when an entry is not finite.
-int split_weight_f16x3(const float* w, size_t rows, size_t cols, uint16_t* pair, bool acc_order = false, bool* clamped = nullptr);
 
 // ---- kernels_gemm_x3p.hip ---------------------------------------------------------------------------------------
 // F16X3 with pre-split operands in the pair layout: A (>= ceil(M/256)*256 rows allocated), W (>= ceil(N/256)*256 rows).

@@ -39,17 +39,14 @@ struct WeightSlot {
   size_t dev_off = 0;  // float offset into the device arena
 };
 
-struct BlockW {
-  const float *n1g, *n1b, *qkvw, *qkvb, *projw, *projb, *n2g, *n2b, *fc1w, *fc1b, *fc2w, *fc2b;
+struct BlockW : BlockSrc {   // (the block's fp32 tensors, here in the device arena)
   // F16X3 mode: fp16 hi/lo planes of the four GEMM weights (same [N][K] layout)
   const uint16_t *qkv_x3 = nullptr, *proj_x3 = nullptr, *fc1_x3 = nullptr, *fc2_x3 = nullptr;   // F16X3 pair layout
-  // LayerNorm-folded forms (X3Fold, d3d_kernels.h): W diag(gamma) in the pair layout, csum[n] = sum_k W[n,k] gamma[k],
-  // b'[n] = b[n] + sum_k W[n,k] beta[k], for norm1 -> qkv and norm2 -> fc1
+  // LayerNorm-folded forms (X3Fold, d3d_kernels.h; fold_layernorm, weight_pack.h) for norm1 -> qkv and norm2 -> fc1
   const uint16_t *qkv_f3 = nullptr, *fc1_f3 = nullptr;
   const float *qkv_cs = nullptr, *qkv_fb = nullptr, *fc1_cs = nullptr, *fc1_fb = nullptr;
-  // spatial blocks, fused qkv + attention kernel (kernels_qkv_sattn.hip): the folded qkv weight / csum / bias with HEAD-MAJOR rows
-  // (row 192 h + 48 wn + 16 part + x = original row 512 part + 64 h + 16 wn + x), so that one head's q, k, v are one contiguous
-  // N-tile and accumulator column tile j of every wave is part j
+  // fused qkv + attention kernels (kernels_qkv_sattn.hip, kernels_qkv_tattn.hip): the folded qkv weight / csum / bias with HEAD-MAJOR
+  // rows (tile_order_src_row, weight_pack.h)
   const uint16_t* qkv_f3h = nullptr;
   const float *qkv_csh = nullptr, *qkv_fbh = nullptr;
   // exponent k of each weight's planes (2^k w; 12 unless a weight exceeds 15.99: split_weight_f16x3)
@@ -106,7 +103,8 @@ struct d3d_engine {
   // its tables, resident like the weights (one allocation): Wg = W_qkv diag(gamma1) of block 0 as fp32 [3 D][D] (the weight of the per-forward
   // small linear that makes Q from the time vector, original row order), G = Wg W_e [3 D][CIN] and P[j] = Wg (b_e + spos[j]) [J][3 D] in the
   // head-major tile order of qkv_f3h / qkv_csh / qkv_fbh, so a tile's slices are contiguous
-  float *b0_tab = nullptr, *b0_wg = nullptr, *b0_G = nullptr, *b0_P = nullptr;
+  DevBuf<float> b0_tab;
+  const float *b0_wg = nullptr, *b0_G = nullptr, *b0_P = nullptr;
   // "fc1_kernel": fc1 on its own kernel (kernels_fc1_x3.hip) where the launch fills the chip for a few rounds; bit-identical
   bool opt_fc1_kernel = true;
   // "proj_kernel": the same for proj (kernels_proj_x3.hip: whole 192-row tiles; the rows behind the last whole tile stay with the template)
@@ -145,10 +143,7 @@ struct d3d_engine {
   // fc1's partials (S M Dm floats) fit no region of the workspace that is dead at that point for every S: an engine-owned buffer,
   // FC1_SPLITK_SCRATCH_FLOATS per slot, allocated when "latency_mode" is switched on and freed when it is switched off.  Slot 1 serves
   // the second half-batch of a two-stream sampling (the halves run concurrently), allocated by the first such call.
-  float* lat_scratch[2] = {nullptr, nullptr};
-  void free_lat_scratch() {
-    for (auto& p : lat_scratch) { if (p) (void)hipFree(p); p = nullptr; }
-  }
+  DevBuf<float> lat_scratch[2];
   // the plan of the most recent forward (of a two-stream sampling: of the first half-batch, the one that holds sequence 0); all zero
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
@@ -158,7 +153,7 @@ struct d3d_engine {
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int device = -1;                // ordinal of the device the weights were committed on
-  unsigned* range_dev = nullptr;  // F16X3 range guard: THIS engine's sticky word (device memory; every plane-writing kernel launched
+  DevBuf<unsigned> range_dev;     // F16X3 range guard: THIS engine's sticky word (device memory; every plane-writing kernel launched
                                   // for this engine ORs into it -- d3d_kernels.h LaunchCtx::range_word)
   // d3d_engine_range_post / _take: snapshots of the word without a blocking synchronisation -- a ring of pinned, device-mapped host
   // slots (one per ticket), each with the event recorded behind its snapshot kernel
@@ -168,18 +163,17 @@ struct d3d_engine {
   std::vector<hipEvent_t> range_ev;
   long long range_posted = 0;          // tickets handed out so far (ticket t lives in slot t % RANGE_TICKETS)
 
-  float* arena = nullptr;  // all weights, device
-  size_t arena_floats = 0;
-  uint16_t* arena16 = nullptr;  // F16X3: hi/lo planes of the GEMM weights
-  float* arena_fold = nullptr;  // F16X3: csum / folded bias vectors of the LN-folded GEMMs
+  DevBuf<float> arena;  // all weights, device
+  DevBuf<uint16_t> arena16;  // F16X3: hi/lo planes of the GEMM weights (BF16: their bf16 copies)
+  DevBuf<float> arena_fold;  // F16X3: csum / folded bias vectors of the LN-folded GEMMs
   std::vector<BlockW> blk;  // execution order: STE0, TTE0, STE1, ...
   const float *fus_w = nullptr, *fus_b = nullptr, *spos = nullptr, *tpos = nullptr;
   const float *sn_g = nullptr, *sn_b = nullptr, *tn_g = nullptr, *tn_b = nullptr;
   const float *hd_g = nullptr, *hd_b = nullptr, *hd_w = nullptr, *hd_bias = nullptr;
   const float *tm1_w = nullptr, *tm1_b = nullptr, *tm3_w = nullptr, *tm3_b = nullptr;
   const float *wm_w = nullptr, *wm_b = nullptr;
-  float *tblk_w = nullptr, *tblk_b = nullptr;  // concatenated per-block time projections (nblk*D, Dt), (nblk*D)
-  float* freqs_dev = nullptr;
+  DevBuf<float> tblk_w, tblk_b;  // concatenated per-block time projections (nblk*D, Dt), (nblk*D)
+  DevBuf<float> freqs_dev;
 
   // schedule
   bool sched_set = false;
@@ -187,8 +181,8 @@ struct d3d_engine {
   float eta = 0.f;
   std::vector<float> ac, somac;
   std::vector<int32_t> times;  // S+1, reversed
-  float *ac_dev = nullptr, *somac_dev = nullptr, *sqrt_ac_dev = nullptr;
-  float* temb_sched = nullptr;  // (S, nblk, D)
+  DevBuf<float> ac_dev, somac_dev, sqrt_ac_dev;
+  DevBuf<float> temb_sched;  // (S, nblk, D)
   bool has_sqrt_ac = false;
 
   // hipGraph replay of the whole S-step loop (d3d_engine_set_graph_mode): one captured graph per (B, workspace)
@@ -214,15 +208,12 @@ struct d3d_engine {
 
   // debug trace (d3d_engine_set_trace): one checksum per buffer a kernel of the F16X3 block flow has just written
   bool tracing = false;
-  unsigned long long* trace_dev = nullptr;
+  DevBuf<unsigned long long> trace_dev;
   int trace_cap = 0, trace_n = 0, trace_fwd = 0, trace_views = 1;
   std::vector<uint32_t> trace_tags;
 
-  ~d3d_engine() {
+  ~d3d_engine() {   // what is not device memory (the DevBuf members free that)
     drop_graphs();
-    free_lat_scratch();
-    (void)hipFree(trace_dev);
-    (void)hipFree(range_dev);
     if (range_host) (void)hipHostFree(range_host);
     for (auto ev : range_ev) (void)hipEventDestroy(ev);
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
@@ -231,9 +222,6 @@ struct d3d_engine {
     if (ev_join) (void)hipEventDestroy(ev_join);
     for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto ev : ev_pool) (void)hipEventDestroy(ev);
-    (void)hipFree(b0_tab);
-    (void)hipFree(arena); (void)hipFree(arena16); (void)hipFree(arena_fold); (void)hipFree(tblk_w); (void)hipFree(tblk_b); (void)hipFree(freqs_dev);
-    (void)hipFree(ac_dev); (void)hipFree(somac_dev); (void)hipFree(sqrt_ac_dev); (void)hipFree(temb_sched);
   }
 };
 
@@ -251,61 +239,36 @@ struct RangeScope {
   ~RangeScope() { tl_launch_ctx.range_word = saved; tl_launch_ctx.deep_stages = saved_deep; }
 };
 
-void add_slot(d3d_engine* e, const std::string& name, int64_t numel) {
-  WeightSlot s;
-  s.name = name;
-  s.numel = numel;
-  e->index[name] = (int)e->slots.size();
-  e->slots.push_back(std::move(s));
+// registers the tensors of `list` (name suffix, element count) that exist in this model: a count of 0 = not a parameter of it
+void add_slots(d3d_engine* e, const std::string& prefix, std::initializer_list<std::pair<const char*, int64_t>> list) {
+  for (const auto& t : list) {
+    if (!t.second) continue;
+    WeightSlot s;
+    s.name = prefix + t.first;
+    s.numel = t.second;
+    e->index[s.name] = (int)e->slots.size();
+    e->slots.push_back(std::move(s));
+  }
 }
 
 void add_block_slots(d3d_engine* e, const std::string& p) {
-  const int64_t D = e->D, Dm = e->Dm, Dt = e->Dt;
-  add_slot(e, p + ".norm1.weight", D);
-  add_slot(e, p + ".norm1.bias", D);
-  add_slot(e, p + ".attn.qkv.weight", 3 * D * D);
-  add_slot(e, p + ".attn.qkv.bias", 3 * D);
-  add_slot(e, p + ".attn.proj.weight", D * D);
-  add_slot(e, p + ".attn.proj.bias", D);
-  add_slot(e, p + ".norm2.weight", D);
-  add_slot(e, p + ".norm2.bias", D);
-  if (Dt) {
-    add_slot(e, p + ".time_mlp.1.weight", D * Dt);
-    add_slot(e, p + ".time_mlp.1.bias", D);
-  }
-  add_slot(e, p + ".mlp.fc1.weight", Dm * D);
-  add_slot(e, p + ".mlp.fc1.bias", Dm);
-  add_slot(e, p + ".mlp.fc2.weight", D * Dm);
-  add_slot(e, p + ".mlp.fc2.bias", D);
+  const int64_t D = e->D, Dm = e->Dm, Dt = e->Dt;   // (time_mlp only with_time_emb: Dt != 0)
+  add_slots(e, p, {{".norm1.weight", D}, {".norm1.bias", D}, {".attn.qkv.weight", 3 * D * D}, {".attn.qkv.bias", 3 * D},
+                   {".attn.proj.weight", D * D}, {".attn.proj.bias", D}, {".norm2.weight", D}, {".norm2.bias", D},
+                   {".time_mlp.1.weight", D * Dt}, {".time_mlp.1.bias", Dt ? D : 0}, {".mlp.fc1.weight", Dm * D}, {".mlp.fc1.bias", Dm},
+                   {".mlp.fc2.weight", D * Dm}, {".mlp.fc2.bias", D}});
 }
 
 // Parameter inventory in the reference's registration order (S2S:160-220, S2F:216-218); mirrors diff3dhpe_amd/spec.py.
 void build_slots(d3d_engine* e) {
-  const int64_t D = e->D, Dt = e->Dt, T = e->T, J = e->J;
-  if (Dt) {
-    add_slot(e, "time_mlp.1.weight", Dt * D);
-    add_slot(e, "time_mlp.1.bias", Dt);
-    add_slot(e, "time_mlp.3.weight", Dt * Dt);
-    add_slot(e, "time_mlp.3.bias", Dt);
-  }
-  add_slot(e, "fusion_layer.weight", D * e->cin);
-  add_slot(e, "fusion_layer.bias", D);
-  add_slot(e, "Spatial_pos_embed", J * D);
+  const int64_t D = e->D, Dt = e->Dt, T = e->T, J = e->J, s2f = e->cfg.seq2frame ? 1 : 0;
+  add_slots(e, "", {{"time_mlp.1.weight", Dt * D}, {"time_mlp.1.bias", Dt}, {"time_mlp.3.weight", Dt * Dt}, {"time_mlp.3.bias", Dt},
+                    {"fusion_layer.weight", D * e->cin}, {"fusion_layer.bias", D}, {"Spatial_pos_embed", J * D}});
   for (int i = 0; i < e->depth; ++i) add_block_slots(e, "STEblocks." + std::to_string(i));
-  add_slot(e, "Spatial_norm.weight", D);
-  add_slot(e, "Spatial_norm.bias", D);
-  add_slot(e, "Temporal_pos_embed", T * D);
+  add_slots(e, "", {{"Spatial_norm.weight", D}, {"Spatial_norm.bias", D}, {"Temporal_pos_embed", T * D}});
   for (int i = 0; i < e->depth; ++i) add_block_slots(e, "TTEblocks." + std::to_string(i));
-  add_slot(e, "Temporal_norm.weight", D);
-  add_slot(e, "Temporal_norm.bias", D);
-  add_slot(e, "head.0.weight", D);
-  add_slot(e, "head.0.bias", D);
-  add_slot(e, "head.1.weight", 3 * D);
-  add_slot(e, "head.1.bias", 3);
-  if (e->cfg.seq2frame) {
-    add_slot(e, "weighted_mean.weight", T);
-    add_slot(e, "weighted_mean.bias", 1);
-  }
+  add_slots(e, "", {{"Temporal_norm.weight", D}, {"Temporal_norm.bias", D}, {"head.0.weight", D}, {"head.0.bias", D}, {"head.1.weight", 3 * D},
+                    {"head.1.bias", 3}, {"weighted_mean.weight", s2f * T}, {"weighted_mean.bias", s2f}});
 }
 
 const float* wptr(const d3d_engine* e, const std::string& name) {
@@ -425,44 +388,6 @@ int attention(d3d_engine* e, const BlockPlan& pl, const float* qkv, float* out, 
   return D3D_OK;
 }
 
-// "block0_direct": the commit-time tables of block 0 (d3d_engine::b0_tab).  wg: W_qkv diag(gamma1) [3 D][D], the fp32 values the commit
-// splits block 0's qkv planes from (q rows as handed over: qk_scale and qkv_bias = False arrive as derived tensors, the LayerNorm's gamma /
-// beta / eps live in wg, the folded bias and the kernel argument).  G and P are summed in fp64 and stored as fp32.  Built where block 0 can
-// take the direct form at all: a spatial F16X3 block on the fused kernel's tile geometry, embedding straight into the planes.
-void block0_tables_host(const float* wg, const float* We, const float* be, const float* spos, int D, int H, int cin, int J, float* G, float* P) {
-  const size_t N = 3 * (size_t)D, dh = (size_t)D / H;
-  std::vector<double> v((size_t)J * D);
-  for (int j = 0; j < J; ++j)
-    for (int k = 0; k < D; ++k) v[(size_t)j * D + k] = (double)be[k] + (double)spos[(size_t)j * D + k];
-  for (size_t n = 0; n < N; ++n) {   // head-major row n <- original row src, as the commit orders qkv_f3h
-    const size_t hd_ = n / (3 * dh), cc = n % (3 * dh), src = ((cc % 48) / 16) * D + hd_ * dh + 16 * (cc / 48) + cc % 16;
-    const float* wr = wg + src * D;
-    for (int c = 0; c < cin; ++c) {
-      double a = 0.0;
-      for (int k = 0; k < D; ++k) a += (double)wr[k] * (double)We[(size_t)k * cin + c];
-      G[n * cin + c] = (float)a;
-    }
-    for (int j = 0; j < J; ++j) {
-      double a = 0.0;
-      for (int k = 0; k < D; ++k) a += (double)wr[k] * v[(size_t)j * D + k];
-      P[(size_t)j * N + n] = (float)a;
-    }
-  }
-}
-int build_block0_tables(d3d_engine* e, const std::vector<float>& wg) {
-  const int D = e->D, J = e->J, cin = e->cin;
-  if (!embed_planes_ok(D, e->cfg.in_chans) || !qkv_sattn_direct_ok(J, D, e->H, e->cfg.in_chans)) return D3D_OK;
-  const size_t N = 3 * (size_t)D, n_wg = N * D, n_G = align_up(N * cin, 64), n_P = (size_t)J * N;
-  std::vector<float> tab(n_G + n_P);
-  block0_tables_host(wg.data(), e->slots[e->index["fusion_layer.weight"]].host.data(), e->slots[e->index["fusion_layer.bias"]].host.data(),
-                     e->slots[e->index["Spatial_pos_embed"]].host.data(), D, e->H, cin, J, tab.data(), tab.data() + n_G);
-  HIP_TRY(hipMalloc(&e->b0_tab, (n_wg + tab.size()) * sizeof(float)));
-  HIP_TRY(hipMemcpy(e->b0_tab, wg.data(), n_wg * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->b0_tab + n_wg, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-  e->b0_wg = e->b0_tab; e->b0_G = e->b0_tab + n_wg; e->b0_P = e->b0_G + n_G;   // (set last: a failed copy leaves the direct form off)
-  return D3D_OK;
-}
-
 // The plan of a forward of B sequences.  A pure function of the options, the shapes, B and the CU count, so an eager run, a capture
 // and a replay agree.
 BlockPlan plan_blocks(const d3d_engine* e, int B) {
@@ -537,7 +462,7 @@ LnArgs ln_postnorm(const d3d_engine* e, int M, const X3PostNorm& q) {
 
 // the scratch slot a forward with fc1 split needs, allocated outside any capture (the eager pass of a graph call comes first)
 int ensure_lat_scratch(d3d_engine* e, int slot) {
-  if (!e->lat_scratch[slot]) HIP_TRY(hipMalloc(&e->lat_scratch[slot], FC1_SPLITK_SCRATCH_FLOATS * sizeof(float)));
+  if (!e->lat_scratch[slot]) HIP_TRY(e->lat_scratch[slot].alloc(FC1_SPLITK_SCRATCH_FLOATS));
   return D3D_OK;
 }
 
@@ -1089,37 +1014,67 @@ int d3d_engine_commit_weights(d3d_engine* e) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(D3D_EHIP, "no HIP device: libd3d_hip has no CPU path");
+  // All or nothing: from here to the last line the engine is "not committed, no schedule" and holds no view into a buffer, so a step
+  // that fails leaves an engine every entry point refuses (check_ready, "schedule not set"), never one that points at freed memory.
+  // The old buffers go before anything is allocated: a re-commit's peak device footprint is one set of images.
+  e->committed = e->sched_set = false;
+  e->drop_graphs();
+  e->blk.clear();
+  const std::pair<const float**, const char*> views[] = {
+      {&e->fus_w, "fusion_layer.weight"}, {&e->fus_b, "fusion_layer.bias"}, {&e->spos, "Spatial_pos_embed"}, {&e->tpos, "Temporal_pos_embed"},
+      {&e->sn_g, "Spatial_norm.weight"}, {&e->sn_b, "Spatial_norm.bias"}, {&e->tn_g, "Temporal_norm.weight"}, {&e->tn_b, "Temporal_norm.bias"},
+      {&e->hd_g, "head.0.weight"}, {&e->hd_b, "head.0.bias"}, {&e->hd_w, "head.1.weight"}, {&e->hd_bias, "head.1.bias"},
+      {&e->wm_w, "weighted_mean.weight"}, {&e->wm_b, "weighted_mean.bias"}, {&e->tm1_w, "time_mlp.1.weight"}, {&e->tm1_b, "time_mlp.1.bias"},
+      {&e->tm3_w, "time_mlp.3.weight"}, {&e->tm3_b, "time_mlp.3.bias"}};   // (a model without the tensor: nullptr)
+  for (auto& v : views) *v.first = nullptr;
+  e->b0_wg = e->b0_G = e->b0_P = nullptr;
+  e->arena.reset(); e->arena16.reset(); e->arena_fold.reset(); e->b0_tab.reset(); e->tblk_w.reset(); e->tblk_b.reset(); e->freqs_dev.reset();
+
+  // ---- host: every image, packed before a byte is allocated (weight_pack.hip)
+  const size_t D = e->D, Dt = e->Dt, N3 = 3 * D, half = D / 2;
+  const bool x3 = e->cfg.precision == D3D_PREC_F16X3;
+  auto blk_name = [](int k) { return std::string((k & 1) ? "TTEblocks." : "STEblocks.") + std::to_string(k / 2); };   // execution order
+  auto host_w = [&](const std::string& name) { return e->slots[e->index[name]].host.data(); };                        // (S2S:225-245)
+  auto block_tensors = [&](int k, auto get) {   // host_w: what the packing reads; wptr: the same tensors in the device arena
+    const std::string p = blk_name(k);
+    return BlockSrc{get(p + ".norm1.weight"), get(p + ".norm1.bias"), get(p + ".attn.qkv.weight"), get(p + ".attn.qkv.bias"),
+                    get(p + ".attn.proj.weight"), get(p + ".attn.proj.bias"), get(p + ".norm2.weight"), get(p + ".norm2.bias"),
+                    get(p + ".mlp.fc1.weight"), get(p + ".mlp.fc1.bias"), get(p + ".mlp.fc2.weight"), get(p + ".mlp.fc2.bias")};
+  };
   size_t off = 0;
-  for (auto& s : e->slots) {
-    s.dev_off = off;
-    off += align_up((size_t)s.numel, 64);
+  for (auto& s : e->slots) { s.dev_off = off; off += align_up((size_t)s.numel, 64); }
+  std::vector<BlockSrc> src;
+  for (int k = 0; k < e->nblk; ++k) src.push_back(block_tensors(k, host_w));
+  PackedWeights pk;
+  if (x3 && !pack_f16x3(src, D, e->Dm, e->H, qkv_sattn_ok(e->J, e->D, e->H, e->D), qkv_tattn_ok(e->T, e->J, e->D, e->H, e->D), pk))
+    return fail(D3D_EHIP, "internal: head-major qkv planes got a different exponent");
+  if (e->cfg.precision == D3D_PREC_BF16) pack_bf16(src, D, e->Dm, pk);
+  e->weights_clamped = pk.clamped;
+  // "block0_direct": G and P of block 0 where it can take the direct form (a spatial F16X3 block on the fused kernel's tile geometry,
+  // embedding straight into the planes); they follow Wg in one allocation, G padded to whole 64-float lines
+  const size_t n_G = align_up(N3 * e->cin, 64);
+  std::vector<float> b0;
+  if (x3 && embed_planes_ok(e->D, e->cfg.in_chans) && qkv_sattn_direct_ok(e->J, e->D, e->H, e->cfg.in_chans)) {
+    b0.resize(n_G + (size_t)e->J * N3);
+    block0_tables_host(pk.wg0.data(), host_w("fusion_layer.weight"), host_w("fusion_layer.bias"), host_w("Spatial_pos_embed"), e->D, e->H,
+                       e->cin, e->J, b0.data(), b0.data() + n_G);
   }
-  if (e->arena) { (void)hipFree(e->arena); e->arena = nullptr; }
-  e->arena_floats = off;
-  HIP_TRY(hipMalloc(&e->arena, off * sizeof(float)));
+  if (Dt && !e->freqs_set) {   // SinusoidalPosEmb frequencies (S2S:31-33): exp(k * -(ln 1e4 / (half-1))) with the product formed in fp32
+    e->freqs_host.resize(half);
+    const float neg = (float)(-(std::log(10000.0) / (double)(half - 1)));
+    for (size_t k = 0; k < half; ++k) {
+      volatile float arg = (float)k * neg;
+      e->freqs_host[k] = (float)std::exp((double)arg);
+    }
+  }
+
+  // ---- device: allocate, upload
+  HIP_TRY(e->arena.alloc(off));
   for (auto& s : e->slots)
     HIP_TRY(hipMemcpy(e->arena + s.dev_off, s.host.data(), (size_t)s.numel * sizeof(float), hipMemcpyHostToDevice));
-
-  auto blockw = [&](const std::string& p) {
-    BlockW b{};
-    b.n1g = wptr(e, p + ".norm1.weight"); b.n1b = wptr(e, p + ".norm1.bias");
-    b.qkvw = wptr(e, p + ".attn.qkv.weight"); b.qkvb = wptr(e, p + ".attn.qkv.bias");
-    b.projw = wptr(e, p + ".attn.proj.weight"); b.projb = wptr(e, p + ".attn.proj.bias");
-    b.n2g = wptr(e, p + ".norm2.weight"); b.n2b = wptr(e, p + ".norm2.bias");
-    b.fc1w = wptr(e, p + ".mlp.fc1.weight"); b.fc1b = wptr(e, p + ".mlp.fc1.bias");
-    b.fc2w = wptr(e, p + ".mlp.fc2.weight"); b.fc2b = wptr(e, p + ".mlp.fc2.bias");
-    return b;
-  };
-  e->blk.clear();
-  for (int i = 0; i < e->depth; ++i) {  // execution order (S2S:225-245): STE_i then TTE_i
-    e->blk.push_back(blockw("STEblocks." + std::to_string(i)));
-    e->blk.push_back(blockw("TTEblocks." + std::to_string(i)));
-  }
-  e->weights_clamped = false;
-  if (e->b0_tab) { (void)hipFree(e->b0_tab); e->b0_tab = e->b0_wg = e->b0_G = e->b0_P = nullptr; }
   HIP_TRY(hipGetDevice(&e->device));
   if (!e->range_dev) {
-    HIP_TRY(hipMalloc(&e->range_dev, 256));
+    HIP_TRY(e->range_dev.alloc(256 / sizeof(unsigned)));
     HIP_TRY(hipMemset(e->range_dev, 0, 256));
   }
   if (!e->range_host) {
@@ -1129,170 +1084,41 @@ int d3d_engine_commit_weights(d3d_engine* e) {
     e->range_ev.resize(d3d_engine::RANGE_TICKETS, nullptr);
     for (auto& ev : e->range_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   }
-  if (e->cfg.precision == D3D_PREC_F16X3) {
-    // fp16 hi/lo pair layout of the four GEMM weights of every block, rows padded to a multiple of 256 (zero rows) so
-    // the LDS-DMA of edge tiles never leaves the allocation (kernels_gemm_x3p.hip contract)
-    const size_t D = e->D, Dm = e->Dm;
-    auto pad256 = [](size_t n) { return (n + 255) / 256 * 256; };
-    const size_t per_blk = 2 * (3 * pad256(3 * D) * D + pad256(D) * D + 2 * pad256(Dm) * D + pad256(D) * Dm);
-    std::vector<uint16_t> host(per_blk * e->nblk, 0);
-    const size_t fold_per_blk = 2 * (3 * D + Dm) + 2 * 3 * D;
-    const bool head_major = qkv_sattn_ok(e->J, e->D, e->H, e->D);
-    const bool tile_order_t = qkv_tattn_ok(e->T, e->J, e->D, e->H, e->D);
-    std::vector<float> fold(fold_per_blk * e->nblk, 0.f);
-    if (e->arena_fold) { (void)hipFree(e->arena_fold); e->arena_fold = nullptr; }
-    HIP_TRY(hipMalloc(&e->arena_fold, fold.size() * sizeof(float)));
-    size_t fo = 0;
-    std::vector<float> wg;
-    if (e->arena16) { (void)hipFree(e->arena16); e->arena16 = nullptr; }
-    HIP_TRY(hipMalloc(&e->arena16, host.size() * sizeof(uint16_t)));
-    size_t o = 0;
-    for (int k = 0; k < e->nblk; ++k) {
-      const std::string p = std::string((k & 1) ? "TTEblocks." : "STEblocks.") + std::to_string(k / 2);
-      auto pair = [&](const std::string& name, size_t rows, size_t cols, const uint16_t*& dst, int& wexp, bool acc_order = false) {
-        const WeightSlot& ws = e->slots[e->index[name]];
-        wexp = split_weight_f16x3(ws.host.data(), rows, cols, host.data() + o, acc_order, &e->weights_clamped);
-        dst = e->arena16 + o;
-        o += 2 * pad256(rows) * cols;
-      };
-      BlockW& b = e->blk[k];
-      pair(p + ".attn.qkv.weight", 3 * D, D, b.qkv_x3, b.qkv_e);
-      pair(p + ".attn.proj.weight", D, D, b.proj_x3, b.proj_e);
-      pair(p + ".mlp.fc1.weight", Dm, D, b.fc1_x3, b.fc1_e);
-      pair(p + ".mlp.fc2.weight", D, Dm, b.fc2_x3, b.fc2_e, true);   // its A operand (the hidden activation) is in accumulator order
-      // LayerNorm folded into the consuming GEMM: LN(x) W^T + b = rstd (x (W diag g)^T) - rstd mean csum + (b + W beta)
-      auto folded = [&](const std::string& wname, const std::string& bname, const std::string& norm, size_t rows, size_t cols,
-                        const uint16_t*& w3, const float*& cs, const float*& fb, int& wexp) {
-        const std::vector<float>& W = e->slots[e->index[wname]].host;
-        const std::vector<float>& bb = e->slots[e->index[bname]].host;
-        const std::vector<float>& g = e->slots[e->index[norm + ".weight"]].host;
-        const std::vector<float>& be = e->slots[e->index[norm + ".bias"]].host;
-        wg.resize(rows * cols);
-        for (size_t r = 0; r < rows; ++r) {
-          double c = 0.0, bsum = (double)bb[r];
-          for (size_t q = 0; q < cols; ++q) {
-            const float wv = W[r * cols + q] * g[q];        // the fp32 product the GEMM operand is split from
-            wg[r * cols + q] = wv;
-            c += (double)wv;
-            bsum += (double)W[r * cols + q] * (double)be[q];
-          }
-          fold[fo + r] = (float)c;
-          fold[fo + rows + r] = (float)bsum;
-        }
-        wexp = split_weight_f16x3(wg.data(), rows, cols, host.data() + o, false, &e->weights_clamped);
-        w3 = e->arena16 + o;
-        o += 2 * pad256(rows) * cols;
-        cs = e->arena_fold + fo;
-        fb = e->arena_fold + fo + rows;
-        fo += 2 * rows;
-      };
-      folded(p + ".attn.qkv.weight", p + ".attn.qkv.bias", p + ".norm1", 3 * D, D, b.qkv_f3, b.qkv_cs, b.qkv_fb, b.qkv_fe);
-      if ((k & 1) ? tile_order_t : head_major) {   // the same folded rows once more in tile order (same per-matrix exponent): spatial
-                                                   // blocks for kernels_qkv_sattn.hip, temporal blocks for kernels_qkv_tattn.hip
-        const size_t dh = D / e->H, rows = 3 * D;
-        std::vector<float> whm(rows * D);
-        const size_t f_cs = (size_t)(b.qkv_cs - e->arena_fold), f_fb = (size_t)(b.qkv_fb - e->arena_fold);
-        for (size_t r = 0; r < rows; ++r) {
-          // tile order (kernels_qkv_sattn.hip): row 192 h + 48 wn + 16 part + x <- original row 512 part + 64 h + 16 wn + x
-          const size_t hd_ = r / (3 * dh), c = r % (3 * dh), wn_ = c / 48, part = (c % 48) / 16, x = c % 16;
-          const size_t src = part * D + hd_ * dh + 16 * wn_ + x;
-          memcpy(&whm[r * D], &wg[src * D], D * sizeof(float));     // wg still holds W diag(gamma) of this block's qkv
-          fold[fo + r] = fold[f_cs + src];
-          fold[fo + rows + r] = fold[f_fb + src];
-        }
-        int ke = 12;
-        ke = split_weight_f16x3(whm.data(), rows, D, host.data() + o, false, &e->weights_clamped);
-        if (ke != b.qkv_fe) return fail(D3D_EHIP, "internal: head-major qkv planes got a different exponent");
-        b.qkv_f3h = e->arena16 + o;
-        o += 2 * pad256(rows) * D;
-        b.qkv_csh = e->arena_fold + fo;
-        b.qkv_fbh = e->arena_fold + fo + rows;
-        fo += 2 * rows;
-      }
-      if (k == 0) {   // wg still holds W diag(gamma) of block 0's qkv: the fp32 values its planes are split from
-        const int rc = build_block0_tables(e, wg);
-        if (rc) return rc;
-      }
-      folded(p + ".mlp.fc1.weight", p + ".mlp.fc1.bias", p + ".norm2", Dm, D, b.fc1_f3, b.fc1_cs, b.fc1_fb, b.fc1_fe);
-    }
-    HIP_TRY(hipMemcpy(e->arena16, host.data(), host.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->arena_fold, fold.data(), fold.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (x3) HIP_TRY(e->arena_fold.upload(pk.fold.data(), pk.fold.size()));
+  if (!pk.planes.empty()) HIP_TRY(e->arena16.upload(pk.planes.data(), pk.planes.size()));
+  if (!b0.empty()) {
+    HIP_TRY(e->b0_tab.alloc(N3 * D + b0.size()));
+    HIP_TRY(hipMemcpy(e->b0_tab, pk.wg0.data(), N3 * D * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->b0_tab + N3 * D, b0.data(), b0.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  if (e->cfg.precision == D3D_PREC_BF16) {
-    // bf16 copies (round to nearest even, as torch's .to(bfloat16) and v_cvt_pk_bf16_f32) of the four GEMM weights of every
-    // block, [rows padded to 256][K]: the staging of edge tiles never leaves the allocation (kernels_gemm_x3p.hip contract)
-    const size_t D = e->D, Dm = e->Dm;
-    auto pad256 = [](size_t n) { return (n + 255) / 256 * 256; };
-    const size_t per_blk = pad256(3 * D) * D + pad256(D) * D + pad256(Dm) * D + pad256(D) * Dm;
-    std::vector<uint16_t> host(per_blk * e->nblk, 0);
-    if (e->arena16) { (void)hipFree(e->arena16); e->arena16 = nullptr; }
-    HIP_TRY(hipMalloc(&e->arena16, host.size() * sizeof(uint16_t)));
-    auto rne = [](float f) -> uint16_t {
-      uint32_t u;
-      memcpy(&u, &f, 4);
-      if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);     // NaN stays NaN
-      return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    };
-    size_t o = 0;
+  if (Dt) {   // the 2*depth per-block Linear(Dt -> D) layers (S2S:104-107) concatenated into one (nblk*D, Dt) matrix
+    HIP_TRY(e->tblk_w.alloc(e->nblk * D * Dt));
+    HIP_TRY(e->tblk_b.alloc(e->nblk * D));
     for (int k = 0; k < e->nblk; ++k) {
-      const std::string p = std::string((k & 1) ? "TTEblocks." : "STEblocks.") + std::to_string(k / 2);
-      auto conv = [&](const std::string& name, size_t rows, size_t cols, const uint16_t*& dst) {
-        const std::vector<float>& W = e->slots[e->index[name]].host;
-        for (size_t i = 0; i < rows * cols; ++i) {
-          if (!std::isfinite(W[i])) e->weights_clamped = true;
-          host[o + i] = rne(W[i]);
-        }
-        dst = e->arena16 + o;
-        o += pad256(rows) * cols;
-      };
-      BlockW& b = e->blk[k];
-      conv(p + ".attn.qkv.weight", 3 * D, D, b.qkv_x3);
-      conv(p + ".attn.proj.weight", D, D, b.proj_x3);
-      conv(p + ".mlp.fc1.weight", Dm, D, b.fc1_x3);
-      conv(p + ".mlp.fc2.weight", D, Dm, b.fc2_x3);
+      const std::string p = blk_name(k) + ".time_mlp.1";
+      HIP_TRY(hipMemcpy(e->tblk_w + k * D * Dt, wptr(e, p + ".weight"), D * Dt * sizeof(float), hipMemcpyDeviceToDevice));
+      HIP_TRY(hipMemcpy(e->tblk_b + k * D, wptr(e, p + ".bias"), D * sizeof(float), hipMemcpyDeviceToDevice));
     }
-    HIP_TRY(hipMemcpy(e->arena16, host.data(), host.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIP_TRY(e->freqs_dev.upload(e->freqs_host.data(), half));
   }
-  e->fus_w = wptr(e, "fusion_layer.weight"); e->fus_b = wptr(e, "fusion_layer.bias");
-  e->spos = wptr(e, "Spatial_pos_embed"); e->tpos = wptr(e, "Temporal_pos_embed");
-  e->sn_g = wptr(e, "Spatial_norm.weight"); e->sn_b = wptr(e, "Spatial_norm.bias");
-  e->tn_g = wptr(e, "Temporal_norm.weight"); e->tn_b = wptr(e, "Temporal_norm.bias");
-  e->hd_g = wptr(e, "head.0.weight"); e->hd_b = wptr(e, "head.0.bias");
-  e->hd_w = wptr(e, "head.1.weight"); e->hd_bias = wptr(e, "head.1.bias");
-  e->wm_w = wptr(e, "weighted_mean.weight"); e->wm_b = wptr(e, "weighted_mean.bias");
 
-  if (e->Dt) {
-    e->tm1_w = wptr(e, "time_mlp.1.weight"); e->tm1_b = wptr(e, "time_mlp.1.bias");
-    e->tm3_w = wptr(e, "time_mlp.3.weight"); e->tm3_b = wptr(e, "time_mlp.3.bias");
-    // concatenate the 2*depth per-block Linear(Dt -> D) layers (S2S:104-107) into one (nblk*D, Dt) matrix
-    const size_t wn = (size_t)e->nblk * e->D * e->Dt, bn = (size_t)e->nblk * e->D;
-    (void)hipFree(e->tblk_w); (void)hipFree(e->tblk_b); e->tblk_w = e->tblk_b = nullptr;
-    HIP_TRY(hipMalloc(&e->tblk_w, wn * sizeof(float)));
-    HIP_TRY(hipMalloc(&e->tblk_b, bn * sizeof(float)));
-    for (int k = 0; k < e->nblk; ++k) {
-      const std::string p = std::string((k & 1) ? "TTEblocks." : "STEblocks.") + std::to_string(k / 2) + ".time_mlp.1";
-      HIP_TRY(hipMemcpy(e->tblk_w + (size_t)k * e->D * e->Dt, wptr(e, p + ".weight"), (size_t)e->D * e->Dt * sizeof(float),
-                        hipMemcpyDeviceToDevice));
-      HIP_TRY(hipMemcpy(e->tblk_b + (size_t)k * e->D, wptr(e, p + ".bias"), (size_t)e->D * sizeof(float),
-                        hipMemcpyDeviceToDevice));
-    }
-    // SinusoidalPosEmb frequencies (S2S:31-33): exp(k * -(ln 1e4 / (half-1))) with the product formed in fp32
-    const int half = e->D / 2;
-    if (!e->freqs_set) {
-      e->freqs_host.resize(half);
-      const float neg = (float)(-(std::log(10000.0) / (double)(half - 1)));
-      for (int k = 0; k < half; ++k) {
-        volatile float arg = (float)k * neg;
-        e->freqs_host[k] = (float)std::exp((double)arg);
-      }
-    }
-    (void)hipFree(e->freqs_dev); e->freqs_dev = nullptr;
-    HIP_TRY(hipMalloc(&e->freqs_dev, half * sizeof(float)));
-    HIP_TRY(hipMemcpy(e->freqs_dev, e->freqs_host.data(), half * sizeof(float), hipMemcpyHostToDevice));
+  // ---- views into the buffers: every upload has succeeded
+  auto at16 = [&](size_t o) -> const uint16_t* { return o == NO_OFF ? nullptr : e->arena16 + o; };
+  auto atf = [&](size_t o) -> const float* { return o == NO_OFF ? nullptr : e->arena_fold + o; };
+  for (int k = 0; k < e->nblk; ++k) {
+    BlockW b{};
+    static_cast<BlockSrc&>(b) = block_tensors(k, [&](const std::string& name) { return wptr(e, name); });
+    const BlockOff f = pk.blk.empty() ? BlockOff{} : pk.blk[k];
+    b.qkv_x3 = at16(f.qkv_x3); b.proj_x3 = at16(f.proj_x3); b.fc1_x3 = at16(f.fc1_x3); b.fc2_x3 = at16(f.fc2_x3);
+    b.qkv_f3 = at16(f.qkv_f3); b.fc1_f3 = at16(f.fc1_f3); b.qkv_f3h = at16(f.qkv_f3h);
+    b.qkv_cs = atf(f.qkv_cs); b.qkv_fb = atf(f.qkv_fb); b.fc1_cs = atf(f.fc1_cs); b.fc1_fb = atf(f.fc1_fb);
+    b.qkv_csh = atf(f.qkv_csh); b.qkv_fbh = atf(f.qkv_fbh);
+    b.qkv_e = f.qkv_e; b.proj_e = f.proj_e; b.fc1_e = f.fc1_e; b.fc2_e = f.fc2_e; b.qkv_fe = f.qkv_fe; b.fc1_fe = f.fc1_fe;
+    e->blk.push_back(b);
   }
+  if (e->b0_tab) { e->b0_wg = e->b0_tab; e->b0_G = e->b0_tab + N3 * D; e->b0_P = e->b0_G + n_G; }
+  for (auto& v : views) *v.first = wptr(e, v.second);
   e->committed = true;
-  e->sched_set = false;
-  e->drop_graphs();
   return D3D_OK;
 }
 
@@ -1304,6 +1130,7 @@ int d3d_engine_set_schedule(d3d_engine* e, int32_t num_timesteps, const float* a
   if (sampling_timesteps > num_timesteps) return fail(D3D_EINVAL, "sampling_timesteps <= timesteps required (DIFF:145)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   RangeScope range_scope(e);
+  e->sched_set = false;   // all or nothing: a step that fails below leaves "no schedule", which every reader of the tables checks
   e->drop_graphs();
   e->num_timesteps = num_timesteps; e->S = sampling_timesteps; e->eta = eta; e->clip = clip_denoised ? 1 : 0;
   e->ac.assign(ac_host, ac_host + num_timesteps);
@@ -1311,24 +1138,19 @@ int d3d_engine_set_schedule(d3d_engine* e, int32_t num_timesteps, const float* a
   e->times.resize(sampling_timesteps + 1);
   int rc = d3d_ddim_times(num_timesteps, sampling_timesteps, e->times.data());
   if (rc) return rc;
-  (void)hipFree(e->ac_dev); (void)hipFree(e->somac_dev); (void)hipFree(e->temb_sched);
-  e->ac_dev = e->somac_dev = e->temb_sched = nullptr;
-  HIP_TRY(hipMalloc(&e->ac_dev, num_timesteps * sizeof(float)));
-  HIP_TRY(hipMalloc(&e->somac_dev, num_timesteps * sizeof(float)));
-  HIP_TRY(hipMemcpy(e->ac_dev, ac_host, num_timesteps * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->somac_dev, somac_host, num_timesteps * sizeof(float), hipMemcpyHostToDevice));
+  e->ac_dev.reset(); e->somac_dev.reset(); e->temb_sched.reset();
+  HIP_TRY(e->ac_dev.upload(ac_host, num_timesteps));
+  HIP_TRY(e->somac_dev.upload(somac_host, num_timesteps));
   if (e->Dt) {
     const int S = sampling_timesteps;
     std::vector<float> tf(S);
     for (int i = 0; i < S; ++i) tf[i] = (float)e->times[i];
-    float *tdev = nullptr, *scratch = nullptr;
-    HIP_TRY(hipMalloc(&tdev, S * sizeof(float)));
-    HIP_TRY(hipMalloc(&scratch, (size_t)S * (e->D + 2 * (size_t)e->Dt) * sizeof(float)));
-    HIP_TRY(hipMalloc(&e->temb_sched, (size_t)S * e->nblk * e->D * sizeof(float)));
-    HIP_TRY(hipMemcpy(tdev, tf.data(), S * sizeof(float), hipMemcpyHostToDevice));
+    DevBuf<float> tdev, scratch;
+    HIP_TRY(tdev.upload(tf.data(), S));
+    HIP_TRY(scratch.alloc((size_t)S * (e->D + 2 * (size_t)e->Dt)));
+    HIP_TRY(e->temb_sched.alloc((size_t)S * e->nblk * e->D));
     rc = compute_temb(e, tdev, S, e->temb_sched, scratch, s);
-    hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(tdev); (void)hipFree(scratch);
+    const hipError_t se = hipStreamSynchronize(s);   // (before the temporaries go, whatever rc says)
     if (rc) return rc;
     HIP_TRY(se);
   }
@@ -1579,7 +1401,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
     e->opt_latency_mode = value != 0;
     if (!e->opt_latency_mode) {
       if (e->lat_scratch[0] || e->lat_scratch[1]) (void)hipDeviceSynchronize();   // (a forward that reads the buffer may be in flight)
-      e->free_lat_scratch();
+      for (auto& p : e->lat_scratch) p.reset();
     } else if (e->committed) {        // (an engine that exists on the host only has no device to allocate on: the first forward does it)
       const int rc = ensure_lat_scratch(e, 0);
       if (rc) { e->opt_latency_mode = false; return rc; }
@@ -1671,9 +1493,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
 int d3d_engine_set_sqrt_alphas_cumprod(d3d_engine* e, const float* host, int32_t n) {
   if (!e || !host) return fail(D3D_EINVAL, "null argument");
   if (!e->sched_set || n != e->num_timesteps) return fail(D3D_ESTATE, "set the schedule first; n must equal num_timesteps");
-  (void)hipFree(e->sqrt_ac_dev); e->sqrt_ac_dev = nullptr;
-  HIP_TRY(hipMalloc(&e->sqrt_ac_dev, n * sizeof(float)));
-  HIP_TRY(hipMemcpy(e->sqrt_ac_dev, host, n * sizeof(float), hipMemcpyHostToDevice));
+  e->has_sqrt_ac = false;
+  HIP_TRY(e->sqrt_ac_dev.upload(host, n));
   e->has_sqrt_ac = true;
   return D3D_OK;
 }
@@ -1816,13 +1637,12 @@ int d3d_engine_range_take(d3d_engine* e, int64_t ticket, int32_t block, uint32_t
 int d3d_engine_set_trace(d3d_engine* e, int32_t capacity, int32_t views) {
   if (!e || capacity < 0 || views < 1 || views > 8) return fail(D3D_EINVAL, "bad argument");
   e->trace_views = views;
-  (void)hipFree(e->trace_dev);
-  e->trace_dev = nullptr;
+  e->trace_dev.reset();
   e->trace_cap = e->trace_n = e->trace_fwd = 0;
   e->trace_tags.clear();
   e->tracing = capacity > 0;
   if (e->tracing) {
-    HIP_TRY(hipMalloc(&e->trace_dev, (size_t)capacity * sizeof(unsigned long long)));
+    HIP_TRY(e->trace_dev.alloc((size_t)capacity));
     HIP_TRY(hipMemset(e->trace_dev, 0, (size_t)capacity * sizeof(unsigned long long)));
     e->trace_cap = capacity;
   }

@@ -19,6 +19,21 @@ inline LnArgs ln_rows(int rows, int D, int rows_per_batch) {
   return a;
 }
 
+// device memory of n elements, freed on every return path (HIP_TRY leaves early) and with its owner; reads as the pointer it holds;
+// alloc / upload free first, so a re-allocation never holds both
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }   // (move only)
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+  ~DevBuf() { reset(); }
+  void reset() { if (p) (void)hipFree(p); p = nullptr; }
+  hipError_t alloc(size_t n) { reset(); const hipError_t e = hipMalloc(&p, n * sizeof(T)); if (e != hipSuccess) p = nullptr; return e; }
+  hipError_t upload(const T* host, size_t n) { const hipError_t e = alloc(n); return e ? e : hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice); }
+  operator T*() const { return p; }
+};
+
 }  // namespace d3d
 
 #define HIP_TRY(expr)                                                                                         \

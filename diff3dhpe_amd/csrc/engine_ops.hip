@@ -13,19 +13,6 @@ using namespace d3d;
 
 namespace {
 
-// device memory of n elements, freed on every return path (HIP_TRY leaves early)
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n * sizeof(T)); }
-};
-
-size_t pad256(size_t n) { return (n + 255) / 256 * 256; }
-
 // F16X3 pair buffer of an fp32 device matrix (rows padded to 256, zero rows).  Weights are split on the host with the same routine the
 // engine uses at commit; activations on the device with the producers' split.
 struct TmpPair : DevBuf<uint16_t> {
@@ -250,32 +237,18 @@ int d3d_op_linear_splitk_gelu(const float* X, const float* W, const float* bias,
   HIP_TRY(hipMemcpy(hg.data(), gamma, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(hb.data(), beta, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(hbias.data(), bias, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < (size_t)N; ++r) {
-    double c = 0.0, bsum = (double)hbias[r];
-    for (size_t q = 0; q < (size_t)K; ++q) {
-      const float wv = hw[r * K + q] * hg[q];
-      wg[r * K + q] = wv;
-      c += (double)wv;
-      bsum += (double)hw[r * K + q] * (double)hb[q];
-    }
-    fold[r] = (float)c;
-    fold[N + r] = (float)bsum;
-  }
+  fold_layernorm(hw.data(), hbias.data(), hg.data(), hb.data(), N, K, wg.data(), fold.data(), fold.data() + N);
   TmpPair wp, xp, hp;
   const size_t npad = pad256(N), mpad = pad256(M);
-  {
-    std::vector<uint16_t> pr(2 * npad * K, 0);
-    wp.wexp = split_weight_f16x3(wg.data(), N, K, pr.data());
-    HIP_TRY(wp.alloc(pr.size()));
-    HIP_TRY(hipMemcpy(wp.p, pr.data(), pr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  }
+  std::vector<uint16_t> pr(2 * npad * K, 0);
+  wp.wexp = split_weight_f16x3(wg.data(), N, K, pr.data());
+  HIP_TRY(wp.upload(pr.data(), pr.size()));
   HIP_TRY(xp.alloc(2 * mpad * K));
   HIP_TRY(hipMemsetAsync(xp.p, 0, 2 * mpad * K * sizeof(uint16_t), s));
   HIP_TRY(hp.alloc(2 * mpad * N));
   HIP_TRY(hipMemsetAsync(hp.p, 0, 2 * mpad * N * sizeof(uint16_t), s));
   DevBuf<float> fd, st;
-  HIP_TRY(fd.alloc(fold.size()));
-  HIP_TRY(hipMemcpy(fd.p, fold.data(), fold.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(fd.upload(fold.data(), fold.size()));
   HIP_TRY(st.alloc(mpad * 2));
   HIP_TRY(hipMemsetAsync(st.p, 0, mpad * 2 * sizeof(float), s));
   {  // the stream entry row kernel: planes of 8 x + one (sum, sum of squares) per row

@@ -209,41 +209,4 @@ hipError_t launch_linear_f16x3(const float* A, const void* Wpair, const float* b
   return hipGetLastError();
 }
 
-// Host-side weight split: w [rows, cols] -> pair layout (d3d_kernels.h) of hi/lo fp16 of s*w with s = 2^12
-// (round-to-nearest-even both times).
-// acc_order: the k index of every 32-column group is stored in the order pair_slot_acc() gives it (the layout of the
-// hidden activation that the fc1 epilogue writes straight from its accumulators, kernels_gemm_x3p.hip)
-int split_weight_f16x3(const float* w, size_t rows, size_t cols, uint16_t* pair, bool acc_order, bool* clamped) {
-  // per-matrix scale 2^k: 2^12 whenever the matrix fits (|w| <= 15.99: every matrix of a sane checkpoint -- then the planes are
-  // bit for bit what a fixed 4096 gives), smaller when a weight is larger -- LayerNorm-FOLDED weights W diag(gamma) of a
-  // checkpoint with big gains get there (gamma 6 x |w| 8 = 48).  The GEMM un-scales by 2^-(3+k) (X3Tail::out_scale); powers of
-  // two, so nothing rounds differently.  Small entries whose lo half then falls into fp16 denormals lose bits below
-  // 2^-24 2^-k: < 1e-9 absolute at k >= 5.
-  float amax = 0.0f;
-  bool finite = true;
-  for (size_t i = 0; i < rows * cols; ++i) {
-    const float a = fabsf(w[i]);
-    if (!(a <= 3.0e38f)) finite = false;
-    else if (a > amax) amax = a;
-  }
-  int k = 12;
-  while (k > -14 && ldexpf(amax, k) > 65504.0f) --k;
-  const float scale = ldexpf(1.0f, k);
-  bool in_range = finite;
-  for (size_t r = 0; r < rows; ++r)
-    for (size_t c = 0; c < cols; ++c) {
-      float s = w[r * cols + c] * scale;
-      if (!(s <= 65504.0f && s >= -65504.0f)) in_range = false;
-      if (s > 65504.0f) s = 65504.0f;
-      if (s < -65504.0f) s = -65504.0f;
-      const _Float16 h = (_Float16)s;
-      const _Float16 l = (_Float16)(s - (float)h);
-      uint16_t* o = pair + r * 2 * cols + (acc_order ? pair_col_acc((int)c) : pair_col((int)c));
-      __builtin_memcpy(o, &h, 2);
-      __builtin_memcpy(o + PAIR_LO, &l, 2);
-    }
-  if (clamped && !in_range) *clamped = true;
-  return k;
-}
-
 }  // namespace d3d

@@ -4,6 +4,9 @@
 #                                          tests/test_latency_mode_host.py against it, log under profiles/
 # What it covers: everything those tests reach without a device (test_threads_host.py: two threads with an engine each at the C ABI) -- d3d_engine_create / set_weight / weight_info /
 # d3d_ddim_times / d3d_num_windows / every error path of the C ABI (argument checks, last-error strings), the weight-name tables.
+# The weight commit's packing arithmetic (csrc/weight_pack.hip: split, LayerNorm fold, tile order, block-0 tables, bf16) sits behind the
+# device check of d3d_engine_commit_weights, so these tests do not reach it through the library; it is host-only code with a stand-alone
+# ASan + UBSan program of its own: tests/host/weight_pack_check.cpp, built and run by tests/test_weight_pack_host.py.
 set -eo pipefail
 cd "$(dirname "$0")/.."
 out=/tmp/d3d_asan; mkdir -p $out experiments/_libs
