@@ -261,6 +261,15 @@ hipError_t launch_fc1_x3(const void* Apair, const void* Wpair, const float* bias
 bool qkv_tattn_ok(int T, int J, int D, int H, int K);
 hipError_t launch_qkv_tattn(const void* Apair, const void* Wpair_tileorder, const float* bias_to, const float* csum_to, const float* st_in,
                             int st_np, float eps, int w_exp, void* out_x3, int B, int T, int J, int K, int D, int H, hipStream_t s);
+// kernels_qkv_attn_x3_small.hip ("small_tiles" under "latency_mode"): the same fused step on 128-row tiles -- floor(127 / N) whole groups of
+// N <= 127 tokens x one head per workgroup, one row map for both block types (group u holds rows (u / stride) * N * stride + u % stride +
+// t * stride: spatial (B * T, J, 1) with J in 15 .. 17, temporal (B * J, T, J)), one tile per workgroup; the tile-ordered weight / bias /
+// csum of launch_qkv_sattn.  Bit-identical to the qkv GEMM followed by launch_attn_temporal_x3.  Only the groups * N rows of Apair are read.
+bool qkv_attn_x3_small_ok(int N, int stride, int J, int D, int H, int K);
+long long qkv_attn_x3_small_workgroups(long long groups, int N);
+hipError_t launch_qkv_attn_x3_small(const void* Apair, const void* Wpair_tileorder, const float* bias_to, const float* csum_to, const float* st_in,
+                                    int st_np, float eps, int w_exp, void* out_x3, int groups, int N, int stride, int J, int K, int D, int H,
+                                    hipStream_t s);
 
 // ---- kernels_elem.hip -------------------------------------------------------------------------------------------
 // Row LayerNorm; optionally also writes a second LayerNorm of the first result (post-norm -> next block's norm1).

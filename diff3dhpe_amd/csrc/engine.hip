@@ -73,6 +73,9 @@ struct BlockPlan {
   bool fc1_own = false, proj_own = false, pn = false;
   // FOLD with "latency_mode": the S of the split-K form of each GEMM, 0 = the launches above
   int fc2_split = 0, proj_split = 0, fc1_split = 0;
+  // FOLD with "latency_mode" and "small_tiles": the fused qkv + attention step of the spatial / temporal blocks on 128-row tiles
+  // (kernels_qkv_attn_x3_small.hip) where the 256-row launch would leave CUs without a workgroup; block 0 keeps its direct form
+  bool small_sp = false, small_tp = false;
   // BF16: whole-row proj / fc2 with their LayerNorms in the epilogue; qkv / fc1 on the hand-specialised GEMM kernel
   bool rows = false, bf16q_qkv = false, bf16q_fc1 = false;
 };
@@ -140,6 +143,11 @@ struct d3d_engine {
   // "proj_split" / "fc1_split" (read only while "latency_mode" is on): -1 = the rules of d3d_kernels.h (proj_splitk_choose /
   // fc1_splitk_choose), 0 / 2 / 4 = that S wherever the call fits the kernel pair (else the present launch): measurements and tests
   int opt_proj_split = -1, opt_fc1_split = -1;
+  // "small_tiles" (read only while "latency_mode" is on and the flow is the folded one): 1 = the fused qkv + attention launches of a forward
+  // that would run fewer workgroups than the device has CUs take the 128-row tiles of kernels_qkv_attn_x3_small.hip where those run at
+  // most 5/8 as many workgroups as the device has CUs (bit-identical to the two-kernel flow, so NOT to the grouped temporal form it
+  // replaces); 0 (default) = every launch as without the key
+  bool opt_small_tiles = false;
   // fc1's partials (S M Dm floats) fit no region of the workspace that is dead at that point for every S: an engine-owned buffer,
   // FC1_SPLITK_SCRATCH_FLOATS per slot, allocated when "latency_mode" is switched on and freed when it is switched off.  Slot 1 serves
   // the second half-batch of a two-stream sampling (the halves run concurrently), allocated by the first such call.
@@ -419,6 +427,21 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
         p.proj_split = ps < 0 ? proj_splitk_choose(M, D, D, cus) : (ps && proj_splitk_ok(D, D, ps) && proj_splitk_fits(M, D, ps, cus) ? ps : 0);
         p.fc1_split = fs < 0 ? fc1_splitk_choose(M, Dm, D, cus) : (fs && fc1_splitk_ok(Dm, D, fs) && fc1_splitk_fits(M, Dm, fs, cus) ? fs : 0);
       }
+      if (e->opt_small_tiles) {
+        // the 128-row tiles where the present fused launch runs fewer workgroups than the device has CUs AND the small-tile launch at most
+        // 5/8 of them.  One 137 KiB workgroup holds a CU, so a launch of more workgroups than CUs runs a second round and loses what the
+        // shorter k-loop gained; the 5/8 is the table's: launches of up to 136 workgroups on 256 CUs lead in every
+        // alternation, the next shape class (192: a half-batch of two T = 81 sequences, its twin running beside it on the second stream)
+        // does not.  Present launches: spatial, ceil(frames / 15) tiles (16 at 15 / 16 joints) x 8 heads; temporal (grouped form,
+        // T <= 127), B ceil(J / min(255 / T, J)) x 8
+        const int fpt = J == 17 ? 15 : 16;
+        const long long wg_sp = (long long)((B * T + fpt - 1) / fpt) * 8;
+        const int gj = T <= 127 ? (255 / T < J ? 255 / T : J) : 1;
+        const long long wg_tp = (long long)B * ((J + gj - 1) / gj) * 8;
+        auto fits = [&](long long groups, int N) { return 8 * qkv_attn_x3_small_workgroups(groups, N) <= 5LL * cus; };
+        p.small_sp = p.fused_sp && qkv_attn_x3_small_ok(J, 1, J, D, H, D) && wg_sp < cus && fits((long long)B * T, J);
+        p.small_tp = p.fused_tp && qkv_attn_x3_small_ok(T, J, J, D, H, D) && wg_tp < cus && fits((long long)B * J, T);
+      }
     }
   } else if (e->cfg.precision == D3D_PREC_BF16) {
     p.flow = BlockPlan::BF16;
@@ -549,7 +572,14 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
       Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N * (f.Rp ? 2 : 1)), s, sub);
       return launch_linear_x3p(A, W, bias, nullptr, C, Ch, Cl, M, N, K, epi, outsplit, qcols, 0, s, &f, wexp);
     };
-    if (temporal && pl.fused_tp) {
+    if (temporal ? pl.small_tp : (pl.small_sp && !(k == 0 && pl.b0_direct))) {
+      // latency mode, small tiles: the same fused step on 128-row tiles of whole groups (kernels_qkv_attn_x3_small.hip)
+      const int N = temporal ? T : J;
+      Prof p(e, temporal ? D3D_KC_QKV_TATTN : D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)N * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
+      HIP_TRY(launch_qkv_attn_x3_small(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, temporal ? B * J : B * T, N,
+                                       temporal ? J : 1, J, D, D, e->H, s));
+      TRACE(k, 3, 0, AOx, MDb);
+    } else if (temporal && pl.fused_tp) {
       // temporal block: q, k, v of one (batch, joint) group stay in LDS and feed the T-key attention in the same kernel (kernels_qkv_tattn.hip)
       Prof p(e, D3D_KC_QKV_TATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)T * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_tattn(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, B, T, J, D, D, e->H, s));
@@ -920,7 +950,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 137; }   // 137: skeletons of 15 and 16 joints on the fused spatial kernels and the fp32 spatial kernel; info key "fused_spatial_last"
+int d3d_version(void) { return 138; }   // 138: option / info key "small_tiles", info key "small_tiles_last", d3d_op_qkv_attn_x3_small
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1415,6 +1445,10 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
       return fail(D3D_EUNSUP, k + ": -1 (the rule), 0, or S in {2, 4} with embed_dim / 32 / S >= 4 whole k-tiles, embed_dim 512");
     (proj ? e->opt_proj_split : e->opt_fc1_split) = (int)value;
   }
+  else if (k == "small_tiles") {
+    if (value != 0 && value != 1) return fail(D3D_EINVAL, "small_tiles must be 0 or 1");
+    e->opt_small_tiles = value != 0;
+  }
   else if (k == "streams") {
     if (value != 1 && value != 2) return fail(D3D_EINVAL, "streams must be 1 or 2");
     e->opt_streams = (int)value;
@@ -1482,6 +1516,9 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "fc1_split_last") *value = e->last_plan.fc1_split;
   else if (k == "block0_direct_last") *value = e->last_plan.b0_direct ? 1 : 0;
   else if (k == "proj_split") *value = e->opt_proj_split;
+  else if (k == "small_tiles") *value = e->opt_small_tiles ? 1 : 0;
+  else if (k == "small_tiles_last")
+    *value = e->last_plan.flow == BlockPlan::FOLD ? (e->last_plan.small_sp ? 1 : 0) | (e->last_plan.small_tp ? 2 : 0) : 0;
   else if (k == "fc1_split") *value = e->opt_fc1_split;
   else if (k == "fused_spatial_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.fused_sp;
   else if (k == "bf16_fused_spatial_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_sp;

@@ -614,6 +614,23 @@ def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, gr
     return out
 
 
+def op_qkv_attn_x3_small(x: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                         groups: int, N: int, stride: int, H: int, temporal: bool) -> torch.Tensor:
+    """The fused F16X3 qkv GEMM + attention kernel of "small_tiles" alone (include/d3d.h d3d_op_qkv_attn_x3_small): attention of
+    LayerNorm(x; gamma, beta, eps) Wqkv^T + bias, the LayerNorm folded into the GEMM.  x (groups * N, D) token rows, Wqkv (3 D, D),
+    bias (3 D,) -> (groups * N, D).  Group u holds rows (u // stride) * N * stride + u % stride + t * stride."""
+    dev = x.device
+    D = x.shape[-1]
+    a = _f32c(x, dev).reshape(groups * N, D)
+    out = torch.empty((groups * N, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_qkv_attn_x3_small(_ptr(a), _ptr(_f32c(Wqkv, dev)), _ptr(_f32c(bias, dev)), _ptr(_f32c(gamma, dev)),
+                                                       _ptr(_f32c(beta, dev)), float(eps), int(groups), int(N), int(stride), D, int(H),
+                                                       int(temporal), _ptr(out), st))
+    return out
+
+
 def tta_mpjpe(pred: torch.Tensor, pred_flip: Optional[torch.Tensor], gt: torch.Tensor, target_mask: Optional[torch.Tensor],
               scale: float, joints_left, joints_right, want_merged: bool = False):
     """evaluate() tail on device (RUN:583-590, LOSS:15-22). Returns (sum_err, n_joints[, merged])."""

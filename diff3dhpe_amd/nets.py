@@ -123,6 +123,9 @@ class _MixSTEDenoiser(nn.Module):
     # the chip as a split-K GEMM + an ordered reduce (include/d3d.h "latency_mode").  Inside the 1e-4 gate, but not bit-identical to the
     # default path.  Set on the class or an instance at any time; fp32 / bf16 engines (and the "auto" fallback) ignore it.
     latency_mode = False
+    # with latency_mode: the fused qkv + attention launches of such a forward on 128-row tiles where the 256-row launch leaves CUs without a
+    # workgroup (include/d3d.h "small_tiles").  Inside the 1e-4 gate; differs in the last bits from latency_mode alone.
+    latency_small_tiles = False
     range_check = os.environ.get("D3D_CHECK_RANGE", "1").strip().lower() not in ("0", "false", "no", "off")
     # One process per GPU is the measured multi-GPU form (torchrun; parallel.py).  nn.DataParallel over SEVERAL devices in one
     # process (RUN:216-218 with --gpu_id 0,1,...) drives one engine per device from DataParallel's worker threads: everything that
@@ -269,6 +272,10 @@ class _MixSTEDenoiser(nn.Module):
                 eng.set_option("latency_mode", int(bool(self.latency_mode)))   # (drops the engine's captured graphs)
                 eng._latency_mode = bool(self.latency_mode)
                 eng.release_workspace()
+        if not fallback and want == "f16x3" and getattr(eng, "_small_tiles", False) != bool(self.latency_small_tiles):
+            with eng.lock:
+                eng.set_option("small_tiles", int(bool(self.latency_small_tiles)))   # (read only while "latency_mode" is on)
+                eng._small_tiles = bool(self.latency_small_tiles)
         sig = self._src_sig if self._src_sig is not None else self._param_signature()
         if sigs.get(idx) != sig:
             eng.load_weights(self._named_tensors())

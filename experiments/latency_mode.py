@@ -14,6 +14,11 @@ launch for launch what the tree before those rules ran with the mode on -- and "
 checkout of that earlier tree) the base leg is run from DIR in a child process per round instead, alternating with this tree's.  Per
 cell: both medians, the base leg's spread (max - min of its round medians), and one-stream per-launch times of proj and fc1 with S forced
 to 0, 2 and 4 (profiling API; the split GEMM under its class, the reduce among the row kernels).
+
+--small-tiles: the table behind the "small_tiles" rule (engine.hip plan_blocks), written to profiles/latency_small_tiles.json.  Two
+engines with the same weights, the mode ON in both, "small_tiles" 1 ("on") / 0 ("off": launch for launch latency mode without the key),
+alternating for --repeats rounds of --samples samplings.  Per cell: both medians, the off leg's spread, whether the on leg leads in every
+round, what "small_tiles_last" reported, and one-stream per-launch times of the two fused qkv + attention classes in both legs.
 """
 import argparse
 import json
@@ -158,9 +163,73 @@ def proj_fc1_table(a):
     print(out)
 
 
+def per_launch_qkv_attn(eng, x2d, nz):
+    """us per launch of the fused qkv + attention classes (spatial: block 0's direct launches included) from the profiling API."""
+    eng.set_graph_mode(False)
+    eng.set_profiling(True)
+    eng.ddim_sample(x2d, nz)
+    torch.cuda.synchronize()
+    eng.profile_reset()
+    eng.ddim_sample(x2d, nz)
+    torch.cuda.synchronize()
+    p = eng.profile_read()
+    ran = eng.info("small_tiles_last")   # (profiling runs the whole batch on one stream: for B >= 2 not the replay's half-batches)
+    eng.set_profiling(False)
+    eng.set_graph_mode(True)
+    us = lambda c: (1e3 * p[c]["ms"] / p[c]["launches"]) if p[c]["launches"] else None
+    return {"small_tiles_profiled": ran, "qkv_sattn_us": us("qkv_sattn"), "qkv_sattn_launches": p["qkv_sattn"]["launches"],
+            "qkv_tattn_us": us("qkv_tattn"), "qkv_tattn_launches": p["qkv_tattn"]["launches"]}
+
+
+def small_tiles_table(a):
+    out = a.out if a.out_given else os.path.join(ROOT, "profiles", "latency_small_tiles.json")
+    res = {"what": f"{STEPS}-step DDIM sampling, depth 8, F16X3, hipGraph replay, latency_mode ON in both legs: off = small_tiles 0 (launch for "
+                   f"launch latency mode without the key), on = small_tiles 1; alternating in one process; ms are medians of {a.repeats} round "
+                   f"medians of {a.samples} samplings; spread = max - min of the off leg's round medians; per_launch: one stream, eager, HIP "
+                   "events, the whole batch in one forward (a replay of B >= 2 runs two half-batches on two streams)",
+           "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count, "cells": []}
+    for T in a.frames:
+        legs = {"off": product(T, True), "on": product(T, True)}
+        legs["on"][0].set_option("small_tiles", 1)
+        for B in a.batches:
+            inp = synth_inputs(B, T, seed=1)
+            x2d, nz = torch.from_numpy(inp["x2d"]).cuda(), torch.from_numpy(inp["noise"]).cuda()
+            outs, ran = {}, {}
+            for name, (eng, _, _) in legs.items():      # warm-up: eager pass + capture + replays
+                eng.set_graph_mode(True)
+                for _ in range(3):
+                    outs[name] = eng.ddim_sample(x2d, nz)
+                ran[name] = eng.info("small_tiles_last")
+            torch.cuda.synchronize()
+            med = {"off": [], "on": []}
+            for _ in range(a.repeats):
+                for name in ("on", "off"):
+                    med[name].append(statistics.median(samplings_ms(legs[name][0], x2d, nz, a.samples)))
+            cell = {"B": B, "T": T, "small_tiles_last": ran["on"], "small_tiles_last_off": ran["off"],
+                    "off_ms": statistics.median(med["off"]), "on_ms": statistics.median(med["on"]),
+                    "off_spread_ms": max(med["off"]) - min(med["off"]), "off_round_medians_ms": med["off"], "on_round_medians_ms": med["on"],
+                    "on_leads_in_every_round": all(x < y for x, y in zip(med["on"], med["off"])),
+                    "max_abs_between_legs": (outs["off"] - outs["on"]).abs().max().item(),
+                    "per_launch": {name: per_launch_qkv_attn(eng, x2d, nz) for name, (eng, _, _) in legs.items()}}
+            cell["gain_ms"] = cell["off_ms"] - cell["on_ms"]
+            cell["ahead_by_more_than_spread"] = bool(cell["gain_ms"] > cell["off_spread_ms"])
+            res["cells"].append(cell)
+            pl = cell["per_launch"]
+            print(f"T={T:3d} B={B} small_tiles_last={ran['on']}: off {cell['off_ms']:.3f} ms (spread {cell['off_spread_ms']:.3f}), on "
+                  f"{cell['on_ms']:.3f} ms, gain {cell['gain_ms']:+.3f}, on leads in every round: {cell['on_leads_in_every_round']}; per launch "
+                  f"off -> on: spatial {pl['off']['qkv_sattn_us']:.1f} -> {pl['on']['qkv_sattn_us']:.1f} us, temporal "
+                  f"{pl['off']['qkv_tattn_us']:.1f} -> {pl['on']['qkv_tattn_us']:.1f} us (profiled small_tiles_last {pl['on']['small_tiles_profiled']})",
+                  flush=True)
+            os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+            json.dump(res, open(out, "w"), indent=1)
+        del legs
+    print(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--proj-fc1", action="store_true", help="the proj / fc1 table (profiles/latency_mode_proj_fc1.json)")
+    ap.add_argument("--small-tiles", action="store_true", help='the "small_tiles" table (profiles/latency_small_tiles.json)')
     ap.add_argument("--parent", default=None, help="with --proj-fc1: a built checkout of the tree before the proj / fc1 rules")
     ap.add_argument("--child", nargs=2, type=int, default=None, metavar=("T", "B"), help="internal: one round of the mode-on leg")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "latency_mode.json"))
@@ -175,6 +244,8 @@ def main():
         return child_round(a.child[0], a.child[1], a.samples)
     if a.proj_fc1:
         return proj_fc1_table(a)
+    if a.small_tiles:
+        return small_tiles_table(a)
     res = {"what": f"{STEPS}-step DDIM sampling, F16X3, hipGraph replay, default path vs latency_mode, interleaved in one process; ms are medians "
                    f"of {a.repeats} round medians of {a.samples} samplings; spread = max - min of the default leg's round medians",
            "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count, "cells": []}

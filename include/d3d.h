@@ -227,6 +227,17 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
  *                     measurements and tests.
+ *   "small_tiles"     0 (default) / 1: read only while "latency_mode" is on (F16X3 folded flow, embedding width 512, 8 heads).  The fused
+ *                     qkv + attention launches that open every block tile 256 token rows x one head, whatever the call: 48 workgroups at
+ *                     num_frame 81, B = 1.  With the key on, a spatial launch (15, 16 or 17 joints) / a temporal launch (num_frame <= 127)
+ *                     that would run fewer workgroups than the device has CUs runs on 128-row tiles of whole token groups instead --
+ *                     floor(127 / N) groups of N tokens per workgroup, twice the workgroups, half the k-loop per workgroup -- where that
+ *                     launch has at most 5/8 as many workgroups as the device has CUs (a workgroup holds a CU; measured).  Block 0 keeps
+ *                     its direct form ("block0_direct").  The selection is a function of (options, shapes, B, CU count) alone.  The
+ *                     small-tile kernel is bit-identical to the two-kernel flow ("fused_spatial" = "fused_temporal" = 0), which the grouped
+ *                     temporal kernel it replaces is not: results stay inside the parity gate, but differ in the last bits from the
+ *                     same engine with the key off.  d3d_workspace_bytes does not change.  "small_tiles_last" (d3d_engine_get_info)
+ *                     reports what the latest forward ran.  Other values: D3D_EINVAL.
  *   "deep_stages"     1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches (batches of a few sequences: proj on 128 x 128
  *                     tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead of two, the wait in front
  *                     of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243: 20.8 ->
@@ -270,7 +281,9 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * "long_temporal" (the option value), "long_temporal_last" (1 when the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample
  * call ran the key-streaming F16X3 attention kernel, else 0: num_frame <= 256, option off, another precision, or before any forward),
  * "long_temporal_f32" (the option value), "long_temporal_f32_last" (the same for a D3D_PREC_FP32 engine and the key-streaming fp32
- * attention kernel; "long_temporal_last" stays 0 on such an engine).
+ * attention kernel; "long_temporal_last" stays 0 on such an engine), "small_tiles" (the option value), "small_tiles_last" (bit 0: the
+ * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
+ * kernel; 0 before any forward, with the option or "latency_mode" off, and in the other precisions).
  * Unknown key: D3D_EINVAL. */
 int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value);
 
@@ -492,6 +505,16 @@ int d3d_op_attention_long_f32(const float* qkv_dev, float* out_dev, int32_t B, i
  * N <= 32), groups % stride == 0; anything else: D3D_EUNSUP / D3D_EINVAL. */
 int d3d_op_qkv_attn_bf16(const float* A_dev, const float* Wqkv_dev, const float* bias_dev, int32_t groups, int32_t N, int32_t stride,
                          int32_t D, int32_t H, int32_t temporal, float* out_dev, void* stream);
+
+/* The fused qkv GEMM + attention kernel of "small_tiles" alone (F16X3): out = attention(LayerNorm(X; gamma, beta, eps) Wqkv^T + bias), the
+ * LayerNorm folded into the GEMM as the weight commit folds it, q / k / v kept on chip as hi / lo fp16 planes -- bit for bit the folded
+ * qkv GEMM followed by d3d_op_attention (D3D_PREC_F16X3) on the same tensors.  X: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias:
+ * (3 D); gamma, beta: (D); out: (groups * N, D) fp32.  Groups as d3d_op_qkv_attn_bf16: spatial blocks groups = B * T, N = J in 15 .. 17,
+ * stride = 1, temporal = 0; temporal blocks groups = B * J, N = T <= 127, stride = J, temporal = 1.  D == 512, H == 8, groups % stride == 0;
+ * anything else: D3D_EUNSUP / D3D_EINVAL. */
+int d3d_op_qkv_attn_x3_small(const float* X_dev, const float* Wqkv_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev,
+                             float eps, int32_t groups, int32_t N, int32_t stride, int32_t D, int32_t H, int32_t temporal, float* out_dev,
+                             void* stream);
 
 /* ---- machine probes (measurement support; no reference counterpart) ------------------------------------------------ */
 /* What THIS device sustains for the two resources that co-limit the F16X3 GEMM k-loop, measured over about ms_target
