@@ -1,6 +1,6 @@
 // LDS layout helpers of the attention kernels (kernels_attn_x3.hip, kernels_attn_x3_long.hip, kernels_attn_bf16.hip and the attention steps of the fused
-// kernels_qkv_sattn.hip, kernels_qkv_tattn.hip, kernels_qkv_attn_bf16.hip), included inside namespace d3d: the row swizzles of the
-// K / Q and V planes, the hi / lo fp16 splits, the output patch.
+// kernels_qkv_sattn.hip, kernels_qkv_tattn.hip, kernels_qkv_attn_bf16.hip, kernels_qkv_attn_x3_small.hip), included inside namespace d3d: the row
+// swizzles of the K / Q and V planes, the hi / lo fp16 splits, the output patch.  The F16X3 tile arithmetic on these layouts is attn_x3_tile.h.
 #pragma once
 
 #include "kloop_common.h"   // h8 / h4 / u32x4 / u32x4_alias

@@ -1,0 +1,219 @@
+// The F16X3 attention arithmetic of the compiler-scheduled kernels, once: k_attn_temporal_x3 and k_attn_temporal_x3p (kernels_attn_x3.hip),
+// k_attn_temporal_x3l (kernels_attn_x3_long.hip) and qm_attention (kernels_qkv_attn_x3_small.hip) are their own staging, walks and
+// stores around these pieces, so every rounding-relevant statement -- MFMA order, key mask, exp2 argument, numerator split, output fma,
+// clamp and hi / lo split -- has one copy and the forms are bit-identical by construction (tests/test_gpu_attn_x3_digests.py pins the
+// bits).  The statically scheduled kernels (attn_x3s_half, qs_attention, k_qkv_tattn) state the same arithmetic as their own
+// instruction streams and are what these pieces are compared against.  Included inside namespace d3d, behind attn_lds.h.
+//
+//   S^T = K Q^T        rows = keys, column = this lane's query; acc = 64 s (q planes hold q / 8, k planes 8 k)
+//   e   = exp(S - max) exact two-pass softmax numerator, fp32, one query column per lane (halves h = 0 / 1 hold different keys)
+//   O^T = V^T E^T      E split in-register into hi / lo of 1024 e; acc = 2^13 sum e v (v planes hold 8 v)
+//   O   = O^T / (2^13 l) - v_query
+#pragma once
+
+#include "attn_lds.h"
+
+constexpr float X3_C_EXP = 1.4426950408889634f / 64.0f;   // acc = 64 s: scale and log2(e) in one fma feeding v_exp_f32
+
+// ---- this lane's query row as MFMA B fragments, d = 16 ks + 8 h .. + 7: from the global planes (o: element offset of a real row's
+// head columns + 8 h; !valid: zeros instead) or from an LDS Q plane pair at a row.  A row >= T is never stored: its caller gives it
+// zeros or a real row.
+__device__ __forceinline__ void x3_q_global(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, size_t o, bool valid, h8 (&qh)[4],
+                                            h8 (&ql)[4]) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    if (valid) {
+      qh[ks] = *reinterpret_cast<const h8*>(Ph + o + 16 * ks);
+      ql[ks] = *reinterpret_cast<const h8*>(Pl + o + 16 * ks);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { qh[ks][e] = (_Float16)0.0f; ql[ks][e] = (_Float16)0.0f; }
+    }
+  }
+}
+__device__ __forceinline__ void x3_q_lds(const unsigned char* sQh, const unsigned char* sQl, int row, int h, h8 (&qh)[4], h8 (&ql)[4]) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int qo = kswz(row, 2 * ks + h);
+    qh[ks] = *reinterpret_cast<const h8*>(sQh + qo);
+    ql[ks] = *reinterpret_cast<const h8*>(sQl + qo);
+  }
+}
+
+// ---- one 32 x 32 S^T tile of the K rows row0 .. row0 + 31 (r = lane & 31, h = lane >> 5): register q of half h is key
+// (q & 3) + 8 (q >> 2) + 4 h of the tile.  Three fp16 MFMAs per 16-deep d-step, small terms first.
+__device__ __forceinline__ f32x16 x3_score_tile(const unsigned char* sKh, const unsigned char* sKl, int row0, int r, int h, const h8 (&qh)[4],
+                                                const h8 (&ql)[4]) {
+  f32x16 s;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) s[q] = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int ko = kswz(row0 + r, 2 * ks + h);
+    const h8 kh = *reinterpret_cast<const h8*>(sKh + ko);
+    const h8 kl = *reinterpret_cast<const h8*>(sKl + ko);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], s, 0, 0, 0);
+  }
+  return s;
+}
+
+// keys >= T score -inf: their numerator is an exact 0, whatever bits the K rows hold.  Register q of lane half h, tile's first key key0.
+__device__ __forceinline__ float x3_mask_key(float s, int key0, int q, int h, int T) {
+  return key0 + (q & 3) + 8 * (q >> 2) + 4 * h >= T ? -INFINITY : s;
+}
+__device__ __forceinline__ void x3_mask_keys(f32x16& s, int key0, int h, int T) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q) s[q] = x3_mask_key(s[q], key0, q, h, T);
+}
+
+// numerators of one tile in place, e = 2^((acc - max) log2(e) / 64) with mb = max * X3_C_EXP, summed into l in register order
+__device__ __forceinline__ void x3_exp_tile(f32x16& s, float mb, float& l) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const float e = __builtin_amdgcn_exp2f(fmaf(s[q], X3_C_EXP, -mb));
+    s[q] = e;
+    l += e;
+  }
+}
+
+// ---- exact (max-subtracted) softmax over the NKT resident tiles of this query column: sacc becomes the numerators, their sum over
+// both lane halves is returned.  Only the last key tile can hold keys >= T, so only it pays for the mask.
+template <int NKT>
+__device__ __forceinline__ float x3_softmax(f32x16 (&sacc)[NKT], int h, int T) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      if (kt == NKT - 1) sacc[kt][q] = x3_mask_key(sacc[kt][q], kt * 32, q, h, T);
+      m = fmaxf(m, sacc[kt][q]);
+    }
+  }
+  m = fmaxf(m, __shfl_xor(m, 32, 64));
+  const float mb = m * X3_C_EXP;
+  float l = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) x3_exp_tile(sacc[kt], mb, l);
+  l += __shfl_xor(l, 32, 64);
+  return l;
+}
+
+// ---- O^T[d][query] += sum over the 32 keys of key tile kt of V^T[d][key] E^T[key][query]; the group's V rows start at plane row rb.
+// k-step s takes numerator registers 8 s .. 8 s + 7: element jj of lane half h is key 32 kt + 16 s + 8 (jj >> 2) + 4 h + (jj & 3), and
+// the V^T fragment is read in that order.  ds_read_b64_tr_b16: within a 16-lane group, lane 4 q + p supplies the address of (row k0 + q,
+// columns d0 + 4 p .. + 3) and lane i receives column d0 + i of the four rows, i.e. V[k0 .. k0 + 3][d] for this lane's d -- the MFMA A
+// fragment.
+// VMASK: for planes whose rows behind the group's T are not zeros -- compact planes, where they are the next group's (or the next
+// plane's) rows and may hold NaN / Inf of ANOTHER group (the GEMM epilogues store a NaN as a NaN).  E is an exact 0 there, and 0 x NaN is
+// NaN: the V bits of keys >= T are masked to +0 in registers; element e of a fragment is key k0 + e (e < 4) / k0 + 4 + e (e >= 4).  Only
+// the half-tile that holds keys >= T pays for it (wave-uniform branch).
+template <bool VMASK>
+__device__ __forceinline__ void x3_pv_tile(const f32x16& e, const unsigned char* sVh, const unsigned char* sVl, int rb, int kt, int T, int lane,
+                                           int h, f32x16 (&oacc)[2]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    h8 eh, el;                                                  // e in [0, 1] -> hi / lo of 2^10 e
+    {
+      float e8[8];
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) e8[jj] = e[8 * s + jj];
+      split8_e(e8, eh, el);
+    }
+    const int k0 = kt * 32 + 16 * s + 4 * h;                    // first key of this lane half's fragment
+    const int gi = lane & 15, tq_ = gi >> 2, tp_ = gi & 3;
+    const bool vpad = VMASK && kt * 32 + 16 * s + 16 > T;
+    u32x4 vmask = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    if (vpad) {
+#pragma unroll
+      for (int j2 = 0; j2 < 4; ++j2) {
+        const int ka = k0 + 8 * (j2 >> 1) + 2 * (j2 & 1);       // key of element 2 j2; element 2 j2 + 1 is the next key
+        vmask[j2] = (ka < T ? 0x0000ffffu : 0u) | (ka + 1 < T ? 0xffff0000u : 0u);
+      }
+    }
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      const int d0 = dt * 32 + 16 * ((lane >> 4) & 1);
+      const int ch = (d0 >> 3) + (tp_ >> 1), sub = (tp_ & 1) * 8;
+      const int o0 = vswz(rb + k0 + tq_, ch) + sub, o1 = vswz(rb + k0 + 8 + tq_, ch) + sub;
+      const s4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o0));
+      const s4v a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o1));
+      const s4v c0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o0));
+      const s4v c1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o1));
+      h8 vh, vl;
+      {
+        const h4 a0h = __builtin_bit_cast(h4, a0), a1h = __builtin_bit_cast(h4, a1);
+        const h4 c0h = __builtin_bit_cast(h4, c0), c1h = __builtin_bit_cast(h4, c1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { vh[i] = a0h[i]; vh[4 + i] = a1h[i]; vl[i] = c0h[i]; vl[4 + i] = c1h[i]; }
+      }
+      if (vpad) {
+        vh = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vh) & vmask);
+        vl = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vl) & vmask);
+      }
+      oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, eh, oacc[dt], 0, 0, 0);
+      oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, el, oacc[dt], 0, 0, 0);
+      oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, eh, oacc[dt], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the V^T reads / conversions of later k-steps from being hoisted (VGPR pressure)
+  }
+}
+
+// ---- output columns 8 g4 + 4 h .. + 3 of d half dt (acc: that half's O^T accumulator; vqh / vql: the query row's own V there, hi / lo
+// of 8 v): o = acc / (2^13 l) - v_query with inv = 1 / (2^13 l), the range-guard maximum, and hi / lo of 8 o for the proj GEMM.  The one
+// place this is rounded: fma, clamp, split.
+__device__ __forceinline__ void x3_out_chunk(const f32x16& acc, int g4, float inv, h4 vqh, h4 vql, float& amax, h4& oh, h4& ol) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float vq = ((float)vqh[e] + (float)vql[e]) * 0.125f;
+    const float o = __builtin_fmaf(acc[4 * g4 + e], inv, -vq);
+    amax = fmaxf(amax, fabsf(o));
+    const float sc = __builtin_amdgcn_fmed3f(o * 8.0f, -65504.0f, 65504.0f);
+    oh[e] = (_Float16)sc;
+    ol[e] = (_Float16)(sc - (float)oh[e]);
+  }
+}
+
+// ---- rows [row0, row0 + 32 nkt) of a unit's K (and V) planes, head hd, through registers into rows [0, 32 nkt) of the swizzled LDS
+// planes; rows >= T as zeros.  Batches of four 16-byte slots per thread, all global loads of a batch issued before its LDS writes.
+template <bool WITH_V>
+__device__ __forceinline__ void x3_stage_rows(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, unsigned char* sKh,
+                                              unsigned char* sKl, unsigned char* sVh, unsigned char* sVl, size_t tok0, int J, int D, int hd,
+                                              int row0, int nkt, int T, int tid, int nthr) {
+  constexpr int NIT = 4;
+  const int slots = nkt * 32 * 8;
+  const int D3 = 3 * D;
+  for (int base = 0; base < slots; base += NIT * nthr) {
+    uint4 kh[NIT], kl[NIT], vh[NIT], vl[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int idx = base + tid + it * nthr;
+      const int row = idx >> 3, c8 = idx & 7;
+      kh[it] = make_uint4(0, 0, 0, 0); kl[it] = kh[it]; vh[it] = kh[it]; vl[it] = kh[it];
+      if (idx < slots && row0 + row < T) {
+        const size_t o = (tok0 + (size_t)(row0 + row) * J) * D3 + hd * 64 + c8 * 8;
+        kh[it] = *reinterpret_cast<const uint4*>(Ph + o + D);
+        kl[it] = *reinterpret_cast<const uint4*>(Pl + o + D);
+        if (WITH_V) {
+          vh[it] = *reinterpret_cast<const uint4*>(Ph + o + 2 * D);
+          vl[it] = *reinterpret_cast<const uint4*>(Pl + o + 2 * D);
+        }
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int idx = base + tid + it * nthr;
+      const int row = idx >> 3, c8 = idx & 7;
+      if (idx < slots) {
+        const int ko = kswz(row, c8), vo = vswz(row, c8);
+        *reinterpret_cast<uint4*>(sKh + ko) = kh[it];
+        *reinterpret_cast<uint4*>(sKl + ko) = kl[it];
+        if (WITH_V) {
+          *reinterpret_cast<uint4*>(sVh + vo) = vh[it];
+          *reinterpret_cast<uint4*>(sVl + vo) = vl[it];
+        }
+      }
+    }
+  }
+}

@@ -13,6 +13,9 @@
 // (ds_read_b128) and the V fragment reads (ds_read_b64_tr_b16, the hardware transpose read: 4 keys of one d per lane)
 // are bank-conflict free) live in LDS for the whole workgroup; each wave owns 32 queries.  12 + 12 MFMAs of 32 cycles replace 32 + 32 fp32 MFMAs of 64
 // cycles per 32x32 score tile: 5.3x less matrix-pipe time than k_attn_temporal_f32.
+// The tile arithmetic itself -- query fragments, score tile, key mask, softmax, PV steps, output chunk, register staging -- is
+// attn_x3_tile.h: k_attn_temporal_x3 (the base form every other F16X3 attention kernel is pinned to) and k_attn_temporal_x3p are the
+// staging, synchronisation, walk and stores around those pieces; k_attn_temporal_x3s states the same arithmetic as its own instruction stream.
 #include "d3d_kernels.h"
 
 #include <math.h>
@@ -20,7 +23,8 @@
 
 namespace d3d {
 
-#include "attn_lds.h"   // typedefs, kswz / vkey / vswz, patch_wr / patch_rd, split_pair / split_pair_s / split8_e
+#include "attn_lds.h"       // typedefs, kswz / vkey / vswz, patch_wr / patch_rd, split_pair / split_pair_s / split8_e
+#include "attn_x3_tile.h"   // the tile arithmetic: query fragments, score tile, softmax, PV steps, output chunk, register staging
 
 constexpr int XDH = 64;
 
@@ -54,141 +58,26 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3(const _Float
   const int r = lane & 31, h = lane >> 5;
   const size_t tok0 = (size_t)b * T * J + j;          // token(t) = tok0 + t*J
 
-  // ---- stage K and V rows of this (batch, joint, head) (pad rows zero); all global loads are issued before the LDS writes
-  {
-    constexpr int NIT = 4;                            // TP*8 chunk slots / (64*NKT threads)
-    uint4 kh[NIT], kl[NIT], vh[NIT], vl[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int idx = tid + it * 64 * NKT;
-      const int row = idx >> 3, c8 = idx & 7;
-      kh[it] = make_uint4(0, 0, 0, 0); kl[it] = kh[it]; vh[it] = kh[it]; vl[it] = kh[it];
-      if (row < T) {
-        const size_t o = (tok0 + (size_t)row * J) * D3 + hd * XDH + c8 * 8;
-        kh[it] = *reinterpret_cast<const uint4*>(Ph + o + D);
-        kl[it] = *reinterpret_cast<const uint4*>(Pl + o + D);
-        vh[it] = *reinterpret_cast<const uint4*>(Ph + o + 2 * D);
-        vl[it] = *reinterpret_cast<const uint4*>(Pl + o + 2 * D);
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int idx = tid + it * 64 * NKT;
-      const int row = idx >> 3, c8 = idx & 7;
-      const int ko = kswz(row, c8), vo = vswz(row, c8);
-      *reinterpret_cast<uint4*>(sKh + ko) = kh[it];
-      *reinterpret_cast<uint4*>(sKl + ko) = kl[it];
-      *reinterpret_cast<uint4*>(sVh + vo) = vh[it];
-      *reinterpret_cast<uint4*>(sVl + vo) = vl[it];
-    }
-  }
+  // ---- stage K and V rows of this (batch, joint, head) (pad rows zero): one batch of four slots per thread covers the unit
+  __builtin_assume(tid < 64 * NKT);   // (blockDim = 64 NKT MU: the slot bound of the staging loop folds away)
+  x3_stage_rows<true>(Ph, Pl, sKh, sKl, sVh, sVl, tok0, J, D, hd, 0, NKT, T, tid, 64 * NKT);
 
-  // ---- this lane's query row as MFMA B fragments: d = 16 ks + 8 h .. +7
+  // ---- this lane's query row (rows >= T: zeros)
   const int tq = 32 * wave + r;
   h8 qh[4], ql[4];
-  {
-    const size_t o = (tok0 + (size_t)(tq < T ? tq : 0) * J) * D3 + hd * XDH + 8 * h;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      if (tq < T) {
-        qh[ks] = *reinterpret_cast<const h8*>(Ph + o + 16 * ks);
-        ql[ks] = *reinterpret_cast<const h8*>(Pl + o + 16 * ks);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { qh[ks][e] = (_Float16)0.0f; ql[ks][e] = (_Float16)0.0f; }
-      }
-    }
-  }
+  x3_q_global(Ph, Pl, (tok0 + (size_t)(tq < T ? tq : 0) * J) * D3 + hd * XDH + 8 * h, tq < T, qh, ql);
   __syncthreads();
 
-  // ---- S^T tiles: rows = keys kt*32 + (reg&3) + 8*(reg>>2) + 4*h, column = query tq; acc = 64 * s
+  // ---- S^T tiles, softmax numerators (in sacc) and their sum, O^T
   f32x16 sacc[NKT];
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sacc[kt][q] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int ko = kswz(kt * 32 + r, 2 * ks + h);
-      const h8 kh = *reinterpret_cast<const h8*>(sKh + ko);
-      const h8 kl = *reinterpret_cast<const h8*>(sKl + ko);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], sacc[kt], 0, 0, 0);
-    }
-  }
-
-  // ---- exact (max-subtracted) softmax numerator over the keys of this query column, fp32.  acc = 64 s; the scale and
-  // log2(e) are folded into one fma feeding v_exp_f32: e = 2^((acc - max) * log2(e)/64).  Only the last key tile can hold
-  // padding keys (>= T), so only it pays for the mask.
-  float m = -INFINITY;
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      if (kt == NKT - 1) {
-        const int key = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-        if (key >= T) sacc[kt][q] = -INFINITY;
-      }
-      m = fmaxf(m, sacc[kt][q]);
-    }
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  constexpr float C_EXP = 1.4426950408889634f / 64.0f;
-  const float mb = m * C_EXP;
-  float l = 0.f;
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float e = __builtin_amdgcn_exp2f(fmaf(sacc[kt][q], C_EXP, -mb));
-      sacc[kt][q] = e;
-      l += e;
-    }
-  l += __shfl_xor(l, 32, 64);
-
-  // ---- O^T[d][query] = sum_key V^T[d][key] * E^T[key][query].  k-step (kt, s) takes accumulator registers 8s..8s+7:
-  // element jj of lane half h is key kt*32 + 16 s + 8 (jj>>2) + 4 h + (jj&3); the V^T fragment is read in that order.
+  for (int kt = 0; kt < NKT; ++kt) sacc[kt] = x3_score_tile(sKh, sKl, kt * 32, r, h, qh, ql);
+  const float l = x3_softmax<NKT>(sacc, h, T);
   f32x16 oacc[2];
 #pragma unroll
   for (int q = 0; q < 16; ++q) { oacc[0][q] = 0.f; oacc[1][q] = 0.f; }
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      h8 eh, el;                                                  // e in [0,1] -> hi/lo of 2^10 e
-      {
-        float e8[8];
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) e8[jj] = sacc[kt][8 * s + jj];
-        split8_e(e8, eh, el);
-      }
-      const int k0 = kt * 32 + 16 * s + 4 * h;
-      // ds_read_b64_tr_b16: within a 16-lane group, lane 4q+p supplies the address of (row k0+q, columns d0+4p..+3) and
-      // lane i receives column d0+i of the four rows, i.e. V[k0..k0+3][d] for this lane's d -- the MFMA A fragment.
-      const int gi = lane & 15, tq_ = gi >> 2, tp_ = gi & 3;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int d0 = dt * 32 + 16 * ((lane >> 4) & 1);
-        const int ch = (d0 >> 3) + (tp_ >> 1), sub = (tp_ & 1) * 8;
-        const int o0 = vswz(k0 + tq_, ch) + sub, o1 = vswz(k0 + 8 + tq_, ch) + sub;
-        const s4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o0));
-        const s4v a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o1));
-        const s4v c0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o0));
-        const s4v c1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o1));
-        h8 vh, vl;
-        {
-          const h4 a0h = __builtin_bit_cast(h4, a0), a1h = __builtin_bit_cast(h4, a1);
-          const h4 c0h = __builtin_bit_cast(h4, c0), c1h = __builtin_bit_cast(h4, c1);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { vh[e] = a0h[e]; vh[4 + e] = a1h[e]; vl[e] = c0h[e]; vl[4 + e] = c1h[e]; }
-        }
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, eh, oacc[dt], 0, 0, 0);
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, el, oacc[dt], 0, 0, 0);
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, eh, oacc[dt], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // keep the V^T reads / conversions of later k-steps from being hoisted (VGPR pressure)
-    }
-  }
+  for (int kt = 0; kt < NKT; ++kt) x3_pv_tile<false>(sacc[kt], sVh, sVl, 0, kt, T, lane, h, oacc);
 
   // ---- O = O^T / (2^13 l) - v_query, written as hi/lo planes of 8*o for the proj GEMM
   if (tq < T && unit_ok) {
@@ -202,18 +91,8 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3(const _Float
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int d = dt * 32 + 8 * g4 + 4 * h;
-        const h4 vqh = *reinterpret_cast<const h4*>(Ph + vo + d);
-        const h4 vql = *reinterpret_cast<const h4*>(Pl + vo + d);
         h4 oh, ol;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float vq = ((float)vqh[e] + (float)vql[e]) * 0.125f;
-          const float o = __builtin_fmaf(oacc[dt][4 * g4 + e], inv, -vq);   // stated: every form of this kernel must round the same way
-          amax = fmaxf(amax, fabsf(o));
-          const float sc = __builtin_amdgcn_fmed3f(o * 8.0f, -65504.0f, 65504.0f);
-          oh[e] = (_Float16)sc;
-          ol[e] = (_Float16)(sc - (float)oh[e]);
-        }
+        x3_out_chunk(oacc[dt], g4, inv, *reinterpret_cast<const h4*>(Ph + vo + d), *reinterpret_cast<const h4*>(Pl + vo + d), amax, oh, ol);
         *reinterpret_cast<h4*>(out_x3 + oo + pair_col(d)) = oh;
         *reinterpret_cast<h4*>(out_x3 + oo + pair_col(d) + PAIR_LO) = ol;
       }
@@ -238,6 +117,8 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3(const _Float
 // MU > 1 (NKT == 1: groups of <= 32 tokens, the spatial blocks): every wave is its own persistent worker on its own LDS
 // slice (units blockIdx * MU + wave, + gridDim * MU, ...); the barriers become wave-local waits, so the MU waves of a
 // workgroup drift apart and their load / MFMA / VALU phases overlap.
+// The arithmetic is attn_x3_tile.h's, as in the kernel above: what differs is the DMA plan, the syncs, v_query from the V planes in LDS,
+// the output patch, and (MU > 1) the V fragments of pad keys masked in registers.
 // wave-uniform pointer pinned into an SGPR pair (the DMA then takes the saddr + 32-bit voffset form)
 __device__ __forceinline__ const char* sgpr_ptr_x(const char* p) {
   const unsigned long long v = reinterpret_cast<unsigned long long>(p);
@@ -337,12 +218,7 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3p(const _Floa
   h8 qh[4], ql[4];
   auto load_q = [&](size_t tok0, int hd) {
     const int tq = 32 * wave + r;
-    const size_t o = (tok0 + (size_t)(tq < T ? tq : 0) * J) * D3 + hd * XDH + 8 * h;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      qh[ks] = *reinterpret_cast<const h8*>(Ph + o + 16 * ks);     // rows >= T reuse row 0: their columns are never stored
-      ql[ks] = *reinterpret_cast<const h8*>(Pl + o + 16 * ks);
-    }
+    x3_q_global(Ph, Pl, (tok0 + (size_t)(tq < T ? tq : 0) * J) * D3 + hd * XDH + 8 * h, true, qh, ql);   // rows >= T reuse row 0: never stored
   };
 
   int hd;
@@ -389,46 +265,11 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3p(const _Floa
         }
     }
 
-    // ---- S^T tiles (rows = keys, column = query tq); acc = 64 * s
+    // ---- S^T tiles, softmax numerators (in sacc) and their sum
     f32x16 sacc[NKT];
 #pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sacc[kt][q] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const int ko = kswz(kt * 32 + r, 2 * ks + h);
-        const h8 kh = *reinterpret_cast<const h8*>(sKh + ko);
-        const h8 kl = *reinterpret_cast<const h8*>(sKl + ko);
-        sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], sacc[kt], 0, 0, 0);
-        sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], sacc[kt], 0, 0, 0);
-        sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], sacc[kt], 0, 0, 0);
-      }
-    }
-    float m = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        if (kt == NKT - 1) {
-          const int key = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-          if (key >= T) sacc[kt][q] = -INFINITY;
-        }
-        m = fmaxf(m, sacc[kt][q]);
-      }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    constexpr float C_EXP = 1.4426950408889634f / 64.0f;
-    const float mb = m * C_EXP;
-    float l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float e = __builtin_amdgcn_exp2f(fmaf(sacc[kt][q], C_EXP, -mb));
-        sacc[kt][q] = e;
-        l += e;
-      }
-    l += __shfl_xor(l, 32, 64);
+    for (int kt = 0; kt < NKT; ++kt) sacc[kt] = x3_score_tile(sKh, sKl, kt * 32, r, h, qh, ql);
+    const float l = x3_softmax<NKT>(sacc, h, T);
 
     if (WAVEP) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's K fragments are in registers
     else D3D_ATTN_SYNC();       // V(u) landed (and the stores above acknowledged); everybody is done with K
@@ -442,62 +283,14 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3p(const _Floa
       if (WAVEP) dma(2, tok0_n, hd_n, vb ^ 1);   // (that buffer was last read by unit u-1)
     }
 
-    // ---- O^T[d][query] = sum_key V^T[d][key] E^T[key][query]
+    // ---- O^T.  WAVEP: the planes hold T rows, so the V fragments of the pad keys [T, TP) are whatever follows the plane -- the wave's
+    // other V buffer (another unit's V) or the next wave's K: masked in registers
     f32x16 oacc[2];
 #pragma unroll
     for (int q = 0; q < 16; ++q) { oacc[0][q] = 0.f; oacc[1][q] = 0.f; }
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        h8 eh, el;
-        {
-          float e8[8];
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) e8[jj] = sacc[kt][8 * s2 + jj];
-          split8_e(e8, eh, el);
-        }
-        const int k0 = kt * 32 + 16 * s2 + 4 * h;
-        const int gi = lane & 15, tq_ = gi >> 2, tp_ = gi & 3;
-        // WAVEP: the planes hold T rows, so the V fragments of the pad keys [T, TP) are whatever follows the plane -- the wave's other V
-        // buffer (another unit's V) or the next wave's K -- and may be NaN / Inf planes of ANOTHER group (the GEMM epilogues store a NaN
-        // as a NaN): E is an exact 0 there, and 0 x NaN is NaN.  Their bits are masked to +0 in registers; element e of a fragment is
-        // key k0 + e (e < 4) / k0 + 4 + e (e >= 4).  Only the half-tile that holds keys >= T pays for it (wave-uniform branch).
-        const bool vpad = WAVEP && kt * 32 + 16 * s2 + 16 > T;
-        u32x4 vmask = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-        if (vpad) {
-#pragma unroll
-          for (int j2 = 0; j2 < 4; ++j2) {
-            const int ka = k0 + 8 * (j2 >> 1) + 2 * (j2 & 1);      // key of element 2 j2; element 2 j2 + 1 is the next key
-            vmask[j2] = (ka < T ? 0x0000ffffu : 0u) | (ka + 1 < T ? 0xffff0000u : 0u);
-          }
-        }
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const int d0 = dt * 32 + 16 * ((lane >> 4) & 1);
-          const int ch = (d0 >> 3) + (tp_ >> 1), sub = (tp_ & 1) * 8;
-          const int o0 = vswz(k0 + tq_, ch) + sub, o1 = vswz(k0 + 8 + tq_, ch) + sub;
-          const s4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o0));
-          const s4v a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o1));
-          const s4v c0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o0));
-          const s4v c1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o1));
-          h8 vh, vl;
-          {
-            const h4 a0h = __builtin_bit_cast(h4, a0), a1h = __builtin_bit_cast(h4, a1);
-            const h4 c0h = __builtin_bit_cast(h4, c0), c1h = __builtin_bit_cast(h4, c1);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { vh[e] = a0h[e]; vh[4 + e] = a1h[e]; vl[e] = c0h[e]; vl[4 + e] = c1h[e]; }
-          }
-          if (vpad) {
-            vh = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vh) & vmask);
-            vl = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vl) & vmask);
-          }
-          oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, eh, oacc[dt], 0, 0, 0);
-          oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, el, oacc[dt], 0, 0, 0);
-          oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, eh, oacc[dt], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      x3_pv_tile<WAVEP>(sacc[kt], sVh, sVl, 0, kt, T, lane, h, oacc);
       // the next unit's query fragments go into the dead Q registers once two score tiles have been consumed (register room)
       if (kt == (NKT > 2 ? 2 : NKT - 1) && has_next) load_q(tok0_n, hd_n);
     }
@@ -515,15 +308,7 @@ __global__ __launch_bounds__(64 * NKT * MU) void k_attn_temporal_x3p(const _Floa
           const h4 vqh = *reinterpret_cast<const h4*>(sVh + vo);
           const h4 vql = *reinterpret_cast<const h4*>(sVl + vo);
           h4 oh, ol;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float vq = ((float)vqh[e] + (float)vql[e]) * 0.125f;
-            const float o = __builtin_fmaf(oacc[dt][4 * g4 + e], inv, -vq);   // stated: every form of this kernel must round the same way
-            amax = fmaxf(amax, fabsf(o));
-            const float sc = __builtin_amdgcn_fmed3f(o * 8.0f, -65504.0f, 65504.0f);
-            oh[e] = (_Float16)sc;
-            ol[e] = (_Float16)(sc - (float)oh[e]);
-          }
+          x3_out_chunk(oacc[dt], g4, inv, vqh, vql, amax, oh, ol);
           // columns 8 g4 + 4 h .. + 3 of line dt: hi halves in chunk g4, lo halves in chunk 4 + g4 (pair layout)
           patch_wr(WAVEP ? patch : patch1, r, h, g4, oh, ol);
           if (g4 == 3) {

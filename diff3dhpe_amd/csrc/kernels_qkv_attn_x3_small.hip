@@ -14,7 +14,7 @@
 // columns; accumulator column tile j of wave wn IS part j (q, k, v) at head columns 16 wn .. + 15.  Per output element the same three
 // fp16 MFMAs in the same k order as every other F16X3 GEMM shape, and the epilogue arithmetic of x3q_epilogue8<LN-folded, planes> (fold
 // with the row statistics partials, bias, hi / lo split): the LDS planes hold bit for bit what the unfused qkv GEMM writes to HBM.  The
-// attention step is k_attn_temporal_x3<NKT>'s arithmetic (what launch_attn_temporal_x3 runs for N <= 127, and what qs_attention of
+// attention step is attn_x3_tile.h's arithmetic, the pieces of k_attn_temporal_x3<NKT> (what launch_attn_temporal_x3 runs for N <= 127, and what qs_attention of
 // kernels_qkv_sattn.hip reproduces for the joints of a frame) on those planes, per (group, 32-query tile) job over the eight waves.
 // The planes are COMPACT: group u of the tile starts at plane row u N, so the pad keys [N, 32 ceil(N / 32)) of a group are the next
 // group's rows (or the tile's pad rows, or the rows behind the plane): their scores are overwritten with -inf and their V^T fragment
@@ -38,6 +38,7 @@ namespace {
 
 #include "kloop_common.h"
 #include "attn_lds.h"
+#include "attn_x3_tile.h"
 
 QF_SHAPE(4, 3, 128, 192, 2, 3);                                          // 128 x 192 x 32 stage of 40960 bytes
 constexpr int QM_ROWS = 127;                                             // token rows of a tile at most
@@ -80,8 +81,8 @@ __device__ __forceinline__ unsigned qm_row(const QmArgs& a, int mt, int i) {
   return qm_unit_row(a, mt * a.g + u) + (unsigned)(t * a.udiv);
 }
 
-// One 32-query tile `qt` of the group whose plane rows start at rb: k_attn_temporal_x3<NKT>'s arithmetic (same MFMAs in the same order,
-// same softmax, same conversions) on the LDS planes; outputs through the wave's patch as whole 128-byte lines of the pair layout.
+// One 32-query tile `qt` of the group whose plane rows start at rb: the pieces of attn_x3_tile.h (k_attn_temporal_x3<NKT>'s arithmetic) on
+// the LDS planes; outputs through the wave's patch as whole 128-byte lines of the pair layout.
 template <int NKT>
 __device__ __forceinline__ void qm_attention(unsigned char* lds, int wave, int lane, int rb, int qt, int T, _Float16* out0, size_t tstride,
                                              unsigned* rw) {
@@ -94,109 +95,18 @@ __device__ __forceinline__ void qm_attention(unsigned char* lds, int wave, int l
   const int tq = 32 * qt + r;
   const int tqc = tq < T ? tq : 0;                                   // rows >= T reuse row 0: never stored
   h8 qh[4], ql[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    const int qo = kswz(rb + tqc, 2 * ks + h);
-    qh[ks] = *reinterpret_cast<const h8*>(sQh + qo);
-    ql[ks] = *reinterpret_cast<const h8*>(sQh + QM_PLANE + qo);
-  }
-  // ---- S^T tiles: rows = keys kt * 32 + (reg & 3) + 8 (reg >> 2) + 4 h, column = query tq; acc = 64 s
+  x3_q_lds(sQh, sQh + QM_PLANE, rb + tqc, h, qh, ql);
+  // ---- S^T tiles, softmax numerators (in sacc) and their sum; only the last key tile can hold keys of other groups
   f32x16 sacc[NKT];
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sacc[kt][q] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int ko = kswz(rb + kt * 32 + r, 2 * ks + h);
-      const h8 kh = *reinterpret_cast<const h8*>(sKh + ko);
-      const h8 kl = *reinterpret_cast<const h8*>(sKh + QM_PLANE + ko);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], sacc[kt], 0, 0, 0);
-    }
-  }
-  // ---- exact softmax numerators over the keys of this query column (fp32); only the last key tile can hold keys of other groups
-  float m = -INFINITY;
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      if (kt == NKT - 1) {
-        const int key = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-        if (key >= T) sacc[kt][q] = -INFINITY;
-      }
-      m = fmaxf(m, sacc[kt][q]);
-    }
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  constexpr float C_EXP = 1.4426950408889634f / 64.0f;
-  const float mb = m * C_EXP;
-  float l = 0.f;
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float e = __builtin_amdgcn_exp2f(fmaf(sacc[kt][q], C_EXP, -mb));
-      sacc[kt][q] = e;
-      l += e;
-    }
-  l += __shfl_xor(l, 32, 64);
-  // ---- O^T[d][query] = sum_key V^T[d][key] E^T[key][query]
+  for (int kt = 0; kt < NKT; ++kt) sacc[kt] = x3_score_tile(sKh, sKh + QM_PLANE, rb + kt * 32, r, h, qh, ql);
+  const float l = x3_softmax<NKT>(sacc, h, T);
+  // ---- O^T; the pad keys [T, 32 NKT) are other groups' rows here and zeros in the stand-alone kernel: their V bits are masked
   f32x16 oacc[2];
 #pragma unroll
   for (int q = 0; q < 16; ++q) { oacc[0][q] = 0.f; oacc[1][q] = 0.f; }
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      h8 eh, el;
-      {
-        float e8[8];
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) e8[jj] = sacc[kt][8 * s2 + jj];
-        split8_e(e8, eh, el);
-      }
-      const int k0 = kt * 32 + 16 * s2 + 4 * h;                       // first key of this lane half's fragment
-      const int gi = lane & 15, tq_ = gi >> 2, tp_ = gi & 3;
-      // pad keys [T, 32 NKT) are other groups' rows here and zeros in the stand-alone kernel: E is an exact 0 there, and 0 x NaN / Inf of
-      // a neighbour would be NaN -- their V bits are masked to +0 in registers (element e of a fragment is key k0 + e, e < 4, and
-      // k0 + 4 + e, e >= 4).  Only the half-tile that holds keys >= T pays for it (wave-uniform branch).
-      const bool vpad = kt * 32 + 16 * s2 + 16 > T;
-      u32x4 vmask = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-      if (vpad) {
-#pragma unroll
-        for (int j2 = 0; j2 < 4; ++j2) {
-          const int ka = k0 + 8 * (j2 >> 1) + 2 * (j2 & 1);
-          vmask[j2] = (ka < T ? 0x0000ffffu : 0u) | (ka + 1 < T ? 0xffff0000u : 0u);
-        }
-      }
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int d0 = dt * 32 + 16 * ((lane >> 4) & 1);
-        const int ch = (d0 >> 3) + (tp_ >> 1), sub = (tp_ & 1) * 8;
-        const int o0 = vswz(rb + k0 + tq_, ch) + sub, o1 = vswz(rb + k0 + 8 + tq_, ch) + sub;
-        const s4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o0));
-        const s4v a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVh + o1));
-        const s4v c0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o0));
-        const s4v c1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(sVl + o1));
-        h8 vh, vl;
-        {
-          const h4 a0h = __builtin_bit_cast(h4, a0), a1h = __builtin_bit_cast(h4, a1);
-          const h4 c0h = __builtin_bit_cast(h4, c0), c1h = __builtin_bit_cast(h4, c1);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { vh[e] = a0h[e]; vh[4 + e] = a1h[e]; vl[e] = c0h[e]; vl[4 + e] = c1h[e]; }
-        }
-        if (vpad) {
-          vh = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vh) & vmask);
-          vl = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, vl) & vmask);
-        }
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, eh, oacc[dt], 0, 0, 0);
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, el, oacc[dt], 0, 0, 0);
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, eh, oacc[dt], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // keeps the V^T reads / conversions of later k-steps from being hoisted (VGPR pressure)
-    }
-  }
+  for (int kt = 0; kt < NKT; ++kt) x3_pv_tile<true>(sacc[kt], sVh, sVl, rb, kt, T, lane, h, oacc);
   // ---- O = O^T / (2^13 l) - v_query (v_query from the V planes), packed as hi / lo of 8 o; whole lines out through the patch
   u32x4 po[8];                  // [dt * 4 + pp]: row 32 qt + 8 pp + (lane >> 3), chunk lane & 7 of line dt
   {
@@ -207,18 +117,8 @@ __device__ __forceinline__ void qm_attention(unsigned char* lds, int wave, int l
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int vo = vswz(rb + tqc, dt * 4 + g4) + 8 * h;
-        const h4 vqh = *reinterpret_cast<const h4*>(sVh + vo);
-        const h4 vql = *reinterpret_cast<const h4*>(sVl + vo);
         h4 oh, ol;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float vq = ((float)vqh[e] + (float)vql[e]) * 0.125f;
-          const float o = __builtin_fmaf(oacc[dt][4 * g4 + e], inv, -vq);   // stated: every form of this arithmetic must round the same way
-          amax = fmaxf(amax, fabsf(o));
-          const float sc = __builtin_amdgcn_fmed3f(o * 8.0f, -65504.0f, 65504.0f);
-          oh[e] = (_Float16)sc;
-          ol[e] = (_Float16)(sc - (float)oh[e]);
-        }
+        x3_out_chunk(oacc[dt], g4, inv, *reinterpret_cast<const h4*>(sVh + vo), *reinterpret_cast<const h4*>(sVl + vo), amax, oh, ol);
         patch_wr(patch, r, h, g4, oh, ol);
       }
       asm volatile("" ::: "memory");     // (the rows read back were written by other lanes)
