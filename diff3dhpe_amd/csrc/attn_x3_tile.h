@@ -14,6 +14,13 @@
 #include "attn_lds.h"
 
 constexpr float X3_C_EXP = 1.4426950408889634f / 64.0f;   // acc = 64 s: scale and log2(e) in one fma feeding v_exp_f32
+// The same constant for a head width DH.  The planes hold raw q and 8 k whatever the width, so acc = 8 q.k and the exponent argument is
+// acc log2(e) / (8 sqrt(DH)): X3_C_EXP itself at 64; at 32 (kernels_attn_x3_h32.hip) evaluated in double and rounded once.
+template <int DH>
+constexpr float x3_c_exp() {
+  static_assert(DH == 64 || DH == 32, "head widths with a tile form");
+  return DH == 64 ? X3_C_EXP : (float)(1.4426950408889634 / (8.0 * 5.656854249492380195 /* sqrt(32) */));
+}
 
 // ---- this lane's query row as MFMA B fragments, d = 16 ks + 8 h .. + 7: from the global planes (o: element offset of a real row's
 // head columns + 8 h; !valid: zeros instead) or from an LDS Q plane pair at a row.  A row >= T is never stored: its caller gives it
@@ -41,14 +48,16 @@ __device__ __forceinline__ void x3_q_lds(const unsigned char* sQh, const unsigne
 }
 
 // ---- one 32 x 32 S^T tile of the K rows row0 .. row0 + 31 (r = lane & 31, h = lane >> 5): register q of half h is key
-// (q & 3) + 8 (q >> 2) + 4 h of the tile.  Three fp16 MFMAs per 16-deep d-step, small terms first.
+// (q & 3) + 8 (q >> 2) + 4 h of the tile.  Three fp16 MFMAs per 16-deep d-step, small terms first.  KS0 / NKS: the d-steps of the 64-wide
+// LDS row that belong to the head (all four; a 32-wide head of a pair takes two).
+template <int KS0 = 0, int NKS = 4>
 __device__ __forceinline__ f32x16 x3_score_tile(const unsigned char* sKh, const unsigned char* sKl, int row0, int r, int h, const h8 (&qh)[4],
                                                 const h8 (&ql)[4]) {
   f32x16 s;
 #pragma unroll
   for (int q = 0; q < 16; ++q) s[q] = 0.f;
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
+  for (int ks = KS0; ks < KS0 + NKS; ++ks) {
     const int ko = kswz(row0 + r, 2 * ks + h);
     const h8 kh = *reinterpret_cast<const h8*>(sKh + ko);
     const h8 kl = *reinterpret_cast<const h8*>(sKl + ko);
@@ -69,10 +78,12 @@ __device__ __forceinline__ void x3_mask_keys(f32x16& s, int key0, int h, int T) 
 }
 
 // numerators of one tile in place, e = 2^((acc - max) log2(e) / 64) with mb = max * X3_C_EXP, summed into l in register order
+// (DH: the head width, x3_c_exp<DH>() in place of X3_C_EXP)
+template <int DH = 64>
 __device__ __forceinline__ void x3_exp_tile(f32x16& s, float mb, float& l) {
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    const float e = __builtin_amdgcn_exp2f(fmaf(s[q], X3_C_EXP, -mb));
+    const float e = __builtin_amdgcn_exp2f(fmaf(s[q], x3_c_exp<DH>(), -mb));
     s[q] = e;
     l += e;
   }
@@ -80,7 +91,7 @@ __device__ __forceinline__ void x3_exp_tile(f32x16& s, float mb, float& l) {
 
 // ---- exact (max-subtracted) softmax over the NKT resident tiles of this query column: sacc becomes the numerators, their sum over
 // both lane halves is returned.  Only the last key tile can hold keys >= T, so only it pays for the mask.
-template <int NKT>
+template <int NKT, int DH = 64>
 __device__ __forceinline__ float x3_softmax(f32x16 (&sacc)[NKT], int h, int T) {
   float m = -INFINITY;
 #pragma unroll
@@ -92,10 +103,10 @@ __device__ __forceinline__ float x3_softmax(f32x16 (&sacc)[NKT], int h, int T) {
     }
   }
   m = fmaxf(m, __shfl_xor(m, 32, 64));
-  const float mb = m * X3_C_EXP;
+  const float mb = m * x3_c_exp<DH>();
   float l = 0.f;
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) x3_exp_tile(sacc[kt], mb, l);
+  for (int kt = 0; kt < NKT; ++kt) x3_exp_tile<DH>(sacc[kt], mb, l);
   l += __shfl_xor(l, 32, 64);
   return l;
 }
@@ -109,7 +120,8 @@ __device__ __forceinline__ float x3_softmax(f32x16 (&sacc)[NKT], int h, int T) {
 // plane's) rows and may hold NaN / Inf of ANOTHER group (the GEMM epilogues store a NaN as a NaN).  E is an exact 0 there, and 0 x NaN is
 // NaN: the V bits of keys >= T are masked to +0 in registers; element e of a fragment is key k0 + e (e < 4) / k0 + 4 + e (e >= 4).  Only
 // the half-tile that holds keys >= T pays for it (wave-uniform branch).
-template <bool VMASK>
+// DT0 / NDT: the 32-column halves of the 64-wide LDS row that belong to the head (both; a 32-wide head of a pair takes its own one).
+template <bool VMASK, int DT0 = 0, int NDT = 2>
 __device__ __forceinline__ void x3_pv_tile(const f32x16& e, const unsigned char* sVh, const unsigned char* sVl, int rb, int kt, int T, int lane,
                                            int h, f32x16 (&oacc)[2]) {
 #pragma unroll
@@ -133,7 +145,7 @@ __device__ __forceinline__ void x3_pv_tile(const f32x16& e, const unsigned char*
       }
     }
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
+    for (int dt = DT0; dt < DT0 + NDT; ++dt) {
       const int d0 = dt * 32 + 16 * ((lane >> 4) & 1);
       const int ch = (d0 >> 3) + (tp_ >> 1), sub = (tp_ & 1) * 8;
       const int o0 = vswz(rb + k0 + tq_, ch) + sub, o1 = vswz(rb + k0 + 8 + tq_, ch) + sub;
@@ -177,6 +189,7 @@ __device__ __forceinline__ void x3_out_chunk(const f32x16& acc, int g4, float in
 
 // ---- rows [row0, row0 + 32 nkt) of a unit's K (and V) planes, head hd, through registers into rows [0, 32 nkt) of the swizzled LDS
 // planes; rows >= T as zeros.  Batches of four 16-byte slots per thread, all global loads of a batch issued before its LDS writes.
+// (hd counts heads of 64 columns: for 32-wide heads it is the index of the pair.)
 template <bool WITH_V>
 __device__ __forceinline__ void x3_stage_rows(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, unsigned char* sKh,
                                               unsigned char* sKl, unsigned char* sVh, unsigned char* sVl, size_t tok0, int J, int D, int hd,

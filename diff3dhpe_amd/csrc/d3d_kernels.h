@@ -387,6 +387,11 @@ bool attn_temporal_x3_ok(int T, int D, int H);
 hipError_t launch_attn_temporal_x3_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                         hipStream_t s);
 bool attn_temporal_x3_long_ok(int T, int D, int H);
+// ---- kernels_attn_x3_h32.hip: the same attention for heads of 32 columns (D == 32 H, H even: two adjacent heads share the 128-byte LDS
+// rows of the kernels above), groups of T <= 256 tokens.  The contract of launch_attn_temporal_x3: same planes in (raw q, 8 k, 8 v), same
+// pair layout out; spatial blocks call it with (B T, J, 1).
+hipError_t launch_attn_x3_h32(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h32_ok(int N, int D, int H);
 // ---- kernels_attn_f32_long.hip: launch_attn_temporal_f32's attention (exact fp32, v_mfma_f32_32x32x2_f32) for windows of any length:
 // the keys stream through LDS in chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out, no
 // pair-layout form; bit-identical to launch_attn_temporal_f32 wherever that runs (T <= 256).  The launch also refuses

@@ -62,6 +62,9 @@ struct BlockPlan {
   bool fused_sp = false, fused_tp = false;
   // FOLD: the temporal blocks' attention on the key-streaming kernel (kernels_attn_x3_long.hip: windows of more than 256 frames)
   bool tp_long = false;
+  // FOLD: every block's attention on the kernel for heads of 32 columns (kernels_attn_x3_h32.hip: D == 32 H, which no other F16X3
+  // attention kernel takes); always the two-kernel branch
+  bool attn_h32 = false;
   // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel (kernels_attn_f32_long.hip: windows of more than 256
   // frames, which k_attn_temporal_f32 cannot hold in LDS); false = k_attn_generic there
   bool tp_long_f32 = false;
@@ -137,6 +140,9 @@ struct d3d_engine {
   // "long_temporal_f32" (on by default): an FP32 engine whose window is longer than 256 frames runs its temporal blocks' attention on the
   // key-streaming fp32 MFMA kernel (kernels_attn_f32_long.hip); 0 = the generic one-thread-per-row kernel.  F16X3 / BF16 engines: no effect
   bool opt_long_temporal_f32 = true;
+  // "attn_h32": an F16X3 engine whose heads are 32 columns wide (embed_dim 256 with 8 heads) runs the folded flow with the attention of
+  // every block on kernels_attn_x3_h32.hip (windows of up to 256 frames); 0 = the plain row-kernel flow with the generic fp32 attention
+  bool opt_attn_h32 = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -156,7 +162,7 @@ struct d3d_engine {
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
   // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip, "long_temporal_f32_last" = the same for
-  // kernels_attn_f32_long.hip
+  // kernels_attn_f32_long.hip, "attn_h32_last" = whether the blocks ran kernels_attn_x3_h32.hip
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -404,8 +410,12 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   BlockPlan p;
   // windows of more than 256 frames: no F16X3 attention kernel holds their keys in LDS; the long kernel streams them
   const bool tp_long = e->opt_long_temporal && T > 256 && attn_temporal_x3_long_ok(T, D, H);
-  if (x3 && (attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H) && D % 32 == 0 && e->opt_fold_layernorm) {
+  // heads of 32 columns: the one attention kernel of that width takes both block types (no D == 64 H predicate holds there, so the fused
+  // kernels, block 0 direct and the post-norm in fc2 stay off by their own predicates)
+  const bool h32 = e->opt_attn_h32 && attn_x3_h32_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
+  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32) && D % 32 == 0 && e->opt_fold_layernorm) {
     p.flow = BlockPlan::FOLD;
+    p.attn_h32 = h32;
     p.tp_long = tp_long;      // (qkv_tattn_ok refuses T > 255: such temporal blocks take the two-kernel branch)
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
@@ -607,7 +617,8 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
     {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD4, s);
-      if (temporal && pl.tp_long) HIP_TRY(launch_attn_temporal_x3_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
+      if (pl.attn_h32) HIP_TRY(temporal ? launch_attn_x3_h32(QKVh, QKVl, AOx, B, T, J, D, e->H, s) : launch_attn_x3_h32(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
+      else if (temporal && pl.tp_long) HIP_TRY(launch_attn_temporal_x3_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
     }
@@ -950,7 +961,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 138; }   // 138: option / info key "small_tiles", info key "small_tiles_last", d3d_op_qkv_attn_x3_small
+int d3d_version(void) { return 139; }   // 139: option / info key "attn_h32", info key "attn_h32_last", d3d_op_attention_h32
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1439,6 +1450,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   }
   else if (k == "long_temporal") e->opt_long_temporal = value != 0;
   else if (k == "long_temporal_f32") e->opt_long_temporal_f32 = value != 0;
+  else if (k == "attn_h32") e->opt_attn_h32 = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1509,6 +1521,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "long_temporal") *value = e->opt_long_temporal ? 1 : 0;
   else if (k == "long_temporal_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.tp_long;
   else if (k == "long_temporal_f32") *value = e->opt_long_temporal_f32 ? 1 : 0;
+  else if (k == "attn_h32") *value = e->opt_attn_h32 ? 1 : 0;
+  else if (k == "attn_h32_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.attn_h32;
   else if (k == "long_temporal_f32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
