@@ -16,6 +16,11 @@
 // scores computed three times, 128 instead of 64 MFMAs per 32 x 32 tile (and expf twice); one score tile (16 registers) is live at a
 // time.
 //
+// The - 1 of the diagonal, T > 256 (no resident kernel to agree with): once - v[query] is in the accumulator it stands at |v| instead of
+// |sum p v| << |v|, and every product behind it is rounded to an ulp of |v| -- an error that grows with the keys still to come (T = 769,
+// hashed inputs at scale 2.0: 6.4e-6 against fp64 where plain fp32 math loses 3.1e-6; tests/test_gpu_group_lengths.py).  There the
+// products are summed without it and v[query] is subtracted once, at the store.
+//
 // One workgroup per (batch, joint, head, query block): the T queries of a unit are cut into ceil(T / 256) balanced blocks of at most
 // 8 waves of 32 queries (T = 300: two blocks of 160; T = 513: three of 192), blockDim = 64 x that wave count -- a run-time value, the
 // staging loops stride by it.  Staging is the resident kernel's: through registers, all global loads of a batch issued before its LDS
@@ -91,6 +96,7 @@ __global__ __launch_bounds__(512) void k_attn_temporal_f32l(const float* __restr
   const size_t tok0 = (size_t)b * T * J + j;          // token(t) = tok0 + t*J
   const int ntiles = (T + 31) >> 5;                   // key tiles of the unit
   const int nchunks = (ntiles + KC - 1) / KC;
+  const bool late_diag = nchunks > 1;                 // T > 256: - v[query] at the store instead of - 1 in P (block-uniform)
 
   // this lane's query row, pre-scaled by dh^-0.5 = 2^-3 (exact): lane half hh holds d in [32hh, 32hh+32)
   const int tq = qb * (nthr >> 1) + 32 * wave + r;    // (a query block is blockDim / 2 queries)
@@ -177,7 +183,7 @@ __global__ __launch_bounds__(512) void k_attn_temporal_f32l(const float* __restr
         const int lkey = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * hh;   // row of the chunk
         const float e = expf(sacc[q] - m);
         float pv = e / l;
-        if (c * CH + lkey == tq) pv -= 1.0f;   // attn - I (S2S:82-83)
+        if (!late_diag && c * CH + lkey == tq) pv -= 1.0f;   // attn - I (S2S:82-83)
         sacc[q] = pv;
       }
 #pragma unroll
@@ -194,12 +200,19 @@ __global__ __launch_bounds__(512) void k_attn_temporal_f32l(const float* __restr
 
   if (tq < T) {
     const size_t oo = (tok0 + (size_t)tq * J) * D + hd * LDH;
+    const float* vq = qkv + (tok0 + (size_t)tq * J) * D3 + 2 * D + hd * LDH;   // this query's own v row: the columns the lane stores
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4)
-        *reinterpret_cast<float4*>(out + oo + dt * 32 + 8 * g4 + 4 * hh) =
-            make_float4(oacc[dt][4 * g4], oacc[dt][4 * g4 + 1], oacc[dt][4 * g4 + 2], oacc[dt][4 * g4 + 3]);
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int col = dt * 32 + 8 * g4 + 4 * hh;
+        float4 o = make_float4(oacc[dt][4 * g4], oacc[dt][4 * g4 + 1], oacc[dt][4 * g4 + 2], oacc[dt][4 * g4 + 3]);
+        if (late_diag) {
+          const float4 v = *reinterpret_cast<const float4*>(vq + col);
+          o.x -= v.x; o.y -= v.y; o.z -= v.z; o.w -= v.w;
+        }
+        *reinterpret_cast<float4*>(out + oo + col) = o;
+      }
   }
 }
 

@@ -220,7 +220,7 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     reference arithmetic).  The resident fp32 MFMA attention kernel holds K and V of at most 256 frames in LDS; with the key
  *                     on, the temporal blocks of such an engine run the key-streaming fp32 kernel (v_mfma_f32_32x32x2_f32, keys pass
  *                     through LDS in chunks of 256 frames, three passes: maximum, sum, normalised product -- the resident kernel's
- *                     arithmetic in its order) / 0: the generic one-thread-per-row kernel, as before version 136.  The two differ in the
+ *                     arithmetic in its order, the diagonal's - v[query] applied at the store instead of inside the product) / 0: the generic one-thread-per-row kernel, as before version 136.  The two differ in the
  *                     last bits, both inside the parity gate.  num_frame <= 256, F16X3 and BF16 engines: no effect.  d3d_workspace_bytes
  *                     does not change.  "long_temporal_f32_last" (d3d_engine_get_info) reports what the latest forward ran.
  *   "attn_h32"        1 (default) / 0: F16X3 engines whose heads are 32 columns wide with an even head count (embed_dim 256 with the

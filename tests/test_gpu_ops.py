@@ -190,6 +190,9 @@ def _attn_ref(qkv, B, T, J, H, temporal):
     (1, 243, 2, 512, 8, True, True), (1, 256, 1, 512, 8, True, False), (1, 33, 2, 128, 2, True, False),
     (2, 9, 17, 32, 8, False, False), (2, 27, 17, 32, 8, True, False), (1, 100, 2, 64, 8, True, False),
     (1, 160, 1, 512, 8, True, False), (1, 1, 17, 512, 8, True, False),
+    # six and seven key tiles, both sides of their 32-key edges (every length: tests/test_gpu_group_lengths.py)
+    (1, 161, 2, 512, 8, True, False), (1, 192, 2, 512, 8, True, False), (1, 193, 2, 512, 8, True, False),
+    (1, 224, 2, 512, 8, True, False), (1, 225, 2, 512, 8, True, False),
 ])
 def test_attention_core(B, T, J, D, H, temporal, generic):
     E = _eng()
