@@ -398,6 +398,14 @@ bool attn_x3_h32_ok(int N, int D, int H);
 // B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_temporal_f32_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_temporal_f32_long_ok(int T, int D, int H);
+// ---- kernels_attn_f32_h32.hip: the exact fp32 cores of kernels_attn.hip for heads of 32 columns (D == 32 H, any head count).  fp32 rows
+// in, fp32 rows out, no pair-layout form (FP32 engines only).  Temporal: v_mfma_f32_32x32x2_f32, T <= 256; spatial: the VALU form, 15 .. 17
+// joints.  The scores are scaled by 1 / sqrt(32) after the sum over d and v[query] is subtracted at the store, so the bits are not those of
+// launch_attn_generic.  The launches return hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
+hipError_t launch_attn_temporal_f32_h32(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+hipError_t launch_attn_spatial_f32_h32(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_temporal_f32_h32_ok(int T, int D, int H);
+bool attn_spatial_f32_h32_ok(int J, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

@@ -68,6 +68,9 @@ struct BlockPlan {
   // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel (kernels_attn_f32_long.hip: windows of more than 256
   // frames, which k_attn_temporal_f32 cannot hold in LDS); false = k_attn_generic there
   bool tp_long_f32 = false;
+  // PLAIN in FP32: the spatial / temporal blocks' attention on the exact fp32 kernels for heads of 32 columns (kernels_attn_f32_h32.hip:
+  // D == 32 H, 15 .. 17 joints / windows of up to 256 frames); false = k_attn_generic there
+  bool sp_f32_h32 = false, tp_f32_h32 = false;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
   // PLAIN in F16X3: q / k / v go to the fp16-MFMA attention kernel as planes
@@ -143,6 +146,10 @@ struct d3d_engine {
   // "attn_h32": an F16X3 engine whose heads are 32 columns wide (embed_dim 256 with 8 heads) runs the folded flow with the attention of
   // every block on kernels_attn_x3_h32.hip (windows of up to 256 frames); 0 = the plain row-kernel flow with the generic fp32 attention
   bool opt_attn_h32 = true;
+  // "attn_f32_h32": an FP32 engine whose heads are 32 columns wide runs the attention of its spatial blocks (15 .. 17 joints) and of its
+  // temporal blocks (windows of up to 256 frames) on kernels_attn_f32_h32.hip; 0 = the generic one-thread-per-row kernel.  Changes the
+  // order of additions: inside the parity gate, not bit-identical.  F16X3 / BF16 engines and every D == 64 H engine: no effect
+  bool opt_attn_f32_h32 = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -162,7 +169,8 @@ struct d3d_engine {
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
   // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip, "long_temporal_f32_last" = the same for
-  // kernels_attn_f32_long.hip, "attn_h32_last" = whether the blocks ran kernels_attn_x3_h32.hip
+  // kernels_attn_f32_long.hip, "attn_h32_last" = whether the blocks ran kernels_attn_x3_h32.hip, "attn_f32_h32_last" = bit 0 / bit 1:
+  // whether the spatial / temporal blocks ran kernels_attn_f32_h32.hip
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -392,10 +400,12 @@ int compute_temb(d3d_engine* e, const float* times_dev, int n, float* out, float
 
 int attention(d3d_engine* e, const BlockPlan& pl, const float* qkv, float* out, void* out_x3, int B, bool temporal, hipStream_t s) {
   if (!temporal) {
-    if (attn_spatial_fast_ok(e->J, e->D, e->H)) HIP_TRY(launch_attn_spatial_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
+    if (pl.sp_f32_h32) HIP_TRY(launch_attn_spatial_f32_h32(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (FP32 engines only: no out_x3)
+    else if (attn_spatial_fast_ok(e->J, e->D, e->H)) HIP_TRY(launch_attn_spatial_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
     else HIP_TRY(launch_attn_generic(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, 0, s));
   } else {
-    if (pl.tp_long_f32) HIP_TRY(launch_attn_temporal_f32_long(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (FP32 engines only: no out_x3)
+    if (pl.tp_f32_h32) HIP_TRY(launch_attn_temporal_f32_h32(qkv, out, B, e->T, e->J, e->D, e->H, s));
+    else if (pl.tp_long_f32) HIP_TRY(launch_attn_temporal_f32_long(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (FP32 engines only: no out_x3)
     else if (attn_temporal_fast_ok(e->T, e->D, e->H)) HIP_TRY(launch_attn_temporal_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
     else HIP_TRY(launch_attn_generic(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, 1, s));
   }
@@ -469,6 +479,9 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   } else if (e->cfg.precision == D3D_PREC_FP32) {
     // windows of more than 256 frames: the resident fp32 MFMA kernel cannot hold their keys; the long kernel streams them
     p.tp_long_f32 = e->opt_long_temporal_f32 && T > 256 && attn_temporal_f32_long_ok(T, D, H);
+    // heads of 32 columns: no D == 64 H predicate holds there; each block type takes its kernel of that width where its group length fits
+    p.sp_f32_h32 = e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H);
+    p.tp_f32_h32 = e->opt_attn_f32_h32 && attn_temporal_f32_h32_ok(T, D, H);
   }
   return p;
 }
@@ -961,7 +974,7 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 139; }   // 139: option / info key "attn_h32", info key "attn_h32_last", d3d_op_attention_h32
+int d3d_version(void) { return 140; }   // 140: option / info key "attn_f32_h32", info key "attn_f32_h32_last", d3d_op_attention_f32_h32
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1451,6 +1464,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "long_temporal") e->opt_long_temporal = value != 0;
   else if (k == "long_temporal_f32") e->opt_long_temporal_f32 = value != 0;
   else if (k == "attn_h32") e->opt_attn_h32 = value != 0;
+  else if (k == "attn_f32_h32") e->opt_attn_f32_h32 = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1523,6 +1537,9 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "long_temporal_f32") *value = e->opt_long_temporal_f32 ? 1 : 0;
   else if (k == "attn_h32") *value = e->opt_attn_h32 ? 1 : 0;
   else if (k == "attn_h32_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.attn_h32;
+  else if (k == "attn_f32_h32") *value = e->opt_attn_f32_h32 ? 1 : 0;
+  else if (k == "attn_f32_h32_last")
+    *value = e->last_plan.flow == BlockPlan::PLAIN ? (e->last_plan.sp_f32_h32 ? 1 : 0) | (e->last_plan.tp_f32_h32 ? 2 : 0) : 0;
   else if (k == "long_temporal_f32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;

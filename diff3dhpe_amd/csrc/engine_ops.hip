@@ -408,6 +408,19 @@ int d3d_op_attention_h32(const float* qkv, float* out, int32_t B, int32_t T, int
   return finish(le, s);
 }
 
+int d3d_op_attention_f32_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (temporal) {
+    if (!attn_temporal_f32_h32_ok(T, D, H)) return fail(D3D_EUNSUP, "fp32 temporal attention for head_dim 32: window length <= 256");
+    HIP_TRY(launch_attn_temporal_f32_h32(qkv, out, B, T, J, D, H, s));
+  } else {
+    if (!attn_spatial_f32_h32_ok(J, D, H)) return fail(D3D_EUNSUP, "fp32 spatial attention for head_dim 32: 15 to 17 joints");
+    HIP_TRY(launch_attn_spatial_f32_h32(qkv, out, B, T, J, D, H, s));
+  }
+  return D3D_OK;
+}
+
 int d3d_op_attention_long_f32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
   if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
   if (!attn_temporal_f32_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 64");

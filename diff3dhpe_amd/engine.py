@@ -216,7 +216,9 @@ class Engine:
         temporal blocks on the key-streaming attention kernel; 0 gives such an engine the plain row-kernel flow, "long_temporal_f32": 1 (default)
         runs the temporal blocks of an FP32 engine with num_frame > 256 on the key-streaming fp32 MFMA attention kernel; 0 keeps the generic
         one-thread-per-row kernel there, "attn_h32": 1 (default) keeps an F16X3 engine with heads of 32 columns (embed_dim 256, 8 heads,
-        num_frame <= 256) on the folded flow, its attention on the fp16-MFMA kernel for that width; 0 gives it the plain row-kernel flow);
+        num_frame <= 256) on the folded flow, its attention on the fp16-MFMA kernel for that width; 0 gives it the plain row-kernel flow,
+        "attn_f32_h32": 1 (default) runs the attention of an FP32 engine with heads of 32 columns on the exact fp32 kernels for that width
+        (15 to 17 joints in the spatial blocks, num_frame <= 256 in the temporal ones); 0 keeps the generic one-thread-per-row kernel);
         the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
@@ -230,7 +232,9 @@ class Engine:
         (1 when the temporal blocks of the most recent forward ran the key-streaming F16X3 attention kernel: num_frame > 256 with the
         option on; else 0), "long_temporal_f32" (the option), "long_temporal_f32_last" (the same for an FP32 engine and the key-streaming
         fp32 attention kernel; "long_temporal_last" stays 0 there), "attn_h32" (the option), "attn_h32_last" (1 when the blocks of the
-        most recent forward ran the F16X3 attention kernel for heads of 32 columns; else 0)."""
+        most recent forward ran the F16X3 attention kernel for heads of 32 columns; else 0), "attn_f32_h32" (the option),
+        "attn_f32_h32_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent forward of an FP32 engine ran the
+        fp32 attention kernels for heads of 32 columns; else 0)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -599,6 +603,19 @@ def op_attention_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib().d3d_op_attention_h32(_ptr(q), _ptr(out), B, T, J, D, H, int(bool(temporal)), st))
+    return out
+
+
+def op_attention_f32_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
+    """The exact fp32 attention kernels for heads of 32 columns alone (include/d3d.h d3d_op_attention_f32_h32): qkv (B*T*J, 3*D) ->
+    (B*T*J, D), D == 32 H; temporal: T <= 256 keys, else 15 <= J <= 17 keys; anything else raises D3DError."""
+    dev = qkv.device
+    D = qkv.shape[-1] // 3
+    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
+    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_attention_f32_h32(_ptr(q), _ptr(out), B, T, J, D, H, int(bool(temporal)), st))
     return out
 
 

@@ -232,6 +232,17 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     fp32 attention kernel, as before version 139.  The two differ in the last bits, both inside the parity gate.
  *                     num_frame > 256, every embed_dim == 64 num_heads engine, FP32 and BF16 engines: no effect.  d3d_workspace_bytes
  *                     does not change.  "attn_h32_last" (d3d_engine_get_info) reports what the latest forward ran.
+ *   "attn_f32_h32"    1 (default) / 0: FP32 engines whose heads are 32 columns wide (embed_dim 256 with the runner's 8 heads; any head
+ *                     count) -- the exact reference arithmetic, and the engine a precision-"auto" model falls back to.  The fp32
+ *                     MFMA / LDS attention kernels need embed_dim == 64 num_heads; with the key on, the spatial blocks of such an engine
+ *                     (15 to 17 joints) and its temporal blocks (num_frame <= 256) run the exact fp32 kernels of that width
+ *                     (temporal: v_mfma_f32_32x32x2_f32, K and V resident in LDS, exact two-pass softmax; spatial: one lane per query
+ *                     row, K and V broadcast from LDS; the scores scaled by 1 / sqrt(32) after the sum, v[query] of the diagonal
+ *                     subtracted at the store) / 0: the generic one-thread-per-row kernel, as before version 140.  The two differ in
+ *                     the order of additions, so in the last bits, both inside the parity gate.  Other joint counts, num_frame > 256
+ *                     (that block type keeps the generic kernel), every embed_dim == 64 num_heads engine, F16X3 and BF16 engines: no
+ *                     effect.  d3d_workspace_bytes does not change.  "attn_f32_h32_last" (d3d_engine_get_info) reports what the latest
+ *                     forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -292,7 +303,10 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * "long_temporal_f32" (the option value), "long_temporal_f32_last" (the same for a D3D_PREC_FP32 engine and the key-streaming fp32
  * attention kernel; "long_temporal_last" stays 0 on such an engine), "attn_h32" (the option value), "attn_h32_last" (1 when the blocks
  * of the most recent d3d_denoise / d3d_ddim_sample call ran the F16X3 attention kernel for heads of 32 columns, else 0: another head
- * width, num_frame > 256, option off, another precision, or before any forward), "small_tiles" (the option value), "small_tiles_last" (bit 0: the
+ * width, num_frame > 256, option off, another precision, or before any forward), "attn_f32_h32" (the option value), "attn_f32_h32_last"
+ * (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the exact fp32 attention
+ * kernels for heads of 32 columns; 0 before any forward, with the option off, on every embed_dim == 64 num_heads engine and in the other
+ * precisions), "small_tiles" (the option value), "small_tiles_last" (bit 0: the
  * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
  * kernel; 0 before any forward, with the option or "latency_mode" off, and in the other precisions).
  * Unknown key: D3D_EINVAL. */
@@ -509,6 +523,11 @@ int d3d_op_attention_long(const float* qkv_dev, float* out_dev, int32_t B, int32
  * even and N <= 256; anything else (head_dim 32 is the only width it takes): D3D_EUNSUP. */
 int d3d_op_attention_h32(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
                          void* stream);
+/* The exact fp32 attention kernels for heads of 32 columns alone (option "attn_f32_h32"): fp32 qkv in, fp32 out.  temporal as in
+ * d3d_op_attention (0: N = J keys, 1: N = T keys).  D == 32 H with T <= 256 (temporal) or 15 <= J <= 17 (spatial); anything else
+ * (head_dim 32 is the only width they take): D3D_EUNSUP.  Not the bits of d3d_op_attention, which keeps the generic kernel at this width. */
+int d3d_op_attention_f32_h32(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                             void* stream);
 /* The temporal core of the FP32 mode from the key-streaming fp32 kernel alone (option "long_temporal_f32"): fp32 qkv in, fp32 out.  Any
  * T >= 1, head width D / H == 64 (else D3D_EUNSUP); for T <= 256 bit for bit the result of d3d_op_attention (temporal = 1,
  * D3D_PREC_FP32, force_generic = 0). */
