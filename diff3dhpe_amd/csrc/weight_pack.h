@@ -13,7 +13,20 @@ namespace d3d {
 inline size_t pad256(size_t n) { return (n + 255) / 256 * 256; }
 // Planes of 2^k * w, k chosen per matrix: 12 whenever |w| <= 15.99 everywhere, smaller for larger weights (LayerNorm-folded
 // weights of checkpoints with big gains).  Returns k (the GEMM's w_exp argument); *clamped is set when an entry is not finite.
+// The kernels take any k in [-14, 12]; the commit (pack_f16x3) admits k >= F16X3_MIN_WEIGHT_EXP only.
 int split_weight_f16x3(const float* w, size_t rows, size_t cols, uint16_t* pair, bool acc_order = false, bool* clamped = nullptr);
+// The lowest exponent the commit admits (|w| <= 65504 everywhere in the matrix); a matrix below it sets PackedWeights::clamped, which
+// the engine reports as D3D_RANGE_WEIGHT.  At a low k the lo half -- then the hi half -- of the matrix's ORDINARY entries falls into fp16
+// subnormals and each of them is off by up to 2^-25 2^-k, whatever its size: the floor under every output of that GEMM doubles with
+// each step of k.  The plane model (tests/plane_model.py; a ~ U(-2, 2), w ~ U(+-1 / sqrt(K)), one outlier) puts it at
+//   k          12 .. 5    3        1        0        -1       -4       -14
+//   K =  512   1.9e-7     2.8e-7   8.3e-7   1.7e-6   3.1e-6   3.3e-5   2.5e-2
+//   K = 1024   1.7e-7     3.1e-7   1.1e-6   2.5e-6   4.9e-6   4.5e-5   4.1e-2
+// against the fp32 rounding bound both engines' GEMMs are held to, 2e-6 sqrt(K / 32) = 8.0e-6 / 1.1e-5.  A block chains four GEMMs, so
+// a matrix is admitted while its floor stays within a quarter of that bound: k >= 0 at both depths, k = -1 at neither
+// (tests/test_plane_model_host.py asserts it).  On the device the engine's distance to the fp64 oracle stops being that of the same
+// checkpoint without the outlier at the same exponent, -1 (tests/test_gpu_weight_exponent.py).
+constexpr int F16X3_MIN_WEIGHT_EXP = 0;
 // LayerNorm folded into the consuming GEMM: LN(x) W^T + b = rstd (x (W diag g)^T) - rstd mean csum + (b + W beta).  W [rows][cols] ->
 // wg = W diag(gamma) in fp32, csum[r] = sum_q wg[r][q], fb[r] = b[r] + sum_q W[r][q] beta[q] (fp64 sums, q ascending, stored as fp32)
 void fold_layernorm(const float* W, const float* b, const float* gamma, const float* beta, size_t rows, size_t cols, float* wg,
@@ -45,7 +58,7 @@ struct PackedWeights {
   std::vector<float> fold;        // F16X3: the arena_fold image
   std::vector<float> wg0;         // F16X3: W_qkv diag(gamma1) of block 0, fp32 [3 D][D] (what the block-0 tables are made from)
   std::vector<BlockOff> blk;      // execution order
-  bool clamped = false;           // a GEMM weight was not finite
+  bool clamped = false;           // a GEMM weight was not finite, or F16X3: a matrix's exponent is below F16X3_MIN_WEIGHT_EXP
 };
 // F16X3: the four GEMM weights of every block as planes, the LayerNorm-folded qkv / fc1 forms and, for the spatial (tile_order_s) /
 // temporal (tile_order_t) blocks, the folded qkv once more in tile order.  false: the internal exponent check failed.

@@ -18,7 +18,8 @@ int split_weight_f16x3(const float* w, size_t rows, size_t cols, uint16_t* pair,
   // bit for bit what a fixed 4096 gives), smaller when a weight is larger -- LayerNorm-FOLDED weights W diag(gamma) of a
   // checkpoint with big gains get there (gamma 6 x |w| 8 = 48).  The GEMM un-scales by 2^-(3+k) (X3Tail::out_scale); powers of
   // two, so nothing rounds differently.  Small entries whose lo half then falls into fp16 denormals lose bits below
-  // 2^-24 2^-k: < 1e-9 absolute at k >= 5.
+  // 2^-24 2^-k; what that costs a GEMM per exponent, and the exponent below which the commit refuses a matrix
+  // (F16X3_MIN_WEIGHT_EXP), is tabulated in weight_pack.h.
   float amax = 0.0f;
   bool finite = true;
   for (size_t i = 0; i < rows * cols; ++i) {
@@ -122,6 +123,7 @@ bool pack_f16x3(const std::vector<BlockSrc>& src, size_t D, size_t Dm, size_t H,
     BlockOff& b = out.blk[k];
     auto pair = [&](const float* w, size_t rows, size_t cols, size_t& dst, int& wexp, bool acc_order = false) {
       wexp = split_weight_f16x3(w, rows, cols, host + o, acc_order, &out.clamped);
+      if (wexp < F16X3_MIN_WEIGHT_EXP) out.clamped = true;   // the planes of the matrix's ordinary entries are too coarse (weight_pack.h)
       dst = o;
       o += 2 * pad256(rows) * cols;
     };

@@ -251,7 +251,7 @@ class Engine:
     @staticmethod
     def describe_range_flags(f: int) -> str:
         what = [n for b, n in ((_lib.RANGE_ACT, "an activation (|x| > 8188)"),
-                               (_lib.RANGE_WEIGHT, "a non-finite (or beyond ~1e9: unrepresentable) GEMM weight"),
+                               (_lib.RANGE_WEIGHT, "a non-finite GEMM weight, or one beyond 65504 in magnitude (plane scale below 2^0)"),
                                (_lib.RANGE_STATS, "a LayerNorm input row with |mean| > 16 standard deviations (one-pass statistics)"),
                                (_lib.RANGE_INDEX, "a timestep index outside [0, num_timesteps)"),
                                (_lib.RANGE_RECOMPUTE, "the head kernel's two evaluations of a row disagreeing (repaired by a third; "

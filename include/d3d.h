@@ -394,14 +394,15 @@ const char* d3d_kernel_class_name(int32_t kernel_class);
 
 /* ---- F16X3 range guard.  The F16X3 operand planes hold fp16 (hi, lo) pairs of 8*x (activations: residual stream, q/k/v,
  * attention output, MLP hidden) and 2^k*w (GEMM weights; k is chosen per matrix at commit: 12 unless an entry exceeds 15.99 --
- * LayerNorm-folded weights W diag(gamma) of checkpoints with large gains -- then smaller, nothing is clamped); activations
+ * LayerNorm-folded weights W diag(gamma) of checkpoints with large gains -- then smaller, down to 0: nothing is clamped); activations
  * beyond the fp16 range, |x| > 8188, are not representable (the row and attention kernels clamp them to the range, the GEMM
  * epilogues let them become inf): results are then meaningless.
  * Every kernel that writes such planes raises a sticky flag in a word of device memory that belongs to the ENGINE it was launched
- * for when a value left the range (no cost in a healthy run), and d3d_engine_commit_weights notes non-finite weights.
+ * for when a value left the range (no cost in a healthy run), and d3d_engine_commit_weights notes weights it cannot represent.
  * d3d_engine_range_flags synchronises `stream` and returns
  *   D3D_RANGE_ACT    an activation of THIS engine left the range since its flag was last cleared
- *   D3D_RANGE_WEIGHT a GEMM weight of this engine was not finite at commit
+ *   D3D_RANGE_WEIGHT a GEMM weight of this engine was not finite at commit, or larger than 65504 in magnitude (its matrix would need
+ *                    k < 0, where the planes of the matrix's ordinary entries are too coarse for fp32 accuracy: DESIGN.md section 4.1)
  *   D3D_RANGE_STATS  a LayerNorm folded into a GEMM met a row with |mean| > 16 standard deviations: the folded form works from
  *                    one-pass row statistics (sum, sum of squares), whose variance loses accuracy like eps (1 + mean^2 / var)
  *                    -- beyond ~25 sigma the 1e-4 parity gate is no longer guaranteed (post-norm biases that dwarf the gains)

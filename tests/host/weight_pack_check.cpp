@@ -273,8 +273,138 @@ static void check_images(const Model& m) {
       }
 }
 
+// ---- the per-matrix exponent: the largest k <= 12 with amax 2^k <= 65504, floor -14 (in double: exact for every fp32 amax)
+static int expect_k(double amax) {
+  int k = 12;
+  while (k > -14 && std::ldexp(amax, k) > 65504.0) --k;
+  return k;
+}
+static double amax_of(const std::vector<float>& w) {
+  double a = 0.0;
+  for (float v : w) a = std::max(a, (double)std::fabs(v));
+  return a;
+}
+static std::vector<float> times_gamma(const std::vector<float>& W, const std::vector<float>& g, size_t rows, size_t cols) {
+  std::vector<float> o(rows * cols);
+  for (size_t r = 0; r < rows; ++r)
+    for (size_t q = 0; q < cols; ++q) { volatile float p = W[r * cols + q] * g[q]; o[r * cols + q] = p; }
+  return o;
+}
+
+static void check_exponents() {
+  const size_t rows = 40, cols = 64;
+  std::vector<uint16_t> pr(2 * pad(rows) * cols), pr0(2 * pad(rows) * cols);
+  // every boundary: amax = 65504 2^-k is the last value of exponent k, the next float is the first of k - 1 -- below -14 there is no
+  // exponent left and the entry is clamped (reported)
+  for (int k = 12; k >= -14; --k) {
+    std::vector<float> w = hvec(40, rows * cols, 1.0e-4f);
+    const float edge = std::ldexp(65504.0f, -k), next = std::nextafterf(edge, std::numeric_limits<float>::infinity());
+    bool clamped = false;
+    w[123] = -edge;
+    int got = split_weight_f16x3(w.data(), rows, cols, pr.data(), false, &clamped);
+    CHECK(got == k && !clamped, "amax = 65504 2^%d: k = %d clamped %d", -k, got, (int)clamped);
+    w[123] = next;
+    got = split_weight_f16x3(w.data(), rows, cols, pr.data(), false, &clamped);
+    CHECK(got == std::max(k - 1, -14) && clamped == (k == -14), "the float above 65504 2^%d: k = %d clamped %d", -k, got, (int)clamped);
+    CHECK(expect_k(edge) == k && expect_k(next) == std::max(k - 1, -14), "expect_k at the boundary of %d", k);
+  }
+  {  // finite, but beyond any exponent: reported, planes saturate at +-65504
+    std::vector<float> w = hvec(41, rows * cols, 1.0f);
+    w[7] = 3.0e9f; w[8] = -3.0e38f;
+    bool clamped = false;
+    const int got = split_weight_f16x3(w.data(), rows, cols, pr.data(), false, &clamped);
+    CHECK(got == -14 && clamped, "finite weight above 65504 2^14: k = %d clamped %d", got, (int)clamped);
+    CHECK(f16(pr[pc(7)]) == 65504.0 && f16(pr[pc(8)]) == -65504.0, "saturated planes: %g %g", f16(pr[pc(7)]), f16(pr[pc(8)]));
+  }
+  {  // planes of 2^j W == planes of W, byte for byte (amax pinned inside (7.995, 15.99], so the exponent is exactly 12 - j)
+    std::vector<float> w = hvec(42, rows * cols, 0.125f);
+    for (size_t i = 0; i < w.size(); i += 5) w[i] = std::ldexp(w[i], -17);   // lo (and hi) halves in fp16 subnormals
+    w[77] = -12.5f;
+    for (int acc = 0; acc < 2; ++acc) {
+      const int k0 = split_weight_f16x3(w.data(), rows, cols, pr0.data(), acc != 0);
+      CHECK(k0 == 12, "base exponent %d", k0);
+      for (int j = 1; j <= 26; ++j) {
+        std::vector<float> wj(w.size());
+        for (size_t i = 0; i < w.size(); ++i) wj[i] = std::ldexp(w[i], j);
+        bool clamped = false;
+        const int kj = split_weight_f16x3(wj.data(), rows, cols, pr.data(), acc != 0, &clamped);
+        CHECK(kj == 12 - j && !clamped, "2^%d W: k = %d clamped %d", j, kj, (int)clamped);
+        CHECK(same(pr.data(), pr0.data(), pr.size() * 2), "2^%d W: planes differ from those of W (acc order %d)", j, acc);
+      }
+    }
+  }
+  {  // the commit admits exponents down to F16X3_MIN_WEIGHT_EXP: amax = 65504 2^-MIN passes, the next float is reported (finite as it is)
+    CHECK(F16X3_MIN_WEIGHT_EXP == 0, "F16X3_MIN_WEIGHT_EXP = %d: this check and DESIGN.md section 4.1 state 0", F16X3_MIN_WEIGHT_EXP);
+    const float edge = std::ldexp(65504.0f, -F16X3_MIN_WEIGHT_EXP);
+    for (int which = 0; which < 4; ++which)
+      for (int over = 0; over < 2; ++over) {
+        Model mm;
+        Model::Blk& x = mm.b[1];
+        std::vector<float>* mat[4] = {&x.qkvw, &x.projw, &x.fc1w, &x.fc2w};
+        x.n1g[4321 % Model::D] = 1.0f; x.n2g[4321 % Model::D] = 1.0f;   // (the folded entry is the raw one)
+        (*mat[which])[4321] = over ? -std::nextafterf(edge, std::numeric_limits<float>::infinity()) : -edge;
+        PackedWeights pk;
+        CHECK(pack_f16x3(mm.src, Model::D, Model::Dm, Model::H, true, true, pk), "pack_f16x3 failed at the admission boundary");
+        const int e[4] = {pk.blk[1].qkv_e, pk.blk[1].proj_e, pk.blk[1].fc1_e, pk.blk[1].fc2_e};
+        CHECK(e[which] == F16X3_MIN_WEIGHT_EXP - over, "matrix %d: exponent %d at the boundary (over %d)", which, e[which], over);
+        CHECK(pk.clamped == (over != 0), "matrix %d at exponent %d: clamped = %d", which, e[which], (int)pk.clamped);
+      }
+  }
+  // one block pair whose six matrices carry six different admitted outliers: six different exponents, each where BlockOff says, and the
+  // tile-order copy is made of the folded planes at the folded exponent
+  Model m;
+  const size_t D = Model::D, Dm = Model::Dm, H = Model::H, N = 3 * D;
+  for (size_t k = 0; k < 2; ++k) {
+    Model::Blk& x = m.b[k];
+    x.qkvw[(2 * D + 70) * D + 33] = 100.0f;  x.n1g[33] = 4.0f;     // qkv 9, folded 400 -> 7
+    x.projw[17 * D + 301] = -5.0e3f;                               // proj 3
+    x.fc1w[900 * D + 12] = 40.0f;            x.n2g[12] = 16.0f;    // fc1 10, folded 640 -> 6
+    x.fc2w[300 * Dm + 1000] = 1.0e4f;                              // fc2 2
+    if (k == 1) { x.qkvw[5] = -4.0e4f; x.n1g[5] = 0.5f; }          // the second block: qkv 0, folded 2e4 -> 1
+  }
+  PackedWeights pk;
+  CHECK(pack_f16x3(m.src, D, Dm, H, true, true, pk), "pack_f16x3 failed on the outlier model");
+  CHECK(!pk.clamped, "outlier model reported as clamped");
+  for (size_t k = 0; k < 2 && pk.blk.size() == 2; ++k) {
+    const Model::Blk& x = m.b[k];
+    const BlockOff& b = pk.blk[k];
+    const std::vector<float> qg = times_gamma(x.qkvw, x.n1g, N, D), fg = times_gamma(x.fc1w, x.n2g, Dm, D);
+    const int want[6] = {expect_k(amax_of(x.qkvw)), expect_k(amax_of(x.projw)), expect_k(amax_of(x.fc1w)), expect_k(amax_of(x.fc2w)),
+                         expect_k(amax_of(qg)), expect_k(amax_of(fg))};
+    const int got[6] = {b.qkv_e, b.proj_e, b.fc1_e, b.fc2_e, b.qkv_fe, b.fc1_fe};
+    const int fixed[6] = {k ? 0 : 9, 3, 10, 2, k ? 1 : 7, 6};
+    for (int i = 0; i < 6; ++i) {
+      CHECK(got[i] == want[i] && want[i] == fixed[i], "block %zu matrix %d: exponent %d, own loop %d, intended %d", k, i, got[i], want[i], fixed[i]);
+      for (int j = 0; j < i; ++j) CHECK(got[i] != got[j], "block %zu: matrices %d and %d share exponent %d", k, j, i, got[i]);
+    }
+    // an ordinary entry and the outlier of every matrix, read back at the matrix's own exponent
+    auto elem = [&](size_t off, const std::vector<float>& w, size_t cols, size_t r, size_t c, bool acc, int e, const char* name) {
+      const size_t o = off + r * 2 * cols + (acc ? pc_acc(c) : pc(c));
+      const double s = std::ldexp((double)w[r * cols + c], e), err = std::fabs(f16(pk.planes[o]) + f16(pk.planes[o + 32]) - s);
+      CHECK(err <= std::max(std::ldexp(std::fabs(s), -22), std::ldexp(1.0, -25)), "block %zu %s (%zu, %zu): split error %g at exponent %d", k, name, r, c, err, e);
+    };
+    elem(b.qkv_x3, x.qkvw, D, 2 * D + 70, 33, false, b.qkv_e, "qkv_x3"); elem(b.qkv_x3, x.qkvw, D, 9, 9, false, b.qkv_e, "qkv_x3");
+    elem(b.proj_x3, x.projw, D, 17, 301, false, b.proj_e, "proj_x3");    elem(b.proj_x3, x.projw, D, 9, 9, false, b.proj_e, "proj_x3");
+    elem(b.fc1_x3, x.fc1w, D, 900, 12, false, b.fc1_e, "fc1_x3");        elem(b.fc1_x3, x.fc1w, D, 9, 9, false, b.fc1_e, "fc1_x3");
+    elem(b.fc2_x3, x.fc2w, Dm, 300, 1000, true, b.fc2_e, "fc2_x3");      elem(b.fc2_x3, x.fc2w, Dm, 9, 9, true, b.fc2_e, "fc2_x3");
+    elem(b.qkv_f3, qg, D, 2 * D + 70, 33, false, b.qkv_fe, "qkv_f3");    elem(b.qkv_f3, qg, D, 9, 9, false, b.qkv_fe, "qkv_f3");
+    elem(b.fc1_f3, fg, D, 900, 12, false, b.fc1_fe, "fc1_f3");           elem(b.fc1_f3, fg, D, 9, 9, false, b.fc1_fe, "fc1_f3");
+    // the tile-order copy: the folded planes row by row, hence at qkv_fe (pack_f16x3 refuses a copy whose exponent differs)
+    CHECK(b.qkv_f3h != NO_OFF, "block %zu: no tile-order copy", k);
+    if (b.qkv_f3h != NO_OFF)
+      for (size_t r = 0; r < N; ++r) {
+        const size_t c = r % 192, s = ((c % 48) / 16) * D + r / 192 * 64 + 16 * (c / 48) + c % 16;
+        CHECK(same(&pk.planes[b.qkv_f3h + r * 2 * D], &pk.planes[b.qkv_f3 + s * 2 * D], 2 * D * 2), "block %zu: qkv_f3h row %zu is not folded row %zu", k, r, s);
+      }
+    std::vector<uint16_t> pt(2 * pad(N) * D, 0);
+    std::vector<float> cs(N), fb(N), cst(N), fbt(N);
+    CHECK(tile_order_copy(qg.data(), cs.data(), fb.data(), D, H, pt.data(), cst.data(), fbt.data()) == b.qkv_fe, "block %zu: tile_order_copy's exponent is not qkv_fe", k);
+  }
+}
+
 int main() {
   check_split();
+  check_exponents();
   check_bf16();
   const Model m;
   check_fold_tile_tables(m);

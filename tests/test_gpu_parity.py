@@ -538,6 +538,23 @@ def test_f16x3_range_guard():
     eng = run(big_w)
     assert eng.range_flags() == 0                                                # (2^11 instead of 2^12: nothing is clamped)
 
+    # the lowest plane scale the commit admits is 2^0 (F16X3_MIN_WEIGHT_EXP, weight_pack.h): 65504 still passes, the next float does not --
+    # below it the planes of the matrix's ordinary entries are too coarse for an engine that claims fp32 accuracy.
+    # The entry's input is dead (fc1 row 3 zeroed, its bias -40: GELU gives 0), so the activations stay in range.
+    def edge_w(value):
+        def mutate(sd):
+            sd["STEblocks.0.mlp.fc1.weight"][3, :] = 0.0
+            sd["STEblocks.0.mlp.fc1.bias"][3] = -40.0
+            sd["STEblocks.0.mlp.fc2.weight"][5, 3] = value
+        return mutate
+    eng = run(edge_w(65504.0))
+    assert eng.range_flags() == 0
+    eng = run(edge_w(float(np.nextafter(np.float32(65504.0), np.float32(np.inf)))))
+    f = eng.range_flags(clear=False)
+    assert f & _lib.RANGE_WEIGHT and not (f & _lib.RANGE_ACT)
+    with pytest.raises(_lib.D3DError, match="range"):
+        eng.check_range()
+
     def inf_w(sd):
         sd["STEblocks.0.mlp.fc1.weight"][3, 5] = float("inf")                    # not representable at any scale
     eng = run(inf_w)
