@@ -15,7 +15,7 @@ RANGE_ACT, RANGE_WEIGHT, RANGE_STATS, RANGE_INDEX, RANGE_RECOMPUTE = 1, 2, 4, 8,
 RANGE_PRECISION = RANGE_ACT | RANGE_WEIGHT | RANGE_STATS        # the bits that mean "not fp32-accurate in F16X3"
 PRECISIONS = {"fp32": PREC_FP32, "f16x3": PREC_F16X3, "bf16": PREC_BF16}
 
-# every symbol include/d3d.h declares (tests/test_abi.py checks the library exports all of them)
+# every symbol include/d3d.h declares (tests/test_abi_host.py checks the library exports all of them)
 ABI_SYMBOLS = [
     "d3d_last_error", "d3d_version", "d3d_engine_create", "d3d_engine_destroy", "d3d_engine_num_weights",
     "d3d_engine_weight_info", "d3d_engine_set_weight", "d3d_engine_set_time_freqs", "d3d_engine_commit_weights",

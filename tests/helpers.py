@@ -1,4 +1,9 @@
 """Shared test helpers: seeded weights/inputs (never the reference; never shipped vectors of weights)."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import torch
 
@@ -14,8 +19,12 @@ def cfg_full(T, **kw):
     return DenoiserConfig(num_frame=T, embed_dim=512, depth=8, **kw)
 
 
-def torch_sd(cfg, seed):
-    return {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed).items()}
+def torch_sd(cfg, seed, family="uniform", qkv_bias=True):
+    """The seeded state dict of `family` as torch tensors; qkv_bias=False drops the attention qkv biases (a model built without them)."""
+    sd = {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family=family).items()}
+    if not qkv_bias:
+        sd = {k: v for k, v in sd.items() if not k.endswith("attn.qkv.bias")}
+    return sd
 
 
 def inputs(B, T, seed):
@@ -23,25 +32,101 @@ def inputs(B, T, seed):
     return {k: torch.from_numpy(v) for k, v in d.items()}
 
 
+def xy(B, T, seed, J=17):
+    """(x2d, noise) of the seeded inputs, on the GPU."""
+    inp = synth_inputs(B, T, J, seed=seed)
+    return torch.from_numpy(inp["x2d"]).cuda(), torch.from_numpy(inp["noise"]).cuda()
+
+
+def dev():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def cu_count():
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
 def hashed(name, shape, seed, scale=1.0):
     n = int(np.prod(shape))
     return torch.from_numpy((scale * hash_uniform(name, n, seed)).astype(np.float32).reshape(shape))
 
 
-def build_product(cfg, seed, sampling=9, eta=0.0, clip=True, device="cuda", precision="fp32"):
-    """HPE_model + GaussianDiffusion of the product with the seeded weights, on `device`."""
+def build_net(cfg, seed, precision="fp32", family="uniform", sd=None, **ctor):
+    """HPE_model of the product with the seeded weights of `family` (or the state dict `sd`), on the CPU.  `ctor` overrides constructor
+    arguments (qkv_bias, qk_scale, norm_layer, ...); precision=None leaves the net's default."""
     import diff3dhpe_amd as d3d
     name = d3d.S2F_NAME if cfg.seq2frame else d3d.S2S_NAME
-    net = d3d.HPE_model(name)(num_frame=cfg.num_frame, num_joints=cfg.num_joints, in_chans=cfg.in_chans,
-                              embed_dim=cfg.embed_dim, depth=cfg.depth, num_heads=cfg.num_heads, mlp_ratio=cfg.mlp_ratio,
-                              qkv_bias=True, qk_scale=None, drop_path_rate=0.1, with_time_emb=cfg.with_time_emb)
-    net.load_state_dict(torch_sd(cfg, seed), strict=True)
-    net.precision = precision
+    args = dict(num_frame=cfg.num_frame, num_joints=cfg.num_joints, in_chans=cfg.in_chans,
+                embed_dim=cfg.embed_dim, depth=cfg.depth, num_heads=cfg.num_heads, mlp_ratio=cfg.mlp_ratio,
+                qkv_bias=True, qk_scale=None, drop_path_rate=0.1, with_time_emb=cfg.with_time_emb)
+    args.update(ctor)
+    net = d3d.HPE_model(name)(**args)
+    net.load_state_dict(torch_sd(cfg, seed, family, args["qkv_bias"]) if sd is None else sd, strict=True)
+    if precision is not None:
+        net.precision = precision
+    return net
+
+
+def build_product(cfg, seed, sampling=9, eta=0.0, clip=True, device="cuda", precision="fp32", family="uniform", sd=None, **ctor):
+    """build_net + GaussianDiffusion of the product, on `device`."""
+    import diff3dhpe_amd as d3d
+    net = build_net(cfg, seed, precision, family, sd, **ctor)
     diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2",
                                  clip_denoised=clip, beta_schedule="cosine", ddim_sampling_eta=eta, clipLoss=True).eval()
     if device != "cpu":
         diff = diff.to(device)
     return net, diff
+
+
+def product(cfg, seed, prec, sampling=9, family="uniform", **kw):
+    """build_product in the argument order of the kernel-option tests: (cfg, seed, precision, sampling steps, weight family)."""
+    return build_product(cfg, seed, sampling=sampling, precision=prec, family=family, **kw)
+
+
+def product_with_engine(cfg, seed, prec, sampling=9, family="uniform", **kw):
+    """(net, diff, eng): product() and the engine of the current device."""
+    net, diff = product(cfg, seed, prec, sampling, family, **kw)
+    return net, diff, diff._engine(dev())
+
+
+def attn_ref(qkv, B, T, J, H, temporal, dtype=torch.float64):
+    """(softmax(q k^T / sqrt(dh)) - I) v in `dtype`: the reference of the GRAND attention core over spatial (b, t) or temporal (b, j) groups."""
+    D = qkv.shape[-1] // 3
+    dh = D // H
+    x = qkv.to(dtype).reshape(B, T, J, 3, H, dh)
+    if temporal:
+        x = x.permute(0, 2, 1, 3, 4, 5)            # (B, J, T, 3, H, dh): groups are joints
+    q, k, v = (x[..., i, :, :].transpose(-3, -2) for i in range(3))   # (.., H, N, dh)
+    a = (q @ k.transpose(-2, -1)) * dh ** -0.5
+    a = a.softmax(-1)
+    N = a.shape[-1]
+    o = (a - torch.eye(N, dtype=a.dtype, device=a.device)) @ v          # (B, G2, H, N, dh)
+    o = o.transpose(-3, -2)                                             # (B, G2, N, H, dh)
+    if temporal:
+        o = o.permute(0, 2, 1, 3, 4)                                    # (B, T, J, H, dh)
+    return o.reshape(B * T * J, D)
+
+
+# ------------------------------------------------------------------------------------------------ bench.py as a child process
+_RANK_ENV = ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "D3D_FORCE_DIST", "D3D_BENCH_ONE_DEVICE", "D3D_DIST_BACKEND")
+
+
+def clean_env(**extra):
+    """The environment without a launcher's rank variables and the benchmark's own switches, plus `extra`."""
+    env = {k: v for k, v in os.environ.items() if k not in _RANK_ENV}
+    env.update(extra)
+    return env
+
+
+def bench_subprocess(args, env, timeout=900):
+    """Runs bench.py with `args`; asserts exit code 0 and exactly one JSON line on stdout, and returns it parsed."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, capture_output=True, text=True, env=env, cwd=root,
+                         timeout=timeout)
+    assert run.returncode == 0, run.stderr[-3000:]
+    lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, run.stdout[-2000:]
+    return json.loads(lines[0])
 
 
 def maxabs(a, b):

@@ -5,10 +5,9 @@ import ctypes as C
 import os
 import re
 
-import pytest
-
 from diff3dhpe_amd import _lib
 from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import engine_info, host_engine_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEY, LAST = b"attn_f32_h32", "attn_f32_h32_last"
@@ -23,40 +22,25 @@ def _documented_default():
     return int(m.group(1))
 
 
-@pytest.fixture()
-def host_engine():
-    """An FP32 engine with embed_dim 256 and 8 heads that exists on the host only (created, never committed)."""
-    cfg = DenoiserConfig(num_frame=243, embed_dim=256, depth=8)
-    assert cfg.num_heads == 8 and cfg.head_dim == 32
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS["fp32"])
-    h = C.c_void_p()
-    L = _lib.lib()
-    assert L.d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    yield L, h
-    L.d3d_engine_destroy(h)
-
-
-def _info(L, h, key):
-    v = C.c_int64(-1)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
+CFG = dict(num_frame=243, embed_dim=256, depth=8)
+assert DenoiserConfig(**CFG).num_heads == 8 and DenoiserConfig(**CFG).head_dim == 32
+host_engine = host_engine_fixture(**CFG, prec="fp32")
 
 
 def test_option_reads_the_documented_default_and_round_trips(host_engine):
     L, h = host_engine
     dflt = _documented_default()
-    assert _info(L, h, KEY.decode()) == (0, dflt)
+    assert engine_info(L, h, KEY.decode()) == (0, dflt)
     for v in (1 - dflt, dflt):
         assert L.d3d_engine_set_option(h, KEY, v) == 0
-        assert _info(L, h, KEY.decode()) == (0, v)
+        assert engine_info(L, h, KEY.decode()) == (0, v)
 
 
 def test_last_reads_zero_before_any_forward(host_engine):
     L, h = host_engine
     for v in (1, 0):
         assert L.d3d_engine_set_option(h, KEY, v) == 0
-        assert _info(L, h, LAST) == (0, 0)
+        assert engine_info(L, h, LAST) == (0, 0)
 
 
 def test_workspace_bytes_do_not_depend_on_the_option(host_engine):

@@ -1,14 +1,12 @@
 """Host-side contract of "attn_h32" (include/d3d.h): F16X3 engines whose heads are 32 columns wide (embed_dim 256 with 8 heads) run the
 folded flow with their attention on kernels_attn_x3_h32.hip.  The option and info keys, the op-level export, an unchanged workspace size,
 the build list.  No GPU needed: engines are created on the host only."""
-import ctypes as C
 import os
 import re
 
-import pytest
-
 from diff3dhpe_amd import _lib
 from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import engine_info, host_engine_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -22,40 +20,25 @@ def _documented_default():
     return int(m.group(1))
 
 
-@pytest.fixture()
-def host_engine():
-    """An F16X3 engine with embed_dim 256 and 8 heads that exists on the host only (created, never committed)."""
-    cfg = DenoiserConfig(num_frame=243, embed_dim=256, depth=8)
-    assert cfg.num_heads == 8 and cfg.head_dim == 32
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS["f16x3"])
-    h = C.c_void_p()
-    L = _lib.lib()
-    assert L.d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    yield L, h
-    L.d3d_engine_destroy(h)
-
-
-def _info(L, h, key):
-    v = C.c_int64(-1)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
+CFG = dict(num_frame=243, embed_dim=256, depth=8)
+assert DenoiserConfig(**CFG).num_heads == 8 and DenoiserConfig(**CFG).head_dim == 32
+host_engine = host_engine_fixture(**CFG)
 
 
 def test_option_reads_the_documented_default_and_round_trips(host_engine):
     L, h = host_engine
     dflt = _documented_default()
-    assert _info(L, h, "attn_h32") == (0, dflt)
+    assert engine_info(L, h, "attn_h32") == (0, dflt)
     for v in (1 - dflt, dflt):
         assert L.d3d_engine_set_option(h, b"attn_h32", v) == 0
-        assert _info(L, h, "attn_h32") == (0, v)
+        assert engine_info(L, h, "attn_h32") == (0, v)
 
 
 def test_last_reads_zero_before_any_forward(host_engine):
     L, h = host_engine
     for v in (1, 0):
         assert L.d3d_engine_set_option(h, b"attn_h32", v) == 0
-        assert _info(L, h, "attn_h32_last") == (0, 0)
+        assert engine_info(L, h, "attn_h32_last") == (0, 0)
 
 
 def test_workspace_bytes_do_not_depend_on_the_option(host_engine):

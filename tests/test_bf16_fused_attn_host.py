@@ -1,43 +1,27 @@
 """Host-side contract of the fused bf16 qkv GEMM + attention kernels (kernels_qkv_attn_bf16.hip): both kernels are in the device code
 of the new object file, the file is in build.SOURCES (tests/test_abi_host.py walks that list for the packed-fp32 pin) and built without
 the SLP vectoriser, the op export and the two info keys exist.  No GPU needed: engines are created on the host only."""
-import ctypes as C
 import os
 import re
 
 import pytest
 
 from diff3dhpe_amd import _lib
-from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import create_host_engine, engine_info
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _host_engine(prec, **kw):
-    cfg = DenoiserConfig(num_frame=81, embed_dim=512, depth=8, **kw)
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS[prec])
-    h = C.c_void_p()
-    assert _lib.lib().d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    return h
-
-
-def _info(L, h, key):
-    v = C.c_int64(-1)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
 
 
 @pytest.mark.parametrize("prec", ["bf16", "f16x3"])
 def test_info_keys_read_zero_on_a_fresh_engine(prec):
     L = _lib.lib()
-    h = _host_engine(prec)
+    h = create_host_engine(prec, num_frame=81, embed_dim=512, depth=8)
     try:
-        assert _info(L, h, "bf16_fused_spatial_last") == (0, 0)
-        assert _info(L, h, "bf16_fused_temporal_last") == (0, 0)
+        assert engine_info(L, h, "bf16_fused_spatial_last") == (0, 0)
+        assert engine_info(L, h, "bf16_fused_temporal_last") == (0, 0)
         for key in (b"fused_spatial", b"fused_temporal"):            # the option keys the fused bf16 flow answers to
             assert L.d3d_engine_set_option(h, key, 0) == 0 and L.d3d_engine_set_option(h, key, 1) == 0
-        assert _info(L, h, "bf16_fused_spatial_last") == (0, 0)      # still no forward
+        assert engine_info(L, h, "bf16_fused_spatial_last") == (0, 0)      # still no forward
     finally:
         L.d3d_engine_destroy(h)
 
@@ -45,7 +29,7 @@ def test_info_keys_read_zero_on_a_fresh_engine(prec):
 def test_workspace_bytes_do_not_depend_on_the_options():
     """The attention output of a fused block takes the region the q / k / v tensor would have taken."""
     L = _lib.lib()
-    h = _host_engine("bf16")
+    h = create_host_engine("bf16", num_frame=81, embed_dim=512, depth=8)
     try:
         before = [L.d3d_workspace_bytes(h, B) for B in (1, 4, 128)]
         for key in (b"fused_spatial", b"fused_temporal"):

@@ -83,7 +83,8 @@ def test_allgather_and_reduction_world2_gloo(tmp_path):
         assert p.returncode == 0 and f"rank {r} ok" in o, e[-2000:]
 
 
-def _bench(args, env_extra, timeout=120):
+def _bench_process(args, env_extra, timeout=120):
+    """bench.py's finished process, failing ones included (helpers.bench_subprocess asserts success and parses the line)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(env_extra)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, env=env, cwd=ROOT,
@@ -94,7 +95,7 @@ def test_bench_self_launch_starts_one_rank_process_per_gpu():
     """`python bench.py --gpus N` with no launcher: the parent (which never imports torch) starts N rank processes with the
     torch.distributed rendezvous environment, relays rank 0's stdout alone and returns 0 (launch-check mode: no GPU needed)."""
     import json
-    run = _bench(["--gpus", "4"], {"D3D_BENCH_LAUNCH_CHECK": "1"})
+    run = _bench_process(["--gpus", "4"], {"D3D_BENCH_LAUNCH_CHECK": "1"})
     assert run.returncode == 0, run.stderr
     out = [json.loads(l) for l in run.stdout.splitlines() if l.startswith("{")]
     assert len(out) == 1 and out[0]["rank"] == 0 and out[0]["world_size"] == 4 and out[0]["launcher"] == "self"
@@ -108,20 +109,20 @@ def test_bench_self_launch_propagates_a_failing_rank():
     failing rank's exit code (here rank 2 exits 7 while the others would sleep 30 s)."""
     import time
     t0 = time.time()
-    run = _bench(["--gpus", "3"], {"D3D_BENCH_LAUNCH_CHECK": "1", "D3D_BENCH_LAUNCH_CHECK_FAIL": "2"})
+    run = _bench_process(["--gpus", "3"], {"D3D_BENCH_LAUNCH_CHECK": "1", "D3D_BENCH_LAUNCH_CHECK_FAIL": "2"})
     assert run.returncode == 7 and "rank 2 failed" in run.stderr, (run.returncode, run.stderr)
     assert time.time() - t0 < 20
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
-    run = _bench(["--gpus", "2"], {"WORLD_SIZE": "3", "RANK": "0", "D3D_BENCH_LAUNCH_CHECK": ""})
+    run = _bench_process(["--gpus", "2"], {"WORLD_SIZE": "3", "RANK": "0", "D3D_BENCH_LAUNCH_CHECK": ""})
     assert run.returncode != 0 and "WORLD_SIZE=3" in (run.stderr + run.stdout)
 
 
 def test_bench_self_launch_eight_rank_processes():
     """The N = 8 launch the driver makes at round end, without a GPU (launch-check mode): eight rank processes, ONE JSON line on stdout."""
     import json
-    run = _bench(["--gpus", "8"], {"D3D_BENCH_LAUNCH_CHECK": "1"})
+    run = _bench_process(["--gpus", "8"], {"D3D_BENCH_LAUNCH_CHECK": "1"})
     assert run.returncode == 0, run.stderr
     out = [json.loads(l) for l in run.stdout.splitlines() if l.startswith("{")]
     err = [json.loads(l) for l in run.stderr.splitlines() if l.startswith("{")]
@@ -210,7 +211,7 @@ def test_bench_self_launch_watchdog_names_a_rank_that_never_finishes_its_first_s
     harness's own limit.  Launch-check mode: rank 1 sleeps before it reports ready, the others report and then wait."""
     import time
     t0 = time.time()
-    run = _bench(["--gpus", "3"], {"D3D_BENCH_LAUNCH_CHECK": "1", "D3D_BENCH_LAUNCH_CHECK_HANG": "1", "D3D_BENCH_STARTUP_TIMEOUT_S": "3"})
+    run = _bench_process(["--gpus", "3"], {"D3D_BENCH_LAUNCH_CHECK": "1", "D3D_BENCH_LAUNCH_CHECK_HANG": "1", "D3D_BENCH_STARTUP_TIMEOUT_S": "3"})
     assert run.returncode == 124, (run.returncode, run.stderr)
     assert "rank(s) [1] had not finished a first sampling" in run.stderr and "ending all ranks" in run.stderr
     assert time.time() - t0 < 25
@@ -218,7 +219,7 @@ def test_bench_self_launch_watchdog_names_a_rank_that_never_finishes_its_first_s
 
 def test_bench_self_launch_watchdog_is_quiet_when_every_rank_reports():
     """All ranks report their first sampling: the watchdog never fires even with a tiny limit once they have all reported."""
-    run = _bench(["--gpus", "2"], {"D3D_BENCH_LAUNCH_CHECK": "1", "D3D_BENCH_STARTUP_TIMEOUT_S": "30"})
+    run = _bench_process(["--gpus", "2"], {"D3D_BENCH_LAUNCH_CHECK": "1", "D3D_BENCH_STARTUP_TIMEOUT_S": "30"})
     assert run.returncode == 0 and "had not finished" not in run.stderr, run.stderr
 
 
@@ -246,5 +247,5 @@ def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
 
 
 def test_bench_refuses_zero_steps():
-    run = _bench(["--gpus", "1", "--steps", "0"], {"D3D_BENCH_LAUNCH_CHECK": "1"})
+    run = _bench_process(["--gpus", "1", "--steps", "0"], {"D3D_BENCH_LAUNCH_CHECK": "1"})
     assert run.returncode != 0 and "--steps" in run.stderr

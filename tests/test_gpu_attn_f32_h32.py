@@ -25,11 +25,9 @@ import pytest
 import torch
 
 import group_lengths as gl
-from helpers import hashed, inputs, maxabs
-import diff3dhpe_amd as d3d
+from helpers import hashed, inputs, maxabs, attn_ref, torch_sd, build_net, product_with_engine, xy
 from diff3dhpe_amd._lib import D3DError
 from diff3dhpe_amd.spec import DenoiserConfig
-from diff3dhpe_amd.synth import synth_inputs, synth_state_dict
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
@@ -45,33 +43,10 @@ def _eng():
     return engine
 
 
-def _attn(qkv, Bn, T, Jn, Hn, temporal, dtype):
-    """(softmax(q k^T / sqrt(dh)) - I) v in `dtype`: the _attn_ref of tests/test_gpu_ops.py (fp64) and, line for line, the _attn_f32 of
-    tests/test_gpu_group_lengths.py (fp32: what a plain fp32 evaluation of this problem loses)."""
-    Dn = qkv.shape[-1] // 3
-    dh = Dn // Hn
-    x = qkv.to(dtype).reshape(Bn, T, Jn, 3, Hn, dh)
-    if temporal:
-        x = x.permute(0, 2, 1, 3, 4, 5)            # (B, J, T, 3, H, dh): groups are joints
-    q, k, v = (x[..., i, :, :].transpose(-3, -2) for i in range(3))   # (.., H, N, dh)
-    a = (q @ k.transpose(-2, -1)) * dh ** -0.5
-    a = a.softmax(-1)
-    N = a.shape[-1]
-    o = (a - torch.eye(N, dtype=a.dtype, device=a.device)) @ v          # (B, G2, H, N, dh)
-    o = o.transpose(-3, -2)                                             # (B, G2, N, H, dh)
-    if temporal:
-        o = o.permute(0, 2, 1, 3, 4)                                    # (B, T, J, H, dh)
-    return o.reshape(Bn * T * Jn, Dn)
-
-
-def _attn_ref(qkv, Bn, T, Jn, Hn, temporal):
-    return _attn(qkv, Bn, T, Jn, Hn, temporal, torch.float64)
-
-
 def _bound(qkv_cpu, Bn, T, Jn, Hn, temporal):
     """(fp64 reference, max(5e-6, 2 e32), e32) of one problem, on the CPU."""
-    ref = _attn_ref(qkv_cpu, Bn, T, Jn, Hn, temporal)
-    e32 = maxabs(_attn(qkv_cpu, Bn, T, Jn, Hn, temporal, torch.float32), ref)
+    ref = attn_ref(qkv_cpu, Bn, T, Jn, Hn, temporal)
+    e32 = maxabs(attn_ref(qkv_cpu, Bn, T, Jn, Hn, temporal, torch.float32), ref)
     return ref, max(FLOOR, 2 * e32), e32
 
 
@@ -164,7 +139,7 @@ def test_sharp_softmax(Bn, T, Jn, temporal):
     """Logits up to ~100 (near one-hot rows): the bound of tests/test_gpu_ops.py::test_attention_fast_kernels_agree_with_generic_on_sharp_softmax."""
     E = _eng()
     qkv = hashed(f"sharp{T}", (Bn * T * Jn, 3 * D), 22, 9.0).cuda()
-    ref = _attn_ref(qkv, Bn, T, Jn, H, temporal).cpu()
+    ref = attn_ref(qkv, Bn, T, Jn, H, temporal).cpu()
     a = E.op_attention_f32_h32(qkv, Bn, T, Jn, H, temporal)
     b = E.op_attention(qkv, Bn, T, Jn, H, temporal, force_generic=True)
     print(f"attn_f32_h32 sharp T={T} J={Jn}: new {maxabs(a, ref):.3e} generic {maxabs(b, ref):.3e} apart {maxabs(a, b.cpu()):.3e}")
@@ -200,32 +175,19 @@ def _cfg(T, Dn=256, Jn=17):
     return DenoiserConfig(num_frame=T, num_joints=Jn, embed_dim=Dn, depth=DEPTH, num_heads=8)
 
 
-def _sd(cfg, seed=11):
-    return {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family="trainedlike").items()}
+def _sd(cfg, seed=11):   # this module's weights: seed 11 of the trained-like family
+    return torch_sd(cfg, seed, family="trainedlike")
 
 
 def _net(cfg, seed=11, prec="fp32"):
-    net = d3d.HPE_model(d3d.S2S_NAME)(num_frame=cfg.num_frame, num_joints=cfg.num_joints, in_chans=2, embed_dim=cfg.embed_dim,
-                                      depth=cfg.depth, num_heads=cfg.num_heads, mlp_ratio=2.0, drop_path_rate=0.1,
-                                      with_time_emb=cfg.with_time_emb)
-    net.load_state_dict(_sd(cfg, seed), strict=True)
-    net.precision = prec
-    return net
+    return build_net(cfg, seed, prec, family="trainedlike")
 
 
-def _product(cfg, seed=11, prec="fp32", sampling=2):
-    net = _net(cfg, seed, prec)
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff, diff._engine(torch.device("cuda", torch.cuda.current_device()))
+def _product(cfg, seed=11, prec="fp32", sampling=2):   # this module's defaults; the weights of _sd
+    return product_with_engine(cfg, seed, prec, sampling, family="trainedlike")
 
 
-def _xy(T, Bn, seed, Jn=17):
-    inp = {k: torch.from_numpy(v) for k, v in synth_inputs(Bn, T, Jn, seed=seed).items()}
-    return inp["x2d"].cuda(), inp["noise"].cuda()
-
-
-def _sample(eng, x2d, nz):
+def _sample(eng, x2d, nz):   # reads this feature's proof-of-path key, LAST
     out = eng.ddim_sample(x2d, nz).clone()
     return out, eng.info(LAST)
 
@@ -267,7 +229,7 @@ def test_rows_do_not_depend_on_batch_streams_workspace_contents_or_graph_replay(
     T, Bn = 27, 3
     _, _, eng = _product(_cfg(T))
     eng.set_option(KEY, 1)
-    x2d, nz = _xy(T, Bn, 80)
+    x2d, nz = xy(Bn, T, 80)
     eng.set_option("streams", 2)
     whole, last = _sample(eng, x2d, nz)
     assert last == 3 and torch.isfinite(whole).all()
@@ -296,14 +258,14 @@ def test_each_block_type_takes_its_kernel_where_its_group_length_fits(T, Jn, wan
     _, _, eng = _product(_cfg(T, Jn=Jn))
     eng.set_option(KEY, 1)
     assert eng.info(LAST) == 0                     # before any forward
-    out, last = _sample(eng, *_xy(T, 1, 83, Jn))
+    out, last = _sample(eng, *xy(1, T, 83, Jn))
     assert last == want and torch.isfinite(out).all()
 
 
 def test_engines_with_heads_of_64_columns_ignore_the_option():
     T = 27
     _, _, eng = _product(_cfg(T, Dn=512))
-    x2d, nz = _xy(T, 2, 82)
+    x2d, nz = xy(2, T, 82)
     default = eng.info(KEY)
     res = {}
     try:
@@ -321,7 +283,7 @@ def test_f16x3_engines_are_left_alone():
     selects (which calls the same attention dispatch with the generic kernel) -- takes the fp32 kernels, and neither changes a bit."""
     T = 27
     _, _, e3 = _product(_cfg(T), prec="f16x3")
-    x2d, nz = _xy(T, 1, 83)
+    x2d, nz = xy(1, T, 83)
     default, flow_default = e3.info(KEY), e3.info("attn_h32")
     assert e3.info(LAST) == 0
     try:
@@ -348,7 +310,7 @@ def test_the_auto_fallback_engine_runs_the_kernels():
     dev = torch.device("cuda", torch.cuda.current_device())
     net.engine_for(dev, True).set_option(KEY, 1)       # (whatever the default is)
     net32.engine_for(dev).set_option(KEY, 1)
-    x2d, nz = _xy(T, Bn, 81)
+    x2d, nz = xy(Bn, T, 81)
     big = torch.cat([x2d * 1.0e6, nz], dim=-1)
     t = torch.arange(Bn, device="cuda") * 300 + 11
     want = net32.forward_denoise(big, t).clone()

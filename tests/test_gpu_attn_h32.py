@@ -6,11 +6,9 @@ runner's 8 heads.  Two adjacent heads share the 128-byte LDS rows of the 64-wide
 import pytest
 import torch
 
-from helpers import hashed, inputs, maxabs
-import diff3dhpe_amd as d3d
+from helpers import hashed, inputs, maxabs, attn_ref, torch_sd, product_with_engine, xy
 from diff3dhpe_amd._lib import D3DError
 from diff3dhpe_amd.spec import DenoiserConfig
-from diff3dhpe_amd.synth import synth_state_dict
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
@@ -20,24 +18,6 @@ DEPTH = 1
 def _eng():
     from diff3dhpe_amd import engine
     return engine
-
-
-def _attn_ref(qkv, B, T, J, H, temporal):
-    """(softmax(q k^T / sqrt(dh)) - I) v in fp64: the _attn_ref of tests/test_gpu_ops.py."""
-    D = qkv.shape[-1] // 3
-    dh = D // H
-    x = qkv.double().reshape(B, T, J, 3, H, dh)
-    if temporal:
-        x = x.permute(0, 2, 1, 3, 4, 5)            # (B, J, T, 3, H, dh): groups are joints
-    q, k, v = (x[..., i, :, :].transpose(-3, -2) for i in range(3))   # (.., H, N, dh)
-    a = (q @ k.transpose(-2, -1)) * dh ** -0.5
-    a = a.softmax(-1)
-    N = a.shape[-1]
-    o = (a - torch.eye(N, dtype=a.dtype, device=a.device)) @ v          # (B, G2, H, N, dh)
-    o = o.transpose(-3, -2)                                             # (B, G2, N, H, dh)
-    if temporal:
-        o = o.permute(0, 2, 1, 3, 4)                                    # (B, T, J, H, dh)
-    return o.reshape(B * T * J, D)
 
 
 # ------------------------------------------------------------------------------------------------ 1. op level against fp64
@@ -55,7 +35,7 @@ def test_op_matches_fp64(B, T, J, D, H, temporal):
     input in the same run."""
     E = _eng()
     qkv = hashed(f"qkv{T}_{J}_{D}", (B * T * J, 3 * D), 21, 2.0).cuda()
-    ref = _attn_ref(qkv, B, T, J, H, temporal).cpu()
+    ref = attn_ref(qkv, B, T, J, H, temporal).cpu()
     got = E.op_attention_h32(qkv, B, T, J, H, temporal)
     err = maxabs(got, ref)
     err32 = maxabs(E.op_attention(qkv, B, T, J, H, temporal, force_generic=True), ref)
@@ -70,7 +50,7 @@ def test_sharp_softmax(B, T, J, temporal):
     """Logits up to ~100 (near one-hot rows): the bound of tests/test_gpu_ops.py::test_attention_fast_kernels_agree_with_generic_on_sharp_softmax."""
     E = _eng()
     qkv = hashed(f"sharp{T}", (B * T * J, 3 * 256), 22, 9.0).cuda()
-    ref = _attn_ref(qkv, B, T, J, 8, temporal).cpu()
+    ref = attn_ref(qkv, B, T, J, 8, temporal).cpu()
     a = E.op_attention_h32(qkv, B, T, J, 8, temporal)
     b = E.op_attention(qkv, B, T, J, 8, temporal, force_generic=True)
     print(f"attention_h32 sharp T={T} J={J}: h32 {maxabs(a, ref):.3e} generic {maxabs(b, ref):.3e} apart {maxabs(a, b.cpu()):.3e}")
@@ -91,7 +71,7 @@ def test_launch_forms_agree():
     for lo, hi in ((0, 2), (G - 3, G)):
         small = E.op_attention_h32(qkv[lo * J:hi * J].contiguous(), 1, hi - lo, J, H, False)
         assert torch.equal(small, big[lo * J:hi * J])
-    err = maxabs(big[:4 * J], _attn_ref(qkv[:4 * J], 1, 4, J, H, False).cpu())
+    err = maxabs(big[:4 * J], attn_ref(qkv[:4 * J], 1, 4, J, H, False).cpu())
     assert err < 5e-6, err
 
 
@@ -122,26 +102,15 @@ def _cfg(T, D=256, H=8):
     return DenoiserConfig(num_frame=T, embed_dim=D, depth=DEPTH, num_heads=H)
 
 
-def _sd(cfg, seed=11):
-    return {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family="trainedlike").items()}
+def _sd(cfg, seed=11):   # this module's weights: seed 11 of the trained-like family
+    return torch_sd(cfg, seed, family="trainedlike")
 
 
-def _product(cfg, seed=11, prec="f16x3", sampling=2):
-    net = d3d.HPE_model(d3d.S2S_NAME)(num_frame=cfg.num_frame, num_joints=17, in_chans=2, embed_dim=cfg.embed_dim, depth=cfg.depth,
-                                      num_heads=cfg.num_heads, mlp_ratio=2.0, drop_path_rate=0.1, with_time_emb=cfg.with_time_emb)
-    net.load_state_dict(_sd(cfg, seed), strict=True)
-    net.precision = prec
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff, diff._engine(torch.device("cuda", torch.cuda.current_device()))
+def _product(cfg, seed=11, prec="f16x3", sampling=2):   # this module's defaults; the weights of _sd
+    return product_with_engine(cfg, seed, prec, sampling, family="trainedlike")
 
 
-def _xy(T, B, seed):
-    inp = inputs(B, T, seed)
-    return inp["x2d"].cuda(), inp["noise"].cuda()
-
-
-def _sample(eng, x2d, nz):
+def _sample(eng, x2d, nz):   # reads this feature's proof-of-path key, "attn_h32_last"
     out = eng.ddim_sample(x2d, nz).clone()
     return out, eng.info("attn_h32_last")
 
@@ -185,7 +154,7 @@ def test_rows_do_not_depend_on_batch_streams_workspace_contents_or_graph_replay(
     T, B = 27, 3
     _, _, eng = _product(_cfg(T))
     eng.set_option("attn_h32", 1)
-    x2d, nz = _xy(T, B, 80)
+    x2d, nz = xy(B, T, 80)
     eng.set_option("streams", 2)
     whole, last = _sample(eng, x2d, nz)
     assert last == 1 and torch.isfinite(whole).all()
@@ -214,6 +183,6 @@ def test_other_engines_never_take_the_kernel(T, D, H, prec):
     _, _, eng = _product(_cfg(T, D, H), prec=prec)
     eng.set_option("attn_h32", 1)
     assert eng.info("attn_h32_last") == 0              # before any forward
-    x2d, nz = _xy(T, 1, 83)
+    x2d, nz = xy(1, T, 83)
     out, last = _sample(eng, x2d, nz)
     assert last == 0 and torch.isfinite(out).all()

@@ -12,10 +12,8 @@ from functools import partial
 import pytest
 import torch
 
-from helpers import inputs
-import diff3dhpe_amd as d3d
+from helpers import inputs, torch_sd, product_with_engine, xy
 from diff3dhpe_amd.spec import DenoiserConfig
-from diff3dhpe_amd.synth import synth_state_dict
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
@@ -26,29 +24,17 @@ def _cfg(T, **kw):
     return DenoiserConfig(num_frame=T, embed_dim=512, depth=DEPTH, **kw)
 
 
-def _sd(cfg, seed, family, qkv_bias=True):
-    sd = {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family=family).items()}
-    return sd if qkv_bias else {k: v for k, v in sd.items() if not k.endswith(".attn.qkv.bias")}
+def _product(cfg, seed=11, prec="f16x3", sampling=2, family="trainedlike", **ctor):   # this module's defaults
+    return product_with_engine(cfg, seed, prec, sampling, family, **ctor)
 
 
-def _product(cfg, seed=11, prec="f16x3", sampling=2, family="trainedlike", **ctor):
-    name = d3d.S2F_NAME if cfg.seq2frame else d3d.S2S_NAME
-    net = d3d.HPE_model(name)(num_frame=cfg.num_frame, num_joints=17, in_chans=2, embed_dim=512, depth=cfg.depth, num_heads=8, mlp_ratio=2.0,
-                              drop_path_rate=0.1, with_time_emb=cfg.with_time_emb, **ctor)
-    net.load_state_dict(_sd(cfg, seed, family, ctor.get("qkv_bias", True)), strict=True)
-    net.precision = prec
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff, diff._engine(torch.device("cuda", torch.cuda.current_device()))
-
-
-def _xy(cfg, B, seed):
-    inp = inputs(B, cfg.num_frame, seed)
-    x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
+def _cfg_xy(cfg, B, seed):
+    """xy() at the config's frame and joint counts; a seq2frame model takes the noise of one frame."""
+    x2d, nz = xy(B, cfg.num_frame, seed, cfg.num_joints)
     return x2d, (nz[:, :1].contiguous() if cfg.seq2frame else nz)
 
 
-def _sample(eng, x2d, nz, direct=1, fused=1):
+def _sample(eng, x2d, nz, direct=1, fused=1):   # toggles "block0_direct" and "fused_spatial", reads "block0_direct_last"
     eng.set_option("block0_direct", direct)
     eng.set_option("fused_spatial", fused)
     out = eng.ddim_sample(x2d, nz).clone()
@@ -72,7 +58,7 @@ def test_forward_denoise_against_the_oracle_with_the_option_on_and_off(variant):
     ctor = VARIANTS[variant]
     cfg = _cfg(27)
     net, _, eng = _product(cfg, **ctor)
-    sd = _sd(cfg, 11, "trainedlike", ctor.get("qkv_bias", True))
+    sd = torch_sd(cfg, 11, "trainedlike", ctor.get("qkv_bias", True))
     inp = inputs(2, 27, 500)
     xcat = torch.cat([inp["x2d"], inp["noise"] * 0.7], dim=-1)
     t = torch.tensor([905, 17], dtype=torch.long)
@@ -109,7 +95,7 @@ SHAPES = [(9, 1), (9, 3), (27, 2), (27, 5), (3, 7)]
 def test_fused_and_two_kernel_flow_are_bit_identical_in_a_sampling(T, B):
     cfg = _cfg(T)
     _, _, eng = _product(cfg)
-    x2d, nz = _xy(cfg, B, 77)
+    x2d, nz = _cfg_xy(cfg, B, 77)
     eng.range_flags(clear=True)
     fused, l1 = _sample(eng, x2d, nz, fused=1)
     plain, l0 = _sample(eng, x2d, nz, fused=0)
@@ -140,7 +126,7 @@ def test_fused_and_two_kernel_flow_are_bit_identical_with_a_time_per_row(T, B):
 def test_fused_and_two_kernel_flow_are_bit_identical_without_time_rows_and_with_broadcast_y(kind):
     cfg = _cfg(27, with_time_emb=False) if kind == "no_time_emb" else _cfg(27, seq2frame=True)
     _, _, eng = _product(cfg, family="uniform", seed=5)
-    x2d, nz = _xy(cfg, 3, 79)
+    x2d, nz = _cfg_xy(cfg, 3, 79)
     fused, l1 = _sample(eng, x2d, nz, fused=1)
     plain, l0 = _sample(eng, x2d, nz, fused=0)
     assert l1 == 1 and l0 == 1 and torch.isfinite(fused).all()
@@ -151,7 +137,7 @@ def test_fused_and_two_kernel_flow_are_bit_identical_without_time_rows_and_with_
 def test_rows_do_not_depend_on_batch_streams_or_workspace_contents():
     cfg = _cfg(9)               # 9 frames per batch element: each 15-frame tile of a B = 3 call holds rows of two of them
     _, _, eng = _product(cfg)
-    x2d, nz = _xy(cfg, 3, 80)
+    x2d, nz = _cfg_xy(cfg, 3, 80)
     eng.set_option("streams", 2)
     whole, last = _sample(eng, x2d, nz)
     assert last == 1
@@ -169,7 +155,7 @@ def test_rows_do_not_depend_on_batch_streams_or_workspace_contents():
 def test_graph_replay_equals_eager():
     cfg = _cfg(9)
     _, _, eng = _product(cfg)
-    x2d, nz = _xy(cfg, 2, 81)
+    x2d, nz = _cfg_xy(cfg, 2, 81)
     eager, last = _sample(eng, x2d, nz)
     eng.set_graph_mode(True)
     try:
@@ -186,7 +172,7 @@ def test_graph_replay_equals_eager():
 def test_option_off_is_the_gemm_flow_and_other_precisions_never_take_the_direct_form():
     cfg = _cfg(27)
     _, _, eng = _product(cfg)
-    x2d, nz = _xy(cfg, 2, 82)
+    x2d, nz = _cfg_xy(cfg, 2, 82)
     on, l_on = _sample(eng, x2d, nz, direct=1)
     off_fused, l_off1 = _sample(eng, x2d, nz, direct=0, fused=1)
     off_plain, l_off0 = _sample(eng, x2d, nz, direct=0, fused=0)

@@ -1,105 +1,15 @@
-"""Round-6 evidence on the MI355X, through the product API / the C ABI."""
-from functools import partial
-
+"""evaluate() and what it is made of, on the MI355X: the pose-metrics kernel, the four protocols, and run_evaluation() /
+run_evaluation_3dhp()."""
 import pytest
 import torch
 
-import diff3dhpe_amd as d3d
 from conftest import gold
-from diff3dhpe_amd.spec import DenoiserConfig
-from diff3dhpe_amd.synth import synth_state_dict
-from helpers import cfg_full, inputs, maxabs
-from test_gpu_round4 import _product
+from helpers import inputs, product
 
 pytestmark = pytest.mark.gpu
 
 
-CTOR = {"nobias": (dict(qkv_bias=False), "uniform"), "qkscale": (dict(qk_scale=0.2), "uniform"),
-        "eps": (dict(norm_layer=partial(torch.nn.LayerNorm, eps=1e-3)), "trainedlike")}
-
-
-@pytest.mark.parametrize("prec", ["fp32", "f16x3"])
-@pytest.mark.parametrize("tag", list(CTOR))
-def test_ctor_arguments_golden(tag, prec):
-    """qkv_bias=False, qk_scale=0.2 and norm_layer=partial(nn.LayerNorm, eps=1e-3) (S2S:140-142, 184; the engine refused them until round
-    6) against raw denoiser outputs of the imported reference (oracle/gen_golden.py gen_round6: T = 27, D = 512, depth 2; the oracle equal
-    to the reference bit for bit while generating), in both gated precisions, range guard silent."""
-    g = gold("denoise_ctor_args_T27")
-    kw, family = CTOR[tag]
-    cfg = DenoiserConfig(num_frame=27, embed_dim=512, depth=2)
-    args = dict(num_frame=27, num_joints=17, in_chans=2, embed_dim=512, depth=2, num_heads=8, mlp_ratio=2., qkv_bias=True, qk_scale=None,
-                drop_path_rate=0.1, with_time_emb=True)
-    args.update(kw)
-    net = d3d.HPE_model(d3d.S2S_NAME)(**args)
-    sd = {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, int(g["seed"]), family=family).items()}
-    if tag == "nobias":
-        sd = {k: v for k, v in sd.items() if not k.endswith("attn.qkv.bias")}
-    net.load_state_dict(sd, strict=True)
-    net.precision = prec
-    net = net.cuda()
-    inp = inputs(2, 27, int(g["input_seed"]))
-    xcat = torch.cat([inp["x2d"], inp["noise"] * float(g["y_scale"])], dim=-1).cuda()
-    worst = 0.0
-    for t in (999, 17):
-        out = net.forward_denoise(xcat, torch.full((2,), t, dtype=torch.long, device="cuda"))
-        worst = max(worst, maxabs(out, g[f"{tag}_t{t}"]))
-    assert worst < 1e-4, (tag, prec, worst)
-    eng = net.engine_for(torch.device("cuda", torch.cuda.current_device()))
-    assert eng.range_flags() == 0
-
-
-@pytest.mark.parametrize("B,T,prec", [(1, 243, "f16x3"), (2, 243, "f16x3"), (5, 243, "f16x3"), (3, 81, "f16x3"), (2, 27, "f16x3"), (3, 243, "bf16")])
-def test_deep_operand_staging_of_the_small_batch_gemms_is_bit_identical(B, T, prec):
-    """One-tile-per-workgroup GEMM launches (batches of a few sequences: proj on 128 x 128 tiles, fc1 / proj / qkv on 256 x 128) stage
-    three / four k-tiles deep ("deep_stages", default on: a k-tile no longer lasts a DMA round trip) -- the same MFMAs in the same order
-    as with two stages: the sampling is bit for bit the two-stage one, one and two streams, NaN-filled workspace (S2S:46-54, 84)."""
-    cfg = cfg_full(T)
-    _, diff = _product(cfg, 5, prec, sampling=2)
-    eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
-    inp = inputs(B, T, 84)
-    x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
-    try:
-        eng.set_option("deep_stages", 0)
-        plain = eng.ddim_sample(x2d, nz).clone()
-        eng.set_option("deep_stages", 1)
-        for streams in (2, 1):
-            eng.set_option("streams", streams)
-            eng._workspace(B).view(torch.float32).fill_(float("nan"))
-            own = eng.ddim_sample(x2d, nz).clone()
-            assert torch.isfinite(own).all()
-            assert torch.equal(own, plain), streams
-    finally:
-        eng.set_option("deep_stages", 1)
-        eng.set_option("streams", 2)
-
-
-@pytest.mark.parametrize("M,N,K,epi", [(4131, 512, 512, "residual"), (300, 1024, 512, "gelu"), (8262, 1536, 512, "none"), (97, 512, 64, "none"),
-                                       (1000, 512, 32, "residual")])
-def test_deep_operand_staging_op_level(M, N, K, epi):
-    """The same at the op level (d3d_op_linear), incl. K of one and two k-tiles (fewer k-tiles than stages) and ragged M."""
-    from diff3dhpe_amd import _lib as L
-    from diff3dhpe_amd import engine as E
-    from helpers import hashed
-    A = hashed(f"dsA{M}", (M, K), 41, 2.0).cuda()
-    W = hashed(f"dsW{N}{K}", (N, K), 42, 1.0 / K ** 0.5).cuda()
-    b = hashed("dsb", (N,), 43, 0.5).cuda()
-    R = hashed(f"dsR{M}", (M, N), 44, 1.5).cuda() if epi == "residual" else None
-    try:
-        L.check(L.lib().d3d_engine_set_option(None, b"deep_stages", 0))
-        y0 = E.op_linear(A, W, b, R, epi=epi, precision="f16x3")
-        L.check(L.lib().d3d_engine_set_option(None, b"deep_stages", 1))
-        y1 = E.op_linear(A, W, b, R, epi=epi, precision="f16x3")
-    finally:
-        L.check(L.lib().d3d_engine_set_option(None, b"deep_stages", 1))
-    ref = A.double() @ W.double().t() + b.double()
-    if epi == "gelu":
-        ref = torch.nn.functional.gelu(ref)
-    if epi == "residual":
-        ref = ref + R.double()
-    assert maxabs(y1, ref.cpu()) < 3e-6 * (K / 32) ** 0.5 + 2e-6
-    assert torch.equal(y0, y1)
-
-
+# ------------------------------------------------------------------------------------------------ the four protocols
 def test_pose_metrics_kernel_against_the_reference_values():
     """d3d_pose_metrics (evaluate()'s P-MPJPE / N-MPJPE / MPJVE on the device, one thread per kept frame, fp64 inside, the 3 x 3 SVD by a
     Jacobi eigen-decomposition) against values of the reference's own functions (tests/golden/pose_metrics.npz): near / unrelated / mirrored
@@ -205,7 +115,7 @@ def test_run_evaluation_3dhp_per_sequence_and_stored_predictions(tmp_path):
     from helpers import cfg_small
     test, train = synth_mocap_3dhp(0)
     ed = EvalData3DHP(test, ["TS1", "TS5"], 27, out_all=False, train_data=train)
-    _, diff = _product(cfg_small(27, seq2frame=True, with_time_emb=False), 9, "f16x3", sampling=2)
+    _, diff = product(cfg_small(27, seq2frame=True, with_time_emb=False), 9, "f16x3", sampling=2)
     mat = str(tmp_path / "inference_data.mat")
     torch.manual_seed(11)
     torch.cuda.manual_seed(11)
@@ -223,4 +133,3 @@ def test_run_evaluation_3dhp_per_sequence_and_stored_predictions(tmp_path):
         assert abs(res[key] - (res["sequences"]["TS1"][i] + res["sequences"]["TS5"][i]) / 2) < 1e-9 and np.isfinite(res[key])
     m = scio.loadmat(mat)
     assert np.array_equal(m["TS1"], res["data_inference"]["TS1"]) and m["TS5"].shape[:2] == (3, 17)
-

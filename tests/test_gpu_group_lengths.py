@@ -9,7 +9,7 @@ and the arithmetic; tests/test_group_lengths_host.py keeps them from shrinking.
 1. Op level.  Inputs: hashed rows at scale 2.0, 8 heads, B = 2 and J = 3 (the temporal stride), every length the first B N J rows of
    one tensor per width.  One test per hook and key-tile class (beyond 256 keys: per 256-key chunk count, class id 100 x chunks), which
    loops over the class's lengths and reports every failing N at once.
-     * fp32, F16X3, head-width-32 and key-streaming hooks: err(N) <= max(5e-6, 2 e32(N)) against _attn_ref of test_gpu_ops.py in fp64.
+     * fp32, F16X3, head-width-32 and key-streaming hooks: err(N) <= max(5e-6, 2 e32(N)) against attn_ref of helpers.py in fp64.
        5e-6 is test_attention_core's bound for this data; e32(N) is the error of the same formula in plain fp32 torch on the CPU on the
        same input (median 2.3e-6, at most 3.9e-6 for N <= 256: the floor is almost always the active term).  A wrong mask or row map
        costs 1e-2 and more.
@@ -53,8 +53,7 @@ import pytest
 import torch
 
 import group_lengths as gl
-from helpers import hashed, maxabs, torch_sd
-from test_gpu_ops import _attn_ref
+from helpers import hashed, maxabs, torch_sd, attn_ref
 from diff3dhpe_amd.spec import DenoiserConfig
 from diff3dhpe_amd.synth import synth_inputs
 
@@ -88,24 +87,6 @@ def _base(D):
     return _BASE[D]
 
 
-def _attn_f32(qkv, Bn, T, Jn, Hn, temporal):
-    """_attn_ref's formula, line for line, in fp32: what a plain fp32 evaluation of this problem loses."""
-    Dn = qkv.shape[-1] // 3
-    dh = Dn // Hn
-    x = qkv.float().reshape(Bn, T, Jn, 3, Hn, dh)
-    if temporal:
-        x = x.permute(0, 2, 1, 3, 4, 5)
-    q, k, v = (x[..., i, :, :].transpose(-3, -2) for i in range(3))
-    a = (q @ k.transpose(-2, -1)) * dh ** -0.5
-    a = a.softmax(-1)
-    N = a.shape[-1]
-    o = (a - torch.eye(N, dtype=a.dtype, device=a.device)) @ v
-    o = o.transpose(-3, -2)
-    if temporal:
-        o = o.permute(0, 2, 1, 3, 4)
-    return o.reshape(Bn * T * Jn, Dn)
-
-
 def _shape(N, spatial):
     """(B, T, J) of the temporal call: stride J = 3, or the spatial form -- B J groups of N consecutive tokens, stride 1."""
     return (B * J, N, 1) if spatial else (B, N, J)
@@ -117,8 +98,8 @@ def _case(D, N, spatial):
     cpu, dev = _base(D)
     rows = B * N * J
     if key not in _REF:
-        ref = _attn_ref(cpu[:rows], *_shape(N, spatial), H, True)
-        _REF[key] = (ref, maxabs(_attn_f32(cpu[:rows], *_shape(N, spatial), H, True), ref))
+        ref = attn_ref(cpu[:rows], *_shape(N, spatial), H, True)
+        _REF[key] = (ref, maxabs(attn_ref(cpu[:rows], *_shape(N, spatial), H, True, torch.float32), ref))
     return (dev[:rows],) + _REF[key]
 
 

@@ -162,7 +162,7 @@ def test_a2_attention_groups(B, T, J, Dm, temporal, prec, generic, what):
 _SD = {}
 
 
-def _sd(cfg):
+def _sd(cfg):   # cached per (num_frame, seq2frame): every engine of this module loads the same seed-21 weights
     key = (cfg.num_frame, cfg.seq2frame)
     if key not in _SD:
         _SD[key] = torch_sd(cfg, 21)

@@ -10,20 +10,13 @@ import torch.nn.functional as F
 
 import diff3dhpe_amd as d3d
 from conftest import gold
-from helpers import hashed, torch_sd, maxabs, inputs, cfg_small, cfg_full, build_product
+from helpers import hashed, torch_sd, maxabs, inputs, cfg_small, cfg_full, build_product, cu_count
+from helpers import dev as _dev          # tests here hold the device in a local named dev
 from diff3dhpe_amd.spec import DenoiserConfig
 
 pytestmark = pytest.mark.gpu
 
 GATE = 1e-4
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _cus():
-    return torch.cuda.get_device_properties(_dev()).multi_processor_count
 
 
 def policy_split(M, D, Dm, n_cu):
@@ -125,7 +118,7 @@ def _rows(cfg, B):
 
 
 def _expected_split(cfg, B):
-    return policy_split(_rows(cfg, B), cfg.embed_dim, cfg.mlp_hidden, _cus())
+    return policy_split(_rows(cfg, B), cfg.embed_dim, cfg.mlp_hidden, cu_count())
 
 
 def test_golden_parity_denoise_with_the_mode_on():

@@ -11,15 +11,12 @@ import torch.nn.functional as F
 import diff3dhpe_amd as d3d
 from conftest import gold
 from helpers import hashed, torch_sd, maxabs, inputs, cfg_full, build_product
+from helpers import dev as _dev          # tests here hold the device in a local named dev
 from diff3dhpe_amd.spec import DenoiserConfig
 
 pytestmark = pytest.mark.gpu
 
 GATE = 1e-4
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _force(eng, proj, fc1):
@@ -106,7 +103,7 @@ def test_op_hooks_reject_other_shapes():
 _NETS = {}
 
 
-def _product(tag, cfg, seed, sampling):
+def _product(tag, cfg, seed, sampling):   # cached per golden tag: the mode-on and mode-off tests of one golden share a product
     """One latency-mode product per fixture, shared by the three S settings."""
     key = (tag, sampling)
     if key not in _NETS:
@@ -193,7 +190,7 @@ def _xcat(B, T, seed):
     return torch.cat([inp["x2d"], inp["noise"]], dim=-1).cuda()
 
 
-def _sample(diff, x2d, nz):
+def _sample(diff, x2d, nz):   # through the diffusion object's forward()
     return diff(clean_3d_pose=torch.zeros_like(nz), noisy_2d_pose=x2d, output_loss=False, init_noise=nz)[1]
 
 

@@ -12,10 +12,8 @@ import warnings
 import pytest
 import torch
 
-from helpers import hashed, inputs, maxabs
-import diff3dhpe_amd as d3d
+from helpers import hashed, inputs, maxabs, attn_ref, torch_sd, build_net, product_with_engine, xy
 from diff3dhpe_amd.spec import DenoiserConfig
-from diff3dhpe_amd.synth import synth_state_dict
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
@@ -26,24 +24,6 @@ KEY, LAST = "long_temporal_f32", "long_temporal_f32_last"
 def _eng():
     from diff3dhpe_amd import engine
     return engine
-
-
-def _attn_ref(qkv, B, T, J, H, temporal):
-    """(softmax(q k^T / sqrt(dh)) - I) v in fp64: the _attn_ref of tests/test_gpu_long_temporal.py."""
-    D = qkv.shape[-1] // 3
-    dh = D // H
-    x = qkv.double().reshape(B, T, J, 3, H, dh)
-    if temporal:
-        x = x.permute(0, 2, 1, 3, 4, 5)            # (B, J, T, 3, H, dh): groups are joints
-    q, k, v = (x[..., i, :, :].transpose(-3, -2) for i in range(3))   # (.., H, N, dh)
-    a = (q @ k.transpose(-2, -1)) * dh ** -0.5
-    a = a.softmax(-1)
-    N = a.shape[-1]
-    o = (a - torch.eye(N, dtype=a.dtype, device=a.device)) @ v          # (B, G2, H, N, dh)
-    o = o.transpose(-3, -2)                                             # (B, G2, N, H, dh)
-    if temporal:
-        o = o.permute(0, 2, 1, 3, 4)                                    # (B, T, J, H, dh)
-    return o.reshape(B * T * J, D)
 
 
 # ------------------------------------------------------------------------------------------------ 1. op level, bit identity
@@ -89,7 +69,7 @@ def test_long_windows_match_fp64(B, T, J, D, H):
     1.5 x the error of the generic fp32 kernel (existing code, an equally ordered fp32 sum) on the same input."""
     E = _eng()
     qkv = hashed(f"qkv{T}_{J}_{D}", (B * T * J, 3 * D), 21, 2.0).cuda()
-    ref = _attn_ref(qkv, B, T, J, H, True).cpu()
+    ref = attn_ref(qkv, B, T, J, H, True).cpu()
     got = E.op_attention_long_f32(qkv, B, T, J, H)
     err = maxabs(got, ref)
     err32 = maxabs(E.op_attention(qkv, B, T, J, H, True, force_generic=True), ref)
@@ -116,31 +96,19 @@ def _cfg(T):
     return DenoiserConfig(num_frame=T, embed_dim=512, depth=DEPTH)
 
 
-def _sd(cfg, seed=11):
-    return {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family="trainedlike").items()}
+def _sd(cfg, seed=11):   # this module's weights: seed 11 of the trained-like family
+    return torch_sd(cfg, seed, family="trainedlike")
 
 
 def _net(cfg, seed=11, prec="fp32"):
-    net = d3d.HPE_model(d3d.S2S_NAME)(num_frame=cfg.num_frame, num_joints=17, in_chans=2, embed_dim=512, depth=cfg.depth, num_heads=8,
-                                      mlp_ratio=2.0, drop_path_rate=0.1, with_time_emb=cfg.with_time_emb)
-    net.load_state_dict(_sd(cfg, seed), strict=True)
-    net.precision = prec
-    return net
+    return build_net(cfg, seed, prec, family="trainedlike")
 
 
-def _product(cfg, seed=11, prec="fp32", sampling=2):
-    net = _net(cfg, seed, prec)
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff, diff._engine(torch.device("cuda", torch.cuda.current_device()))
+def _product(cfg, seed=11, prec="fp32", sampling=2):   # this module's defaults; the weights of _sd
+    return product_with_engine(cfg, seed, prec, sampling, family="trainedlike")
 
 
-def _xy(T, B, seed):
-    inp = inputs(B, T, seed)
-    return inp["x2d"].cuda(), inp["noise"].cuda()
-
-
-def _sample(eng, x2d, nz, long=1):
+def _sample(eng, x2d, nz, long=1):   # toggles this feature's option KEY and reads LAST
     eng.set_option(KEY, long)
     out = eng.ddim_sample(x2d, nz).clone()
     last = eng.info(LAST)
@@ -183,7 +151,7 @@ def test_forward_denoise_against_the_oracle_with_the_option_on_and_off(T):
 def test_rows_do_not_depend_on_batch_streams_workspace_contents_or_graph_replay():
     T, B = 257, 3
     _, _, eng = _product(_cfg(T))
-    x2d, nz = _xy(T, B, 80)
+    x2d, nz = xy(B, T, 80)
     eng.set_option("streams", 2)
     whole, last = _sample(eng, x2d, nz)
     assert last == 1 and torch.isfinite(whole).all()
@@ -210,7 +178,7 @@ def test_rows_do_not_depend_on_batch_streams_workspace_contents_or_graph_replay(
 def test_windows_up_to_256_never_take_the_long_kernel_and_ignore_the_option():
     T = 243
     _, _, eng = _product(_cfg(T))
-    x2d, nz = _xy(T, 2, 82)
+    x2d, nz = xy(2, T, 82)
     on, l_on = _sample(eng, x2d, nz, long=1)
     off, l_off = _sample(eng, x2d, nz, long=0)
     assert (l_on, l_off) == (0, 0)
@@ -222,7 +190,7 @@ def test_f16x3_engines_are_left_alone():
     selects -- takes the fp32 long kernel."""
     T = 300
     _, _, e3 = _product(_cfg(T), prec="f16x3")
-    x2d, nz = _xy(T, 1, 83)
+    x2d, nz = xy(1, T, 83)
     assert e3.info(KEY) == 1 and e3.info(LAST) == 0
     for flow in (1, 0):
         e3.set_option("long_temporal", flow)
@@ -240,7 +208,7 @@ def test_the_auto_fallback_engine_runs_the_long_kernel():
     cfg = _cfg(T)
     net = _net(cfg, prec="auto").cuda()
     net32 = _net(cfg, prec="fp32").cuda()
-    x2d, nz = _xy(T, B, 81)
+    x2d, nz = xy(B, T, 81)
     big = torch.cat([x2d * 1.0e6, nz], dim=-1)
     t = torch.arange(B, device="cuda") * 300 + 11
     want = net32.forward_denoise(big, t).clone()

@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import gold
-from helpers import hashed, torch_sd, maxabs
+from helpers import hashed, torch_sd, maxabs, attn_ref, cu_count
 from diff3dhpe_amd.spec import DenoiserConfig
 
 pytestmark = pytest.mark.gpu
@@ -17,10 +17,6 @@ def _eng():
     return engine
 
 
-def _cus():
-    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-
-
 # Row counts that put a launcher on a given branch of its ladder depend on the device's CU count: named here, resolved inside the test
 # (collection does not touch the GPU).
 _ROWS = {"walk256": lambda cu: 256 * 2 * cu + 100,    # 256 x 256 tiles: the persistent walk (>= 4 rounds) with a ragged last round
@@ -29,7 +25,7 @@ _ROWS = {"walk256": lambda cu: 256 * 2 * cu + 100,    # 256 x 256 tiles: the per
 
 
 def _rows(M):
-    return _ROWS[M](_cus()) if isinstance(M, str) else M
+    return _ROWS[M](cu_count()) if isinstance(M, str) else M
 
 
 _LINEAR_SHAPES = [(128, 128, 32), (300, 96, 32), (1000, 1536, 512), (2066, 512, 1024), (17, 64, 64), (4131, 1024, 512), (129, 130, 96)]
@@ -167,23 +163,6 @@ def test_layernorm(rows, D, eps):
     assert maxabs(E.op_layernorm(x, g, b, eps), ref.cpu()) < 3e-6
 
 
-def _attn_ref(qkv, B, T, J, H, temporal):
-    D = qkv.shape[-1] // 3
-    dh = D // H
-    x = qkv.double().reshape(B, T, J, 3, H, dh)
-    if temporal:
-        x = x.permute(0, 2, 1, 3, 4, 5)            # (B, J, T, 3, H, dh): groups are joints
-    q, k, v = (x[..., i, :, :].transpose(-3, -2) for i in range(3))   # (.., H, N, dh)
-    a = (q @ k.transpose(-2, -1)) * dh ** -0.5
-    a = a.softmax(-1)
-    N = a.shape[-1]
-    o = (a - torch.eye(N, dtype=a.dtype, device=a.device)) @ v          # (B, G2, H, N, dh)
-    o = o.transpose(-3, -2)                                             # (B, G2, N, H, dh)
-    if temporal:
-        o = o.permute(0, 2, 1, 3, 4)                                    # (B, T, J, H, dh)
-    return o.reshape(B * T * J, D)
-
-
 @pytest.mark.parametrize("B,T,J,D,H,temporal,generic", [
     (2, 5, 17, 512, 8, False, False), (2, 5, 17, 512, 8, False, True), (3, 81, 17, 512, 8, False, False),
     (1, 27, 17, 512, 8, True, False), (2, 81, 3, 512, 8, True, False), (1, 243, 2, 512, 8, True, False),
@@ -198,7 +177,7 @@ def test_attention_core(B, T, J, D, H, temporal, generic):
     E = _eng()
     qkv = hashed(f"qkv{T}_{J}_{D}", (B * T * J, 3 * D), 21, 2.0).cuda()
     out = E.op_attention(qkv, B, T, J, H, temporal, force_generic=generic)
-    ref = _attn_ref(qkv, B, T, J, H, temporal)
+    ref = attn_ref(qkv, B, T, J, H, temporal)
     assert maxabs(out, ref.cpu()) < 5e-6
     if temporal and not generic:   # the fp16-MFMA (F16X3) temporal kernel: planes in, planes out, fp32-level accuracy
         out3 = E.op_attention(qkv, B, T, J, H, True, precision="f16x3")
@@ -221,7 +200,7 @@ def test_attention_persistent_kernels(B, T, J, temporal):
     n1 = (1 if T > 32 else 8) * T * J                       # a launch small enough for the non-persistent kernels
     b1 = n1 // (T * J)
     one = slice(0, n1)
-    ref = _attn_ref(qkv[one], b1, T, J, H, True)
+    ref = attn_ref(qkv[one], b1, T, J, H, True)
     assert maxabs(out[one], ref.cpu()) < 5e-6
     small = E.op_attention(qkv[one].contiguous(), b1, T, J, H, True, precision="f16x3")
     assert torch.equal(out[one], small)
@@ -239,7 +218,7 @@ def test_attention_fast_kernels_agree_with_generic_on_sharp_softmax():
         qkv = hashed(f"sharp{T}", (B * T * J, 3 * 512), 22, 9.0).cuda()
         a = E.op_attention(qkv, B, T, J, 8, temporal)
         b = E.op_attention(qkv, B, T, J, 8, temporal, force_generic=True)
-        ref = _attn_ref(qkv, B, T, J, 8, temporal)
+        ref = attn_ref(qkv, B, T, J, 8, temporal)
         assert torch.isfinite(a).all() and torch.isfinite(b).all()
         assert maxabs(a, ref.cpu()) < 2e-3 and maxabs(b, ref.cpu()) < 2e-3
         assert maxabs(a, b.cpu()) < 2e-3

@@ -11,29 +11,18 @@ import pytest
 import torch
 
 from conftest import gold
-from helpers import cfg_full, cfg_small, inputs, hashed, build_product, maxabs, torch_sd
+from helpers import cfg_full, cfg_small, inputs, hashed, build_product, product, maxabs, torch_sd
 import diff3dhpe_amd as d3d
 from diff3dhpe_amd import _lib
 from diff3dhpe_amd.spec import DenoiserConfig
-from diff3dhpe_amd.synth import synth_state_dict
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
 PRECS = ["fp32", "f16x3"]
 
 
-def _tl_sd(cfg, seed):
-    return {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family="trainedlike").items()}
-
-
 def _tl_product(cfg, seed, prec, sampling=9):
-    net = d3d.HPE_model(d3d.S2S_NAME)(num_frame=cfg.num_frame, num_joints=17, in_chans=2, embed_dim=512, depth=8, num_heads=8,
-                                      mlp_ratio=2.0, qkv_bias=True, qk_scale=None, drop_path_rate=0.1)
-    net.load_state_dict(_tl_sd(cfg, seed), strict=True)
-    net.precision = prec
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff
+    return product(cfg, seed, prec, sampling, family="trainedlike")
 
 
 @pytest.mark.parametrize("prec", PRECS)

@@ -8,17 +8,12 @@
   * p_losses' weighted loss and the repeat_n tiling / hypothesis mean as engine kernels (d3d_weighted_loss, d3d_repeat_batch,
     d3d_hypothesis_mean) against their host-framework formulas, bit for bit,
   * a module moved with .to() between devices / engines."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
-from conftest import gold, ROOT
-from helpers import cfg_full, cfg_small, inputs, build_product, maxabs, torch_sd
+from conftest import gold
+from helpers import cfg_full, cfg_small, inputs, build_product, product, maxabs, torch_sd, bench_subprocess, clean_env
 import diff3dhpe_amd as d3d
 from diff3dhpe_amd import _lib
 from diff3dhpe_amd.synth import synth_state_dict
@@ -26,17 +21,6 @@ from diff3dhpe_amd.synth import synth_state_dict
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
 PRECS = ["fp32", "f16x3"]
-
-
-def _product(cfg, seed, prec, sampling=9, family="uniform"):
-    name = d3d.S2F_NAME if cfg.seq2frame else d3d.S2S_NAME
-    net = d3d.HPE_model(name)(num_frame=cfg.num_frame, num_joints=17, in_chans=2, embed_dim=cfg.embed_dim, depth=cfg.depth, num_heads=8,
-                              mlp_ratio=2.0, qkv_bias=True, qk_scale=None, drop_path_rate=0.1, with_time_emb=cfg.with_time_emb)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family=family).items()}, strict=True)
-    net.precision = prec
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff
 
 
 # ------------------------------------------------------------------------------------------------ the missing fixtures
@@ -48,7 +32,7 @@ CASES = [("s2f_notemb_T27", cfg_full(27, seq2frame=True, with_time_emb=False), "
 @pytest.mark.parametrize("tag,cfg,family", CASES, ids=[c[0] for c in CASES])
 def test_forward_denoise_golden_round4(tag, cfg, family, prec):
     g = gold("denoise_" + tag)
-    net, diff = _product(cfg, int(g["seed"]), prec, family=family)
+    net, diff = product(cfg, int(g["seed"]), prec, family=family)
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
     eng.range_flags(clear=True)
     inp = inputs(2, 27, int(g["input_seed"]))
@@ -68,7 +52,7 @@ def test_ddim_loop_golden_seq2frame_without_time_embedding(prec):
     """The 3DHP command line (Experiments.sh:15-17): ...S2F... model, with_time_emb False, 7 DDIM steps, (B, 1, J, 3) targets."""
     g = gold("ddim_s2f_notemb_T27_S7")
     cfg = cfg_full(27, seq2frame=True, with_time_emb=False)
-    _, diff = _product(cfg, int(g["seed"]), prec, sampling=int(g["S"]))
+    _, diff = product(cfg, int(g["seed"]), prec, sampling=int(g["S"]))
     inp = inputs(int(g["B"]), 27, int(g["input_seed"]))
     noise = inp["noise"][:, :1].contiguous()
     loss, y0 = diff(clean_3d_pose=torch.zeros_like(noise).cuda(), noisy_2d_pose=inp["x2d"].cuda(), output_loss=False, init_noise=noise.cuda())
@@ -83,7 +67,7 @@ def test_bf16_mode_on_the_trainedlike_family():
     from oracle import d3d_oracle as orc
     from test_gpu_bf16 import _emulations, _mpjpe, GATE_MAXABS, GATE_MPJPE
     cfg = cfg_full(27)
-    net, _ = _product(cfg, 11, "bf16", family="trainedlike")
+    net, _ = product(cfg, 11, "bf16", family="trainedlike")
     sd = {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, 11, family="trainedlike").items()}
     inp = inputs(2, 27, 500)
     xcat = torch.cat([inp["x2d"], inp["noise"] * 0.7], dim=-1)
@@ -98,22 +82,6 @@ def test_bf16_mode_on_the_trainedlike_family():
 
 
 # ------------------------------------------------------------------------------------------------ multi-process / multi-device
-def _bench_line(args, env, timeout=900):
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, env=env, cwd=ROOT,
-                         timeout=timeout)
-    assert run.returncode == 0, run.stderr[-3000:]
-    lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
-    assert len(lines) == 1, run.stdout[-2000:]
-    return json.loads(lines[0])
-
-
-def _clean_env(**extra):
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "D3D_FORCE_DIST",
-                                                             "D3D_BENCH_ONE_DEVICE", "D3D_DIST_BACKEND")}
-    env.update(extra)
-    return env
-
-
 COMMON = ["--steps", "1", "--warmup", "0", "--frames", "27", "--sampling", "3", "--no-cpu-baseline", "--no-extras"]
 
 
@@ -122,7 +90,7 @@ def test_bench_dump_outputs_is_the_timed_result_and_repeats(tmp_path):
     dumped sums are the ones behind the line's MPJPE, and the dumped prediction is the batch's (B, T, J, 3) poses."""
     args = ["--gpus", "1", "--batch", "4", "--steps", "2", "--warmup", "1", "--frames", "27", "--sampling", "3", "--no-cpu-baseline",
             "--no-extras", "--profile-steps", "0"]
-    lines = [_bench_line(args + ["--dump-outputs", str(tmp_path / f"run{i}")], _clean_env()) for i in range(2)]
+    lines = [bench_subprocess(args + ["--dump-outputs", str(tmp_path / f"run{i}")], clean_env()) for i in range(2)]
     assert all(l["steps"] == 2 and l["ms_per_step"] > 0 for l in lines)
     pred = [np.load(tmp_path / f"run{i}" / "pred.npy") for i in range(2)]
     sums = [np.load(tmp_path / f"run{i}" / "mpjpe_sums.npy") for i in range(2)]
@@ -135,8 +103,8 @@ def test_bench_self_launch_two_ranks_on_one_device():
     """`python bench.py --gpus 2` -- NO torchrun in the command: bench.py starts its two rank processes itself (before torch or HIP
     are touched), they share cuda:0 through gloo (D3D_BENCH_ONE_DEVICE=1), rank 0's single JSON line is relayed, and the gathered
     MPJPE equals the one-process value for the same global batch."""
-    two = _bench_line(["--gpus", "2", "--batch", "3"] + COMMON, _clean_env(D3D_BENCH_ONE_DEVICE="1", D3D_DIST_BACKEND="gloo"))
-    one = _bench_line(["--gpus", "1", "--batch", "6"] + COMMON, _clean_env())
+    two = bench_subprocess(["--gpus", "2", "--batch", "3"] + COMMON, clean_env(D3D_BENCH_ONE_DEVICE="1", D3D_DIST_BACKEND="gloo"))
+    one = bench_subprocess(["--gpus", "1", "--batch", "6"] + COMMON, clean_env())
     assert two["n_gpus"] == 2 and two["config"]["global_batch"] == 6 == one["config"]["global_batch"]
     assert two["mpjpe_vs_synthetic_gt"] == one["mpjpe_vs_synthetic_gt"]
     assert two["dist"]["launcher"] == "self" and two["dist"]["world_size"] == 2 and two["dist"]["backend"] == "gloo"
@@ -148,10 +116,10 @@ def test_two_ranks_on_one_device_repeat():
     compiler's free instruction stream; the kept stream is pinned by tests/test_abi_host.py, the mechanism is open): five two-rank
     runs at T = 81 (2 samplings x 9 steps x 2 ranks each = 180 head launches beside the other rank's GEMMs) must all report the same
     MPJPE, bit for bit.  The 20-run T = 243 form stays opt-in (tests/test_gpu_parity.py, D3D_SLOW_TESTS=1)."""
-    env = _clean_env(D3D_BENCH_ONE_DEVICE="1", D3D_DIST_BACKEND="gloo")
+    env = clean_env(D3D_BENCH_ONE_DEVICE="1", D3D_DIST_BACKEND="gloo")
     seen = set()
     for i in range(5):
-        line = _bench_line(["--gpus", "2", "--batch", "2", "--steps", "2", "--warmup", "0", "--frames", "81", "--sampling", "9",
+        line = bench_subprocess(["--gpus", "2", "--batch", "2", "--steps", "2", "--warmup", "0", "--frames", "81", "--sampling", "9",
                             "--no-cpu-baseline", "--no-extras", "--no-selfcheck", "--profile-steps", "0"], env)
         seen.add(line["mpjpe_vs_synthetic_gt"])
     assert len(seen) == 1, seen
@@ -160,8 +128,8 @@ def test_two_ranks_on_one_device_repeat():
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two HIP devices")
 def test_bench_self_launch_two_ranks_on_two_devices_rccl():
     """Plain `python bench.py --gpus 2`, backend nccl (RCCL), one process per GPU: MPJPE == the one-rank value for the same batch."""
-    two = _bench_line(["--gpus", "2", "--batch", "3"] + COMMON, _clean_env(HSA_ENABLE_IPC_MODE_LEGACY="0"))
-    one = _bench_line(["--gpus", "1", "--batch", "6"] + COMMON, _clean_env())
+    two = bench_subprocess(["--gpus", "2", "--batch", "3"] + COMMON, clean_env(HSA_ENABLE_IPC_MODE_LEGACY="0"))
+    one = bench_subprocess(["--gpus", "1", "--batch", "6"] + COMMON, clean_env())
     assert two["dist"]["backend"] == "nccl" and two["dist"]["world_size"] == 2 and two["dist"]["one_process_per_gpu"]
     assert two["mpjpe_vs_synthetic_gt"] == one["mpjpe_vs_synthetic_gt"]
 
@@ -338,7 +306,7 @@ def test_fused_spatial_blocks_are_bit_identical_to_the_two_kernel_flow(T, B, fam
     bit for bit the one of the two-kernel flow -- whose parity against the reference the golden tests establish.  Frame counts
     that are / are not multiples of the 15-frame tile, one to many tiles per workgroup, both weight families, the range guard silent."""
     cfg = cfg_full(T)
-    _, diff = _product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=2, family=family)
+    _, diff = product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=2, family=family)
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
     inp = inputs(B, T, 77)
     x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
@@ -357,7 +325,7 @@ def test_fused_spatial_blocks_with_garbage_workspace_and_large_batch():
     repeats a group's last frame in its pad rows: neither may let them reach a stored value: workspace filled with NaN, B = 32 at
     T = 243 (30 / 17 tiles per workgroup, ragged last M-tile), two streams."""
     cfg = cfg_full(243)
-    _, diff = _product(cfg, 5, "f16x3", sampling=1)
+    _, diff = product(cfg, 5, "f16x3", sampling=1)
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
     inp = inputs(32, 243, 78)
     x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
@@ -397,7 +365,7 @@ def test_fused_temporal_blocks_are_bit_identical_to_the_two_kernel_flow(T, B, fa
     epilogue arithmetic of the qkv GEMM and the attention arithmetic of k_attn_temporal_x3s: the sampling is bit for bit the one of
     the two-kernel flow.  Frame counts with and without pad rows in the tile, few and many groups per workgroup, both weight families."""
     cfg = cfg_full(T)
-    _, diff = _product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=2, family=family)
+    _, diff = product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=2, family=family)
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
     inp = inputs(B, T, 78)
     x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
@@ -446,7 +414,7 @@ def test_fused_temporal_blocks_grouped_form_for_short_sequences(T, B, family, s2
     from oracle import d3d_oracle as orc
     cfg = cfg_full(T, seq2frame=s2f)
     seed = 11 if family == "trainedlike" else 5
-    _, diff = _product(cfg, seed, "f16x3", sampling=2, family=family)
+    _, diff = product(cfg, seed, "f16x3", sampling=2, family=family)
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
     inp = inputs(B, T, 83)
     x2d = inp["x2d"].cuda()
@@ -499,7 +467,7 @@ def test_fc1_kernel_is_bit_identical_to_the_template_form(T, B, family):
     for bit the token GEMM's LN-folded GELU form.  Ragged last M-tile (rows beyond the matrix are staged and multiplied, never read
     back), NaN-filled workspace, the range guard silent."""
     cfg = cfg_full(T)
-    _, diff = _product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=1, family=family)
+    _, diff = product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=1, family=family)
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
     inp = inputs(B, T, 79)
     x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
@@ -519,7 +487,7 @@ def test_proj_kernel_is_bit_identical_to_the_template_form(T, B, family):
     template's own epilogue function; the rows behind the last whole tile through the template's checked forms): bit for bit the
     token GEMM's plane-residual + row-statistics form.  Token counts that are and are not multiples of 192, NaN-filled workspace."""
     cfg = cfg_full(T)
-    _, diff = _product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=1, family=family)
+    _, diff = product(cfg, 11 if family == "trainedlike" else 5, "f16x3", sampling=1, family=family)
     eng = diff._engine(torch.device("cuda", torch.cuda.current_device()))
     inp = inputs(B, T, 80)
     x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import cfg_full, inputs, maxabs, torch_sd
+from helpers import cfg_full, inputs, maxabs, torch_sd, dev, build_product, bench_subprocess, clean_env
 import diff3dhpe_amd as d3d
 from diff3dhpe_amd import _lib
 from diff3dhpe_amd.evaluate import evaluate
@@ -20,10 +20,6 @@ from diff3dhpe_amd.spec import DenoiserConfig
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _outlier_channel(sd):
@@ -44,16 +40,10 @@ def _forty_sigma(sd):
 
 
 def _model(cfg, seed, mutate, precision=None, sampling=3):
+    """(sd, net, diff): the seeded state dict after mutate(sd) and the product built on it; precision=None is the net's default ("auto")."""
     sd = torch_sd(cfg, seed)
     mutate(sd)
-    net = d3d.HPE_model(d3d.S2F_NAME if cfg.seq2frame else d3d.S2S_NAME)(
-        num_frame=cfg.num_frame, num_joints=17, in_chans=2, embed_dim=cfg.embed_dim, depth=cfg.depth, num_heads=8, mlp_ratio=2.0,
-        qkv_bias=True, qk_scale=None, drop_path_rate=0.1, with_time_emb=cfg.with_time_emb)
-    net.load_state_dict(sd, strict=True)
-    if precision is not None:
-        net.precision = precision
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
+    net, diff = build_product(cfg, seed, sampling=sampling, precision=precision, sd=sd)
     return sd, net, diff
 
 
@@ -62,7 +52,7 @@ def test_default_precision_is_auto_and_the_guard_is_on_without_any_environment_v
     net = d3d.HPE_model(d3d.S2S_NAME)(num_frame=9, embed_dim=512, depth=1)
     assert net.precision == "auto" and net.range_check is True
     net.load_state_dict(torch_sd(DenoiserConfig(num_frame=9, embed_dim=512, depth=1), 3))
-    eng = net.cuda().engine_for(_dev())
+    eng = net.cuda().engine_for(dev())
     assert eng.precision == "f16x3"                      # the engine "auto" starts on
     assert not net._engines_fb                           # the fp32 engine exists only once the guard has fired
 
@@ -199,7 +189,7 @@ def test_range_ticket_abi():
     net.range_check = False
     _, neth, diffh = _model(cfg, 8, lambda sd: None, precision="f16x3", sampling=2)
     neth.range_check = False
-    eb, eh = diff._engine(_dev()), diffh._engine(_dev())
+    eb, eh = diff._engine(dev()), diffh._engine(dev())
     eb.range_flags(clear=True)
     t_empty = eb.post_range()
     assert eb.take_range(t_empty) == 0
@@ -224,7 +214,7 @@ def test_range_ticket_abi():
     # the sticky weight flag travels with every ticket
     _, netw, diffw = _model(cfg, 8, lambda sd: sd["STEblocks.0.mlp.fc1.weight"].__setitem__((3, 5), float("inf")), precision="f16x3", sampling=2)
     netw.range_check = False
-    ew = diffw._engine(_dev())
+    ew = diffw._engine(dev())
     assert ew.take_range(ew.post_range()) & _lib.RANGE_WEIGHT
 
 
@@ -248,7 +238,7 @@ def test_timestep_indices_outside_the_tables():
         diff.p_losses(gt, x2d, noise=nz, t=torch.tensor([1, 2]).cuda())      # a short t
     ok = diff.q_sample(gt, torch.tensor([0, 999, 5]).cuda(), nz)
     assert torch.isfinite(ok).all()
-    eng = diff._engine(_dev())
+    eng = diff._engine(dev())
     eng.range_flags(clear=True)
     t = torch.tensor([0, 10 ** 6, -7])
     out = eng.q_sample(gt, t, nz, check_t=False)
@@ -260,25 +250,6 @@ def test_timestep_indices_outside_the_tables():
 
 
 # ------------------------------------------------------------------------------------------------ many ranks, ragged global batches
-def _bench(args, env, timeout=900):
-    import json
-    import subprocess
-    import sys
-    from conftest import ROOT
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, env=env, cwd=ROOT, timeout=timeout)
-    assert run.returncode == 0, run.stderr[-3000:]
-    lines = [l for l in run.stdout.splitlines() if l.startswith("{")]
-    assert len(lines) == 1, run.stdout[-2000:]
-    return json.loads(lines[0])
-
-
-def _env(**extra):
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "D3D_FORCE_DIST",
-                                                             "D3D_BENCH_ONE_DEVICE", "D3D_DIST_BACKEND")}
-    env.update(extra)
-    return env
-
-
 SMALL = ["--steps", "1", "--warmup", "0", "--frames", "27", "--sampling", "3", "--no-cpu-baseline", "--no-extras", "--profile-steps", "0",
          "--no-selfcheck"]
 
@@ -290,8 +261,8 @@ def test_bench_self_launch_five_ranks_on_one_device_ragged_global_batch(gb):
     `python bench.py --gpus 5 --global-batch 7` -> shards of 2,2,1,1,1 rows; `--global-batch 4` -> 1,1,1,1 and a rank with NO row that
     still joins the collective.  One JSON line, MPJPE equal to the one-rank value for the same global batch, start-up time and range
     flags reported over ranks, every rank building only its shard."""
-    many = _bench(["--gpus", "5", "--global-batch", str(gb)] + SMALL, _env(D3D_BENCH_ONE_DEVICE="1", D3D_DIST_BACKEND="gloo"))
-    one = _bench(["--gpus", "1", "--global-batch", str(gb)] + SMALL, _env())
+    many = bench_subprocess(["--gpus", "5", "--global-batch", str(gb)] + SMALL, clean_env(D3D_BENCH_ONE_DEVICE="1", D3D_DIST_BACKEND="gloo"))
+    one = bench_subprocess(["--gpus", "1", "--global-batch", str(gb)] + SMALL, clean_env())
     assert many["n_gpus"] == 5 and many["config"]["global_batch"] == gb == one["config"]["global_batch"]
     assert many["mpjpe_vs_synthetic_gt"] == one["mpjpe_vs_synthetic_gt"]
     r = many["ranks"]
@@ -303,9 +274,9 @@ def test_bench_self_launch_five_ranks_on_one_device_ragged_global_batch(gb):
 
 def test_bench_strong_scaling_mode_names_itself():
     """--scaling strong fixes the GLOBAL batch (512 = BASELINE configs[2] unless --global-batch) and splits it over the ranks."""
-    line = _bench(["--gpus", "1", "--scaling", "strong", "--global-batch", "6"] + SMALL, _env())
+    line = bench_subprocess(["--gpus", "1", "--scaling", "strong", "--global-batch", "6"] + SMALL, clean_env())
     assert line["scaling"] == "strong" and line["config"]["global_batch"] == 6 and "strong scaling" in line["config"]["workload"]
-    weak = _bench(["--gpus", "1", "--batch", "6"] + SMALL, _env())
+    weak = bench_subprocess(["--gpus", "1", "--batch", "6"] + SMALL, clean_env())
     assert weak["scaling"] == "weak" and weak["mpjpe_vs_synthetic_gt"] == line["mpjpe_vs_synthetic_gt"]
 
 
@@ -414,7 +385,7 @@ def test_head_kernel_recompute_fence(prec):
     _, net, diff = _model(cfgd, 6, lambda sd: None, precision=prec, sampling=3)
     inp = inputs(3, 27, 41)
     z, x2d, nz = torch.zeros(3, 27, 17, 3).cuda(), inp["x2d"].cuda(), inp["noise"].cuda()
-    eng = diff._engine(_dev())
+    eng = diff._engine(dev())
     with warnings.catch_warnings():
         warnings.simplefilter("error")
         _, clean = diff(clean_3d_pose=z, noisy_2d_pose=x2d, output_loss=False, init_noise=nz)
@@ -497,7 +468,7 @@ def test_bf16_gemm_kernel_is_bit_identical_to_the_token_gemm_forms(T, B):
     checked epilogue) and the workspace is filled with NaN first (operand pad rows are staged, never stored)."""
     cfg = type(cfg_full(T))(num_frame=T, embed_dim=512, depth=2)
     _, net, diff = _model(cfg, 21, lambda sd: None, precision="bf16", sampling=2)
-    eng = diff._engine(_dev())
+    eng = diff._engine(dev())
     inp = inputs(B, T, 77)
     x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
     assert (B * T * 17) % 256 != 0

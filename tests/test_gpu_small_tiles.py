@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 import diff3dhpe_amd as d3d
 from conftest import gold
-from helpers import hashed, maxabs, inputs, cfg_full, build_product
+from helpers import hashed, maxabs, inputs, cfg_full, build_product, dev, cu_count
 from diff3dhpe_amd.engine import op_layernorm, op_linear, op_attention, op_qkv_attn_x3_small
 from diff3dhpe_amd.spec import DenoiserConfig
 from diff3dhpe_amd.synth import synth_inputs, synth_state_dict
@@ -25,14 +25,6 @@ from diff3dhpe_amd.synth import synth_inputs, synth_state_dict
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
 D, H = 512, 8
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _cus():
-    return torch.cuda.get_device_properties(_dev()).multi_processor_count
 
 
 def expected_small(T, B, J, n_cu):
@@ -85,7 +77,7 @@ def _model(T, J=17, prec="f16x3", sharp=1.0, depth=1):
         net.range_check = False
         diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=2, loss_type="l2", clip_denoised=True,
                                      beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-        _MODELS[key] = (net, diff, diff._engine(_dev()))
+        _MODELS[key] = (net, diff, diff._engine(dev()))
     return _MODELS[key]
 
 
@@ -99,7 +91,7 @@ def _flow(net, small, fused=None, direct=None):
     """latency_mode on; small tiles on / off; the fused kernels and block 0's direct form on (default) or off.  Returns the engine."""
     net.latency_mode = True
     net.latency_small_tiles = bool(small)
-    eng = net.engine_for(_dev())
+    eng = net.engine_for(dev())
     fused = small if fused is None else fused
     direct = small if direct is None else direct
     eng.set_option("fused_spatial", int(fused))
@@ -113,7 +105,7 @@ def _restore(net):
     eng.set_option("streams", 2)
     eng.set_graph_mode(False)
     net.latency_mode = False
-    net.engine_for(_dev())
+    net.engine_for(dev())
 
 
 def _xt(T, B, J, seed):
@@ -140,7 +132,7 @@ def test_small_tiles_equal_the_two_kernel_flow_bit_for_bit(T, B, J):
     net, _, _ = _model(T, J)
     x, t = _xt(T, B, J, 500 + T + J)
     try:
-        bits = expected_small(T, B, J, _cus())
+        bits = expected_small(T, B, J, cu_count())
         assert bits == (0 if (T, B) == (81, 2) else 3), (T, B, J, bits)
         for direct in (True, False):              # False: block 0 through the small spatial kernel's k-loop
             eng = _flow(net, False, direct=direct)
@@ -303,7 +295,7 @@ def test_shapes_outside_the_predicate_keep_their_kernels(T, J):
     there are bit-identical."""
     net, _, _ = _model(T, J)
     x, t = _xt(T, 1, J, 900 + T + J)
-    want_bits = expected_small(T, 1, J, _cus())
+    want_bits = expected_small(T, 1, J, cu_count())
     assert want_bits == {(128, 17): 1, (243, 17): 0, (27, 21): 2}[(T, J)]     # (256 CUs; T = 243: 35 x 8 small spatial workgroups > 160)
     try:
         _flow(net, False, direct=True)
@@ -345,11 +337,11 @@ def test_without_latency_mode_the_key_is_inert():
     x, t = _xt(81, 1, 17, 960)
     net.latency_mode = False
     net.latency_small_tiles = False
-    eng = net.engine_for(_dev())
+    eng = net.engine_for(dev())
     want = net.forward_denoise(x, t).clone()
     try:
         net.latency_small_tiles = True
-        assert net.engine_for(_dev()) is eng
+        assert net.engine_for(dev()) is eng
         got = net.forward_denoise(x, t).clone()
         assert eng.info("small_tiles") == 1 and eng.info("latency_mode") == 0 and eng.info("small_tiles_last") == 0
         assert torch.equal(got, want)
@@ -359,7 +351,7 @@ def test_without_latency_mode_the_key_is_inert():
     finally:
         _restore(net)
         net.latency_small_tiles = False
-        net.engine_for(_dev())
+        net.engine_for(dev())
 
 
 # ------------------------------------------------------------------------------------------------ 7. golden parity
@@ -372,7 +364,7 @@ def test_golden_parity_with_the_option_on(tag, cfg):
     net, _ = build_product(cfg, int(g["seed"]), precision="f16x3")
     net.latency_mode = True
     net.latency_small_tiles = True
-    eng = net.engine_for(_dev())
+    eng = net.engine_for(dev())
     inp = inputs(B, cfg.num_frame, int(g["input_seed"]))
     xcat = torch.cat([inp["x2d"], inp["noise"] * float(g["y_scale"])], dim=-1).cuda()
     worst = 0.0

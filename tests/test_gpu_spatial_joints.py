@@ -11,11 +11,10 @@ each regime of the 16-frame tile: 9 frames (less than a tile), 16 (exactly one, 
 import pytest
 import torch
 
-from helpers import hashed, maxabs
-import diff3dhpe_amd as d3d
+from helpers import hashed, maxabs, attn_ref, torch_sd, product_with_engine, xy
 from diff3dhpe_amd import _lib
 from diff3dhpe_amd.spec import DenoiserConfig
-from diff3dhpe_amd.synth import synth_inputs, synth_state_dict
+from diff3dhpe_amd.synth import synth_inputs
 
 pytestmark = pytest.mark.gpu
 GATE = 1e-4
@@ -27,32 +26,25 @@ def _cfg(T, J, depth=1, **kw):
     return DenoiserConfig(num_frame=T, num_joints=J, embed_dim=512, depth=depth, **kw)
 
 
-def _sd(cfg, seed=11, family="trainedlike"):
-    return {k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, seed, family=family).items()}
+def _sd(cfg, seed=11, family="trainedlike"):   # this module's default weights: seed 11 of the trained-like family
+    return torch_sd(cfg, seed, family)
 
 
-def _product(cfg, seed=11, prec="f16x3", sampling=2, family="trainedlike"):
-    name = d3d.S2F_NAME if cfg.seq2frame else d3d.S2S_NAME
-    net = d3d.HPE_model(name)(num_frame=cfg.num_frame, num_joints=cfg.num_joints, in_chans=2, embed_dim=512, depth=cfg.depth, num_heads=8,
-                              mlp_ratio=2.0, drop_path_rate=0.1, with_time_emb=cfg.with_time_emb)
-    net.load_state_dict(_sd(cfg, seed, family), strict=True)
-    net.precision = prec
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=sampling, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff, diff._engine(torch.device("cuda", torch.cuda.current_device()))
+def _product(cfg, seed=11, prec="f16x3", sampling=2, family="trainedlike"):   # this module's defaults; the weights of _sd
+    return product_with_engine(cfg, seed, prec, sampling, family)
 
 
 def _inputs(cfg, B, seed):
     return {k: torch.from_numpy(v) for k, v in synth_inputs(B, cfg.num_frame, cfg.num_joints, seed=seed).items()}
 
 
-def _xy(cfg, B, seed):
-    inp = _inputs(cfg, B, seed)
-    x2d, nz = inp["x2d"].cuda(), inp["noise"].cuda()
+def _cfg_xy(cfg, B, seed):
+    """xy() at the config's frame and joint counts; a seq2frame model takes the noise of one frame."""
+    x2d, nz = xy(B, cfg.num_frame, seed, cfg.num_joints)
     return x2d, (nz[:, :1].contiguous() if cfg.seq2frame else nz)
 
 
-def _sample(eng, x2d, nz, direct=1, fused=1):
+def _sample(eng, x2d, nz, direct=1, fused=1):   # toggles "block0_direct" and "fused_spatial", reads both *_last keys
     """(output, (fused_spatial_last, block0_direct_last)) of one sampling with the two options set, defaults restored."""
     eng.set_option("block0_direct", direct)
     eng.set_option("fused_spatial", fused)
@@ -69,7 +61,7 @@ def test_the_info_keys_report_the_path_a_sampling_took(J, want):
     cfg = _cfg(9, J)
     _, _, eng = _product(cfg)
     assert (eng.info("fused_spatial_last"), eng.info("block0_direct_last")) == (0, 0)       # before any forward
-    x2d, nz = _xy(cfg, 2, 70 + J)
+    x2d, nz = _cfg_xy(cfg, 2, 70 + J)
     out, last = _sample(eng, x2d, nz)
     assert last == want and torch.isfinite(out).all()
     _, last = _sample(eng, x2d, nz, direct=0, fused=0)
@@ -84,7 +76,7 @@ def test_the_info_keys_report_the_path_a_sampling_took(J, want):
 def test_the_key_stays_zero_on_other_precisions(prec):
     cfg = _cfg(9, 16)
     _, _, eng = _product(cfg, prec=prec)
-    x2d, nz = _xy(cfg, 2, 69)
+    x2d, nz = _cfg_xy(cfg, 2, 69)
     _, last = _sample(eng, x2d, nz)
     assert last == (0, 0)
 
@@ -97,7 +89,7 @@ def test_fused_kernel_and_two_kernel_flow_are_bit_identical(J, T, B):
     block 0 on k_qkv_sattn_direct<J, 2, false> against its plane-writing form + the attention kernel."""
     cfg = _cfg(T, J)
     _, _, eng = _product(cfg)
-    x2d, nz = _xy(cfg, B, 77)
+    x2d, nz = _cfg_xy(cfg, B, 77)
     eng.range_flags(clear=True)
     for direct in (0, 1):
         fused, l1 = _sample(eng, x2d, nz, direct=direct, fused=1)
@@ -134,7 +126,7 @@ def test_bit_identity_at_depth_2_with_a_time_per_row(J):
 def test_bit_identity_without_time_rows_and_with_broadcast_y(J, kind):
     cfg = _cfg(27, J, with_time_emb=False) if kind == "no_time_emb" else _cfg(27, J, seq2frame=True)
     _, _, eng = _product(cfg, family="uniform", seed=5)
-    x2d, nz = _xy(cfg, 3, 79)
+    x2d, nz = _cfg_xy(cfg, 3, 79)
     for direct in (0, 1):
         fused, l1 = _sample(eng, x2d, nz, direct=direct, fused=1)
         plain, l0 = _sample(eng, x2d, nz, direct=direct, fused=0)
@@ -184,7 +176,7 @@ def indep():
     second tile holds the end of element 1 and element 2.  One engine, one clean sampling and one clean denoise for the tests below."""
     cfg = _cfg(9, 15)
     _, _, eng = _product(cfg)
-    x2d, nz = _xy(cfg, 3, 80)
+    x2d, nz = _cfg_xy(cfg, 3, 80)
     t = torch.tensor([508.0, 77.0, 939.0], device="cuda")
     eng.set_option("streams", 2)
     eng.range_flags(clear=True)
@@ -263,24 +255,13 @@ def test_a_non_finite_batch_element_stays_alone(indep, poison, direct):
 
 
 # ------------------------------------------------------------------------------------------------ 5. fp32
-def _attn_ref(qkv, B, T, J, H):
-    """Spatial GRAND core in fp64: groups are the J joints of a frame; O = (softmax(q k^T dh^-0.5) - I) v."""
-    D = qkv.shape[-1] // 3
-    dh = D // H
-    x = qkv.double().reshape(B * T, J, 3, H, dh)
-    q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))          # (G, H, J, dh)
-    a = ((q @ k.transpose(-2, -1)) * dh ** -0.5).softmax(-1)
-    o = (a - torch.eye(J, dtype=a.dtype, device=a.device)) @ v
-    return o.transpose(1, 2).reshape(B * T * J, D)
-
-
 @pytest.mark.parametrize("B,T,J", [(2, 5, 15), (2, 5, 16), (3, 23, 15)])
 def test_fp32_spatial_attention_against_fp64(B, T, J):
     """k_attn_spatial_f32<15> / <16> (four units per wave; at 15 joints four idle lanes, at (3, 23, 15) a ragged last block) to the bound
     test_attention_core holds 17 joints to, the generic kernel beside it."""
     from diff3dhpe_amd import engine as E
     qkv = hashed(f"qkv{T}_{J}_512", (B * T * J, 3 * 512), 21, 2.0).cuda()
-    ref = _attn_ref(qkv, B, T, J, 8).cpu()
+    ref = attn_ref(qkv, B, T, J, 8, False).cpu()
     fast = E.op_attention(qkv, B, T, J, 8, False)
     gen = E.op_attention(qkv, B, T, J, 8, False, force_generic=True)
     print(f"fp32 spatial attention J={J} B={B} T={T}: fast {maxabs(fast, ref):.3e} generic {maxabs(gen, ref):.3e}")
@@ -292,7 +273,7 @@ def test_fp32_spatial_attention_on_a_sharp_softmax(J):
     from diff3dhpe_amd import engine as E
     B, T = 2, 7
     qkv = hashed(f"sharp{T}_{J}", (B * T * J, 3 * 512), 22, 9.0).cuda()
-    ref = _attn_ref(qkv, B, T, J, 8).cpu()
+    ref = attn_ref(qkv, B, T, J, 8, False).cpu()
     a = E.op_attention(qkv, B, T, J, 8, False)
     b = E.op_attention(qkv, B, T, J, 8, False, force_generic=True)
     assert torch.isfinite(a).all() and torch.isfinite(b).all()

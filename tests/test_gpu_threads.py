@@ -11,9 +11,8 @@ import warnings
 import pytest
 import torch
 
-import diff3dhpe_amd as d3d
 from diff3dhpe_amd.spec import DenoiserConfig
-from helpers import inputs, torch_sd
+from helpers import build_product, dev, xy
 
 pytestmark = pytest.mark.gpu
 
@@ -23,26 +22,11 @@ ITERS = 20
 SHAPES = [(27, 3), (243, 1)]
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
+def _product(T, seed, precision="auto"):   # this module's model: D = 512, depth 2, S sampling steps, the default precision
+    return build_product(DenoiserConfig(num_frame=T, embed_dim=512, depth=2), seed, sampling=S, precision=precision)
 
 
-def _product(T, seed, precision="auto"):
-    cfg = DenoiserConfig(num_frame=T, embed_dim=512, depth=2)
-    net = d3d.HPE_model(d3d.S2S_NAME)(num_frame=T, num_joints=17, in_chans=2, embed_dim=512, depth=2, num_heads=8)
-    net.load_state_dict(torch_sd(cfg, seed))
-    net.precision = precision
-    diff = d3d.GaussianDiffusion(model=net, timesteps=1000, sampling_timesteps=S, loss_type="l2", clip_denoised=True,
-                                 beta_schedule="cosine", ddim_sampling_eta=0.0, clipLoss=True).eval().cuda()
-    return net, diff
-
-
-def _batch(B, T, seed):
-    inp = inputs(B, T, seed)
-    return inp["x2d"].cuda(), inp["noise"].cuda()
-
-
-def _sample(diff, x2d, nz):
+def _sample(diff, x2d, nz):   # through the diffusion object's forward(), which is what the threads call
     return diff(clean_3d_pose=torch.zeros_like(nz), noisy_2d_pose=x2d, output_loss=False, init_noise=nz)[1]
 
 
@@ -73,11 +57,11 @@ def _run(*targets):
 def test_lock_is_held_during_a_call(T, B):
     """While another thread holds the engine's lock a call on that engine does not start; released, it runs and gives the serial bits."""
     net, _ = _product(T, 5)
-    x2d, nz = _batch(B, T, 31)
+    x2d, nz = xy(B, T, 31)
     xcat = torch.cat([x2d, nz], dim=-1)
     t = torch.arange(B, device="cuda") * 300 + 7
     serial = net.forward_denoise(xcat, t)
-    eng = net.engine_for(_dev())
+    eng = net.engine_for(dev())
     assert isinstance(eng.lock, type(threading.RLock()))
     out, done = {}, threading.Event()
 
@@ -102,8 +86,8 @@ def test_lock_is_held_during_a_call(T, B):
 def test_two_models_two_threads(T, B, graph):
     """Each thread owns a model and its engine (different weights): 20 samplings each, side by side, every one the serial bits."""
     prods = [_product(T, seed) for seed in (5, 6)]
-    data = [_batch(B, T, seed) for seed in (41, 42)]
-    engs = [net.engine_for(_dev()) for net, _ in prods]
+    data = [xy(B, T, seed) for seed in (41, 42)]
+    engs = [net.engine_for(dev()) for net, _ in prods]
     assert engs[0] is not engs[1]
     serial = [_sample(diff, *xn).clone() for (_, diff), xn in zip(prods, data)]      # eager, one thread
     assert not torch.equal(serial[0], serial[1])
@@ -140,7 +124,7 @@ def test_one_model_two_replicas_two_threads(T):
     each, each sampling its half of a batch of 4 -- ONE engine, one upload, calls serialised by its lock; the halves put together are
     the serial full-batch bits (a row does not depend on the batch it is computed in), and every guarded call posted one ticket."""
     net, diff = _product(T, 7)
-    x2d, nz = _batch(4, T, 51)
+    x2d, nz = xy(4, T, 51)
     serial = _sample(diff, x2d, nz).clone()
     idx = torch.cuda.current_device()
     reps = [torch.nn.parallel.replicate(diff, [idx])[0] for _ in range(2)]
@@ -174,7 +158,7 @@ def test_one_engine_two_threads_on_two_streams():
     T, B = 27, 3
     net, _ = _product(T, 8)
     t = torch.arange(B, device="cuda") * 250 + 3
-    xs = [torch.cat(_batch(B, T, seed), dim=-1) for seed in (61, 62)]
+    xs = [torch.cat(xy(B, T, seed), dim=-1) for seed in (61, 62)]
     serial = [net.forward_denoise(x, t).clone() for x in xs]
     assert not torch.equal(serial[0], serial[1])
     torch.cuda.synchronize()
@@ -204,9 +188,9 @@ def test_deferred_block_beside_a_plain_call(T, B):
     """deferred_range_checks() open in this thread; a guarded call made meanwhile by another thread is read at once and never lands in
     this thread's box; this thread's own call does."""
     net, diff = _product(T, 9)
-    x2d, nz = _batch(B, T, 71)
+    x2d, nz = xy(B, T, 71)
     serial = _sample(diff, x2d, nz).clone()
-    eng = net.engine_for(_dev())
+    eng = net.engine_for(dev())
     takes = []
     real_take = eng.take_range
 
@@ -237,7 +221,7 @@ def test_fallback_decision_is_shared():
     T, B = 27, 3
     net, _ = _product(T, 10)
     net32, _ = _product(T, 10, precision="fp32")
-    x2d, nz = _batch(B, T, 81)
+    x2d, nz = xy(B, T, 81)
     xcat = torch.cat([x2d, nz], dim=-1)
     t = torch.arange(B, device="cuda") * 300 + 11
     want = net32.forward_denoise(xcat, t).clone()

@@ -429,7 +429,7 @@ PFX = ("STEblocks.0", "TTEblocks.0")
 MATS = ("qkv_e", "proj_e", "fc1_e", "fc2_e", "qkv_fe", "fc1_fe")
 
 
-def _sd(cfg, seed=8):
+def _sd(cfg, seed=8):   # clones: _doctor writes into the tensors, and numpy's buffers behind torch_sd are shared
     return {k: torch.from_numpy(v).clone() for k, v in synth_state_dict(cfg, seed).items()}
 
 

@@ -1,50 +1,31 @@
 """Host-side contract of the opt-in "latency_mode" (include/d3d.h): the option and info keys, the op-level export, an unchanged
 workspace size, and the packed-fp32 ISA pin on the new object file.  No GPU needed: engines are created on the host only."""
-import ctypes as C
 import os
 import re
 
-import pytest
-
 from diff3dhpe_amd import _lib
-from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import engine_info, host_engine_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture()
-def host_engine():
-    """An engine that exists on the host only (created, never committed): enough for options, info keys and the workspace size."""
-    cfg = DenoiserConfig(num_frame=243, embed_dim=512, depth=8)
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS["f16x3"])
-    h = C.c_void_p()
-    L = _lib.lib()
-    assert L.d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    yield L, h
-    L.d3d_engine_destroy(h)
-
-
-def _info(L, h, key):
-    v = C.c_int64(-1)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
+host_engine = host_engine_fixture(num_frame=243, embed_dim=512, depth=8)
 
 
 def test_option_and_info_keys(host_engine):
     L, h = host_engine
-    assert _info(L, h, "latency_mode") == (0, 0)                      # off by default
+    assert engine_info(L, h, "latency_mode") == (0, 0)                      # off by default
     assert L.d3d_engine_set_option(h, b"latency_mode", 1) == 0        # D3D_OK
-    assert _info(L, h, "latency_mode") == (0, 1)
+    assert engine_info(L, h, "latency_mode") == (0, 1)
     assert L.d3d_engine_set_option(h, b"latency_mode", 0) == 0
-    assert _info(L, h, "latency_mode") == (0, 0)
+    assert engine_info(L, h, "latency_mode") == (0, 0)
 
 
 def test_split_info_reads_zero_before_any_forward(host_engine):
     L, h = host_engine
-    assert _info(L, h, "fc2_split_last") == (0, 0)
+    assert engine_info(L, h, "fc2_split_last") == (0, 0)
     assert L.d3d_engine_set_option(h, b"latency_mode", 1) == 0
-    assert _info(L, h, "fc2_split_last") == (0, 0)
+    assert engine_info(L, h, "fc2_split_last") == (0, 0)
 
 
 def test_op_entry_is_exported_and_declared():

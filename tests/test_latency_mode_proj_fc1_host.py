@@ -2,13 +2,14 @@
 info keys, the op-level exports and their shape predicates.  No GPU needed: the rules are plain host functions of the library (reached
 through their C++ symbols), engines are created on the host only, and the op hooks refuse a shape before they touch the device."""
 import ctypes as C
+from functools import partial
 import os
 import re
 
 import pytest
 
 from diff3dhpe_amd import _lib
-from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import engine_info, host_engine_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EUNSUP = -5   # D3D_EUNSUP (include/d3d.h)
@@ -26,22 +27,8 @@ MS = [1, 17, 130, 459, 918, 1377, 1836, 2754, 4131, 5508, 8262, 16524, 264384]
 CUS = [1, 8, 64, 104, 256, 304]
 
 
-@pytest.fixture()
-def host_engine():
-    cfg = DenoiserConfig(num_frame=243, embed_dim=512, depth=8)
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS["f16x3"])
-    h = C.c_void_p()
-    L = _lib.lib()
-    assert L.d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    yield L, h
-    L.d3d_engine_destroy(h)
-
-
-def _info(L, h, key):
-    v = C.c_int64(-99)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
+host_engine = host_engine_fixture(num_frame=243, embed_dim=512, depth=8)
+_info = partial(engine_info, sentinel=-99)     # -1 is a value these keys hold
 
 
 def test_error_code_constant():

@@ -1,35 +1,16 @@
 """Host-side contract of "long_temporal_f32" (include/d3d.h): FP32 engines with windows of more than 256 frames run their temporal blocks'
 attention on the key-streaming fp32 MFMA kernel (kernels_attn_f32_long.hip).  The option and info keys, the op-level export and an
 unchanged workspace size.  No GPU needed: engines are created on the host only."""
-import ctypes as C
 import os
 import re
 
-import pytest
-
 from diff3dhpe_amd import _lib
-from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import engine_info, host_engine_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture()
-def host_engine():
-    """An FP32 engine at num_frame = 300 that exists on the host only (created, never committed)."""
-    cfg = DenoiserConfig(num_frame=300, embed_dim=512, depth=8)
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS["fp32"])
-    h = C.c_void_p()
-    L = _lib.lib()
-    assert L.d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    yield L, h
-    L.d3d_engine_destroy(h)
-
-
-def _info(L, h, key):
-    v = C.c_int64(-1)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
+host_engine = host_engine_fixture(num_frame=300, embed_dim=512, depth=8, prec="fp32")
 
 
 def test_version_is_136_or_later():
@@ -38,19 +19,19 @@ def test_version_is_136_or_later():
 
 def test_option_defaults_to_on_and_round_trips(host_engine):
     L, h = host_engine
-    assert _info(L, h, "long_temporal_f32") == (0, 1)
+    assert engine_info(L, h, "long_temporal_f32") == (0, 1)
     assert L.d3d_engine_set_option(h, b"long_temporal_f32", 0) == 0
-    assert _info(L, h, "long_temporal_f32") == (0, 0)
+    assert engine_info(L, h, "long_temporal_f32") == (0, 0)
     assert L.d3d_engine_set_option(h, b"long_temporal_f32", 1) == 0
-    assert _info(L, h, "long_temporal_f32") == (0, 1)
+    assert engine_info(L, h, "long_temporal_f32") == (0, 1)
 
 
 def test_last_reads_zero_before_any_forward(host_engine):
     L, h = host_engine
-    assert _info(L, h, "long_temporal_f32_last") == (0, 0)
+    assert engine_info(L, h, "long_temporal_f32_last") == (0, 0)
     assert L.d3d_engine_set_option(h, b"long_temporal_f32", 0) == 0
-    assert _info(L, h, "long_temporal_f32_last") == (0, 0)
-    assert _info(L, h, "long_temporal_last") == (0, 0)
+    assert engine_info(L, h, "long_temporal_f32_last") == (0, 0)
+    assert engine_info(L, h, "long_temporal_last") == (0, 0)
 
 
 def test_workspace_bytes_do_not_depend_on_the_option(host_engine):

@@ -5,9 +5,8 @@ import ctypes as C
 import os
 import re
 
-import pytest
-
 from diff3dhpe_amd import _lib
+from host_helpers import engine_info, host_engine_fixture
 from diff3dhpe_amd.spec import DenoiserConfig
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,36 +20,23 @@ def _create(prec, T=300):
     return _lib.lib().d3d_engine_create(C.byref(c), C.byref(h)), h
 
 
-@pytest.fixture()
-def host_engine():
-    """An F16X3 engine at num_frame = 300 that exists on the host only (created, never committed)."""
-    rc, h = _create("f16x3")
-    assert rc == 0
-    L = _lib.lib()
-    yield L, h
-    L.d3d_engine_destroy(h)
-
-
-def _info(L, h, key):
-    v = C.c_int64(-1)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
+host_engine = host_engine_fixture(num_frame=300, embed_dim=512, depth=8)
 
 
 def test_option_defaults_to_on_and_round_trips(host_engine):
     L, h = host_engine
-    assert _info(L, h, "long_temporal") == (0, 1)
+    assert engine_info(L, h, "long_temporal") == (0, 1)
     assert L.d3d_engine_set_option(h, b"long_temporal", 0) == 0
-    assert _info(L, h, "long_temporal") == (0, 0)
+    assert engine_info(L, h, "long_temporal") == (0, 0)
     assert L.d3d_engine_set_option(h, b"long_temporal", 1) == 0
-    assert _info(L, h, "long_temporal") == (0, 1)
+    assert engine_info(L, h, "long_temporal") == (0, 1)
 
 
 def test_last_reads_zero_before_any_forward(host_engine):
     L, h = host_engine
-    assert _info(L, h, "long_temporal_last") == (0, 0)
+    assert engine_info(L, h, "long_temporal_last") == (0, 0)
     assert L.d3d_engine_set_option(h, b"long_temporal", 0) == 0
-    assert _info(L, h, "long_temporal_last") == (0, 0)
+    assert engine_info(L, h, "long_temporal_last") == (0, 0)
 
 
 def test_workspace_bytes_do_not_depend_on_the_option(host_engine):

@@ -2,38 +2,21 @@
 predicate, the launch predicate and the translation unit.  No GPU needed: engines are created on the host only, the predicates are plain
 host functions of the library (reached through their C++ symbols), and the op hook refuses a shape before it touches the device."""
 import ctypes as C
+from functools import partial
 import os
 import re
 
 import pytest
 
 from diff3dhpe_amd import _lib
-from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import create_host_engine, engine_info, host_engine_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUP = -1, -5   # D3D_EINVAL, D3D_EUNSUP (include/d3d.h)
 
 
-def _engine(precision):
-    cfg = DenoiserConfig(num_frame=81, embed_dim=512, depth=2)
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS[precision])
-    h = C.c_void_p()
-    assert _lib.lib().d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    return h
-
-
-@pytest.fixture()
-def host_engine():
-    h = _engine("f16x3")
-    yield _lib.lib(), h
-    _lib.lib().d3d_engine_destroy(h)
-
-
-def _info(L, h, key):
-    v = C.c_int64(-99)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
+host_engine = host_engine_fixture(num_frame=81, embed_dim=512, depth=2)
+_info = partial(engine_info, sentinel=-99)     # a value no key of this module holds
 
 
 def test_error_code_constants():
@@ -58,7 +41,7 @@ def test_option_defaults_to_0_and_round_trips(host_engine):
 @pytest.mark.parametrize("precision", ["f16x3", "fp32", "bf16"])
 def test_last_key_reads_0_on_a_fresh_engine(precision):
     L = _lib.lib()
-    h = _engine(precision)
+    h = create_host_engine(precision, num_frame=81, embed_dim=512, depth=2)
     try:
         assert _info(L, h, "small_tiles_last") == (0, 0)
         assert L.d3d_engine_set_option(h, b"latency_mode", 1) == 0

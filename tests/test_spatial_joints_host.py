@@ -3,45 +3,29 @@ the info key "fused_spatial_last" exists and reads 0 before any forward in every
 options that select the path, the
 version and the header name the feature, and every translation unit with a spatial kernel is in build.SOURCES.  No GPU needed: engines are
 created on the host only."""
-import ctypes as C
 import os
 
 import pytest
 
 from diff3dhpe_amd import _lib
-from diff3dhpe_amd.spec import DenoiserConfig
+from host_helpers import create_host_engine, engine_info
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 JOINTS = (15, 16, 17)
-
-
-def _host_engine(prec, J, T=27):
-    cfg = DenoiserConfig(num_frame=T, num_joints=J, embed_dim=512, depth=1)
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS[prec])
-    h = C.c_void_p()
-    assert _lib.lib().d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    return h
-
-
-def _info(L, h, key):
-    v = C.c_int64(-1)
-    rc = L.d3d_engine_get_info(h, key.encode(), C.byref(v))
-    return rc, int(v.value)
 
 
 @pytest.mark.parametrize("J", JOINTS)
 @pytest.mark.parametrize("prec", ["f16x3", "bf16", "fp32"])
 def test_fused_spatial_last_reads_zero_on_a_fresh_engine(prec, J):
     L = _lib.lib()
-    h = _host_engine(prec, J)
+    h = create_host_engine(prec, num_frame=27, num_joints=J, embed_dim=512, depth=1)
     try:
-        assert _info(L, h, "fused_spatial_last") == (0, 0)
-        assert _info(L, h, "block0_direct_last") == (0, 0)
+        assert engine_info(L, h, "fused_spatial_last") == (0, 0)
+        assert engine_info(L, h, "block0_direct_last") == (0, 0)
         for key in (b"fused_spatial", b"block0_direct"):
             assert L.d3d_engine_set_option(h, key, 0) == 0 and L.d3d_engine_set_option(h, key, 1) == 0
-        assert _info(L, h, "fused_spatial_last") == (0, 0)           # still no forward
-        assert _info(L, h, "bf16_fused_spatial_last") == (0, 0)      # the bf16 key is its own
+        assert engine_info(L, h, "fused_spatial_last") == (0, 0)           # still no forward
+        assert engine_info(L, h, "bf16_fused_spatial_last") == (0, 0)      # the bf16 key is its own
     finally:
         L.d3d_engine_destroy(h)
 
@@ -50,7 +34,7 @@ def test_fused_spatial_last_reads_zero_on_a_fresh_engine(prec, J):
 @pytest.mark.parametrize("T", [9, 27, 243])
 def test_workspace_bytes_do_not_depend_on_the_spatial_options(J, T):
     L = _lib.lib()
-    h = _host_engine("f16x3", J, T)
+    h = create_host_engine("f16x3", num_frame=T, num_joints=J, embed_dim=512, depth=1)
     try:
         before = [L.d3d_workspace_bytes(h, B) for B in (1, 3, 8)]
         assert all(b > 0 for b in before)

@@ -14,6 +14,7 @@ import torch
 
 import diff3dhpe_amd as d3d
 from diff3dhpe_amd import _lib, nets
+from host_helpers import create_host_engine, engine_info
 
 JOIN = 30.0
 
@@ -278,38 +279,20 @@ def test_guard_counters_under_contention_and_guard_copies(stub):
 
 
 # ---------------------------------------------------------------------------------------- the C ABI itself (host-only engines)
-def _host_engine(L):
-    import ctypes as C
-    from diff3dhpe_amd.spec import DenoiserConfig
-    cfg = DenoiserConfig(num_frame=27, embed_dim=512, depth=2)
-    c = _lib.Config(cfg.num_frame, cfg.num_joints, cfg.in_chans, cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden,
-                    int(cfg.with_time_emb), int(cfg.seq2frame), _lib.PRECISIONS["f16x3"])
-    h = C.c_void_p()
-    assert L.d3d_engine_create(C.byref(c), C.byref(h)) == 0
-    return h
-
-
-def _info(L, h, key):
-    import ctypes as C
-    v = C.c_int64(-1)
-    assert L.d3d_engine_get_info(h, key.encode(), C.byref(v)) == 0
-    return int(v.value)
-
-
 def test_deep_stages_is_a_field_of_the_engine():
     """ "deep_stages" on an engine is that engine's own setting; with a NULL engine it is the process-wide default, which only engines
     without a value of their own follow (include/d3d.h, version 133)."""
     L = _lib.lib()
     assert L.d3d_version() >= 133
-    a, b = _host_engine(L), _host_engine(L)
+    a, b = (create_host_engine("f16x3", num_frame=27, embed_dim=512, depth=2) for _ in range(2))
     try:
-        assert _info(L, a, "deep_stages") == 1 and _info(L, b, "deep_stages") == 1            # the default stays
+        assert engine_info(L, a, "deep_stages") == (0, 1) and engine_info(L, b, "deep_stages") == (0, 1)            # the default stays
         assert L.d3d_engine_set_option(a, b"deep_stages", 0) == 0
-        assert _info(L, a, "deep_stages") == 0 and _info(L, b, "deep_stages") == 1            # ... and no longer leaks to another engine
+        assert engine_info(L, a, "deep_stages") == (0, 0) and engine_info(L, b, "deep_stages") == (0, 1)            # ... and no longer leaks to another engine
         assert L.d3d_engine_set_option(None, b"deep_stages", 0) == 0
-        assert _info(L, b, "deep_stages") == 0                                                 # b follows the process default
+        assert engine_info(L, b, "deep_stages") == (0, 0)                                                 # b follows the process default
         assert L.d3d_engine_set_option(a, b"deep_stages", 1) == 0
-        assert _info(L, a, "deep_stages") == 1 and _info(L, b, "deep_stages") == 0
+        assert engine_info(L, a, "deep_stages") == (0, 1) and engine_info(L, b, "deep_stages") == (0, 0)
     finally:
         assert L.d3d_engine_set_option(None, b"deep_stages", 1) == 0
         L.d3d_engine_destroy(a)
@@ -328,13 +311,13 @@ def test_distinct_engines_from_distinct_threads_at_the_abi():
         def go():
             barrier.wait()
             for k in range(50):
-                h = _host_engine(L)
+                h = create_host_engine("f16x3", num_frame=27, embed_dim=512, depth=2)
                 try:
                     assert L.d3d_engine_set_option(h, b"deep_stages", (i + k) & 1) == 0
                     assert L.d3d_engine_set_option(h, b"latency_mode", i) == 0
                     assert L.d3d_engine_set_option(h, f"no_such_key_{i}".encode(), 1) != 0
                     seen[i].append(L.d3d_last_error().decode())
-                    assert _info(L, h, "deep_stages") == (i + k) & 1 and _info(L, h, "latency_mode") == i
+                    assert engine_info(L, h, "deep_stages") == (0, (i + k) & 1) and engine_info(L, h, "latency_mode") == (0, i)
                     assert L.d3d_engine_num_weights(h) > 0 and L.d3d_workspace_bytes(h, 1 + i) > 0
                 finally:
                     L.d3d_engine_destroy(h)
