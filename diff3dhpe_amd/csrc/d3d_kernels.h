@@ -406,6 +406,17 @@ hipError_t launch_attn_temporal_f32_h32(const float* qkv, float* out, int B, int
 hipError_t launch_attn_spatial_f32_h32(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_temporal_f32_h32_ok(int T, int D, int H);
 bool attn_spatial_f32_h32_ok(int J, int D, int H);
+// ---- kernels_attn_x3_h32_long.hip: launch_attn_x3_h32's temporal attention for windows of any length (D == 32 H, H even): the head
+// pair's keys stream through LDS in chunks of 256 frames, the scores are computed twice.  Same planes in, same pair layout out;
+// bit-identical to launch_attn_x3_h32 wherever that runs (T <= 256).  The launch also refuses B J (H / 2) ceil(T / 256) workgroups beyond
+// 2^31 - 1.
+hipError_t launch_attn_x3_h32_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h32_long_ok(int T, int D, int H);
+// ---- kernels_attn_f32_h32_long.hip: launch_attn_temporal_f32_h32's attention for windows of any length (D == 32 H, any head count):
+// chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out; bit-identical to
+// launch_attn_temporal_f32_h32 wherever that runs (T <= 256).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_temporal_f32_h32_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_temporal_f32_h32_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

@@ -65,12 +65,19 @@ struct BlockPlan {
   // FOLD: every block's attention on the kernel for heads of 32 columns (kernels_attn_x3_h32.hip: D == 32 H, which no other F16X3
   // attention kernel takes); always the two-kernel branch
   bool attn_h32 = false;
+  // FOLD: heads of 32 columns and a window of more than 256 frames, which attn_h32 does not cover: the temporal blocks' attention on the
+  // key-streaming kernel of that width (kernels_attn_x3_h32_long.hip), the spatial blocks' on kernels_attn_x3_h32.hip (groups of J);
+  // always the two-kernel branch.  attn_h32 stays false on such a plan
+  bool h32_long = false;
   // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel (kernels_attn_f32_long.hip: windows of more than 256
   // frames, which k_attn_temporal_f32 cannot hold in LDS); false = k_attn_generic there
   bool tp_long_f32 = false;
   // PLAIN in FP32: the spatial / temporal blocks' attention on the exact fp32 kernels for heads of 32 columns (kernels_attn_f32_h32.hip:
   // D == 32 H, 15 .. 17 joints / windows of up to 256 frames); false = k_attn_generic there
   bool sp_f32_h32 = false, tp_f32_h32 = false;
+  // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel for heads of 32 columns
+  // (kernels_attn_f32_h32_long.hip: D == 32 H, windows of more than 256 frames); false = k_attn_generic there
+  bool tp_long_f32_h32 = false;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
   // PLAIN in F16X3: q / k / v go to the fp16-MFMA attention kernel as planes
@@ -150,6 +157,14 @@ struct d3d_engine {
   // temporal blocks (windows of up to 256 frames) on kernels_attn_f32_h32.hip; 0 = the generic one-thread-per-row kernel.  Changes the
   // order of additions: inside the parity gate, not bit-identical.  F16X3 / BF16 engines and every D == 64 H engine: no effect
   bool opt_attn_f32_h32 = true;
+  // "long_temporal_h32" (on by default): an F16X3 engine whose heads are 32 columns wide and whose window is longer than 256 frames keeps
+  // the folded flow, its temporal blocks on kernels_attn_x3_h32_long.hip and its spatial blocks on kernels_attn_x3_h32.hip; 0 = the plain
+  // row-kernel flow with the generic fp32 attention
+  bool opt_long_temporal_h32 = true;
+  // "long_temporal_f32_h32" (on by default): an FP32 engine of that width and window runs its temporal blocks' attention on
+  // kernels_attn_f32_h32_long.hip; 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not
+  // bit-identical.  F16X3 / BF16 engines: no effect
+  bool opt_long_temporal_f32_h32 = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -170,7 +185,8 @@ struct d3d_engine {
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
   // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip, "long_temporal_f32_last" = the same for
   // kernels_attn_f32_long.hip, "attn_h32_last" = whether the blocks ran kernels_attn_x3_h32.hip, "attn_f32_h32_last" = bit 0 / bit 1:
-  // whether the spatial / temporal blocks ran kernels_attn_f32_h32.hip
+  // whether the spatial / temporal blocks ran kernels_attn_f32_h32.hip, "long_temporal_h32_last" / "long_temporal_f32_h32_last" = whether
+  // the temporal blocks ran kernels_attn_x3_h32_long.hip / kernels_attn_f32_h32_long.hip
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -406,6 +422,7 @@ int attention(d3d_engine* e, const BlockPlan& pl, const float* qkv, float* out, 
   } else {
     if (pl.tp_f32_h32) HIP_TRY(launch_attn_temporal_f32_h32(qkv, out, B, e->T, e->J, e->D, e->H, s));
     else if (pl.tp_long_f32) HIP_TRY(launch_attn_temporal_f32_long(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (FP32 engines only: no out_x3)
+    else if (pl.tp_long_f32_h32) HIP_TRY(launch_attn_temporal_f32_h32_long(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (the same)
     else if (attn_temporal_fast_ok(e->T, e->D, e->H)) HIP_TRY(launch_attn_temporal_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
     else HIP_TRY(launch_attn_generic(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, 1, s));
   }
@@ -423,9 +440,13 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   // heads of 32 columns: the one attention kernel of that width takes both block types (no D == 64 H predicate holds there, so the fused
   // kernels, block 0 direct and the post-norm in fc2 stay off by their own predicates)
   const bool h32 = e->opt_attn_h32 && attn_x3_h32_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
-  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32) && D % 32 == 0 && e->opt_fold_layernorm) {
+  // the same width with a window of more than 256 frames: the spatial blocks keep that kernel (groups of J), the temporal blocks stream
+  const bool h32_long = e->opt_long_temporal_h32 && T > 256 && attn_x3_h32_long_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
+  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long) && D % 32 == 0 &&
+      e->opt_fold_layernorm) {
     p.flow = BlockPlan::FOLD;
     p.attn_h32 = h32;
+    p.h32_long = h32_long;
     p.tp_long = tp_long;      // (qkv_tattn_ok refuses T > 255: such temporal blocks take the two-kernel branch)
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
@@ -482,6 +503,7 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
     // heads of 32 columns: no D == 64 H predicate holds there; each block type takes its kernel of that width where its group length fits
     p.sp_f32_h32 = e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H);
     p.tp_f32_h32 = e->opt_attn_f32_h32 && attn_temporal_f32_h32_ok(T, D, H);
+    p.tp_long_f32_h32 = e->opt_long_temporal_f32_h32 && T > 256 && attn_temporal_f32_h32_long_ok(T, D, H);
   }
   return p;
 }
@@ -631,6 +653,7 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD4, s);
       if (pl.attn_h32) HIP_TRY(temporal ? launch_attn_x3_h32(QKVh, QKVl, AOx, B, T, J, D, e->H, s) : launch_attn_x3_h32(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
+      else if (pl.h32_long) HIP_TRY(temporal ? launch_attn_x3_h32_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s) : launch_attn_x3_h32(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
       else if (temporal && pl.tp_long) HIP_TRY(launch_attn_temporal_x3_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
@@ -974,7 +997,9 @@ unsigned* d3d::range_sink_word() {
 extern "C" {
 
 const char* d3d_last_error(void) { return g_err.c_str(); }
-int d3d_version(void) { return 140; }   // 140: option / info key "attn_f32_h32", info key "attn_f32_h32_last", d3d_op_attention_f32_h32
+// 141: option / info keys "long_temporal_h32", "long_temporal_f32_h32", info keys "long_temporal_h32_last", "long_temporal_f32_h32_last",
+// d3d_op_attention_long_h32, d3d_op_attention_long_f32_h32
+int d3d_version(void) { return 141; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1465,6 +1490,8 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "long_temporal_f32") e->opt_long_temporal_f32 = value != 0;
   else if (k == "attn_h32") e->opt_attn_h32 = value != 0;
   else if (k == "attn_f32_h32") e->opt_attn_f32_h32 = value != 0;
+  else if (k == "long_temporal_h32") e->opt_long_temporal_h32 = value != 0;
+  else if (k == "long_temporal_f32_h32") e->opt_long_temporal_f32_h32 = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1541,6 +1568,10 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "attn_f32_h32_last")
     *value = e->last_plan.flow == BlockPlan::PLAIN ? (e->last_plan.sp_f32_h32 ? 1 : 0) | (e->last_plan.tp_f32_h32 ? 2 : 0) : 0;
   else if (k == "long_temporal_f32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32;
+  else if (k == "long_temporal_h32") *value = e->opt_long_temporal_h32 ? 1 : 0;
+  else if (k == "long_temporal_h32_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.h32_long;
+  else if (k == "long_temporal_f32_h32") *value = e->opt_long_temporal_f32_h32 ? 1 : 0;
+  else if (k == "long_temporal_f32_h32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32_h32;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

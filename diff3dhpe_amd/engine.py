@@ -218,8 +218,11 @@ class Engine:
         one-thread-per-row kernel there, "attn_h32": 1 (default) keeps an F16X3 engine with heads of 32 columns (embed_dim 256, 8 heads,
         num_frame <= 256) on the folded flow, its attention on the fp16-MFMA kernel for that width; 0 gives it the plain row-kernel flow,
         "attn_f32_h32": 1 (default) runs the attention of an FP32 engine with heads of 32 columns on the exact fp32 kernels for that width
-        (15 to 17 joints in the spatial blocks, num_frame <= 256 in the temporal ones); 0 keeps the generic one-thread-per-row kernel);
-        the library reads no environment."""
+        (15 to 17 joints in the spatial blocks, num_frame <= 256 in the temporal ones); 0 keeps the generic one-thread-per-row kernel, "long_temporal_h32": 1
+        (default) keeps an F16X3 engine with heads of 32 columns and num_frame > 256 on the folded flow, its temporal blocks on the
+        key-streaming attention kernel of that width; 0 gives it the plain row-kernel flow, "long_temporal_f32_h32": 1 (default) runs the
+        temporal blocks of an FP32 engine with heads of 32 columns and num_frame > 256 on the key-streaming fp32 kernel of that width; 0
+        keeps the generic one-thread-per-row kernel there); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
@@ -234,7 +237,9 @@ class Engine:
         fp32 attention kernel; "long_temporal_last" stays 0 there), "attn_h32" (the option), "attn_h32_last" (1 when the blocks of the
         most recent forward ran the F16X3 attention kernel for heads of 32 columns; else 0), "attn_f32_h32" (the option),
         "attn_f32_h32_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent forward of an FP32 engine ran the
-        fp32 attention kernels for heads of 32 columns; else 0)."""
+        fp32 attention kernels for heads of 32 columns; else 0), "long_temporal_h32" / "long_temporal_f32_h32" (the options),
+        "long_temporal_h32_last" / "long_temporal_f32_h32_last" (1 when the temporal blocks of the most recent forward of an F16X3 / FP32
+        engine ran the key-streaming attention kernel for heads of 32 columns: num_frame > 256 with the option on; else 0)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -629,6 +634,34 @@ def op_attention_long_f32(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> 
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib().d3d_op_attention_long_f32(_ptr(q), _ptr(out), B, T, J, D, H, st))
+    return out
+
+
+def op_attention_long_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming F16X3 temporal attention kernel for heads of 32 columns alone (include/d3d.h d3d_op_attention_long_h32): qkv
+    (B*T*J, 3*D) -> (B*T*J, D), D == 32 H with H even, any T >= 1; for T <= 256 bit for bit op_attention_h32(..., temporal=True);
+    anything else raises D3DError."""
+    dev = qkv.device
+    D = qkv.shape[-1] // 3
+    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
+    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_attention_long_h32(_ptr(q), _ptr(out), B, T, J, D, H, st))
+    return out
+
+
+def op_attention_long_f32_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming fp32 temporal attention kernel for heads of 32 columns alone (include/d3d.h d3d_op_attention_long_f32_h32): qkv
+    (B*T*J, 3*D) -> (B*T*J, D), D == 32 H, any T >= 1; for T <= 256 bit for bit op_attention_f32_h32(..., temporal=True); anything else
+    raises D3DError."""
+    dev = qkv.device
+    D = qkv.shape[-1] // 3
+    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
+    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_attention_long_f32_h32(_ptr(q), _ptr(out), B, T, J, D, H, st))
     return out
 
 

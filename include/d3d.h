@@ -243,6 +243,27 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     (that block type keeps the generic kernel), every embed_dim == 64 num_heads engine, F16X3 and BF16 engines: no
  *                     effect.  d3d_workspace_bytes does not change.  "attn_f32_h32_last" (d3d_engine_get_info) reports what the latest
  *                     forward ran.
+ *   "long_temporal_h32"  1 (default) / 0: F16X3 engines whose heads are 32 columns wide with an even head count and num_frame > 256, which
+ *                     "attn_h32" does not cover.  With the key on, such an engine keeps the folded flow of "attn_h32": its spatial blocks
+ *                     on the fp16-MFMA kernel of that width (groups of num_joints <= 256 tokens) and its temporal blocks on the
+ *                     key-streaming kernel of that width (a head pair's keys pass through LDS in chunks of 256 frames, the scores are
+ *                     computed twice: the exact two-pass softmax of every other form, bit-identical to the resident kernel wherever that
+ *                     runs) / 0: the plain row-kernel flow with the generic fp32 attention kernel in every block, as before version 141.
+ *                     The two differ in the last bits, both inside the parity gate.  A 9-step sampling at depth 8, num_frame 300: 43.0
+ *                     -> 11.2 ms at B = 1, 1168 -> 308 ms at B = 64.  num_frame <= 256, every embed_dim == 64 num_heads
+ *                     engine, FP32 and BF16 engines: no effect.  "attn_h32_last" and "long_temporal_last" stay 0 on such an engine.
+ *                     d3d_workspace_bytes does not change.  "long_temporal_h32_last" (d3d_engine_get_info) reports what the latest
+ *                     forward ran.
+ *   "long_temporal_f32_h32"  1 (default) / 0: FP32 engines whose heads are 32 columns wide (any head count) and num_frame > 256, which the
+ *                     temporal kernel of "attn_f32_h32" does not cover.  With the key on, the temporal blocks of such an engine run the
+ *                     key-streaming fp32 kernel of that width (v_mfma_f32_32x32x2_f32, keys pass through LDS in chunks of 256 frames,
+ *                     three passes: maximum, sum, normalised product -- the resident kernel's arithmetic in its order, bit-identical to
+ *                     it wherever that runs) / 0: the generic one-thread-per-row kernel, as before version 141.  The two differ in the
+ *                     order of additions, so in the last bits, both inside the parity gate.  A 9-step sampling at depth 8, num_frame 300:
+ *                     54.3 -> 30.5 ms at B = 1, 1328 -> 734 ms at B = 64.  The spatial blocks go on choosing by
+ *                     num_joints alone ("attn_f32_h32").  num_frame <= 256, every embed_dim == 64 num_heads engine, F16X3 and BF16
+ *                     engines: no effect.  d3d_workspace_bytes does not change.  "long_temporal_f32_h32_last" (d3d_engine_get_info)
+ *                     reports what the latest forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -306,7 +327,11 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * width, num_frame > 256, option off, another precision, or before any forward), "attn_f32_h32" (the option value), "attn_f32_h32_last"
  * (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the exact fp32 attention
  * kernels for heads of 32 columns; 0 before any forward, with the option off, on every embed_dim == 64 num_heads engine and in the other
- * precisions), "small_tiles" (the option value), "small_tiles_last" (bit 0: the
+ * precisions), "long_temporal_h32" (the option value), "long_temporal_h32_last" (1 when the temporal blocks of the most recent
+ * d3d_denoise / d3d_ddim_sample call ran the key-streaming F16X3 attention kernel for heads of 32 columns, else 0: another head width,
+ * num_frame <= 256, option off, another precision, or before any forward), "long_temporal_f32_h32" (the option value),
+ * "long_temporal_f32_h32_last" (the same for a D3D_PREC_FP32 engine and the key-streaming fp32 kernel of that width),
+ * "small_tiles" (the option value), "small_tiles_last" (bit 0: the
  * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
  * kernel; 0 before any forward, with the option or "latency_mode" off, and in the other precisions).
  * Unknown key: D3D_EINVAL. */
@@ -533,6 +558,16 @@ int d3d_op_attention_f32_h32(const float* qkv_dev, float* out_dev, int32_t B, in
  * T >= 1, head width D / H == 64 (else D3D_EUNSUP); for T <= 256 bit for bit the result of d3d_op_attention (temporal = 1,
  * D3D_PREC_FP32, force_generic = 0). */
 int d3d_op_attention_long_f32(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
+/* The temporal core of an F16X3 engine with heads of 32 columns from the key-streaming kernel of that width alone (option
+ * "long_temporal_h32"): fp32 qkv in, fp32 out, split into / merged from the hi / lo fp16 planes on the device as in d3d_op_attention
+ * (D3D_PREC_F16X3).  Any T >= 1; D == 32 H with H even, anything else (head_dim 32 is the only width it takes): D3D_EUNSUP.  For
+ * T <= 256 bit for bit the result of d3d_op_attention_h32 (temporal = 1). */
+int d3d_op_attention_long_h32(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
+/* The same for an FP32 engine (option "long_temporal_f32_h32"): fp32 qkv in, fp32 out.  Any T >= 1; D == 32 H, any head count, anything
+ * else (head_dim 32 is the only width it takes): D3D_EUNSUP.  For T <= 256 bit for bit the result of d3d_op_attention_f32_h32
+ * (temporal = 1). */
+int d3d_op_attention_long_f32_h32(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
+                                  void* stream);
 /* The fused qkv GEMM + attention kernel of the BF16 mode alone: out = attention(bf16(A) bf16(Wqkv)^T + bias) with q / k / v rounded to
  * bf16 (q third times dh^-1/2) and kept on chip -- bit for bit d3d_op_linear (D3D_PREC_BF16) followed by d3d_op_attention (D3D_PREC_BF16)
  * on the same tensors.  A: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias: (3 D); out: (groups * N, D) fp32.  Group u holds the N
