@@ -15,11 +15,14 @@
 
 constexpr float X3_C_EXP = 1.4426950408889634f / 64.0f;   // acc = 64 s: scale and log2(e) in one fma feeding v_exp_f32
 // The same constant for a head width DH.  The planes hold raw q and 8 k whatever the width, so acc = 8 q.k and the exponent argument is
-// acc log2(e) / (8 sqrt(DH)): X3_C_EXP itself at 64; at 32 (kernels_attn_x3_h32.hip) evaluated in double and rounded once.
+// acc log2(e) / (8 sqrt(DH)): X3_C_EXP itself at 64; at 32 (kernels_attn_x3_h32.hip) and at 128
+// (kernels_attn_x3_h128.hip) evaluated in double and rounded once.
 template <int DH>
 constexpr float x3_c_exp() {
-  static_assert(DH == 64 || DH == 32, "head widths with a tile form");
-  return DH == 64 ? X3_C_EXP : (float)(1.4426950408889634 / (8.0 * 5.656854249492380195 /* sqrt(32) */));
+  static_assert(DH == 64 || DH == 32 || DH == 128, "head widths with a tile form");
+  return DH == 64 ? X3_C_EXP
+                  : DH == 32 ? (float)(1.4426950408889634 / (8.0 * 5.656854249492380195 /* sqrt(32) */))
+                             : (float)(1.4426950408889634 / (8.0 * 11.313708498984760390 /* sqrt(128) */));
 }
 
 // ---- this lane's query row as MFMA B fragments, d = 16 ks + 8 h .. + 7: from the global planes (o: element offset of a real row's
@@ -66,6 +69,22 @@ __device__ __forceinline__ f32x16 x3_score_tile(const unsigned char* sKh, const 
     s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], s, 0, 0, 0);
   }
   return s;
+}
+
+// The accumulate-into form: the same four d-steps added onto s, for heads wider than one 64-column LDS row (kernels_attn_x3_h128.hip: one
+// chain over the row halves in ascending d, each half's K rows in planes of their own).  x3_score_tile is left as it is, so its
+// instantiations' code does not change.
+__device__ __forceinline__ void x3_score_acc(f32x16& s, const unsigned char* sKh, const unsigned char* sKl, int row0, int r, int h,
+                                             const h8 (&qh)[4], const h8 (&ql)[4]) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int ko = kswz(row0 + r, 2 * ks + h);
+    const h8 kh = *reinterpret_cast<const h8*>(sKh + ko);
+    const h8 kl = *reinterpret_cast<const h8*>(sKl + ko);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], s, 0, 0, 0);
+  }
 }
 
 // keys >= T score -inf: their numerator is an exact 0, whatever bits the K rows hold.  Register q of lane half h, tile's first key key0.

@@ -417,6 +417,16 @@ bool attn_x3_h32_long_ok(int T, int D, int H);
 // launch_attn_temporal_f32_h32 wherever that runs (T <= 256).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_temporal_f32_h32_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_temporal_f32_h32_long_ok(int T, int D, int H);
+// ---- kernels_attn_x3_h128.hip: the F16X3 attention for heads of 128 columns (D == 128 H, any head count: a head is two adjacent
+// 64-column halves, each in LDS rows of the kernels above), groups of T <= 128 tokens.  The contract of launch_attn_temporal_x3: same
+// planes in (raw q, 8 k, 8 v), same pair layout out; spatial blocks call it with (B T, J, 1).
+hipError_t launch_attn_x3_h128(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h128_ok(int N, int D, int H);
+// ---- kernels_attn_x3_h128_long.hip: launch_attn_x3_h128's temporal attention for windows of any length: the head's keys stream through
+// LDS in chunks of 128 frames, the scores are computed twice.  Same planes in, same pair layout out; bit-identical to
+// launch_attn_x3_h128 wherever that runs (T <= 128).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h128_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

@@ -69,6 +69,10 @@ struct BlockPlan {
   // key-streaming kernel of that width (kernels_attn_x3_h32_long.hip), the spatial blocks' on kernels_attn_x3_h32.hip (groups of J);
   // always the two-kernel branch.  attn_h32 stays false on such a plan
   bool h32_long = false;
+  // FOLD: heads of 128 columns (D == 128 H, which no other F16X3 attention kernel takes); always the two-kernel branch.  Bit 0: the
+  // spatial blocks on kernels_attn_x3_h128.hip (groups of J <= 128), bit 1: the temporal blocks on it (T <= 128), bit 2: the temporal
+  // blocks on the key-streaming kernels_attn_x3_h128_long.hip (T > 128).  0 on every other plan
+  int attn_h128 = 0;
   // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel (kernels_attn_f32_long.hip: windows of more than 256
   // frames, which k_attn_temporal_f32 cannot hold in LDS); false = k_attn_generic there
   bool tp_long_f32 = false;
@@ -165,6 +169,10 @@ struct d3d_engine {
   // kernels_attn_f32_h32_long.hip; 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not
   // bit-identical.  F16X3 / BF16 engines: no effect
   bool opt_long_temporal_f32_h32 = true;
+  // "attn_h128" (on by default): an F16X3 engine whose heads are 128 columns wide (embed_dim 1024 with 8 heads) runs the folded flow with
+  // its attention on kernels_attn_x3_h128.hip (groups of up to 128 tokens) and kernels_attn_x3_h128_long.hip (windows of more than 128
+  // frames); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of that width run the generic kernel either way
+  bool opt_attn_h128 = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -186,7 +194,7 @@ struct d3d_engine {
   // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip, "long_temporal_f32_last" = the same for
   // kernels_attn_f32_long.hip, "attn_h32_last" = whether the blocks ran kernels_attn_x3_h32.hip, "attn_f32_h32_last" = bit 0 / bit 1:
   // whether the spatial / temporal blocks ran kernels_attn_f32_h32.hip, "long_temporal_h32_last" / "long_temporal_f32_h32_last" = whether
-  // the temporal blocks ran kernels_attn_x3_h32_long.hip / kernels_attn_f32_h32_long.hip
+  // the temporal blocks ran kernels_attn_x3_h32_long.hip / kernels_attn_f32_h32_long.hip, "attn_h128_last" = BlockPlan::attn_h128
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -442,9 +450,13 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   const bool h32 = e->opt_attn_h32 && attn_x3_h32_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
   // the same width with a window of more than 256 frames: the spatial blocks keep that kernel (groups of J), the temporal blocks stream
   const bool h32_long = e->opt_long_temporal_h32 && T > 256 && attn_x3_h32_long_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
-  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long) && D % 32 == 0 &&
+  // heads of 128 columns: the spatial blocks need their groups resident (J <= 128); the temporal blocks stream beyond 128 frames.  As at
+  // width 32 no D == 64 H predicate holds, so the fused kernels, block 0 direct and the post-norm in fc2 stay off by their own predicates
+  const bool h128 = e->opt_attn_h128 && attn_x3_h128_ok(J, D, H) && (attn_x3_h128_ok(T, D, H) || attn_x3_h128_long_ok(T, D, H));
+  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long || h128) && D % 32 == 0 &&
       e->opt_fold_layernorm) {
     p.flow = BlockPlan::FOLD;
+    p.attn_h128 = h128 ? 1 | (attn_x3_h128_ok(T, D, H) ? 2 : 4) : 0;
     p.attn_h32 = h32;
     p.h32_long = h32_long;
     p.tp_long = tp_long;      // (qkv_tattn_ok refuses T > 255: such temporal blocks take the two-kernel branch)
@@ -654,6 +666,9 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD4, s);
       if (pl.attn_h32) HIP_TRY(temporal ? launch_attn_x3_h32(QKVh, QKVl, AOx, B, T, J, D, e->H, s) : launch_attn_x3_h32(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
       else if (pl.h32_long) HIP_TRY(temporal ? launch_attn_x3_h32_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s) : launch_attn_x3_h32(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
+      else if (pl.attn_h128 && !temporal) HIP_TRY(launch_attn_x3_h128(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
+      else if (pl.attn_h128 & 2) HIP_TRY(launch_attn_x3_h128(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
+      else if (pl.attn_h128 & 4) HIP_TRY(launch_attn_x3_h128_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else if (temporal && pl.tp_long) HIP_TRY(launch_attn_temporal_x3_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
       else HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
@@ -999,7 +1014,9 @@ extern "C" {
 const char* d3d_last_error(void) { return g_err.c_str(); }
 // 141: option / info keys "long_temporal_h32", "long_temporal_f32_h32", info keys "long_temporal_h32_last", "long_temporal_f32_h32_last",
 // d3d_op_attention_long_h32, d3d_op_attention_long_f32_h32
-int d3d_version(void) { return 141; }
+// 142: head_dim 128 admitted (FP32 and F16X3), option / info key "attn_h128", info key "attn_h128_last", d3d_op_attention_h128,
+// d3d_op_attention_long_h128
+int d3d_version(void) { return 142; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1034,7 +1051,8 @@ int d3d_engine_create(const d3d_config* c, d3d_engine** out) {
   if (c->embed_dim > 1024) return fail(D3D_EUNSUP, "embed_dim > 1024 unsupported by the row kernels");
   {
     const int dh = c->embed_dim / c->num_heads;
-    if (dh != 4 && dh != 8 && dh != 16 && dh != 32 && dh != 64) return fail(D3D_EUNSUP, "head_dim must be 4,8,16,32 or 64");
+    if (dh != 4 && dh != 8 && dh != 16 && dh != 32 && dh != 64 && dh != 128)
+      return fail(D3D_EUNSUP, "head_dim must be 4,8,16,32,64 or 128");
   }
   if (c->precision != D3D_PREC_FP32 && c->precision != D3D_PREC_F16X3 && c->precision != D3D_PREC_BF16)
     return fail(D3D_EUNSUP, "precision must be D3D_PREC_FP32, D3D_PREC_F16X3 or D3D_PREC_BF16");
@@ -1492,6 +1510,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "attn_f32_h32") e->opt_attn_f32_h32 = value != 0;
   else if (k == "long_temporal_h32") e->opt_long_temporal_h32 = value != 0;
   else if (k == "long_temporal_f32_h32") e->opt_long_temporal_f32_h32 = value != 0;
+  else if (k == "attn_h128") e->opt_attn_h128 = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1572,6 +1591,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "long_temporal_h32_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.h32_long;
   else if (k == "long_temporal_f32_h32") *value = e->opt_long_temporal_f32_h32 ? 1 : 0;
   else if (k == "long_temporal_f32_h32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32_h32;
+  else if (k == "attn_h128") *value = e->opt_attn_h128 ? 1 : 0;
+  else if (k == "attn_h128_last") *value = e->last_plan.flow == BlockPlan::FOLD ? e->last_plan.attn_h128 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

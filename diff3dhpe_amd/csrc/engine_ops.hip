@@ -449,4 +449,35 @@ int d3d_op_attention_long_f32_h32(const float* qkv, float* out, int32_t B, int32
   return D3D_OK;
 }
 
+int d3d_op_attention_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                          void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_x3_h128_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "F16X3 attention for head_dim 128: groups of up to 128 tokens");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
+  // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> the head-width-128 kernel alone -> pair layout -> fp32
+  DevBuf<uint16_t> tmp;
+  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
+  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
+  if (le == hipSuccess)
+    le = temporal ? launch_attn_x3_h128(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s)
+                  : launch_attn_x3_h128(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B * T, J, 1, D, H, s);
+  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
+  return finish(le, s);
+}
+
+int d3d_op_attention_long_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_x3_h128_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 128");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
+  // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> the key-streaming head-width-128 kernel alone -> pair layout -> fp32
+  DevBuf<uint16_t> tmp;
+  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
+  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
+  if (le == hipSuccess) le = launch_attn_x3_h128_long(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s);
+  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
+  return finish(le, s);
+}
+
 }  // extern "C"

@@ -222,7 +222,10 @@ class Engine:
         (default) keeps an F16X3 engine with heads of 32 columns and num_frame > 256 on the folded flow, its temporal blocks on the
         key-streaming attention kernel of that width; 0 gives it the plain row-kernel flow, "long_temporal_f32_h32": 1 (default) runs the
         temporal blocks of an FP32 engine with heads of 32 columns and num_frame > 256 on the key-streaming fp32 kernel of that width; 0
-        keeps the generic one-thread-per-row kernel there); the library reads no environment."""
+        keeps the generic one-thread-per-row kernel there, "attn_h128": 1 (default) keeps an F16X3 engine with heads of 128 columns
+        (embed_dim 1024, 8 heads, num_joints <= 128) on the folded flow, its attention on the fp16-MFMA kernels of that width (resident for
+        groups of up to 128 tokens, key-streaming for num_frame > 128); 0 gives it the plain row-kernel flow with the generic fp32
+        attention kernel); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
@@ -239,7 +242,10 @@ class Engine:
         "attn_f32_h32_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent forward of an FP32 engine ran the
         fp32 attention kernels for heads of 32 columns; else 0), "long_temporal_h32" / "long_temporal_f32_h32" (the options),
         "long_temporal_h32_last" / "long_temporal_f32_h32_last" (1 when the temporal blocks of the most recent forward of an F16X3 / FP32
-        engine ran the key-streaming attention kernel for heads of 32 columns: num_frame > 256 with the option on; else 0)."""
+        engine ran the key-streaming attention kernel for heads of 32 columns: num_frame > 256 with the option on; else 0), "attn_h128"
+        (the option), "attn_h128_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent forward of an F16X3
+        engine ran the resident attention kernel for heads of 128 columns, bit 2: the temporal blocks ran the key-streaming kernel of
+        that width; 0 before any forward, with the option off, at every other width and in the other precisions)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -662,6 +668,33 @@ def op_attention_long_f32_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int)
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib().d3d_op_attention_long_f32_h32(_ptr(q), _ptr(out), B, T, J, D, H, st))
+    return out
+
+
+def op_attention_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
+    """The resident F16X3 attention kernel for heads of 128 columns alone (include/d3d.h d3d_op_attention_h128): qkv (B*T*J, 3*D) ->
+    (B*T*J, D), D == 128 H, groups of at most 128 tokens (temporal: T keys, else J); anything else raises D3DError."""
+    dev = qkv.device
+    D = qkv.shape[-1] // 3
+    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
+    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_attention_h128(_ptr(q), _ptr(out), B, T, J, D, H, int(bool(temporal)), st))
+    return out
+
+
+def op_attention_long_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming F16X3 temporal attention kernel for heads of 128 columns alone (include/d3d.h d3d_op_attention_long_h128): qkv
+    (B*T*J, 3*D) -> (B*T*J, D), D == 128 H, any T >= 1; for T <= 128 bit for bit op_attention_h128(..., temporal=True); anything else
+    raises D3DError."""
+    dev = qkv.device
+    D = qkv.shape[-1] // 3
+    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
+    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_attention_long_h128(_ptr(q), _ptr(out), B, T, J, D, H, st))
     return out
 
 
