@@ -1,9 +1,9 @@
 // The F16X3 attention arithmetic of the compiler-scheduled kernels, once: k_attn_temporal_x3 and k_attn_temporal_x3p (kernels_attn_x3.hip),
-// k_attn_temporal_x3l (kernels_attn_x3_long.hip) and qm_attention (kernels_qkv_attn_x3_small.hip) are their own staging, walks and
+// k_attn_x3_stream (kernels_attn_x3_long.hip) and qm_attention (kernels_qkv_attn_x3_small.hip) are their own staging, walks and
 // stores around these pieces, so every rounding-relevant statement -- MFMA order, key mask, exp2 argument, numerator split, output fma,
-// clamp and hi / lo split -- has one copy and the forms are bit-identical by construction (tests/test_gpu_attn_x3_digests.py pins the
-// bits).  The statically scheduled kernels (attn_x3s_half, qs_attention, k_qkv_tattn) state the same arithmetic as their own
-// instruction streams and are what these pieces are compared against.  Included inside namespace d3d, behind attn_lds.h.
+// clamp and hi / lo split -- has one copy and the forms are bit-identical by construction (tests/test_gpu_attn_x3_digests.py and
+// test_gpu_attn_x3_width_digests.py pin the bits).  The statically scheduled kernels (attn_x3s_half, qs_attention, k_qkv_tattn) state the
+// same arithmetic as their own instruction streams and are what these pieces are compared against.  Included inside namespace d3d, behind attn_lds.h.
 //
 //   S^T = K Q^T        rows = keys, column = this lane's query; acc = 64 s (q planes hold q / 8, k planes 8 k)
 //   e   = exp(S - max) exact two-pass softmax numerator, fp32, one query column per lane (halves h = 0 / 1 hold different keys)
@@ -190,6 +190,55 @@ __device__ __forceinline__ void x3_pv_tile(const f32x16& e, const unsigned char*
     __builtin_amdgcn_sched_barrier(0);   // keep the V^T reads / conversions of later k-steps from being hoisted (VGPR pressure)
   }
 }
+
+// ---- the shape of a head of DH columns on the 64-column (128-byte) LDS rows, for a kernel that is written once for every width
+// (k_attn_x3_stream, kernels_attn_x3_long.hip).  A unit -- what one workgroup's waves attend over -- is SUB adjacent 64-column segments of
+// the plane rows, each in a sub-plane of its own (sub-plane f of a plane starts pl bytes behind sub-plane f - 1), and carries STREAMS
+// independent softmax streams, each with its own score tile, maximum and sum:
+//   DH = 32    a PAIR of heads in one segment; head p is stream p: d-steps 2 p, 2 p + 1 of the score product, 32-column half p of the PV
+//              product and of the output
+//   DH = 64    one head, one segment, one stream
+//   DH = 128   one head in two segments: one score chain over segment 0 then segment 1, one stream, a PV step per segment
+// The MFMA order of every accumulator is the one of k_attn_x3_h32 / k_attn_temporal_x3 / k_attn_x3_h128.
+template <int DH>
+struct x3_head_shape {
+  static_assert(DH == 32 || DH == 64 || DH == 128, "head widths with a tile form");
+  static constexpr int SUB = DH == 128 ? 2 : 1;
+  static constexpr int STREAMS = DH == 32 ? 2 : 1;
+  static constexpr bool heads_ok(int H) { return DH == 32 ? H >= 2 && H % 2 == 0 : H >= 1; }
+  static constexpr int units_per_token(int H) { return DH == 32 ? H / 2 : H; }
+  // the stream whose 1 / (2^13 l) scales 32-column line dt of a segment
+  static constexpr int line_stream(int dt) { return DH == 32 ? dt : 0; }
+
+  // the S^T tile(s) of the 32 staged K rows from row0 on, unmasked
+  static __device__ __forceinline__ void scores(f32x16 (&s)[STREAMS], const unsigned char* sKh, const unsigned char* sKl, int pl, int row0, int r,
+                                                int h, const h8 (&qh)[SUB][4], const h8 (&ql)[SUB][4]) {
+    if constexpr (DH == 32) {
+      s[0] = x3_score_tile<0, 2>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+      s[1] = x3_score_tile<2, 2>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+    } else if constexpr (DH == 64) {
+      s[0] = x3_score_tile<>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) s[0][q] = 0.f;
+      x3_score_acc(s[0], sKh, sKl, row0, r, h, qh[0], ql[0]);
+      x3_score_acc(s[0], sKh + pl, sKl + pl, row0, r, h, qh[1], ql[1]);
+    }
+  }
+  // O^T += V^T E^T over staged key tile kt; oacc[f][dt]: 32-column line dt of segment f
+  static __device__ __forceinline__ void pv(const f32x16 (&e)[STREAMS], const unsigned char* sVh, const unsigned char* sVl, int pl, int kt, int T,
+                                            int lane, int h, f32x16 (&oacc)[SUB][2]) {
+    if constexpr (DH == 32) {
+      x3_pv_tile<false, 0, 1>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+      x3_pv_tile<false, 1, 1>(e[1], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+    } else if constexpr (DH == 64) {
+      x3_pv_tile<false>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+    } else {
+      x3_pv_tile<false>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+      x3_pv_tile<false>(e[0], sVh + pl, sVl + pl, 0, kt, T, lane, h, oacc[1]);
+    }
+  }
+};
 
 // ---- output columns 8 g4 + 4 h .. + 3 of d half dt (acc: that half's O^T accumulator; vqh / vql: the query row's own V there, hi / lo
 // of 8 v): o = acc / (2^13 l) - v_query with inv = 1 / (2^13 l), the range-guard maximum, and hi / lo of 8 o for the proj GEMM.  The one

@@ -381,8 +381,8 @@ hipError_t launch_attn_generic(const float* qkv, float* out, void* out_x3, int B
 hipError_t launch_attn_temporal_x3(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                    hipStream_t s);
 bool attn_temporal_x3_ok(int T, int D, int H);
-// ---- kernels_attn_x3_long.hip: the same attention for windows of any length (the keys stream through LDS in chunks of 256 frames;
-// the scores are computed twice, for the exact maximum and for the numerators).  Same planes in, same pair layout out; bit-identical to
+// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<64, 8>: the same attention for windows of any length (the keys stream through LDS in
+// chunks of 256 frames; the scores are computed twice, for the exact maximum and for the numerators).  Same planes in, same pair layout out; bit-identical to
 // launch_attn_temporal_x3 wherever that runs (T <= 256).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_temporal_x3_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                         hipStream_t s);
@@ -406,8 +406,8 @@ hipError_t launch_attn_temporal_f32_h32(const float* qkv, float* out, int B, int
 hipError_t launch_attn_spatial_f32_h32(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_temporal_f32_h32_ok(int T, int D, int H);
 bool attn_spatial_f32_h32_ok(int J, int D, int H);
-// ---- kernels_attn_x3_h32_long.hip: launch_attn_x3_h32's temporal attention for windows of any length (D == 32 H, H even): the head
-// pair's keys stream through LDS in chunks of 256 frames, the scores are computed twice.  Same planes in, same pair layout out;
+// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<32, 8>: launch_attn_x3_h32's temporal attention for windows of any length (D == 32 H,
+// H even): the head pair's keys stream through LDS in chunks of 256 frames, the scores are computed twice.  Same planes in, same pair layout out;
 // bit-identical to launch_attn_x3_h32 wherever that runs (T <= 256).  The launch also refuses B J (H / 2) ceil(T / 256) workgroups beyond
 // 2^31 - 1.
 hipError_t launch_attn_x3_h32_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
@@ -422,8 +422,8 @@ bool attn_temporal_f32_h32_long_ok(int T, int D, int H);
 // planes in (raw q, 8 k, 8 v), same pair layout out; spatial blocks call it with (B T, J, 1).
 hipError_t launch_attn_x3_h128(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h128_ok(int N, int D, int H);
-// ---- kernels_attn_x3_h128_long.hip: launch_attn_x3_h128's temporal attention for windows of any length: the head's keys stream through
-// LDS in chunks of 128 frames, the scores are computed twice.  Same planes in, same pair layout out; bit-identical to
+// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<128, 4>: launch_attn_x3_h128's temporal attention for windows of any length: the
+// head's keys stream through LDS in chunks of 128 frames, the scores are computed twice.  Same planes in, same pair layout out; bit-identical to
 // launch_attn_x3_h128 wherever that runs (T <= 128).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h128_long_ok(int T, int D, int H);

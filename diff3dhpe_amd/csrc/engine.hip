@@ -60,32 +60,12 @@ struct BlockPlan {
   Flow flow = PLAIN;          // run_blocks / run_blocks_fold / run_blocks_bf16
   // FOLD, BF16: the qkv GEMM and the attention of the spatial / temporal blocks as one kernel
   bool fused_sp = false, fused_tp = false;
-  // FOLD: the temporal blocks' attention on the key-streaming kernel (kernels_attn_x3_long.hip: windows of more than 256 frames)
-  bool tp_long = false;
-  // FOLD: every block's attention on the kernel for heads of 32 columns (kernels_attn_x3_h32.hip: D == 32 H, which no other F16X3
-  // attention kernel takes); always the two-kernel branch
-  bool attn_h32 = false;
-  // FOLD: heads of 32 columns and a window of more than 256 frames, which attn_h32 does not cover: the temporal blocks' attention on the
-  // key-streaming kernel of that width (kernels_attn_x3_h32_long.hip), the spatial blocks' on kernels_attn_x3_h32.hip (groups of J);
-  // always the two-kernel branch.  attn_h32 stays false on such a plan
-  bool h32_long = false;
-  // FOLD: heads of 128 columns (D == 128 H, which no other F16X3 attention kernel takes); always the two-kernel branch.  Bit 0: the
-  // spatial blocks on kernels_attn_x3_h128.hip (groups of J <= 128), bit 1: the temporal blocks on it (T <= 128), bit 2: the temporal
-  // blocks on the key-streaming kernels_attn_x3_h128_long.hip (T > 128).  0 on every other plan
-  int attn_h128 = 0;
-  // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel (kernels_attn_f32_long.hip: windows of more than 256
-  // frames, which k_attn_temporal_f32 cannot hold in LDS); false = k_attn_generic there
-  bool tp_long_f32 = false;
-  // PLAIN in FP32: the spatial / temporal blocks' attention on the exact fp32 kernels for heads of 32 columns (kernels_attn_f32_h32.hip:
-  // D == 32 H, 15 .. 17 joints / windows of up to 256 frames); false = k_attn_generic there
-  bool sp_f32_h32 = false, tp_f32_h32 = false;
-  // PLAIN in FP32: the temporal blocks' attention on the key-streaming fp32 kernel for heads of 32 columns
-  // (kernels_attn_f32_h32_long.hip: D == 32 H, windows of more than 256 frames); false = k_attn_generic there
-  bool tp_long_f32_h32 = false;
+  // The attention kernel of the spatial / of the temporal blocks wherever the qkv GEMM and the attention are two launches: one value per
+  // launch, listed with its shapes at launch_attention().  A BF16 plan runs launch_attn_bf16 and leaves both at GENERIC.
+  enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG };
+  Attn attn_sp = GENERIC, attn_tp = GENERIC;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
-  // PLAIN in F16X3: q / k / v go to the fp16-MFMA attention kernel as planes
-  bool attn_x3_sp = false, attn_x3_tp = false;
   // FOLD: fc1 / proj on their own kernels; the post-norm inside the fc2 epilogue
   bool fc1_own = false, proj_own = false, pn = false;
   // FOLD with "latency_mode": the S of the split-K form of each GEMM, 0 = the launches above
@@ -149,7 +129,7 @@ struct d3d_engine {
   // order of additions: results stay inside the parity gate but are no longer bit-identical to the default path's.
   bool opt_latency_mode = false;
   // "long_temporal" (on by default): an F16X3 engine whose window is longer than 256 frames keeps the folded flow, its temporal blocks on
-  // the key-streaming attention kernel (kernels_attn_x3_long.hip); 0 = the plain row-kernel flow with the generic fp32 attention
+  // the key-streaming attention kernel (kernels_attn_x3_long.hip at width 64); 0 = the plain row-kernel flow with the generic fp32 attention
   bool opt_long_temporal = true;
   // "long_temporal_f32" (on by default): an FP32 engine whose window is longer than 256 frames runs its temporal blocks' attention on the
   // key-streaming fp32 MFMA kernel (kernels_attn_f32_long.hip); 0 = the generic one-thread-per-row kernel.  F16X3 / BF16 engines: no effect
@@ -162,16 +142,16 @@ struct d3d_engine {
   // order of additions: inside the parity gate, not bit-identical.  F16X3 / BF16 engines and every D == 64 H engine: no effect
   bool opt_attn_f32_h32 = true;
   // "long_temporal_h32" (on by default): an F16X3 engine whose heads are 32 columns wide and whose window is longer than 256 frames keeps
-  // the folded flow, its temporal blocks on kernels_attn_x3_h32_long.hip and its spatial blocks on kernels_attn_x3_h32.hip; 0 = the plain
-  // row-kernel flow with the generic fp32 attention
+  // the folded flow, its temporal blocks on kernels_attn_x3_long.hip at width 32 and its spatial blocks on kernels_attn_x3_h32.hip; 0 = the
+  // plain row-kernel flow with the generic fp32 attention
   bool opt_long_temporal_h32 = true;
   // "long_temporal_f32_h32" (on by default): an FP32 engine of that width and window runs its temporal blocks' attention on
   // kernels_attn_f32_h32_long.hip; 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not
   // bit-identical.  F16X3 / BF16 engines: no effect
   bool opt_long_temporal_f32_h32 = true;
   // "attn_h128" (on by default): an F16X3 engine whose heads are 128 columns wide (embed_dim 1024 with 8 heads) runs the folded flow with
-  // its attention on kernels_attn_x3_h128.hip (groups of up to 128 tokens) and kernels_attn_x3_h128_long.hip (windows of more than 128
-  // frames); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of that width run the generic kernel either way
+  // its attention on kernels_attn_x3_h128.hip (groups of up to 128 tokens) and kernels_attn_x3_long.hip at width 128 (windows of more than
+  // 128 frames); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of that width run the generic kernel either way
   bool opt_attn_h128 = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
@@ -191,10 +171,7 @@ struct d3d_engine {
   // the plan of the most recent forward (of a two-stream sampling: of the first half-batch, the one that holds sequence 0); all zero
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
-  // "long_temporal_last" = whether the temporal blocks ran kernels_attn_x3_long.hip, "long_temporal_f32_last" = the same for
-  // kernels_attn_f32_long.hip, "attn_h32_last" = whether the blocks ran kernels_attn_x3_h32.hip, "attn_f32_h32_last" = bit 0 / bit 1:
-  // whether the spatial / temporal blocks ran kernels_attn_f32_h32.hip, "long_temporal_h32_last" / "long_temporal_f32_h32_last" = whether
-  // the temporal blocks ran kernels_attn_x3_h32_long.hip / kernels_attn_f32_h32_long.hip, "attn_h128_last" = BlockPlan::attn_h128
+  // and the seven keys of the attention kernels that ran, which attention_plan_info() states
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -422,19 +399,52 @@ int compute_temb(d3d_engine* e, const float* times_dev, int n, float* out, float
   return D3D_OK;
 }
 
-int attention(d3d_engine* e, const BlockPlan& pl, const float* qkv, float* out, void* out_x3, int B, bool temporal, hipStream_t s) {
-  if (!temporal) {
-    if (pl.sp_f32_h32) HIP_TRY(launch_attn_spatial_f32_h32(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (FP32 engines only: no out_x3)
-    else if (attn_spatial_fast_ok(e->J, e->D, e->H)) HIP_TRY(launch_attn_spatial_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
-    else HIP_TRY(launch_attn_generic(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, 0, s));
-  } else {
-    if (pl.tp_f32_h32) HIP_TRY(launch_attn_temporal_f32_h32(qkv, out, B, e->T, e->J, e->D, e->H, s));
-    else if (pl.tp_long_f32) HIP_TRY(launch_attn_temporal_f32_long(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (FP32 engines only: no out_x3)
-    else if (pl.tp_long_f32_h32) HIP_TRY(launch_attn_temporal_f32_h32_long(qkv, out, B, e->T, e->J, e->D, e->H, s));   // (the same)
-    else if (attn_temporal_fast_ok(e->T, e->D, e->H)) HIP_TRY(launch_attn_temporal_f32(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, s));
-    else HIP_TRY(launch_attn_generic(qkv, out, out_x3, B, e->T, e->J, e->D, e->H, 1, s));
+// The launch of every BlockPlan::Attn value, for a spatial or a temporal block of B sequences.  qkv: the block's q / k / v, (M, 3 D)
+// fp32 rows for the fp32 kernels; for the X3 kernels the fp16 hi plane at the same address and the lo plane M 3 D halves behind it.
+// out: fp32 rows; out_x3: the pair layout -- written instead of out by the kernels_attn.hip launches where it is not null (F16X3
+// engines), the only output of the X3 kernels, not a form the other fp32 kernels have (FP32 engines only).  The X3 kernels attend over
+// the T tokens of (batch, joint) groups, J tokens apart: a spatial block is B T batches of J consecutive tokens and one joint.
+int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal, const void* qkv, float* out, void* out_x3, int B,
+                     hipStream_t s) {
+  const int T = e->T, J = e->J, D = e->D, H = e->H, gB = temporal ? B : B * T, gT = temporal ? T : J, gJ = temporal ? J : 1;
+  const float* q = static_cast<const float*>(qkv);
+  const uint16_t *qh = static_cast<const uint16_t*>(qkv), *ql = qh + (size_t)B * T * J * 3 * D;
+  hipError_t le = hipErrorInvalidValue;
+  switch (kernel) {
+    case BlockPlan::GENERIC:      le = launch_attn_generic(q, out, out_x3, B, T, J, D, H, temporal ? 1 : 0, s); break;   // any shape
+    case BlockPlan::F32_SPATIAL:  le = launch_attn_spatial_f32(q, out, out_x3, B, T, J, D, H, s); break;                 // D == 64 H, 15 .. 17 joints
+    case BlockPlan::F32_TEMPORAL: le = launch_attn_temporal_f32(q, out, out_x3, B, T, J, D, H, s); break;                // D == 64 H, T <= 256
+    case BlockPlan::F32_H32:      // D == 32 H, FP32 engines: T <= 256 / 15 .. 17 joints
+      le = temporal ? launch_attn_temporal_f32_h32(q, out, B, T, J, D, H, s) : launch_attn_spatial_f32_h32(q, out, B, T, J, D, H, s); break;
+    case BlockPlan::F32_LONG:     le = launch_attn_temporal_f32_long(q, out, B, T, J, D, H, s); break;                   // D == 64 H, T > 256, FP32 engines
+    case BlockPlan::F32_H32_LONG: le = launch_attn_temporal_f32_h32_long(q, out, B, T, J, D, H, s); break;               // D == 32 H, T > 256, FP32 engines
+    case BlockPlan::X3:           le = launch_attn_temporal_x3(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 64 H, groups <= 256
+    case BlockPlan::X3_LONG:      le = launch_attn_temporal_x3_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;         // D == 64 H, T > 256 (FOLD)
+    case BlockPlan::X3_H32:       le = launch_attn_x3_h32(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                   // D == 32 H, groups <= 256 (FOLD)
+    case BlockPlan::X3_H32_LONG:  le = launch_attn_x3_h32_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 32 H, T > 256 (FOLD)
+    case BlockPlan::X3_H128:      le = launch_attn_x3_h128(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                  // D == 128 H, groups <= 128 (FOLD)
+    case BlockPlan::X3_H128_LONG: le = launch_attn_x3_h128_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;             // D == 128 H, T > 128 (FOLD)
   }
+  HIP_TRY(le);
   return D3D_OK;
+}
+
+// The "*_last" info keys of the attention plan, from the flow and the two kernel choices: which block types ran which kernel family
+// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last" bit 2 temporal
+// streaming).  false = not one of the keys.
+bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* value) {
+  const bool fold = p.flow == BlockPlan::FOLD, plain = p.flow == BlockPlan::PLAIN;
+  const BlockPlan::Attn sp = p.attn_sp, tp = p.attn_tp;
+  if (k == "long_temporal_last") *value = fold && tp == BlockPlan::X3_LONG;
+  else if (k == "attn_h32_last") *value = fold && sp == BlockPlan::X3_H32 && tp == BlockPlan::X3_H32;
+  else if (k == "long_temporal_h32_last") *value = fold && tp == BlockPlan::X3_H32_LONG;
+  else if (k == "attn_h128_last")
+    *value = fold ? (sp == BlockPlan::X3_H128 ? 1 : 0) | (tp == BlockPlan::X3_H128 ? 2 : 0) | (tp == BlockPlan::X3_H128_LONG ? 4 : 0) : 0;
+  else if (k == "long_temporal_f32_last") *value = plain && tp == BlockPlan::F32_LONG;
+  else if (k == "attn_f32_h32_last") *value = plain ? (sp == BlockPlan::F32_H32 ? 1 : 0) | (tp == BlockPlan::F32_H32 ? 2 : 0) : 0;
+  else if (k == "long_temporal_f32_h32_last") *value = plain && tp == BlockPlan::F32_H32_LONG;
+  else return false;
+  return true;
 }
 
 // The plan of a forward of B sequences.  A pure function of the options, the shapes, B and the CU count, so an eager run, a capture
@@ -450,16 +460,16 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   const bool h32 = e->opt_attn_h32 && attn_x3_h32_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
   // the same width with a window of more than 256 frames: the spatial blocks keep that kernel (groups of J), the temporal blocks stream
   const bool h32_long = e->opt_long_temporal_h32 && T > 256 && attn_x3_h32_long_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
-  // heads of 128 columns: the spatial blocks need their groups resident (J <= 128); the temporal blocks stream beyond 128 frames.  As at
-  // width 32 no D == 64 H predicate holds, so the fused kernels, block 0 direct and the post-norm in fc2 stay off by their own predicates
+  // heads of 128 columns: the spatial blocks need their groups resident (J <= 128); the temporal blocks stream beyond 128 frames (as at 32)
   const bool h128 = e->opt_attn_h128 && attn_x3_h128_ok(J, D, H) && (attn_x3_h128_ok(T, D, H) || attn_x3_h128_long_ok(T, D, H));
   if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long || h128) && D % 32 == 0 &&
       e->opt_fold_layernorm) {
     p.flow = BlockPlan::FOLD;
-    p.attn_h128 = h128 ? 1 | (attn_x3_h128_ok(T, D, H) ? 2 : 4) : 0;
-    p.attn_h32 = h32;
-    p.h32_long = h32_long;
-    p.tp_long = tp_long;      // (qkv_tattn_ok refuses T > 255: such temporal blocks take the two-kernel branch)
+    // (the predicates of the three widths exclude each other: D == 32 H, 128 H, 64 H)
+    p.attn_sp = h32 || h32_long ? BlockPlan::X3_H32 : h128 ? BlockPlan::X3_H128 : BlockPlan::X3;
+    p.attn_tp = h32 ? BlockPlan::X3_H32 : h32_long ? BlockPlan::X3_H32_LONG
+              : h128 ? (attn_x3_h128_ok(T, D, H) ? BlockPlan::X3_H128 : BlockPlan::X3_H128_LONG)
+              : tp_long ? BlockPlan::X3_LONG : BlockPlan::X3;   // (qkv_tattn_ok refuses T > 255: the long kernel is always the two-kernel branch)
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
     // block 0 from the raw channels: every forward of this flow whose block 0 has the tables (fused or not, any B, any time rows)
@@ -506,16 +516,21 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
     };
     p.bf16q_qkv = own(3 * D);
     p.bf16q_fc1 = own(Dm);
-  } else if (x3) {
-    p.attn_x3_sp = attn_temporal_x3_ok(J, D, H);
-    p.attn_x3_tp = attn_temporal_x3_ok(T, D, H);
-  } else if (e->cfg.precision == D3D_PREC_FP32) {
-    // windows of more than 256 frames: the resident fp32 MFMA kernel cannot hold their keys; the long kernel streams them
-    p.tp_long_f32 = e->opt_long_temporal_f32 && T > 256 && attn_temporal_f32_long_ok(T, D, H);
-    // heads of 32 columns: no D == 64 H predicate holds there; each block type takes its kernel of that width where its group length fits
-    p.sp_f32_h32 = e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H);
-    p.tp_f32_h32 = e->opt_attn_f32_h32 && attn_temporal_f32_h32_ok(T, D, H);
-    p.tp_long_f32_h32 = e->opt_long_temporal_f32_h32 && T > 256 && attn_temporal_f32_h32_long_ok(T, D, H);
+  } else {
+    // the row-kernel flow.  F16X3: the fp16-MFMA kernel where the group length fits, q / k / v going to it as planes.  FP32: heads of 32
+    // columns (no D == 64 H predicate holds there) on the kernels of that width where the group length fits; windows of more than 256
+    // frames, which the resident fp32 MFMA kernels cannot hold in LDS, on the key-streaming ones.  Else kernels_attn.hip.
+    const bool fp32 = e->cfg.precision == D3D_PREC_FP32;
+    p.attn_sp = x3 && attn_temporal_x3_ok(J, D, H)                                    ? BlockPlan::X3
+              : fp32 && e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H)       ? BlockPlan::F32_H32
+              : attn_spatial_fast_ok(J, D, H)                                         ? BlockPlan::F32_SPATIAL
+                                                                                      : BlockPlan::GENERIC;
+    p.attn_tp = x3 && attn_temporal_x3_ok(T, D, H)                                    ? BlockPlan::X3
+              : fp32 && e->opt_attn_f32_h32 && attn_temporal_f32_h32_ok(T, D, H)      ? BlockPlan::F32_H32
+              : fp32 && e->opt_long_temporal_f32 && T > 256 && attn_temporal_f32_long_ok(T, D, H)          ? BlockPlan::F32_LONG
+              : fp32 && e->opt_long_temporal_f32_h32 && T > 256 && attn_temporal_f32_h32_long_ok(T, D, H)  ? BlockPlan::F32_H32_LONG
+              : attn_temporal_fast_ok(T, D, H)                                        ? BlockPlan::F32_TEMPORAL
+                                                                                      : BlockPlan::GENERIC;
   }
   return p;
 }
@@ -664,14 +679,8 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
     {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD4, s);
-      if (pl.attn_h32) HIP_TRY(temporal ? launch_attn_x3_h32(QKVh, QKVl, AOx, B, T, J, D, e->H, s) : launch_attn_x3_h32(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
-      else if (pl.h32_long) HIP_TRY(temporal ? launch_attn_x3_h32_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s) : launch_attn_x3_h32(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
-      else if (pl.attn_h128 && !temporal) HIP_TRY(launch_attn_x3_h128(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
-      else if (pl.attn_h128 & 2) HIP_TRY(launch_attn_x3_h128(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
-      else if (pl.attn_h128 & 4) HIP_TRY(launch_attn_x3_h128_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
-      else if (temporal && pl.tp_long) HIP_TRY(launch_attn_temporal_x3_long(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
-      else if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B, T, J, D, e->H, s));
-      else HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, AOx, B * T, J, 1, D, e->H, s));
+      const int rc = launch_attention(e, temporal ? pl.attn_tp : pl.attn_sp, temporal, QKVh, nullptr, AOx, B, s);
+      if (rc) return rc;
     }
     TRACE(k, 3, 0, AOx, MDb);
     }
@@ -915,7 +924,8 @@ int run_blocks(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float
     const bool temporal = (k & 1) != 0;
     // F16X3: the qkv GEMM hands q/k/v to the fp16-MFMA attention kernel as hi/lo planes.  A spatial block is the same
     // kernel over groups of J consecutive tokens (one "joint", "frames" = the J tokens of a frame, B*T "batches").
-    const bool attn_x3 = temporal ? pl.attn_x3_tp : pl.attn_x3_sp;
+    const BlockPlan::Attn kernel = temporal ? pl.attn_tp : pl.attn_sp;
+    const bool attn_x3 = kernel == BlockPlan::X3;
     uint16_t* QKVh = reinterpret_cast<uint16_t*>(w.QKV);
     uint16_t* QKVl = QKVh + (size_t)M * 3 * D;
     qcols_ = attn_x3 ? D : 0;
@@ -925,13 +935,8 @@ int run_blocks(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float
     {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD4, s);
-      if (attn_x3) {
-        if (temporal) HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, HNx, B, T, J, D, e->H, s));
-        else HIP_TRY(launch_attn_temporal_x3(QKVh, QKVl, HNx, B * T, J, 1, D, e->H, s));
-      } else {
-        int rc = attention(e, pl, w.QKV, w.HN, x3 ? HNx : nullptr, B, temporal, s);
-        if (rc) return rc;
-      }
+      const int rc = launch_attention(e, kernel, temporal, w.QKV, w.HN, x3 ? HNx : nullptr, B, s);
+      if (rc) return rc;
     }
     HIP_TRY(linear(w.HN, HNx, bw.projw, bw.proj_x3, bw.proj_e, bw.projb, w.X, w.X, nullptr, nullptr, 0, D, D, EPI_RESIDUAL));
     {  // h = norm2(x)
@@ -1577,22 +1582,15 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "graphs_captured") *value = (int64_t)e->graphs_captured;
   else if (k == "streams") *value = e->opt_streams;
   else if (k == "device") *value = e->device;
+  else if (attention_plan_info(e->last_plan, k, value)) {}   // the seven "*_last" keys of the attention kernels
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
   else if (k == "long_temporal") *value = e->opt_long_temporal ? 1 : 0;
-  else if (k == "long_temporal_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.tp_long;
   else if (k == "long_temporal_f32") *value = e->opt_long_temporal_f32 ? 1 : 0;
   else if (k == "attn_h32") *value = e->opt_attn_h32 ? 1 : 0;
-  else if (k == "attn_h32_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.attn_h32;
   else if (k == "attn_f32_h32") *value = e->opt_attn_f32_h32 ? 1 : 0;
-  else if (k == "attn_f32_h32_last")
-    *value = e->last_plan.flow == BlockPlan::PLAIN ? (e->last_plan.sp_f32_h32 ? 1 : 0) | (e->last_plan.tp_f32_h32 ? 2 : 0) : 0;
-  else if (k == "long_temporal_f32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32;
   else if (k == "long_temporal_h32") *value = e->opt_long_temporal_h32 ? 1 : 0;
-  else if (k == "long_temporal_h32_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.h32_long;
   else if (k == "long_temporal_f32_h32") *value = e->opt_long_temporal_f32_h32 ? 1 : 0;
-  else if (k == "long_temporal_f32_h32_last") *value = e->last_plan.flow == BlockPlan::PLAIN && e->last_plan.tp_long_f32_h32;
   else if (k == "attn_h128") *value = e->opt_attn_h128 ? 1 : 0;
-  else if (k == "attn_h128_last") *value = e->last_plan.flow == BlockPlan::FOLD ? e->last_plan.attn_h128 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

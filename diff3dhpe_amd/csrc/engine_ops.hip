@@ -91,6 +91,19 @@ int finish(hipError_t le, hipStream_t s) {
   return D3D_OK;
 }
 
+// The round trip of the single-op hooks of the F16X3 attention kernels: fp32 qkv (rows, 3 D) -> hi / lo planes (as the qkv GEMM
+// epilogue writes them) -> the kernel alone, launch(hi, lo, out_pair) -> pair layout -> fp32 out (rows, D).
+template <class Launch>
+int attention_x3_round_trip(const float* qkv, float* out, size_t rows, int D, hipStream_t s, Launch launch) {
+  const size_t nq = rows * 3 * D, no = rows * D;
+  DevBuf<uint16_t> tmp;
+  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
+  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
+  if (le == hipSuccess) le = launch(tmp.p, tmp.p + nq, tmp.p + 2 * nq);
+  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
+  return finish(le, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,13 +373,9 @@ int d3d_op_attention(const float* qkv, float* out, int32_t B, int32_t T, int32_t
     return finish(le, s);
   }
   if (precision == D3D_PREC_F16X3 && temporal && !force_generic && attn_temporal_x3_ok(T, D, H)) {
-    // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> fp16-MFMA attention -> pair layout -> fp32
-    DevBuf<uint16_t> tmp;
-    HIP_TRY(tmp.alloc(2 * nq + 2 * no));
-    hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
-    if (le == hipSuccess) le = launch_attn_temporal_x3(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s);
-    if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
-    return finish(le, s);
+    return attention_x3_round_trip(qkv, out, rows, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+      return launch_attn_temporal_x3(hi, lo, o, B, T, J, D, H, s);
+    });
   }
   if (!force_generic && !temporal && attn_spatial_fast_ok(J, D, H)) {
     HIP_TRY(launch_attn_spatial_f32(qkv, out, nullptr, B, T, J, D, H, s));
@@ -382,30 +391,18 @@ int d3d_op_attention_long(const float* qkv, float* out, int32_t B, int32_t T, in
   if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
   if (!attn_temporal_x3_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 64");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-  // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> the key-streaming attention kernel alone -> pair layout -> fp32
-  DevBuf<uint16_t> tmp;
-  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
-  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
-  if (le == hipSuccess) le = launch_attn_temporal_x3_long(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s);
-  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
-  return finish(le, s);
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return launch_attn_temporal_x3_long(hi, lo, o, B, T, J, D, H, s);
+  });
 }
 
 int d3d_op_attention_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
   if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
   if (!attn_x3_h32_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "F16X3 attention for head_dim 32: an even head count, group length <= 256");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-  // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> the head-width-32 attention kernel alone -> pair layout -> fp32
-  DevBuf<uint16_t> tmp;
-  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
-  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
-  if (le == hipSuccess)
-    le = temporal ? launch_attn_x3_h32(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s)
-                  : launch_attn_x3_h32(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B * T, J, 1, D, H, s);
-  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
-  return finish(le, s);
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return temporal ? launch_attn_x3_h32(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_h32(hi, lo, o, B * T, J, 1, D, H, s);
+  });
 }
 
 int d3d_op_attention_f32_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
@@ -432,14 +429,9 @@ int d3d_op_attention_long_h32(const float* qkv, float* out, int32_t B, int32_t T
   if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
   if (!attn_x3_h32_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention for head_dim 32: an even head count");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-  // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> the key-streaming head-width-32 kernel alone -> pair layout -> fp32
-  DevBuf<uint16_t> tmp;
-  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
-  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
-  if (le == hipSuccess) le = launch_attn_x3_h32_long(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s);
-  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
-  return finish(le, s);
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return launch_attn_x3_h32_long(hi, lo, o, B, T, J, D, H, s);
+  });
 }
 
 int d3d_op_attention_long_f32_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
@@ -454,30 +446,18 @@ int d3d_op_attention_h128(const float* qkv, float* out, int32_t B, int32_t T, in
   if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
   if (!attn_x3_h128_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "F16X3 attention for head_dim 128: groups of up to 128 tokens");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-  // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> the head-width-128 kernel alone -> pair layout -> fp32
-  DevBuf<uint16_t> tmp;
-  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
-  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
-  if (le == hipSuccess)
-    le = temporal ? launch_attn_x3_h128(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s)
-                  : launch_attn_x3_h128(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B * T, J, 1, D, H, s);
-  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
-  return finish(le, s);
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return temporal ? launch_attn_x3_h128(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_h128(hi, lo, o, B * T, J, 1, D, H, s);
+  });
 }
 
 int d3d_op_attention_long_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
   if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
   if (!attn_x3_h128_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 128");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-  // fp32 qkv -> planes (as the qkv GEMM epilogue writes them) -> the key-streaming head-width-128 kernel alone -> pair layout -> fp32
-  DevBuf<uint16_t> tmp;
-  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
-  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
-  if (le == hipSuccess) le = launch_attn_x3_h128_long(tmp.p, tmp.p + nq, tmp.p + 2 * nq, B, T, J, D, H, s);
-  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
-  return finish(le, s);
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return launch_attn_x3_h128_long(hi, lo, o, B, T, J, D, H, s);
+  });
 }
 
 }  // extern "C"

@@ -577,125 +577,74 @@ def op_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: 
     return out.reshape(x.shape)
 
 
-def op_attention(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool, precision: str = "fp32",
-                 force_generic: bool = False) -> torch.Tensor:
-    """qkv: (B*T*J, 3*D) packed GEMM output -> (B*T*J, D)."""
+def _attention_op(symbol: str, qkv: torch.Tensor, B: int, T: int, J: int, H: int, *flags: int) -> torch.Tensor:
+    """What every attention hook shares: qkv as contiguous fp32 rows (B*T*J, 3*D), a fresh (B*T*J, D) output, qkv's device and its
+    current stream; `flags` are the hook's int arguments between H and the stream."""
     dev = qkv.device
     D = qkv.shape[-1] // 3
     q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
     out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention(_ptr(q), _ptr(out), B, T, J, D, H, int(temporal),
-                                               _lib.PRECISIONS[precision], int(force_generic), st))
+        _lib.check(getattr(_lib.lib(), symbol)(_ptr(q), _ptr(out), B, T, J, D, H, *flags, st))
     return out
+
+
+def op_attention(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool, precision: str = "fp32",
+                 force_generic: bool = False) -> torch.Tensor:
+    """qkv: (B*T*J, 3*D) packed GEMM output -> (B*T*J, D)."""
+    return _attention_op("d3d_op_attention", qkv, B, T, J, H, int(temporal), _lib.PRECISIONS[precision], int(force_generic))
 
 
 def op_attention_long(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
     """The key-streaming F16X3 temporal attention kernel alone (include/d3d.h d3d_op_attention_long): qkv (B*T*J, 3*D) -> (B*T*J, D),
     any T >= 1; for T <= 256 bit for bit op_attention(..., temporal=True, precision="f16x3")."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_long(_ptr(q), _ptr(out), B, T, J, D, H, st))
-    return out
+    return _attention_op("d3d_op_attention_long", qkv, B, T, J, H)
 
 
 def op_attention_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
     """The F16X3 attention kernel for heads of 32 columns alone (include/d3d.h d3d_op_attention_h32): qkv (B*T*J, 3*D) -> (B*T*J, D),
     D == 32 H with H even, groups of at most 256 tokens (temporal: T keys, else J); anything else raises D3DError."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_h32(_ptr(q), _ptr(out), B, T, J, D, H, int(bool(temporal)), st))
-    return out
+    return _attention_op("d3d_op_attention_h32", qkv, B, T, J, H, int(bool(temporal)))
 
 
 def op_attention_f32_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
     """The exact fp32 attention kernels for heads of 32 columns alone (include/d3d.h d3d_op_attention_f32_h32): qkv (B*T*J, 3*D) ->
     (B*T*J, D), D == 32 H; temporal: T <= 256 keys, else 15 <= J <= 17 keys; anything else raises D3DError."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_f32_h32(_ptr(q), _ptr(out), B, T, J, D, H, int(bool(temporal)), st))
-    return out
+    return _attention_op("d3d_op_attention_f32_h32", qkv, B, T, J, H, int(bool(temporal)))
 
 
 def op_attention_long_f32(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
     """The key-streaming fp32 temporal attention kernel alone (include/d3d.h d3d_op_attention_long_f32): qkv (B*T*J, 3*D) -> (B*T*J, D),
     any T >= 1; for T <= 256 bit for bit op_attention(..., temporal=True, precision="fp32")."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_long_f32(_ptr(q), _ptr(out), B, T, J, D, H, st))
-    return out
+    return _attention_op("d3d_op_attention_long_f32", qkv, B, T, J, H)
 
 
 def op_attention_long_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
     """The key-streaming F16X3 temporal attention kernel for heads of 32 columns alone (include/d3d.h d3d_op_attention_long_h32): qkv
     (B*T*J, 3*D) -> (B*T*J, D), D == 32 H with H even, any T >= 1; for T <= 256 bit for bit op_attention_h32(..., temporal=True);
     anything else raises D3DError."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_long_h32(_ptr(q), _ptr(out), B, T, J, D, H, st))
-    return out
+    return _attention_op("d3d_op_attention_long_h32", qkv, B, T, J, H)
 
 
 def op_attention_long_f32_h32(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
     """The key-streaming fp32 temporal attention kernel for heads of 32 columns alone (include/d3d.h d3d_op_attention_long_f32_h32): qkv
     (B*T*J, 3*D) -> (B*T*J, D), D == 32 H, any T >= 1; for T <= 256 bit for bit op_attention_f32_h32(..., temporal=True); anything else
     raises D3DError."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_long_f32_h32(_ptr(q), _ptr(out), B, T, J, D, H, st))
-    return out
+    return _attention_op("d3d_op_attention_long_f32_h32", qkv, B, T, J, H)
 
 
 def op_attention_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
     """The resident F16X3 attention kernel for heads of 128 columns alone (include/d3d.h d3d_op_attention_h128): qkv (B*T*J, 3*D) ->
     (B*T*J, D), D == 128 H, groups of at most 128 tokens (temporal: T keys, else J); anything else raises D3DError."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_h128(_ptr(q), _ptr(out), B, T, J, D, H, int(bool(temporal)), st))
-    return out
+    return _attention_op("d3d_op_attention_h128", qkv, B, T, J, H, int(bool(temporal)))
 
 
 def op_attention_long_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
     """The key-streaming F16X3 temporal attention kernel for heads of 128 columns alone (include/d3d.h d3d_op_attention_long_h128): qkv
     (B*T*J, 3*D) -> (B*T*J, D), D == 128 H, any T >= 1; for T <= 128 bit for bit op_attention_h128(..., temporal=True); anything else
     raises D3DError."""
-    dev = qkv.device
-    D = qkv.shape[-1] // 3
-    q = _f32c(qkv, dev).reshape(B * T * J, 3 * D)
-    out = torch.empty((B * T * J, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_attention_long_h128(_ptr(q), _ptr(out), B, T, J, D, H, st))
-    return out
+    return _attention_op("d3d_op_attention_long_h128", qkv, B, T, J, H)
 
 
 def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, groups: int, N: int, stride: int, H: int,

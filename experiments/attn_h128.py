@@ -2,7 +2,7 @@
 """Heads of 128 columns (embed_dim 1024 with the runner's 8 heads): the F16X3 attention kernels of that width against the plain flow.
 
   "attn_h128" = 1: the folded flow, spatial blocks and temporal blocks of up to 128 frames on kernels_attn_x3_h128.hip, temporal blocks
-                   of more than 128 frames on kernels_attn_x3_h128_long.hip
+                   of more than 128 frames on kernels_attn_x3_long.hip (width 128)
               / 0: the plain row-kernel flow with the generic fp32 attention in all 16 blocks
 
 The tree before the option refuses this width, so it cannot be a leg; the off leg stands for what a bare admission would have run.

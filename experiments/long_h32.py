@@ -2,7 +2,7 @@
 """Heads of 32 columns (embed_dim 256 with the runner's 8 heads) beyond 256 frames: the key-streaming attention kernels of that width
 against what the tree before them ran.
 
-  f16x3   "long_temporal_h32" = 1: the folded flow, temporal blocks on kernels_attn_x3_h32_long.hip, spatial blocks on
+  f16x3   "long_temporal_h32" = 1: the folded flow, temporal blocks on kernels_attn_x3_long.hip (width 32), spatial blocks on
           kernels_attn_x3_h32.hip / 0: the plain row-kernel flow with the generic fp32 attention in all 16 blocks
   fp32    "long_temporal_f32_h32" = 1: the temporal blocks on kernels_attn_f32_h32_long.hip / 0: the generic kernel there
 

@@ -1,5 +1,5 @@
 """Host-side contract of head width 128 (include/d3d.h): embed_dim 1024 with the runner's 8 heads is admitted in FP32 and F16X3, an F16X3
-engine of that width runs its attention on kernels_attn_x3_h128.hip / kernels_attn_x3_h128_long.hip behind the option "attn_h128".
+engine of that width runs its attention on kernels_attn_x3_h128.hip / kernels_attn_x3_long.hip (width 128) behind the option "attn_h128".
 Admission and refusals, the weight inventory, the option and info keys, the op-level exports, an unchanged workspace size, the build list,
 the predicates.  No GPU needed: engines are created on the host only."""
 import ctypes as C
@@ -18,7 +18,7 @@ KEY, LAST = "attn_h128", "attn_h128_last"
 VERSION = 142
 # (op symbol, Python wrapper, translation unit)
 OPS = [("d3d_op_attention_h128", "op_attention_h128", "kernels_attn_x3_h128.hip"),
-       ("d3d_op_attention_long_h128", "op_attention_long_h128", "kernels_attn_x3_h128_long.hip")]
+       ("d3d_op_attention_long_h128", "op_attention_long_h128", "kernels_attn_x3_long.hip")]
 CFG = dict(num_frame=243, embed_dim=1024, depth=8, num_heads=8)
 assert DenoiserConfig(**CFG).head_dim == 128
 

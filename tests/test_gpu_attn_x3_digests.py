@@ -1,5 +1,5 @@
 """Recorded output digests of the four compiler-scheduled F16X3 attention kernels that share csrc/attn_x3_tile.h: k_attn_temporal_x3,
-k_attn_temporal_x3p, k_attn_temporal_x3l and the attention step of k_qkv_attn_x3_small.  The "form A torch.equal form B" tests compare
+k_attn_temporal_x3p, k_attn_x3_stream<64, 8> and the attention step of k_qkv_attn_x3_small.  The "form A torch.equal form B" tests compare
 kernels that are built from the same pieces, so a change to a shared piece moves both sides together; these digests pin every touched
 instantiation to the bits of the hand-written bodies the header replaced.
 

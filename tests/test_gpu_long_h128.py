@@ -1,4 +1,4 @@
-"""Windows of more than 128 frames with heads of 128 columns on the MI355X ("attn_h128", kernels_attn_x3_h128_long.hip k_attn_x3l_h128):
+"""Windows of more than 128 frames with heads of 128 columns on the MI355X ("attn_h128", kernels_attn_x3_long.hip k_attn_x3_stream<128, 4>):
 embed_dim 1024 with the runner's 8 heads.  The keys of a head stream through LDS in chunks of 128 frames, the queries are cut into
 balanced blocks of at most 8 waves, and the arithmetic is k_attn_x3_h128's in the same order.
   * op level: bit for bit op_attention_h128 wherever that runs (T <= 128: one chunk, one query block);

@@ -1,5 +1,5 @@
-"""F16X3 windows of more than 256 frames with heads of 32 columns on the MI355X ("long_temporal_h32", kernels_attn_x3_h32_long.hip
-k_attn_x3l_h32): embed_dim 256 with the runner's 8 heads.  The keys of a head pair stream through LDS in chunks of 256 frames, the queries
+"""F16X3 windows of more than 256 frames with heads of 32 columns on the MI355X ("long_temporal_h32", kernels_attn_x3_long.hip
+k_attn_x3_stream<32, 8>): embed_dim 256 with the runner's 8 heads.  The keys of a head pair stream through LDS in chunks of 256 frames, the queries
 are cut into balanced blocks of at most 8 waves, and the arithmetic of each sub-head is k_attn_x3_h32's in the same order.
   * op level: bit for bit op_attention_h32 wherever that runs (T <= 256: one chunk, one query block, every wave count);
   * op level: windows of 257 .. 513 frames against fp64 math (one key in the second chunk, full and ragged last tiles, two full chunks,

@@ -1,4 +1,4 @@
-"""F16X3 windows of more than 256 frames on the MI355X ("long_temporal", kernels_attn_x3_long.hip k_attn_temporal_x3l): the keys of a unit
+"""F16X3 windows of more than 256 frames on the MI355X ("long_temporal", kernels_attn_x3_long.hip k_attn_x3_stream<64, 8>): the keys of a unit
 stream through LDS in chunks of 256 frames, the queries are cut into balanced blocks of at most 8 waves, and the arithmetic is the exact
 two-pass softmax of k_attn_temporal_x3 in the same order.
   * op level: bit for bit the existing kernels wherever those run (T <= 256: one chunk, one query block, every wave count);

@@ -1,6 +1,6 @@
 """Host-side contract of "long_temporal_h32" and "long_temporal_f32_h32" (include/d3d.h): engines whose heads are 32 columns wide
-(embed_dim 256 with 8 heads) and whose window is longer than 256 frames run their temporal blocks on kernels_attn_x3_h32_long.hip (F16X3)
-/ kernels_attn_f32_h32_long.hip (FP32).  The option and info keys, the op-level exports, an unchanged workspace size, the build list, the
+(embed_dim 256 with 8 heads) and whose window is longer than 256 frames run their temporal blocks on kernels_attn_x3_long.hip at width 32
+(F16X3) / kernels_attn_f32_h32_long.hip (FP32).  The option and info keys, the op-level exports, an unchanged workspace size, the build list, the
 predicates.  No GPU needed: engines are created on the host only."""
 import ctypes as C
 import os
@@ -14,7 +14,7 @@ from host_helpers import create_host_engine, engine_info
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (option key, engine precision, op symbol, Python wrapper, translation unit)
-FEATURES = [("long_temporal_h32", "f16x3", "d3d_op_attention_long_h32", "op_attention_long_h32", "kernels_attn_x3_h32_long.hip"),
+FEATURES = [("long_temporal_h32", "f16x3", "d3d_op_attention_long_h32", "op_attention_long_h32", "kernels_attn_x3_long.hip"),
             ("long_temporal_f32_h32", "fp32", "d3d_op_attention_long_f32_h32", "op_attention_long_f32_h32", "kernels_attn_f32_h32_long.hip")]
 KEYS = [(f[0], f[1]) for f in FEATURES]
 CFG = dict(num_frame=300, embed_dim=256, depth=8)
