@@ -427,6 +427,19 @@ bool attn_x3_h128_ok(int N, int D, int H);
 // launch_attn_x3_h128 wherever that runs (T <= 128).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h128_long_ok(int T, int D, int H);
+// ---- kernels_attn_f32_h128.hip: the exact fp32 attention (v_mfma_f32_32x32x2_f32) for heads of 128 columns (D == 128 H, any head
+// count), groups of N <= 128 tokens resident in LDS.  fp32 rows in, fp32 rows out, no pair-layout form (FP32 engines only); spatial blocks
+// call it with (B T, J, 1), so any joint count 1 .. 128 is served.  The scores are scaled by 1 / sqrt(128) after the sum over d, the
+// second product takes the unnormalised numerators, and the store divides by their sum and subtracts v[query], so the bits are not those
+// of launch_attn_generic.  The launch returns hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
+hipError_t launch_attn_f32_h128(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_f32_h128_ok(int N, int D, int H);
+// ---- kernels_attn_f32_h128.hip, k_attn_f32_h128_stream: launch_attn_f32_h128's temporal attention for windows of any length: the keys
+// stream through LDS in chunks of 128 frames, two passes (maximum; numerators, their sum and the product).  fp32 rows in, fp32 rows out;
+// bit-identical to launch_attn_f32_h128 wherever that runs (T <= 128).  The launch also refuses B J H ceil(T / 256) workgroups beyond
+// 2^31 - 1.
+hipError_t launch_attn_f32_h128_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_f32_h128_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

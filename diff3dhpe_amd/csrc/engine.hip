@@ -62,7 +62,8 @@ struct BlockPlan {
   bool fused_sp = false, fused_tp = false;
   // The attention kernel of the spatial / of the temporal blocks wherever the qkv GEMM and the attention are two launches: one value per
   // launch, listed with its shapes at launch_attention().  A BF16 plan runs launch_attn_bf16 and leaves both at GENERIC.
-  enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG };
+  enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, F32_H128, F32_H128_LONG,
+              X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG };
   Attn attn_sp = GENERIC, attn_tp = GENERIC;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
@@ -151,8 +152,13 @@ struct d3d_engine {
   bool opt_long_temporal_f32_h32 = true;
   // "attn_h128" (on by default): an F16X3 engine whose heads are 128 columns wide (embed_dim 1024 with 8 heads) runs the folded flow with
   // its attention on kernels_attn_x3_h128.hip (groups of up to 128 tokens) and kernels_attn_x3_long.hip at width 128 (windows of more than
-  // 128 frames); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of that width run the generic kernel either way
+  // 128 frames); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of that width: "attn_f32_h128"
   bool opt_attn_h128 = true;
+  // "attn_f32_h128": an FP32 engine whose heads are 128 columns wide runs the attention of its spatial blocks (up to 128 joints) and of
+  // its temporal blocks on kernels_attn_f32_h128.hip (windows of up to 128 frames resident, longer ones key-streaming); 0 = the generic
+  // one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical.  F16X3 / BF16 engines and every
+  // other head width: no effect
+  bool opt_attn_f32_h128 = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -424,14 +430,16 @@ int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal,
     case BlockPlan::X3_H32_LONG:  le = launch_attn_x3_h32_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 32 H, T > 256 (FOLD)
     case BlockPlan::X3_H128:      le = launch_attn_x3_h128(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                  // D == 128 H, groups <= 128 (FOLD)
     case BlockPlan::X3_H128_LONG: le = launch_attn_x3_h128_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;             // D == 128 H, T > 128 (FOLD)
+    case BlockPlan::F32_H128:     le = launch_attn_f32_h128(q, out, gB, gT, gJ, D, H, s); break;                         // D == 128 H, groups <= 128, FP32 engines
+    case BlockPlan::F32_H128_LONG: le = launch_attn_f32_h128_long(q, out, gB, gT, gJ, D, H, s); break;                   // D == 128 H, T > 128, FP32 engines
   }
   HIP_TRY(le);
   return D3D_OK;
 }
 
 // The "*_last" info keys of the attention plan, from the flow and the two kernel choices: which block types ran which kernel family
-// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last" bit 2 temporal
-// streaming).  false = not one of the keys.
+// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last" and
+// "attn_f32_h128_last" bit 2 temporal streaming).  false = not one of the keys.
 bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* value) {
   const bool fold = p.flow == BlockPlan::FOLD, plain = p.flow == BlockPlan::PLAIN;
   const BlockPlan::Attn sp = p.attn_sp, tp = p.attn_tp;
@@ -443,6 +451,8 @@ bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* valu
   else if (k == "long_temporal_f32_last") *value = plain && tp == BlockPlan::F32_LONG;
   else if (k == "attn_f32_h32_last") *value = plain ? (sp == BlockPlan::F32_H32 ? 1 : 0) | (tp == BlockPlan::F32_H32 ? 2 : 0) : 0;
   else if (k == "long_temporal_f32_h32_last") *value = plain && tp == BlockPlan::F32_H32_LONG;
+  else if (k == "attn_f32_h128_last")
+    *value = plain ? (sp == BlockPlan::F32_H128 ? 1 : 0) | (tp == BlockPlan::F32_H128 ? 2 : 0) | (tp == BlockPlan::F32_H128_LONG ? 4 : 0) : 0;
   else return false;
   return true;
 }
@@ -519,16 +529,20 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   } else {
     // the row-kernel flow.  F16X3: the fp16-MFMA kernel where the group length fits, q / k / v going to it as planes.  FP32: heads of 32
     // columns (no D == 64 H predicate holds there) on the kernels of that width where the group length fits; windows of more than 256
-    // frames, which the resident fp32 MFMA kernels cannot hold in LDS, on the key-streaming ones.  Else kernels_attn.hip.
+    // frames, which the resident fp32 MFMA kernels cannot hold in LDS, on the key-streaming ones; heads of 128 columns on the kernels of
+    // that width, each block type deciding alone (groups of up to 128 tokens resident, longer windows streaming).  Else kernels_attn.hip.
     const bool fp32 = e->cfg.precision == D3D_PREC_FP32;
     p.attn_sp = x3 && attn_temporal_x3_ok(J, D, H)                                    ? BlockPlan::X3
               : fp32 && e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H)       ? BlockPlan::F32_H32
+              : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_ok(J, D, H)             ? BlockPlan::F32_H128
               : attn_spatial_fast_ok(J, D, H)                                         ? BlockPlan::F32_SPATIAL
                                                                                       : BlockPlan::GENERIC;
     p.attn_tp = x3 && attn_temporal_x3_ok(T, D, H)                                    ? BlockPlan::X3
               : fp32 && e->opt_attn_f32_h32 && attn_temporal_f32_h32_ok(T, D, H)      ? BlockPlan::F32_H32
               : fp32 && e->opt_long_temporal_f32 && T > 256 && attn_temporal_f32_long_ok(T, D, H)          ? BlockPlan::F32_LONG
               : fp32 && e->opt_long_temporal_f32_h32 && T > 256 && attn_temporal_f32_h32_long_ok(T, D, H)  ? BlockPlan::F32_H32_LONG
+              : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_ok(T, D, H)             ? BlockPlan::F32_H128
+              : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_long_ok(T, D, H)        ? BlockPlan::F32_H128_LONG
               : attn_temporal_fast_ok(T, D, H)                                        ? BlockPlan::F32_TEMPORAL
                                                                                       : BlockPlan::GENERIC;
   }
@@ -1021,7 +1035,8 @@ const char* d3d_last_error(void) { return g_err.c_str(); }
 // d3d_op_attention_long_h32, d3d_op_attention_long_f32_h32
 // 142: head_dim 128 admitted (FP32 and F16X3), option / info key "attn_h128", info key "attn_h128_last", d3d_op_attention_h128,
 // d3d_op_attention_long_h128
-int d3d_version(void) { return 142; }
+// 143: option / info key "attn_f32_h128", info key "attn_f32_h128_last", d3d_op_attention_f32_h128, d3d_op_attention_long_f32_h128
+int d3d_version(void) { return 143; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1516,6 +1531,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "long_temporal_h32") e->opt_long_temporal_h32 = value != 0;
   else if (k == "long_temporal_f32_h32") e->opt_long_temporal_f32_h32 = value != 0;
   else if (k == "attn_h128") e->opt_attn_h128 = value != 0;
+  else if (k == "attn_f32_h128") e->opt_attn_f32_h128 = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1591,6 +1607,7 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "long_temporal_h32") *value = e->opt_long_temporal_h32 ? 1 : 0;
   else if (k == "long_temporal_f32_h32") *value = e->opt_long_temporal_f32_h32 ? 1 : 0;
   else if (k == "attn_h128") *value = e->opt_attn_h128 ? 1 : 0;
+  else if (k == "attn_f32_h128") *value = e->opt_attn_f32_h128 ? 1 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

@@ -225,7 +225,9 @@ class Engine:
         keeps the generic one-thread-per-row kernel there, "attn_h128": 1 (default) keeps an F16X3 engine with heads of 128 columns
         (embed_dim 1024, 8 heads, num_joints <= 128) on the folded flow, its attention on the fp16-MFMA kernels of that width (resident for
         groups of up to 128 tokens, key-streaming for num_frame > 128); 0 gives it the plain row-kernel flow with the generic fp32
-        attention kernel); the library reads no environment."""
+        attention kernel, "attn_f32_h128": 1 (default) runs the attention of an FP32 engine with heads of 128 columns on the exact fp32
+        MFMA kernels of that width (resident for groups of up to 128 tokens, key-streaming for num_frame > 128); 0 keeps the generic
+        one-thread-per-row kernel); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
@@ -245,7 +247,8 @@ class Engine:
         engine ran the key-streaming attention kernel for heads of 32 columns: num_frame > 256 with the option on; else 0), "attn_h128"
         (the option), "attn_h128_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent forward of an F16X3
         engine ran the resident attention kernel for heads of 128 columns, bit 2: the temporal blocks ran the key-streaming kernel of
-        that width; 0 before any forward, with the option off, at every other width and in the other precisions)."""
+        that width; 0 before any forward, with the option off, at every other width and in the other precisions), "attn_f32_h128"
+        (the option), "attn_f32_h128_last" (the same three bits for an FP32 engine and the exact fp32 kernels of that width)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -645,6 +648,19 @@ def op_attention_long_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int) ->
     (B*T*J, 3*D) -> (B*T*J, D), D == 128 H, any T >= 1; for T <= 128 bit for bit op_attention_h128(..., temporal=True); anything else
     raises D3DError."""
     return _attention_op("d3d_op_attention_long_h128", qkv, B, T, J, H)
+
+
+def op_attention_f32_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
+    """The resident exact fp32 attention kernel for heads of 128 columns alone (include/d3d.h d3d_op_attention_f32_h128): qkv
+    (B*T*J, 3*D) -> (B*T*J, D), D == 128 H, groups of at most 128 tokens (temporal: T keys, else J); anything else raises D3DError."""
+    return _attention_op("d3d_op_attention_f32_h128", qkv, B, T, J, H, int(bool(temporal)))
+
+
+def op_attention_long_f32_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming fp32 temporal attention kernel for heads of 128 columns alone (include/d3d.h d3d_op_attention_long_f32_h128):
+    qkv (B*T*J, 3*D) -> (B*T*J, D), D == 128 H, any T >= 1; for T <= 128 bit for bit op_attention_f32_h128(..., temporal=True);
+    anything else raises D3DError."""
+    return _attention_op("d3d_op_attention_long_f32_h128", qkv, B, T, J, H)
 
 
 def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, groups: int, N: int, stride: int, H: int,

@@ -85,7 +85,8 @@ int d3d_version(void);
 /* ---- construction: replaces HPE_model(name)(**kw) + GaussianDiffusion(model=...) (RUN:176-189) ------------------- */
 /* Head widths embed_dim / num_heads of 4, 8, 16, 32, 64 and 128 (D3D_PREC_BF16: 64 alone), embed_dim <= 1024; anything else:
  * D3D_EUNSUP.  Width 128 (embed_dim 1024 with the runner's 8 heads) runs the fp16-MFMA attention kernels of that width on a
- * D3D_PREC_F16X3 engine (option "attn_h128") and the generic one-thread-per-row kernel on a D3D_PREC_FP32 engine. */
+ * D3D_PREC_F16X3 engine (option "attn_h128") and the exact fp32 MFMA attention kernels of that width on a D3D_PREC_FP32 engine
+ * (option "attn_f32_h128"). */
 int d3d_engine_create(const d3d_config* cfg, d3d_engine** out);
 void d3d_engine_destroy(d3d_engine* e);
 
@@ -276,9 +277,23 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     wherever that runs) / 0: the plain row-kernel flow with the generic fp32 attention kernel in every block.  The
  *                     two differ in the last bits, both inside the parity gate.  A 9-step sampling at depth 8, embed_dim 1024,
  *                     num_frame 243: 187.5 -> 48.9 ms at B = 1, 6479 -> 1754 ms at B = 64.  Every other head
- *                     width, FP32 engines (the generic kernel at this width) and BF16 engines (refused at this width): no effect.
+ *                     width, FP32 engines ("attn_f32_h128") and BF16 engines (refused at this width): no effect.
  *                     d3d_workspace_bytes does not change.  "attn_h128_last" (d3d_engine_get_info) reports what the latest forward
  *                     ran.
+ *   "attn_f32_h128"   1 (default) / 0: FP32 engines whose heads are 128 columns wide (embed_dim == 128 num_heads, e.g. 1024 with 8
+ *                     heads) -- the exact reference arithmetic, and the engine a precision-"auto" model falls back to.  With the key
+ *                     on, the spatial blocks of such an engine (num_joints <= 128) and, for num_frame <= 128, its temporal blocks run
+ *                     the resident exact fp32 kernel of that width (v_mfma_f32_32x32x2_f32, K and V of a group resident in LDS, the
+ *                     scores scaled by 1 / sqrt(128) after the sum, exact two-pass softmax, the second product on the unnormalised
+ *                     numerators, the division by their sum and v[query] of the diagonal at the store), its temporal blocks for
+ *                     num_frame > 128 the key-streaming kernel of that width (keys pass through LDS in chunks of 128 frames, the
+ *                     scores are computed twice -- the resident kernel's arithmetic in its order, bit-identical to it wherever that
+ *                     runs); each block type is decided on its own / 0: the generic one-thread-per-row kernel, as before version 143.
+ *                     The two differ in the order of additions, so in the last bits, both inside the parity gate.  A 9-step sampling
+ *                     at depth 8, embed_dim 1024: 87.4 -> 61.6 ms at num_frame 27, B = 1; num_frame 243: 270.7 -> 138.6 ms at B = 1,
+ *                     2610 -> 1377 ms at B = 16.  Every other head
+ *                     width, F16X3 and BF16 engines: no effect.  d3d_workspace_bytes does not change.  "attn_f32_h128_last"
+ *                     (d3d_engine_get_info) reports what the latest forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -349,6 +364,8 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * "attn_h128" (the option value), "attn_h128_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent
  * d3d_denoise / d3d_ddim_sample call ran the resident F16X3 attention kernel for heads of 128 columns, bit 2: the temporal blocks ran
  * the key-streaming kernel of that width; 0 before any forward, with the option off, at every other head width and in the other
+ * precisions), "attn_f32_h128" (the option value), "attn_f32_h128_last" (the same three bits for a D3D_PREC_FP32 engine and the exact
+ * fp32 kernels for heads of 128 columns; 0 before any forward, with the option off, at every other head width and in the other
  * precisions),
  * "small_tiles" (the option value), "small_tiles_last" (bit 0: the
  * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
@@ -596,6 +613,16 @@ int d3d_op_attention_h128(const float* qkv_dev, float* out_dev, int32_t B, int32
 /* The temporal core of such an engine from the key-streaming kernel of that width alone.  Any T >= 1; D == 128 H, anything else:
  * D3D_EUNSUP.  For T <= 128 bit for bit the result of d3d_op_attention_h128 (temporal = 1). */
 int d3d_op_attention_long_h128(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
+/* The resident exact fp32 attention kernel for heads of 128 columns alone (option "attn_f32_h128"): fp32 qkv in, fp32 out.  temporal as
+ * in d3d_op_attention (0: N = J keys, 1: N = T keys).  D == 128 H and a group length N <= 128; anything else (head_dim 128 is the only
+ * width it takes): D3D_EUNSUP.  Not the bits of d3d_op_attention, which keeps the generic kernel at this width. */
+int d3d_op_attention_f32_h128(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
+                              int32_t temporal, void* stream);
+/* The temporal core of such an engine from the key-streaming fp32 kernel of that width alone.  Any T >= 1; D == 128 H, anything else
+ * (head_dim 128 is the only width it takes): D3D_EUNSUP.  For T <= 128 bit for bit the result of d3d_op_attention_f32_h128
+ * (temporal = 1). */
+int d3d_op_attention_long_f32_h128(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
+                                   void* stream);
 /* The fused qkv GEMM + attention kernel of the BF16 mode alone: out = attention(bf16(A) bf16(Wqkv)^T + bias) with q / k / v rounded to
  * bf16 (q third times dh^-1/2) and kept on chip -- bit for bit d3d_op_linear (D3D_PREC_BF16) followed by d3d_op_attention (D3D_PREC_BF16)
  * on the same tensors.  A: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias: (3 D); out: (groups * N, D) fp32.  Group u holds the N
