@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "d3d_engine_set_trace", "d3d_engine_trace_read", "d3d_engine_range_flags", "d3d_op_head", "d3d_engine_set_option",
     "d3d_weighted_loss", "d3d_repeat_batch", "d3d_hypothesis_mean", "d3d_engine_get_info", "d3d_probe_machine",
     "d3d_engine_range_post", "d3d_engine_range_take", "d3d_window_gather_s2f", "d3d_pose_metrics", "d3d_op_qkv_attn_bf16",
-    "d3d_op_qkv_attn_x3_small",
+    "d3d_op_qkv_attn_x3_small", "d3d_op_linear_folded", "d3d_op_linear_plane_residual", "d3d_op_layernorm_forms",
 ]
 
 
@@ -92,6 +92,10 @@ def _bind(lib: C.CDLL) -> None:
                                                    vp, i32, C.POINTER(C.c_float), vp]),
         "d3d_op_linear_splitk_residual": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, C.POINTER(C.c_float), vp]),
         "d3d_op_linear_splitk_gelu": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp, i32, C.POINTER(C.c_float), vp]),
+        "d3d_op_linear_folded": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp]),
+        "d3d_op_linear_plane_residual": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "d3d_op_layernorm_forms": (C.c_int, [vp, vp, vp, f32, i32, vp, i32, i32, vp, i64, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32,
+                                             vp]),
         "d3d_op_head": (C.c_int, [vp, vp, vp, i32, vp]),
         "d3d_op_layernorm": (C.c_int, [vp, vp, vp, vp, i32, i32, f32, vp]),
         "d3d_op_attention": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

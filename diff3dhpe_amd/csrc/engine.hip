@@ -1036,7 +1036,7 @@ const char* d3d_last_error(void) { return g_err.c_str(); }
 // 142: head_dim 128 admitted (FP32 and F16X3), option / info key "attn_h128", info key "attn_h128_last", d3d_op_attention_h128,
 // d3d_op_attention_long_h128
 // 143: option / info key "attn_f32_h128", info key "attn_f32_h128_last", d3d_op_attention_f32_h128, d3d_op_attention_long_f32_h128
-int d3d_version(void) { return 143; }
+int d3d_version(void) { return 144; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed

@@ -19,7 +19,7 @@ struct TmpPair : DevBuf<uint16_t> {
   int wexp = 12;
 };
 int make_pair(TmpPair& t, const float* src_dev, int rows, int cols, bool weight, hipStream_t s) {
-  const size_t n16 = 2 * pad256(rows) * cols;
+  const size_t n16 = 2 * pad256(rows + 191) * cols;   // (whole 256-row tiles, and whole 192-row ones of proj's walk, as the engine's workspace)
   HIP_TRY(t.alloc(n16));
   HIP_TRY(hipMemsetAsync(t.p, 0, n16 * sizeof(uint16_t), s));
   if (weight) {
@@ -44,6 +44,24 @@ int make_operands(X3Operands& o, const float* A, const float* W, const float* R,
   if (!rc && R) rc = make_pair(o.r, R, M, N, false, s);
   if (!rc && with_y) rc = make_pair(o.y, R, M, N, false, s);
   return rc;
+}
+
+// The LayerNorm fold of the weight commit, on the host: W diag(gamma) as planes wp (rows padded to 256, zero rows), and fd = [csum | b + W beta]
+int make_folded(TmpPair& wp, DevBuf<float>& fd, const float* W, const float* bias, const float* gamma, const float* beta, int N, int K,
+                hipStream_t s) {
+  const size_t nk = (size_t)N * K;
+  std::vector<float> hw(nk), hg(K), hb(K), hbias(N), wg(nk), fold(2 * (size_t)N);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(hw.data(), W, nk * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hg.data(), gamma, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hb.data(), beta, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hbias.data(), bias, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
+  fold_layernorm(hw.data(), hbias.data(), hg.data(), hb.data(), N, K, wg.data(), fold.data(), fold.data() + N);
+  std::vector<uint16_t> pr(2 * pad256(N) * K, 0);
+  wp.wexp = split_weight_f16x3(wg.data(), N, K, pr.data());
+  HIP_TRY(wp.upload(pr.data(), pr.size()));
+  HIP_TRY(fd.upload(fold.data(), fold.size()));
+  return D3D_OK;
 }
 
 // mean time of `once` over reps launches on s, behind `warm` untimed ones (the op hooks' avg_ms)
@@ -242,26 +260,15 @@ int d3d_op_linear_splitk_gelu(const float* X, const float* W, const float* bias,
   if (S == 0 ? !(N > 0 && N % 512 == 0 && K > 0 && K % 64 == 0) : !fc1_splitk_ok(N, K, S))
     return fail(D3D_EUNSUP, "the split-K fc1 pair exists for N % 512 == 0, K % 64 == 0, S in {2, 4}, K / 32 / S >= 4 whole k-tiles (S == 0: the default kernel)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // the LayerNorm fold of the weight commit: W diag(gamma) as planes, csum, b + W beta
-  const size_t nk = (size_t)N * K;
-  std::vector<float> hw(nk), hg(K), hb(K), hbias(N), wg(nk), fold(2 * (size_t)N);
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(hw.data(), W, nk * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hg.data(), gamma, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hb.data(), beta, (size_t)K * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hbias.data(), bias, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
-  fold_layernorm(hw.data(), hbias.data(), hg.data(), hb.data(), N, K, wg.data(), fold.data(), fold.data() + N);
   TmpPair wp, xp, hp;
-  const size_t npad = pad256(N), mpad = pad256(M);
-  std::vector<uint16_t> pr(2 * npad * K, 0);
-  wp.wexp = split_weight_f16x3(wg.data(), N, K, pr.data());
-  HIP_TRY(wp.upload(pr.data(), pr.size()));
+  DevBuf<float> fd, st;
+  const int rc = make_folded(wp, fd, W, bias, gamma, beta, N, K, s);
+  if (rc) return rc;
+  const size_t mpad = pad256(M);
   HIP_TRY(xp.alloc(2 * mpad * K));
   HIP_TRY(hipMemsetAsync(xp.p, 0, 2 * mpad * K * sizeof(uint16_t), s));
   HIP_TRY(hp.alloc(2 * mpad * N));
   HIP_TRY(hipMemsetAsync(hp.p, 0, 2 * mpad * N * sizeof(uint16_t), s));
-  DevBuf<float> fd, st;
-  HIP_TRY(fd.upload(fold.data(), fold.size()));
   HIP_TRY(st.alloc(mpad * 2));
   HIP_TRY(hipMemsetAsync(st.p, 0, mpad * 2 * sizeof(float), s));
   {  // the stream entry row kernel: planes of 8 x + one (sum, sum of squares) per row
@@ -278,6 +285,60 @@ int d3d_op_linear_splitk_gelu(const float* X, const float* W, const float* bias,
   };
   hipError_t le = run_timed(once, reps, avg_ms, s);
   if (le == hipSuccess) le = launch_unsplit_acc(hp.p, H, (size_t)M, N, s);
+  return finish(le, s);
+}
+
+int d3d_op_linear_folded(const float* X, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
+                         const float* st, int32_t st_np, int32_t epi, int32_t qcols, float* H, void* hi, void* lo, int32_t M, int32_t N,
+                         int32_t K, void* stream) {
+  if (!X || !W || !bias || !gamma || !beta || !st || M < 1 || st_np < 1 || !(eps > 0.f) || (epi != EPI_NONE && epi != EPI_GELU))
+    return fail(D3D_EINVAL, "bad argument");
+  if (!(N > 0 && N % 128 == 0 && K > 0 && K % 32 == 0)) return fail(D3D_EUNSUP, "the folded forms are exposed for N % 128 == 0, K % 32 == 0");
+  if (epi == EPI_NONE ? (!hi || !lo || qcols < 0 || qcols > N || qcols % 64) : !H)
+    return fail(D3D_EINVAL, "qkv form: hi / lo planes and 0 <= qcols <= N, qcols % 64 == 0; fc1 form: H");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  TmpPair wp, xp, hp;
+  DevBuf<float> fd, stb;
+  int rc = make_folded(wp, fd, W, bias, gamma, beta, N, K, s);
+  if (!rc) rc = make_pair(xp, X, M, K, false, s);
+  if (rc) return rc;
+  // the statistics as the engine's buffers hold them: whole 256-row tiles; the pad rows are NaN here (staged by the walk, read by nothing)
+  const size_t nst = pad256(M) * st_np * 2, mst = (size_t)M * st_np * 2;
+  HIP_TRY(stb.alloc(nst));
+  HIP_TRY(hipMemsetAsync(stb.p, 0xff, nst * sizeof(float), s));
+  HIP_TRY(hipMemcpyAsync(stb.p, st, mst * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (epi == EPI_GELU) {
+    HIP_TRY(hp.alloc(2 * pad256(M) * N));
+    HIP_TRY(hipMemsetAsync(hp.p, 0, 2 * pad256(M) * N * sizeof(uint16_t), s));
+  }
+  X3Fold f{};
+  f.st_in = stb.p; f.st_np = st_np; f.csum = fd.p; f.eps = eps;
+  hipError_t le = epi == EPI_NONE
+                      ? launch_linear_x3p(xp.p, wp.p, fd.p + N, nullptr, nullptr, hi, lo, M, N, K, EPI_NONE, 1, qcols, 0, s, &f, wp.wexp)
+                      : launch_linear_x3p(xp.p, wp.p, fd.p + N, nullptr, nullptr, hp.p, nullptr, M, N, K, EPI_GELU, 2, 0, 0, s, &f, wp.wexp);
+  if (le == hipSuccess && epi == EPI_GELU) le = launch_unsplit_acc(hp.p, H, (size_t)M, N, s);
+  return finish(le, s);
+}
+
+int d3d_op_linear_plane_residual(const float* A, const float* W, const float* bias, const float* R, float* Y, float* stats,
+                                 int32_t with_stats, int32_t M, int32_t N, int32_t K, void* stream) {
+  if (!A || !W || !bias || !R || !Y || (with_stats && !stats) || M < 1) return fail(D3D_EINVAL, "bad argument");
+  if (!(N > 0 && N % 128 == 0 && K > 0 && K % 32 == 0))
+    return fail(D3D_EUNSUP, "the plane-residual forms are exposed for N % 128 == 0, K % 32 == 0");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  X3Operands o;
+  const int rc = make_operands(o, A, W, R, M, N, K, false, s);
+  if (rc) return rc;
+  const int np = x3q_ntiles(M, N);
+  DevBuf<float> part;   // (whole 256-row tiles, as the engine's statistics buffers)
+  if (with_stats) HIP_TRY(part.alloc(pad256(M) * np * 2));
+  X3Fold f{};
+  f.Rp = o.r.p; f.st_out = part.p;
+  // proj form: the stream planes updated in place, as the engine runs it; fc2 form: fp32 out
+  hipError_t le = with_stats ? launch_linear_x3p(o.a.p, o.w.p, bias, nullptr, nullptr, o.r.p, nullptr, M, N, K, EPI_RESIDUAL, 2, 0, 0, s, &f, o.w.wexp)
+                             : launch_linear_x3p(o.a.p, o.w.p, bias, nullptr, Y, nullptr, nullptr, M, N, K, EPI_RESIDUAL, 0, 0, 0, s, &f, o.w.wexp);
+  if (le == hipSuccess && with_stats) le = launch_unsplit_x3(o.r.p, Y, (size_t)M, N, nullptr, 0, nullptr, s);
+  if (le == hipSuccess && with_stats) le = hipMemcpyAsync(stats, part.p, (size_t)M * np * 2 * sizeof(float), hipMemcpyDeviceToDevice, s);
   return finish(le, s);
 }
 
@@ -349,6 +410,32 @@ int d3d_op_layernorm(const float* x, const float* gamma, const float* beta, floa
   a.x = x; a.y = out; a.g1 = gamma; a.b1 = beta; a.eps1 = eps;
   HIP_TRY(launch_layernorm(a, reinterpret_cast<hipStream_t>(stream)));
   return D3D_OK;
+}
+
+int d3d_op_layernorm_forms(const float* x, const float* gamma1, const float* beta1, float eps1, int32_t skip_ln1, const float* pos,
+                           int32_t pos_div, int32_t pos_mod, const float* tvec, int64_t tvec_stride, int32_t rows_per_batch,
+                           const float* gamma2, const float* beta2, float eps2, float* y, float* yx3, float* stats, float* h, float* hx3,
+                           void* hbf16, int32_t rows, int32_t D, void* stream) {
+  const int nh = (h != nullptr) + (hx3 != nullptr) + (hbf16 != nullptr);
+  if (!x || rows < 1 || D < 1 || (!skip_ln1 && (!gamma1 || !beta1)) || nh > 1 || (nh && (!gamma2 || !beta2 || (!y && !yx3))) ||
+      (!y && !yx3 && !stats && !nh))
+    return fail(D3D_EINVAL, "bad argument");
+  if (!row_class_args_ok(pos, pos_div, pos_mod, tvec, tvec_stride, rows_per_batch)) return fail(D3D_EINVAL, "bad row-class arguments");
+  if (D % 4 || D > 1024 || ((yx3 || hx3) && D % 32)) return fail(D3D_EUNSUP, "row kernel: D % 4 == 0, D <= 1024, plane outputs D % 32 == 0");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  DevBuf<uint16_t> yp, hp;
+  if (yx3) HIP_TRY(yp.alloc(2 * (size_t)rows * D));
+  if (hx3) HIP_TRY(hp.alloc(2 * (size_t)rows * D));
+  LnArgs a = ln_rows(rows, D, rows_per_batch > 0 ? rows_per_batch : 1);
+  a.x = x; a.y = y; a.y_x3 = yp.p; a.stats = stats; a.h = h; a.h_x3 = hp.p; a.h_bf16 = hbf16;
+  a.g1 = gamma1; a.b1 = beta1; a.eps1 = eps1; a.skip_ln1 = skip_ln1 ? 1 : 0;
+  a.g2 = gamma2; a.b2 = beta2; a.eps2 = eps2;
+  a.pos = pos; a.pos_div = pos ? pos_div : 1; a.pos_mod = pos ? pos_mod : 1;
+  a.tvec = tvec; a.tvec_stride = tvec_stride;
+  hipError_t le = launch_layernorm(a, s);
+  if (le == hipSuccess && yx3) le = launch_unsplit_x3(yp.p, yx3, (size_t)rows, D, nullptr, 0, nullptr, s);
+  if (le == hipSuccess && hx3) le = launch_unsplit_x3(hp.p, hx3, (size_t)rows, D, nullptr, 0, nullptr, s);
+  return finish(le, s);
 }
 
 int d3d_op_attention(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,

@@ -568,6 +568,74 @@ def op_linear_splitk_gelu(x: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, 
     return out, ms.value
 
 
+def op_linear_folded(x: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, stats: torch.Tensor,
+                     eps: float = 1e-6, epi: str = "none", qcols: int = 0):
+    """One launch of the F16X3 token GEMM in a LayerNorm-folded form with the caller's row statistics (include/d3d.h
+    d3d_op_linear_folded).  stats: (M, st_np, 2) fp32 (sum, sum of squares) partials of the rows of x.  epi "none" (the qkv form)
+    returns the raw (hi, lo) fp16 planes, (M, N) each: value = (hi.float() + lo.float()) / scale, scale 1 for columns < qcols and 8
+    for the others; epi "gelu" (the fc1 form) returns gelu(LN(x) W^T + bias) as fp32."""
+    epi_id = {"none": 0, "gelu": 1}[epi]
+    M, K = x.shape
+    N = W.shape[0]
+    dev = x.device
+    x, W, bias, gamma, beta = _f32c(x, dev), _f32c(W, dev), _f32c(bias, dev), _f32c(gamma, dev), _f32c(beta, dev)
+    stats = _f32c(stats, dev)
+    if stats.dim() != 3 or stats.shape[0] != M or stats.shape[2] != 2:
+        raise ValueError(f"stats must be (M, st_np, 2), got {tuple(stats.shape)}")
+    out = hi = lo = None
+    if epi_id:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    else:
+        hi, lo = (torch.empty((M, N), dtype=torch.float16, device=dev) for _ in range(2))
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_linear_folded(_ptr(x), _ptr(W), _ptr(bias), _ptr(gamma), _ptr(beta), float(eps), _ptr(stats),
+                                                   int(stats.shape[1]), epi_id, int(qcols), _ptr(out), _ptr(hi), _ptr(lo), M, N, K, st))
+    return out if epi_id else (hi, lo)
+
+
+def op_linear_plane_residual(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, residual: torch.Tensor, with_stats: bool = True):
+    """One launch of the F16X3 token GEMM in a plane-residual form (include/d3d.h d3d_op_linear_plane_residual): x = residual + bias +
+    A W^T.  with_stats (the proj form): (x un-split from the stream planes, the (sum, sum of squares) partials per row and 64 columns,
+    shape (M, N / 64, 2)); otherwise (the fc2 form that writes fp32): (x, None)."""
+    M, K = A.shape
+    N = W.shape[0]
+    dev = A.device
+    A, W, bias, residual = _f32c(A, dev), _f32c(W, dev), _f32c(bias, dev), _f32c(residual, dev)
+    out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    stats = torch.empty((M, max(N // 64, 1), 2), dtype=torch.float32, device=dev) if with_stats else None
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_linear_plane_residual(_ptr(A), _ptr(W), _ptr(bias), _ptr(residual), _ptr(out), _ptr(stats),
+                                                           int(with_stats), M, N, K, st))
+    return out, stats
+
+
+def op_layernorm_forms(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                       skip_ln1: bool = False, pos: Optional[torch.Tensor] = None, pos_div: int = 1, tvec: Optional[torch.Tensor] = None,
+                       rows_per_batch: int = 1, gamma2: Optional[torch.Tensor] = None, beta2: Optional[torch.Tensor] = None,
+                       eps2: float = 1e-6, outputs=("y",)) -> dict:
+    """The LayerNorm row kernel with the output forms named in `outputs` (include/d3d.h d3d_op_layernorm_forms), one launch:
+    "y" fp32, "y_x3" (fp32 decoded from the stream planes the kernel wrote), "stats" (rows, 2), and one of "h", "h_x3" (decoded),
+    "h_bf16" (torch.bfloat16) for the second LayerNorm.  x: (rows, D).  Returns {name: tensor}."""
+    known = ("y", "y_x3", "stats", "h", "h_x3", "h_bf16")
+    if not outputs or any(o not in known for o in outputs):
+        raise ValueError(f"outputs must name some of {known}")
+    rows, D = x.shape
+    dev = x.device
+    opt = lambda t: _f32c(t, dev) if t is not None else None
+    x, gamma, beta, pos, tvec, gamma2, beta2 = _f32c(x, dev), opt(gamma), opt(beta), opt(pos), opt(tvec), opt(gamma2), opt(beta2)
+    stride = 0 if tvec is None or tvec.dim() == 1 or tvec.shape[0] == 1 else D
+    res = {o: torch.empty((rows, 2) if o == "stats" else (rows, D), dtype=torch.bfloat16 if o == "h_bf16" else torch.float32, device=dev)
+           for o in outputs}
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_layernorm_forms(
+            _ptr(x), _ptr(gamma), _ptr(beta), float(eps), int(skip_ln1), _ptr(pos), int(pos_div), int(pos.shape[0]) if pos is not None else 1,
+            _ptr(tvec), stride, int(rows_per_batch), _ptr(gamma2), _ptr(beta2), float(eps2), *(_ptr(res.get(o)) for o in known), rows, D, st))
+    return res
+
+
 def op_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
     dev = x.device
     D = x.shape[-1]

@@ -565,6 +565,37 @@ int d3d_op_linear_splitk_residual(const float* A_dev, const float* W_dev, const 
 int d3d_op_linear_splitk_gelu(const float* X_dev, const float* W_dev, const float* bias_dev, const float* gamma_dev,
                               const float* beta_dev, float eps, float* H_dev, int32_t M, int32_t N, int32_t K, int32_t S,
                               float* partials_dev, int32_t reps, float* avg_ms, void* stream);
+/* ONE launch of the F16X3 token GEMM in a LayerNorm-folded form of the engine's plane-resident block, with the CALLER's row statistics:
+ *   epi 0 (the qkv form):  LayerNorm(X; gamma, beta, eps) W^T + bias as the hi / lo fp16 planes the attention kernels read -- hi_dev, lo_dev:
+ *                          (M, N) fp16 each; columns < qcols hold 1 * value, the others 8 * value, so value = (hi + lo) / scale.  H_dev unused.
+ *   epi 1 (the fc1 form):  gelu(the same) read back as fp32 H_dev (M, N) from the accumulator-order planes fc2 consumes.  hi_dev, lo_dev,
+ *                          qcols unused.
+ * X: (M, K) raw fp32 rows (split into planes of 8 x on the device); W: (N, K), folded with gamma / beta on the host as the weight commit
+ * folds it.  st_dev: (M, st_np, 2) fp32 (sum, sum of squares) partials of every X row -- the kernel only adds a row's st_np partials, so
+ * st_np is the caller's (>= 1), whatever K; the hook copies them into a buffer of whole 256-row tiles whose pad rows hold NaN (the
+ * persistent walk stages them, nothing may read them).  N % 128 == 0, K % 32 == 0 (else D3D_EUNSUP); 0 <= qcols <= N, qcols % 4 == 0. */
+int d3d_op_linear_folded(const float* X_dev, const float* W_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev,
+                         float eps, const float* st_dev, int32_t st_np, int32_t epi, int32_t qcols, float* H_dev, void* hi_dev,
+                         void* lo_dev, int32_t M, int32_t N, int32_t K, void* stream);
+/* ONE launch of the F16X3 token GEMM in a plane-residual form: Y = R + bias + A W^T with the residual read from stream planes.
+ *   with_stats != 0 (the proj form): Y written as stream planes in place of R's and un-split to fp32 Y_dev; stats_dev (M, N / 64, 2)
+ *                   receives the (sum, sum of squares) of every new row per 64-column block (what the folded fc1 reads).
+ *   with_stats == 0 (the fc2 form of every width but 512): Y written as fp32; stats_dev unused.
+ * The launch shape is the engine's choice from (M, N, K, CU count).  N % 128 == 0, K % 32 == 0 (else D3D_EUNSUP). */
+int d3d_op_linear_plane_residual(const float* A_dev, const float* W_dev, const float* bias_dev, const float* R_dev, float* Y_dev,
+                                 float* stats_dev, int32_t with_stats, int32_t M, int32_t N, int32_t K, void* stream);
+/* Every output form of the LayerNorm row kernel in one launch (d3d_op_layernorm is its plain y = LN(x) form):
+ *   y = [LN(x; gamma1, beta1, eps1) unless skip_ln1] [+ pos[(row / pos_div) % pos_mod]] [+ tvec[(row / rows_per_batch) * tvec_stride]]
+ *   h = LN(y; gamma2, beta2, eps2)
+ * Each output is written where its pointer is given: y_dev fp32; yx3_dev fp32, decoded from the stream planes of 8 y the kernel wrote;
+ * stats_dev (rows, 2) the (sum, sum of squares) of every y row; h_dev fp32; hx3_dev fp32, decoded from h's planes; hbf16_dev (rows, D)
+ * bf16.  At most one of h_dev / hx3_dev / hbf16_dev, and then y_dev or yx3_dev as well (the kernel forms h from y; gamma2 / beta2
+ * required); at least one output.  D % 4 == 0, D <= 1024, D % 32 == 0 for the plane outputs (else D3D_EUNSUP). */
+int d3d_op_layernorm_forms(const float* x_dev, const float* gamma1_dev, const float* beta1_dev, float eps1, int32_t skip_ln1,
+                           const float* pos_dev, int32_t pos_div, int32_t pos_mod, const float* tvec_dev, int64_t tvec_stride,
+                           int32_t rows_per_batch, const float* gamma2_dev, const float* beta2_dev, float eps2, float* y_dev,
+                           float* yx3_dev, float* stats_dev, float* h_dev, float* hx3_dev, void* hbf16_dev, int32_t rows, int32_t D,
+                           void* stream);
 /* Regression head of the engine's weights (S2S:217-220: LayerNorm eps 1e-5 + Linear D -> 3) on rows x D fp32 rows:
  * x0 (rows, 3), raw (no clamp, no DDIM update). */
 int d3d_op_head(d3d_engine* e, const float* X_dev, float* x0_dev, int32_t rows, void* stream);

@@ -46,6 +46,23 @@ def cu_count():
     return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
 
 
+# Row counts that put a launcher on a given branch of its ladder depend on the device's CU count: named here, resolved inside the test
+# (collection does not touch the GPU).
+_ROWS = {"walk256": lambda cu: 256 * 2 * cu + 100,    # 256 x 256 tiles: the persistent walk (>= 4 rounds) with a ragged last round
+         "rows128": lambda cu: 128 * cu + 77,         # whole-row tiles: more 128-row tiles than CUs, one tile per workgroup
+         "rowswalk": lambda cu: 128 * 4 * cu + 77}    # whole-row tiles: the persistent walk
+
+
+def _rows(M):
+    return _ROWS[M](cu_count()) if isinstance(M, str) else M
+
+
+# The bounds of tests/test_gpu_latency_mode.py::test_splitk_postnorm_matches_fp64: 3e-6 sqrt(K / 32) + 2e-6 for the GEMM part, 2e-6 more
+# for a result read back from planes (22 bits), 2e-3 / 1e-2 for sums / sums of squares.  Operands from the same generators.
+def _tol(K):
+    return 3e-6 * np.sqrt(K / 32) + 2e-6
+
+
 def hashed(name, shape, seed, scale=1.0):
     n = int(np.prod(shape))
     return torch.from_numpy((scale * hash_uniform(name, n, seed)).astype(np.float32).reshape(shape))

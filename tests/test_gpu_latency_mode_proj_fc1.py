@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 import diff3dhpe_amd as d3d
 from conftest import gold
-from helpers import hashed, torch_sd, maxabs, inputs, cfg_full, build_product
+from helpers import hashed, torch_sd, maxabs, inputs, cfg_full, build_product, _tol
 from helpers import dev as _dev          # tests here hold the device in a local named dev
 from diff3dhpe_amd.spec import DenoiserConfig
 
@@ -29,12 +29,7 @@ def _splits(eng):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. op level
-# The bounds of tests/test_gpu_latency_mode.py::test_splitk_postnorm_matches_fp64: 3e-6 sqrt(K / 32) + 2e-6 for the GEMM part, 2e-6 more
-# for a result read back from planes (22 bits), 2e-3 / 1e-2 for sums / sums of squares.  Operands from the same generators.
-def _tol(K):
-    return 3e-6 * np.sqrt(K / 32) + 2e-6
-
-
+# (the bounds: helpers._tol)
 @pytest.mark.parametrize("M", [130, 459, 1377])
 @pytest.mark.parametrize("S", [2, 4])
 def test_splitk_residual_matches_fp64(S, M):

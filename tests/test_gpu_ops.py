@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import gold
-from helpers import hashed, torch_sd, maxabs, attn_ref, cu_count
+from helpers import hashed, torch_sd, maxabs, attn_ref, _ROWS, _rows
 from diff3dhpe_amd.spec import DenoiserConfig
 
 pytestmark = pytest.mark.gpu
@@ -15,17 +15,6 @@ pytestmark = pytest.mark.gpu
 def _eng():
     from diff3dhpe_amd import engine
     return engine
-
-
-# Row counts that put a launcher on a given branch of its ladder depend on the device's CU count: named here, resolved inside the test
-# (collection does not touch the GPU).
-_ROWS = {"walk256": lambda cu: 256 * 2 * cu + 100,    # 256 x 256 tiles: the persistent walk (>= 4 rounds) with a ragged last round
-         "rows128": lambda cu: 128 * cu + 77,         # whole-row tiles: more 128-row tiles than CUs, one tile per workgroup
-         "rowswalk": lambda cu: 128 * 4 * cu + 77}    # whole-row tiles: the persistent walk
-
-
-def _rows(M):
-    return _ROWS[M](cu_count()) if isinstance(M, str) else M
 
 
 _LINEAR_SHAPES = [(128, 128, 32), (300, 96, 32), (1000, 1536, 512), (2066, 512, 1024), (17, 64, 64), (4131, 1024, 512), (129, 130, 96)]
