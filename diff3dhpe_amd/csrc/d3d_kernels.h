@@ -392,7 +392,10 @@ bool attn_temporal_x3_long_ok(int T, int D, int H);
 // pair layout out; spatial blocks call it with (B T, J, 1).
 hipError_t launch_attn_x3_h32(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h32_ok(int N, int D, int H);
-// ---- kernels_attn_f32_long.hip: launch_attn_temporal_f32's attention (exact fp32, v_mfma_f32_32x32x2_f32) for windows of any length:
+// ---- The exact fp32 MFMA attention kernels (v_mfma_f32_32x32x2_f32) of kernels_attn.hip (width 64, resident), kernels_attn_f32_h32.hip
+// (width 32, resident), kernels_attn_f32_long.hip and kernels_attn_f32_h32_long.hip (widths 64 and 32, key-streaming) and kernels_attn_f32_h128.hip (width 128, both) share
+// their arithmetic, staging, launch ladder and streaming geometry: attn_f32_tile.h.
+// ---- kernels_attn_f32_long.hip, k_attn_f32_stream3<64>: launch_attn_temporal_f32's attention for windows of any length:
 // the keys stream through LDS in chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out, no
 // pair-layout form; bit-identical to launch_attn_temporal_f32 wherever that runs (T <= 256).  The launch also refuses
 // B J H ceil(T / 256) workgroups beyond 2^31 - 1.
@@ -412,7 +415,7 @@ bool attn_spatial_f32_h32_ok(int J, int D, int H);
 // 2^31 - 1.
 hipError_t launch_attn_x3_h32_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h32_long_ok(int T, int D, int H);
-// ---- kernels_attn_f32_h32_long.hip: launch_attn_temporal_f32_h32's attention for windows of any length (D == 32 H, any head count):
+// ---- kernels_attn_f32_h32_long.hip, k_attn_f32_stream3<32>: launch_attn_temporal_f32_h32's attention for windows of any length (D == 32 H, any head count):
 // chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out; bit-identical to
 // launch_attn_temporal_f32_h32 wherever that runs (T <= 256).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_temporal_f32_h32_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);

@@ -8,15 +8,13 @@
 //            unit are staged in LDS and broadcast-read, the 17-wide softmax is lane-local (no shuffles needed at all).
 //   temporal (one group = the T<=256 frames of a joint): v_mfma_f32_32x32x2_f32 on swapped operands -- S^T = K Q^T so a
 //            lane holds one query column of scores in registers; the softmax is over registers + one cross-half
-//            shuffle, and P^T feeds O^T = V^T P^T straight from the accumulator registers (never touches LDS).
+//            shuffle, and P^T feeds O^T = V^T P^T straight from the accumulator registers (never touches LDS).  The
+//            pieces are those of attn_f32_tile.h, shared with the other head widths and the key-streaming kernels.
 //   generic  any (N, dh): one thread per query row, used for the small test model (dh = 4) and as a cross-check.
-#include "d3d_kernels.h"
-
-#include <math.h>
+#include "attn_f32_tile.h"
 
 namespace d3d {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 h4a __attribute__((ext_vector_type(4)));
 typedef _Float16 h8a __attribute__((ext_vector_type(8)));
 
@@ -194,7 +192,10 @@ hipError_t launch_attn_spatial_f32(const float* qkv, float* out, void* out_x3, i
 }
 
 // =============================================================================================== temporal (MFMA f32)
-constexpr int TP_DH = 64, K_LD = 68, V_LD = 64;
+// k_attn_temporal_f32<NKT>, one workgroup of NKT waves per (batch, joint, head), T <= 32 NKT <= 256, on the pieces of attn_f32_tile.h at
+// DH = 64: q pre-scaled by the exact 2^-3, 32 MFMAs per score tile, P normalised and the - 1 of the diagonal put into it before the
+// second product, two accumulator tiles.  K and V of 256 rows are 132 of the 160 KiB.
+using T64 = F32Tile<64>;
 
 template <int NKT>
 __global__ __launch_bounds__(64 * NKT) void k_attn_temporal_f32(const float* __restrict__ qkv, float* __restrict__ out,
@@ -202,148 +203,81 @@ __global__ __launch_bounds__(64 * NKT) void k_attn_temporal_f32(const float* __r
                                                                 int T, int J, int H, int D, unsigned* rw) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TP = 32 * NKT;
-  float* Ks = lds;                 // [TP][K_LD]  (272-B rows: ds_read_b128 of 16 consecutive keys is conflict-free)
-  float* Vs = lds + TP * K_LD;     // [TP][V_LD]
+  float* Ks = lds;                    // [TP][K_LD]
+  float* Vs = lds + TP * T64::K_LD;   // [TP][V_LD]
 
   const int unit = blockIdx.x;     // (b*J + j)*H + h
   const int h = unit % H;
   const int bj = unit / H;
   const int j = bj % J, b = bj / J;
-  const int D3 = 3 * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
   const size_t tok0 = (size_t)b * T * J + j;   // token(t) = tok0 + t*J
 
-  for (int idx = tid; idx < TP * 16; idx += 64 * NKT) {
-    const int row = idx >> 4, c4 = idx & 15;
-    float4 kk = make_float4(0, 0, 0, 0), vv = kk;
-    if (row < T) {
-      const float* p = qkv + (tok0 + (size_t)row * J) * D3 + h * TP_DH + c4 * 4;
-      kk = *reinterpret_cast<const float4*>(p + D);
-      vv = *reinterpret_cast<const float4*>(p + 2 * D);
-    }
-    *reinterpret_cast<float4*>(&Ks[row * K_LD + c4 * 4]) = kk;
-    *reinterpret_cast<float4*>(&Vs[row * V_LD + c4 * 4]) = vv;
-  }
-
-  // this lane's query row, pre-scaled by dh^-0.5 = 2^-3 (exact): lane half hh holds d in [32hh, 32hh+32)
+  f32_stage_rows<64, true>(qkv, Ks, Vs, tok0, J, D, h, 0, NKT, T, tid, 64 * NKT);
   const int tq = 32 * wave + r;
-  float qreg[32];
-  {
-    const float* qp = qkv + (tok0 + (size_t)(tq < T ? tq : 0) * J) * D3 + h * TP_DH + 32 * hh;
-#pragma unroll
-    for (int c = 0; c < 32; c += 4) {
-      float4 v = (tq < T) ? *reinterpret_cast<const float4*>(qp + c) : make_float4(0, 0, 0, 0);
-      qreg[c] = v.x * 0.125f; qreg[c + 1] = v.y * 0.125f; qreg[c + 2] = v.z * 0.125f; qreg[c + 3] = v.w * 0.125f;
-    }
-  }
+  float qreg[T64::QR];
+  f32_load_query<64>(qkv, qreg, tok0, J, D, h, tq, T, hh);
   __syncthreads();
 
-  // S^T tile kt: rows = keys kt*32 + (reg&3) + 8*(reg>>2) + 4*hh, column = query tq   (C/D map of the 32x32 MFMA)
-  f32x16 sacc[NKT];
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sacc[kt][q] = 0.f;
-    const float* kp = &Ks[(kt * 32 + r) * K_LD + 32 * hh];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const float4 k4 = *reinterpret_cast<const float4*>(kp + 4 * u);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.x, qreg[4 * u + 0], sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.y, qreg[4 * u + 1], sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.z, qreg[4 * u + 2], sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.w, qreg[4 * u + 3], sacc[kt], 0, 0, 0);
-    }
-  }
-
   // exact (max-subtracted, two-pass) softmax over the keys of this query column
+  f32x16 sacc[NKT];
   float m = -INFINITY;
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int key = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * hh;
-      if (key >= T) sacc[kt][q] = -INFINITY;
-      m = fmaxf(m, sacc[kt][q]);
-    }
+  for (int kt = 0; kt < NKT; ++kt) {
+    sacc[kt] = f32_score_tile<64>(Ks, qreg, kt, {kt, kt == NKT - 1, T}, r, hh);
+    m = f32_tile_max<64>(sacc[kt], {kt, kt == NKT - 1, T}, hh, m);
+  }
   m = fmaxf(m, __shfl_xor(m, 32, 64));
   float l = 0.f;
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float e = expf(sacc[kt][q] - m);
-      sacc[kt][q] = e;
-      l += e;
-    }
+  for (int kt = 0; kt < NKT; ++kt) {
+    f32_exp_tile<64>(sacc[kt], {kt, kt == NKT - 1, T}, hh, m);
+    f32_sum_tile(sacc[kt], l);
+    // one key tile per scheduling region, as in k_attn_temporal_f32_h32: expf's range selects live in SGPR pairs, and a scheduler free
+    // to batch the compares of several tiles runs out of them (SGPR spills at NKT = 5)
+    __builtin_amdgcn_sched_barrier(0);
+  }
   l += __shfl_xor(l, 32, 64);
 #pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int key = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * hh;
-      float pv = sacc[kt][q] / l;
-      if (key == tq) pv -= 1.0f;   // attn - I (S2S:82-83)
-      sacc[kt][q] = pv;
-    }
+  for (int kt = 0; kt < NKT; ++kt) {
+    f32_normalise_tile(sacc[kt], l);
+    f32_sub_diag_tile(sacc[kt], kt, tq, hh);
+  }
 
-  // O^T[d][query] = sum_key V[key][d] * P^T[key][query]; B operand = the accumulator registers as they stand
-  f32x16 oacc[2];
+  f32x16 oacc[T64::NDT];
+  f32_zero_acc<64>(oacc);
 #pragma unroll
-  for (int q = 0; q < 16; ++q) { oacc[0][q] = 0.f; oacc[1][q] = 0.f; }
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int key = kt * 32 + (q & 3) + 8 * (q >> 2) + 4 * hh;
-      const float v0 = Vs[key * V_LD + r];
-      const float v1 = Vs[key * V_LD + 32 + r];
-      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, sacc[kt][q], oacc[0], 0, 0, 0);
-      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, sacc[kt][q], oacc[1], 0, 0, 0);
-    }
+  for (int kt = 0; kt < NKT; ++kt) f32_pv_tile<64>(Vs, sacc[kt], oacc, kt, r, hh);
 
   if (tq < T) {
-    const size_t oo = (tok0 + (size_t)tq * J) * D + h * TP_DH;
+    const size_t tok = tok0 + (size_t)tq * J;
+    if (out_x3) {   // pair layout: oo % 32 == 0, the 32-column tile dt is one 128-byte line
+      const size_t oo = tok * D + h * 64;
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+      for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const size_t o = oo + dt * 32 + 8 * g4 + 4 * hh;
-        if (out_x3)   // pair layout: oo % 32 == 0, the 32-column tile dt is one 128-byte line
+        for (int g4 = 0; g4 < 4; ++g4)
           store4_x3(out_x3 + 2 * oo + dt * 64 + 8 * g4 + 4 * hh, out_x3 + 2 * oo + dt * 64 + 8 * g4 + 4 * hh + PAIR_LO,
                     oacc[dt][4 * g4], oacc[dt][4 * g4 + 1], oacc[dt][4 * g4 + 2], oacc[dt][4 * g4 + 3], rw);
-        else
-          *reinterpret_cast<float4*>(out + o) =
-              make_float4(oacc[dt][4 * g4], oacc[dt][4 * g4 + 1], oacc[dt][4 * g4 + 2], oacc[dt][4 * g4 + 3]);
-      }
+    } else {
+      f32_store_query<64>(qkv, out, oacc, l, tok, D, h, hh, false);
+    }
   }
 }
 
-bool attn_temporal_fast_ok(int T, int D, int H) { return T >= 1 && T <= 256 && H > 0 && D == H * TP_DH; }
-
-template <int NKT>
-static hipError_t launch_temporal_nkt(const float* qkv, float* out, void* out_x3, int B, int T, int J, int D, int H,
-                                      hipStream_t s) {
-  const size_t lds_bytes = (size_t)32 * NKT * (K_LD + V_LD) * sizeof(float);
-  const long long grid = (long long)B * J * H;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  return launch_lds<k_attn_temporal_f32<NKT>>(dim3((unsigned)grid), dim3(64 * NKT), lds_bytes, s, qkv, out, (_Float16*)out_x3, T, J, H, D,
-                                              launch_range_word());
-}
+bool attn_temporal_fast_ok(int T, int D, int H) { return T >= 1 && T <= 256 && H > 0 && D == H * 64; }
 
 hipError_t launch_attn_temporal_f32(const float* qkv, float* out, void* out_x3, int B, int T, int J, int D, int H,
                                     hipStream_t s) {
   if (!attn_temporal_fast_ok(T, D, H)) return hipErrorInvalidValue;
-  switch ((T + 31) / 32) {
-    case 1: return launch_temporal_nkt<1>(qkv, out, out_x3, B, T, J, D, H, s);
-    case 2: return launch_temporal_nkt<2>(qkv, out, out_x3, B, T, J, D, H, s);
-    case 3: return launch_temporal_nkt<3>(qkv, out, out_x3, B, T, J, D, H, s);
-    case 4: return launch_temporal_nkt<4>(qkv, out, out_x3, B, T, J, D, H, s);
-    case 5: return launch_temporal_nkt<5>(qkv, out, out_x3, B, T, J, D, H, s);
-    case 6: return launch_temporal_nkt<6>(qkv, out, out_x3, B, T, J, D, H, s);
-    case 7: return launch_temporal_nkt<7>(qkv, out, out_x3, B, T, J, D, H, s);
-    default: return launch_temporal_nkt<8>(qkv, out, out_x3, B, T, J, D, H, s);
-  }
+  const long long grid = (long long)B * J * H;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  return f32_resident_ladder<8>(T, [&](auto nkt) {
+    constexpr int NKT = decltype(nkt)::value;
+    return launch_lds<k_attn_temporal_f32<NKT>>(dim3((unsigned)grid), dim3(64 * NKT), T64::lds_bytes(NKT), s, qkv, out, (_Float16*)out_x3, T,
+                                                J, H, D, launch_range_word());
+  });
 }
 
 // =============================================================================================== generic (any N, dh)

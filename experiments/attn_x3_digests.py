@@ -3,8 +3,8 @@ the file's path live there), with the ROCm version and the commit of the library
 
     python experiments/attn_x3_digests.py [--cases MODULE] [--out FILE] [--commit REV]
 
---cases: test_gpu_attn_x3_digests (the default; tests/golden/attn_x3_digests.json) or test_gpu_attn_x3_width_digests
-(tests/golden/attn_x3_width_digests.json).
+--cases: test_gpu_attn_x3_digests (the default; tests/golden/attn_x3_digests.json), test_gpu_attn_x3_width_digests
+(tests/golden/attn_x3_width_digests.json) or test_gpu_attn_f32_digests (tests/golden/attn_f32_digests.json).
 
 Run it on the MI355X with the library of the commit whose bits are to be pinned -- the commit BEFORE a change to the shared attention
 pieces, never the change itself.  --commit names that revision where the tree is not a git checkout."""
@@ -23,7 +23,8 @@ import torch  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="test_gpu_attn_x3_digests", choices=["test_gpu_attn_x3_digests", "test_gpu_attn_x3_width_digests"])
+    ap.add_argument("--cases", default="test_gpu_attn_x3_digests",
+                    choices=["test_gpu_attn_x3_digests", "test_gpu_attn_x3_width_digests", "test_gpu_attn_f32_digests"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     args = ap.parse_args()

@@ -1,5 +1,5 @@
 """FP32 windows of more than 256 frames with heads of 32 columns on the MI355X ("long_temporal_f32_h32", kernels_attn_f32_h32_long.hip
-k_attn_temporal_f32l_h32): embed_dim 256 with the runner's 8 heads on an FP32 engine -- the exact mode, and the engine a precision-"auto"
+k_attn_f32_stream3<32>): embed_dim 256 with the runner's 8 heads on an FP32 engine -- the exact mode, and the engine a precision-"auto"
 model falls back to.  The keys of a unit stream through LDS in chunks of 256 frames, three passes (maximum, sum, normalised product), the
 arithmetic of k_attn_temporal_f32_h32 in the same order.
   * op level: bit for bit op_attention_f32_h32 wherever that runs (T <= 256: every wave count, an odd head count, sharp softmax);

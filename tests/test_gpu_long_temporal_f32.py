@@ -1,4 +1,4 @@
-"""FP32 windows of more than 256 frames on the MI355X ("long_temporal_f32", kernels_attn_f32_long.hip k_attn_temporal_f32l): the keys of a
+"""FP32 windows of more than 256 frames on the MI355X ("long_temporal_f32", kernels_attn_f32_long.hip k_attn_f32_stream3<64>): the keys of a
 unit stream through LDS in chunks of 256 frames, the queries are cut into balanced blocks of at most 8 waves, and the arithmetic is that of
 k_attn_temporal_f32 (v_mfma_f32_32x32x2_f32, softmax normalised before the second product) in the same order, in three passes.
   * op level: bit for bit the resident kernel wherever that runs (T <= 256: one chunk, one query block, every wave count);
