@@ -15,24 +15,28 @@
 
 constexpr float X3_C_EXP = 1.4426950408889634f / 64.0f;   // acc = 64 s: scale and log2(e) in one fma feeding v_exp_f32
 // The same constant for a head width DH.  The planes hold raw q and 8 k whatever the width, so acc = 8 q.k and the exponent argument is
-// acc log2(e) / (8 sqrt(DH)): X3_C_EXP itself at 64; at 32 (kernels_attn_x3_h32.hip) and at 128
-// (kernels_attn_x3_h128.hip) evaluated in double and rounded once.
+// acc log2(e) / (8 sqrt(DH)): X3_C_EXP itself at 64; at 32 (kernels_attn_x3_h32.hip), at 128 (kernels_attn_x3_h128.hip) and at 48
+// and 96 (kernels_attn_x3_hx.hip) evaluated in double and rounded once.
 template <int DH>
 constexpr float x3_c_exp() {
-  static_assert(DH == 64 || DH == 32 || DH == 128, "head widths with a tile form");
+  static_assert(DH == 64 || DH == 32 || DH == 128 || DH == 48 || DH == 96, "head widths with a tile form");
   return DH == 64 ? X3_C_EXP
-                  : DH == 32 ? (float)(1.4426950408889634 / (8.0 * 5.656854249492380195 /* sqrt(32) */))
-                             : (float)(1.4426950408889634 / (8.0 * 11.313708498984760390 /* sqrt(128) */));
+       : DH == 32 ? (float)(1.4426950408889634 / (8.0 * 5.656854249492380195 /* sqrt(32) */))
+       : DH == 48 ? (float)(1.4426950408889634 / (8.0 * 6.928203230275509174 /* sqrt(48) */))
+       : DH == 96 ? (float)(1.4426950408889634 / (8.0 * 9.797958971132712393 /* sqrt(96) */))
+                  : (float)(1.4426950408889634 / (8.0 * 11.313708498984760390 /* sqrt(128) */));
 }
 
 // ---- this lane's query row as MFMA B fragments, d = 16 ks + 8 h .. + 7: from the global planes (o: element offset of a real row's
 // head columns + 8 h; !valid: zeros instead) or from an LDS Q plane pair at a row.  A row >= T is never stored: its caller gives it
-// zeros or a real row.
+// zeros or a real row.  NKS: the d-steps that belong to the head where it ends inside the 64 columns (widths 48 and 96); the others
+// are exact zeros, never the neighbouring head's columns.
+template <int NKS = 4>
 __device__ __forceinline__ void x3_q_global(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, size_t o, bool valid, h8 (&qh)[4],
                                             h8 (&ql)[4]) {
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
-    if (valid) {
+    if (valid && ks < NKS) {
       qh[ks] = *reinterpret_cast<const h8*>(Ph + o + 16 * ks);
       ql[ks] = *reinterpret_cast<const h8*>(Pl + o + 16 * ks);
     } else {
@@ -73,11 +77,12 @@ __device__ __forceinline__ f32x16 x3_score_tile(const unsigned char* sKh, const 
 
 // The accumulate-into form: the same four d-steps added onto s, for heads wider than one 64-column LDS row (kernels_attn_x3_h128.hip: one
 // chain over the row halves in ascending d, each half's K rows in planes of their own).  x3_score_tile is left as it is, so its
-// instantiations' code does not change.
+// instantiations' code does not change.  NKS: the leading d-steps of the row that belong to the head (a 96-wide head's second row: two).
+template <int NKS = 4>
 __device__ __forceinline__ void x3_score_acc(f32x16& s, const unsigned char* sKh, const unsigned char* sKl, int row0, int r, int h,
                                              const h8 (&qh)[4], const h8 (&ql)[4]) {
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
+  for (int ks = 0; ks < NKS; ++ks) {
     const int ko = kswz(row0 + r, 2 * ks + h);
     const h8 kh = *reinterpret_cast<const h8*>(sKh + ko);
     const h8 kl = *reinterpret_cast<const h8*>(sKl + ko);
@@ -199,16 +204,27 @@ __device__ __forceinline__ void x3_pv_tile(const f32x16& e, const unsigned char*
 //              product and of the output
 //   DH = 64    one head, one segment, one stream
 //   DH = 128   one head in two segments: one score chain over segment 0 then segment 1, one stream, a PV step per segment
-// The MFMA order of every accumulator is the one of k_attn_x3_h32 / k_attn_temporal_x3 / k_attn_x3_h128.
+// Widths 48 and 96 are no multiple of 64 columns: a head starts at plane column hd DH, wherever that falls, and ends inside its last
+// LDS row (x3_stage_cols stages from a column offset; the rest of that row is zeros or not read):
+//   DH = 48    one head in one LDS row: three d-steps of the score product, two PV lines of which the second is half used (columns 48 .. 63
+//              of the K and V rows are exact zeros)
+//   DH = 96    one head in two LDS rows, 64 + 32 columns: the chain of DH = 128 with two d-steps and one PV line in the second row
+//              (its upper 32 columns are neither staged nor read)
+// The MFMA order of every accumulator is the one of k_attn_x3_h32 / k_attn_temporal_x3 / k_attn_x3_h128 / k_attn_x3_hx.
 template <int DH>
 struct x3_head_shape {
-  static_assert(DH == 32 || DH == 64 || DH == 128, "head widths with a tile form");
-  static constexpr int SUB = DH == 128 ? 2 : 1;
+  static_assert(DH == 32 || DH == 64 || DH == 128 || DH == 48 || DH == 96, "head widths with a tile form");
+  static constexpr int SUB = DH > 64 ? 2 : 1;
   static constexpr int STREAMS = DH == 32 ? 2 : 1;
+  static constexpr int COLS = DH == 32 ? 64 : DH;                  // plane columns of a unit
+  static constexpr bool ALIGNED = COLS % 64 == 0;                  // a unit is whole 64-column segments of the plane rows
   static constexpr bool heads_ok(int H) { return DH == 32 ? H >= 2 && H % 2 == 0 : H >= 1; }
   static constexpr int units_per_token(int H) { return DH == 32 ? H / 2 : H; }
   // the stream whose 1 / (2^13 l) scales 32-column line dt of a segment
   static constexpr int line_stream(int dt) { return DH == 32 ? dt : 0; }
+  // the columns of segment f that belong to the unit, and of them those of 32-column line dt
+  static constexpr int seg_cols(int f) { return COLS - 64 * f < 64 ? COLS - 64 * f : 64; }
+  static constexpr int line_cols(int f, int dt) { return seg_cols(f) - 32 * dt >= 32 ? 32 : seg_cols(f) - 32 * dt > 0 ? seg_cols(f) - 32 * dt : 0; }
 
   // the S^T tile(s) of the 32 staged K rows from row0 on, unmasked
   static __device__ __forceinline__ void scores(f32x16 (&s)[STREAMS], const unsigned char* sKh, const unsigned char* sKl, int pl, int row0, int r,
@@ -218,11 +234,13 @@ struct x3_head_shape {
       s[1] = x3_score_tile<2, 2>(sKh, sKl, row0, r, h, qh[0], ql[0]);
     } else if constexpr (DH == 64) {
       s[0] = x3_score_tile<>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+    } else if constexpr (DH == 48) {
+      s[0] = x3_score_tile<0, 3>(sKh, sKl, row0, r, h, qh[0], ql[0]);
     } else {
 #pragma unroll
       for (int q = 0; q < 16; ++q) s[0][q] = 0.f;
       x3_score_acc(s[0], sKh, sKl, row0, r, h, qh[0], ql[0]);
-      x3_score_acc(s[0], sKh + pl, sKl + pl, row0, r, h, qh[1], ql[1]);
+      x3_score_acc<DH == 96 ? 2 : 4>(s[0], sKh + pl, sKl + pl, row0, r, h, qh[1], ql[1]);
     }
   }
   // O^T += V^T E^T over staged key tile kt; oacc[f][dt]: 32-column line dt of segment f
@@ -231,8 +249,11 @@ struct x3_head_shape {
     if constexpr (DH == 32) {
       x3_pv_tile<false, 0, 1>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
       x3_pv_tile<false, 1, 1>(e[1], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
-    } else if constexpr (DH == 64) {
+    } else if constexpr (DH == 64 || DH == 48) {
       x3_pv_tile<false>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+    } else if constexpr (DH == 96) {
+      x3_pv_tile<false>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+      x3_pv_tile<false, 0, 1>(e[0], sVh + pl, sVl + pl, 0, kt, T, lane, h, oacc[1]);
     } else {
       x3_pv_tile<false>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
       x3_pv_tile<false>(e[0], sVh + pl, sVl + pl, 0, kt, T, lane, h, oacc[1]);
@@ -296,5 +317,67 @@ __device__ __forceinline__ void x3_stage_rows(const _Float16* __restrict__ Ph, c
         }
       }
     }
+  }
+}
+
+// ---- the same staging from a plane column: rows [row0, row0 + 32 nkt) of the K (and V) columns col0 .. col0 + 8 NCH - 1 into 16-byte
+// chunks 0 .. NCH - 1 of rows [0, 32 nkt) of the swizzled LDS planes, for heads that do not start on a 64-column boundary (widths 48 and
+// 96; col0 % 8 == 0, so every load is 16-byte aligned and ends inside the head).  WCH (4 or 8, >= NCH) chunks of a row are written:
+// those from NCH on as exact zeros -- never the neighbouring head's columns -- and those from WCH on not at all (nothing may read them).
+// Rows >= T as zeros.
+template <bool WITH_V, int NCH, int WCH>
+__device__ __forceinline__ void x3_stage_cols(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, unsigned char* sKh,
+                                              unsigned char* sKl, unsigned char* sVh, unsigned char* sVl, size_t tok0, int J, int D, int col0,
+                                              int row0, int nkt, int T, int tid, int nthr) {
+  static_assert((WCH == 4 || WCH == 8) && NCH >= 1 && NCH <= WCH, "whole chunks of a 128-byte row");
+  constexpr int NIT = 4;
+  const int slots = nkt * 32 * WCH;
+  const int D3 = 3 * D;
+  for (int base = 0; base < slots; base += NIT * nthr) {
+    uint4 kh[NIT], kl[NIT], vh[NIT], vl[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int idx = base + tid + it * nthr;
+      const int row = idx / WCH, c8 = idx % WCH;
+      kh[it] = make_uint4(0, 0, 0, 0); kl[it] = kh[it]; vh[it] = kh[it]; vl[it] = kh[it];
+      if (idx < slots && row0 + row < T && c8 < NCH) {
+        const size_t o = (tok0 + (size_t)(row0 + row) * J) * D3 + col0 + c8 * 8;
+        kh[it] = *reinterpret_cast<const uint4*>(Ph + o + D);
+        kl[it] = *reinterpret_cast<const uint4*>(Pl + o + D);
+        if (WITH_V) {
+          vh[it] = *reinterpret_cast<const uint4*>(Ph + o + 2 * D);
+          vl[it] = *reinterpret_cast<const uint4*>(Pl + o + 2 * D);
+        }
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int idx = base + tid + it * nthr;
+      const int row = idx / WCH, c8 = idx % WCH;
+      if (idx < slots) {
+        const int ko = kswz(row, c8), vo = vswz(row, c8);
+        *reinterpret_cast<uint4*>(sKh + ko) = kh[it];
+        *reinterpret_cast<uint4*>(sKl + ko) = kl[it];
+        if (WITH_V) {
+          *reinterpret_cast<uint4*>(sVh + vo) = vh[it];
+          *reinterpret_cast<uint4*>(sVl + vo) = vl[it];
+        }
+      }
+    }
+  }
+}
+
+// A unit's segment f through whichever staging its width takes: whole 64-column segments by index (x3_stage_rows), or from the unit's
+// first plane column col0 (x3_stage_cols: the head's columns of the segment, zeros up to the last chunk that is read).
+template <int DH, bool WITH_V, int F>
+__device__ __forceinline__ void x3_stage_segment(const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, unsigned char* sKh,
+                                                 unsigned char* sKl, unsigned char* sVh, unsigned char* sVl, size_t tok0, int J, int D, int col0,
+                                                 int row0, int nkt, int T, int tid, int nthr) {
+  using HS = x3_head_shape<DH>;
+  if constexpr (HS::ALIGNED) {
+    x3_stage_rows<WITH_V>(Ph, Pl, sKh, sKl, sVh, sVl, tok0, J, D, (col0 >> 6) + F, row0, nkt, T, tid, nthr);
+  } else {
+    constexpr int NCH = HS::seg_cols(F) / 8;
+    x3_stage_cols<WITH_V, NCH, (NCH <= 4 ? 4 : 8)>(Ph, Pl, sKh, sKl, sVh, sVl, tok0, J, D, col0 + 64 * F, row0, nkt, T, tid, nthr);
   }
 }

@@ -430,6 +430,17 @@ bool attn_x3_h128_ok(int N, int D, int H);
 // launch_attn_x3_h128 wherever that runs (T <= 128).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h128_long_ok(int T, int D, int H);
+// ---- kernels_attn_x3_hx.hip: the F16X3 attention for heads of 48 and 96 columns (D == 48 H or 96 H, any head count; the width is D / H),
+// groups of T <= 256 (width 48) / T <= 128 (width 96) tokens.  A head is DH adjacent plane columns from column hd DH on, not whole
+// 64-column segments.  The contract of launch_attn_temporal_x3: same planes in (raw q, 8 k, 8 v), same pair layout out, its rows
+// 2 ceil32(D) halves apart (2 D wherever D % 32 == 0, as in every engine); spatial blocks call it with (B T, J, 1).
+hipError_t launch_attn_x3_hx(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_hx_ok(int N, int D, int H);
+// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<48, 8> / <96, 4>: launch_attn_x3_hx's temporal attention for windows of any length:
+// chunks of 256 (width 48) / 128 (width 96) frames, the scores computed twice.  Same planes in, same pair layout out; bit-identical to
+// launch_attn_x3_hx wherever that runs.  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_x3_hx_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_hx_long_ok(int T, int D, int H);
 // ---- kernels_attn_f32_h128.hip: the exact fp32 attention (v_mfma_f32_32x32x2_f32) for heads of 128 columns (D == 128 H, any head
 // count), groups of N <= 128 tokens resident in LDS.  fp32 rows in, fp32 rows out, no pair-layout form (FP32 engines only); spatial blocks
 // call it with (B T, J, 1), so any joint count 1 .. 128 is served.  The scores are scaled by 1 / sqrt(128) after the sum over d, the

@@ -63,7 +63,7 @@ struct BlockPlan {
   // The attention kernel of the spatial / of the temporal blocks wherever the qkv GEMM and the attention are two launches: one value per
   // launch, listed with its shapes at launch_attention().  A BF16 plan runs launch_attn_bf16 and leaves both at GENERIC.
   enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, F32_H128, F32_H128_LONG,
-              X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG };
+              X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG, X3_HX, X3_HX_LONG };
   Attn attn_sp = GENERIC, attn_tp = GENERIC;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
@@ -159,6 +159,10 @@ struct d3d_engine {
   // one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical.  F16X3 / BF16 engines and every
   // other head width: no effect
   bool opt_attn_f32_h128 = true;
+  // "attn_hx" (on by default): an F16X3 engine whose heads are 48 or 96 columns wide (embed_dim 384 / 768 with 8 heads) runs the folded
+  // flow with its attention on kernels_attn_x3_hx.hip (groups of up to 256 / 128 tokens) and kernels_attn_x3_long.hip at that width
+  // (longer windows); 0 = the plain row-kernel flow with the generic fp32 attention, which FP32 engines of these widths run in any case
+  bool opt_attn_hx = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -430,6 +434,8 @@ int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal,
     case BlockPlan::X3_H32_LONG:  le = launch_attn_x3_h32_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 32 H, T > 256 (FOLD)
     case BlockPlan::X3_H128:      le = launch_attn_x3_h128(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                  // D == 128 H, groups <= 128 (FOLD)
     case BlockPlan::X3_H128_LONG: le = launch_attn_x3_h128_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;             // D == 128 H, T > 128 (FOLD)
+    case BlockPlan::X3_HX:        le = launch_attn_x3_hx(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                    // D == 48 H / 96 H, groups <= 256 / 128 (FOLD)
+    case BlockPlan::X3_HX_LONG:   le = launch_attn_x3_hx_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;               // D == 48 H / 96 H, longer windows (FOLD)
     case BlockPlan::F32_H128:     le = launch_attn_f32_h128(q, out, gB, gT, gJ, D, H, s); break;                         // D == 128 H, groups <= 128, FP32 engines
     case BlockPlan::F32_H128_LONG: le = launch_attn_f32_h128_long(q, out, gB, gT, gJ, D, H, s); break;                   // D == 128 H, T > 128, FP32 engines
   }
@@ -438,7 +444,7 @@ int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal,
 }
 
 // The "*_last" info keys of the attention plan, from the flow and the two kernel choices: which block types ran which kernel family
-// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last" and
+// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last", "attn_hx_last" and
 // "attn_f32_h128_last" bit 2 temporal streaming).  false = not one of the keys.
 bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* value) {
   const bool fold = p.flow == BlockPlan::FOLD, plain = p.flow == BlockPlan::PLAIN;
@@ -448,6 +454,8 @@ bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* valu
   else if (k == "long_temporal_h32_last") *value = fold && tp == BlockPlan::X3_H32_LONG;
   else if (k == "attn_h128_last")
     *value = fold ? (sp == BlockPlan::X3_H128 ? 1 : 0) | (tp == BlockPlan::X3_H128 ? 2 : 0) | (tp == BlockPlan::X3_H128_LONG ? 4 : 0) : 0;
+  else if (k == "attn_hx_last")
+    *value = fold ? (sp == BlockPlan::X3_HX ? 1 : 0) | (tp == BlockPlan::X3_HX ? 2 : 0) | (tp == BlockPlan::X3_HX_LONG ? 4 : 0) : 0;
   else if (k == "long_temporal_f32_last") *value = plain && tp == BlockPlan::F32_LONG;
   else if (k == "attn_f32_h32_last") *value = plain ? (sp == BlockPlan::F32_H32 ? 1 : 0) | (tp == BlockPlan::F32_H32 ? 2 : 0) : 0;
   else if (k == "long_temporal_f32_h32_last") *value = plain && tp == BlockPlan::F32_H32_LONG;
@@ -472,13 +480,16 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   const bool h32_long = e->opt_long_temporal_h32 && T > 256 && attn_x3_h32_long_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
   // heads of 128 columns: the spatial blocks need their groups resident (J <= 128); the temporal blocks stream beyond 128 frames (as at 32)
   const bool h128 = e->opt_attn_h128 && attn_x3_h128_ok(J, D, H) && (attn_x3_h128_ok(T, D, H) || attn_x3_h128_long_ok(T, D, H));
-  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long || h128) && D % 32 == 0 &&
+  // heads of 48 or 96 columns: the same pattern, the resident limit being the width's own (256 / 128 tokens)
+  const bool hx = e->opt_attn_hx && attn_x3_hx_ok(J, D, H) && (attn_x3_hx_ok(T, D, H) || attn_x3_hx_long_ok(T, D, H));
+  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long || h128 || hx) && D % 32 == 0 &&
       e->opt_fold_layernorm) {
     p.flow = BlockPlan::FOLD;
-    // (the predicates of the three widths exclude each other: D == 32 H, 128 H, 64 H)
-    p.attn_sp = h32 || h32_long ? BlockPlan::X3_H32 : h128 ? BlockPlan::X3_H128 : BlockPlan::X3;
+    // (the predicates of the widths exclude each other: D == 32 H, 128 H, 48 H or 96 H, 64 H)
+    p.attn_sp = h32 || h32_long ? BlockPlan::X3_H32 : h128 ? BlockPlan::X3_H128 : hx ? BlockPlan::X3_HX : BlockPlan::X3;
     p.attn_tp = h32 ? BlockPlan::X3_H32 : h32_long ? BlockPlan::X3_H32_LONG
               : h128 ? (attn_x3_h128_ok(T, D, H) ? BlockPlan::X3_H128 : BlockPlan::X3_H128_LONG)
+              : hx ? (attn_x3_hx_ok(T, D, H) ? BlockPlan::X3_HX : BlockPlan::X3_HX_LONG)
               : tp_long ? BlockPlan::X3_LONG : BlockPlan::X3;   // (qkv_tattn_ok refuses T > 255: the long kernel is always the two-kernel branch)
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
@@ -1036,7 +1047,9 @@ const char* d3d_last_error(void) { return g_err.c_str(); }
 // 142: head_dim 128 admitted (FP32 and F16X3), option / info key "attn_h128", info key "attn_h128_last", d3d_op_attention_h128,
 // d3d_op_attention_long_h128
 // 143: option / info key "attn_f32_h128", info key "attn_f32_h128_last", d3d_op_attention_f32_h128, d3d_op_attention_long_f32_h128
-int d3d_version(void) { return 144; }
+// 145: head_dim 48 and 96 admitted (FP32 and F16X3), option / info key "attn_hx", info key "attn_hx_last", d3d_op_attention_hx,
+// d3d_op_attention_long_hx
+int d3d_version(void) { return 145; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1066,13 +1079,16 @@ int d3d_engine_create(const d3d_config* c, d3d_engine** out) {
       c->num_heads < 1 || c->mlp_hidden < 1)
     return fail(D3D_EINVAL, "d3d_config: non-positive dimension");
   if (c->embed_dim % c->num_heads) return fail(D3D_EINVAL, "embed_dim must be divisible by num_heads");
-  if (c->embed_dim % 32 || c->mlp_hidden % 32)
-    return fail(D3D_EUNSUP, "embed_dim and mlp_hidden must be multiples of 32 (MFMA k-tile)");
+  // embed_dim 48 h with h odd (heads of 48 columns) is a multiple of 16 alone: the fp32 GEMM zero-fills its last k-tile of 16, the fp16
+  // plane forms (pair layout: groups of 32 columns) do not exist there -- such an engine runs the FP32 kernels (below)
+  const bool half_tile = c->embed_dim % 32 == 16 && c->embed_dim == 48 * c->num_heads;
+  if ((c->embed_dim % 32 && !half_tile) || c->mlp_hidden % 32)
+    return fail(D3D_EUNSUP, "embed_dim and mlp_hidden must be multiples of 32 (MFMA k-tile; embed_dim: or 16 more with head_dim 48)");
   if (c->embed_dim > 1024) return fail(D3D_EUNSUP, "embed_dim > 1024 unsupported by the row kernels");
   {
     const int dh = c->embed_dim / c->num_heads;
-    if (dh != 4 && dh != 8 && dh != 16 && dh != 32 && dh != 64 && dh != 128)
-      return fail(D3D_EUNSUP, "head_dim must be 4,8,16,32,64 or 128");
+    if (dh != 4 && dh != 8 && dh != 16 && dh != 32 && dh != 48 && dh != 64 && dh != 96 && dh != 128)
+      return fail(D3D_EUNSUP, "head_dim must be 4,8,16,32,48,64,96 or 128");
   }
   if (c->precision != D3D_PREC_FP32 && c->precision != D3D_PREC_F16X3 && c->precision != D3D_PREC_BF16)
     return fail(D3D_EUNSUP, "precision must be D3D_PREC_FP32, D3D_PREC_F16X3 or D3D_PREC_BF16");
@@ -1082,6 +1098,7 @@ int d3d_engine_create(const d3d_config* c, d3d_engine** out) {
     return fail(D3D_EUNSUP, "D3D_PREC_BF16 needs head_dim 64, num_frame <= 256, num_joints <= 32 and widths that are multiples of 64");
   d3d_engine* e = new d3d_engine();
   e->cfg = *c;
+  if (half_tile) e->cfg.precision = D3D_PREC_FP32;   // F16X3 asked for: every kernel of the engine is the exact FP32 one
   e->T = c->num_frame; e->J = c->num_joints; e->D = c->embed_dim; e->H = c->num_heads; e->Dm = c->mlp_hidden;
   e->Dt = c->with_time_emb ? 2 * c->embed_dim : 0;
   e->depth = c->depth; e->nblk = 2 * c->depth; e->cin = c->in_chans + 3;
@@ -1532,6 +1549,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "long_temporal_f32_h32") e->opt_long_temporal_f32_h32 = value != 0;
   else if (k == "attn_h128") e->opt_attn_h128 = value != 0;
   else if (k == "attn_f32_h128") e->opt_attn_f32_h128 = value != 0;
+  else if (k == "attn_hx") e->opt_attn_hx = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1608,6 +1626,7 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "long_temporal_f32_h32") *value = e->opt_long_temporal_f32_h32 ? 1 : 0;
   else if (k == "attn_h128") *value = e->opt_attn_h128 ? 1 : 0;
   else if (k == "attn_f32_h128") *value = e->opt_attn_f32_h128 ? 1 : 0;
+  else if (k == "attn_hx") *value = e->opt_attn_hx ? 1 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

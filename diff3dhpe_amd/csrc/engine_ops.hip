@@ -122,6 +122,26 @@ int attention_x3_round_trip(const float* qkv, float* out, size_t rows, int D, hi
   return finish(le, s);
 }
 
+// The round trip of the width-48 / 96 kernels.  Their pair-layout rows are 2 ceil32(D) halves apart: where D is no multiple of 32 (an odd
+// head count at width 48 -- no engine, only these ops) the rows are unpacked at that pitch and their first D columns copied out.
+template <class Launch>
+int attention_hx_round_trip(const float* qkv, float* out, size_t rows, int D, hipStream_t s, Launch launch) {
+  if (D % 32 == 0) return attention_x3_round_trip(qkv, out, rows, D, s, launch);
+  const int Dp = (D + 31) & ~31;
+  const size_t nq = rows * 3 * D, np = rows * Dp;
+  DevBuf<uint16_t> tmp;
+  DevBuf<float> wide;
+  HIP_TRY(tmp.alloc(2 * nq + 2 * np));
+  HIP_TRY(wide.alloc(np));
+  hipError_t le = hipMemsetAsync(tmp.p + 2 * nq, 0, 2 * np * sizeof(uint16_t), s);   // the columns behind D are read back, not written
+  if (le == hipSuccess) le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
+  if (le == hipSuccess) le = launch(tmp.p, tmp.p + nq, tmp.p + 2 * nq);
+  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, wide.p, rows, Dp, s);
+  if (le == hipSuccess)
+    le = hipMemcpy2DAsync(out, (size_t)D * sizeof(float), wide.p, (size_t)Dp * sizeof(float), (size_t)D * sizeof(float), rows, hipMemcpyDeviceToDevice, s);
+  return finish(le, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -141,7 +161,8 @@ int d3d_op_linear_bench(const float* A, const float* W, const float* bias, const
                         int32_t K, int32_t epi, int32_t precision, int32_t variant, int32_t reps, float* avg_ms, void* stream) {
   if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16) return fail(D3D_EUNSUP, "precision not implemented");
   if (!A || !W || !C || reps < 1) return fail(D3D_EINVAL, "bad argument");
-  if (K % 32) return fail(D3D_EUNSUP, "K must be a multiple of 32");
+  if (K % 32 && !(precision == D3D_PREC_FP32 && K % 16 == 0))
+    return fail(D3D_EUNSUP, "K must be a multiple of 32 (D3D_PREC_FP32: of 16, a last k-tile of 16 columns is zero-filled)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (precision == D3D_PREC_BF16) {
     // the bf16 operand mode: operands rounded to bf16 on the device (rows padded to 256, zero), the product through launch_linear_bf16;
@@ -544,6 +565,26 @@ int d3d_op_attention_long_h128(const float* qkv, float* out, int32_t B, int32_t 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
     return launch_attn_x3_h128_long(hi, lo, o, B, T, J, D, H, s);
+  });
+}
+
+int d3d_op_attention_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                        void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_x3_hx_ok(temporal ? T : J, D, H))
+    return fail(D3D_EUNSUP, "F16X3 attention for head_dim 48 or 96: groups of up to 256 (head_dim 48) / 128 (head_dim 96) tokens");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return attention_hx_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return temporal ? launch_attn_x3_hx(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_hx(hi, lo, o, B * T, J, 1, D, H, s);
+  });
+}
+
+int d3d_op_attention_long_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_x3_hx_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 48 or 96");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return attention_hx_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return launch_attn_x3_hx_long(hi, lo, o, B, T, J, D, H, s);
   });
 }
 

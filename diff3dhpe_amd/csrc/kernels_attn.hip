@@ -353,6 +353,7 @@ hipError_t launch_attn_generic(const float* qkv, float* out, void* out_x3, int B
   switch (dh) {
     D3D_GEN(4) D3D_GEN(8) D3D_GEN(16) D3D_GEN(32) D3D_GEN(64)
     D3D_GEN(128)   // q and o rows of 128 floats per thread: 256 of its registers (DESIGN.md section 4.2 has the count)
+    D3D_GEN(48) D3D_GEN(96)   // embed_dim 384 / 768 with 8 heads: what FP32 engines of these widths and "attn_hx" = 0 run
     default: return hipErrorInvalidValue;
   }
 #undef D3D_GEN

@@ -1,4 +1,4 @@
-// Temporal GRAND attention on the fp16 matrix pipe for windows of ANY length, at head widths 64, 32 and 128: the keys stream through
+// Temporal GRAND attention on the fp16 matrix pipe for windows of ANY length, at head widths 64, 32, 128, 48 and 96: the keys stream through
 // LDS in chunks of 32 KC frames instead of all living there (kernels_attn_x3.hip, kernels_attn_x3_h32.hip, kernels_attn_x3_h128.hip: four
 // planes of resident rows = 128 of the 160 KiB).  One kernel template, k_attn_x3_stream<DH, KC>; what differs by width is
 // x3_head_shape<DH> (attn_x3_tile.h): the 64-column segments of a unit, its softmax streams, its score tile(s) and PV step(s).
@@ -9,6 +9,10 @@
 //              are independent, so interleaving them per key tile leaves each one's MFMA and addition order as k_attn_x3_h32 has it
 //   DH = 128   a unit is a head of two 64-column halves; every plane is two sub-planes of 32 KC rows, half 0 then half 1, chunks of
 //              128 frames (KC = 4: 4 planes x 128 rows x 256 B = 128 KiB).  One score chain over the eight d-steps, four 32-column quarters of PV
+//   DH = 48    a unit is a head of 48 plane columns from column 48 hd on -- not a whole 64-column segment: staged from that column, the rest
+//              of its 128-byte row zeros; chunks of 256 frames (the walk of DH = 64), three d-steps, two PV lines, 48 output columns
+//   DH = 96    a unit is a head of 96 plane columns from column 96 hd on, in two LDS rows of 64 + 32 columns (the upper half of the second
+//              neither staged nor read); chunks of 128 frames (the walk of DH = 128), six d-steps, three PV lines
 //
 // The arithmetic is attn_x3_tile.h's, the pieces the resident kernels are built from: the exact two-pass softmax, not an online rescaling.
 //
@@ -19,7 +23,8 @@
 //
 // So every exp2 sees the same m, l is summed in the same order and every accumulator takes the same MFMAs in the same order as in the
 // resident kernel of its width: for T <= 256 (DH = 128: T <= 128) the output is bit-identical to launch_attn_temporal_x3 /
-// launch_attn_x3_h32 / launch_attn_x3_h128 whatever KC is (tests/test_gpu_long_temporal.py, test_gpu_long_h32.py, test_gpu_long_h128.py);
+// launch_attn_x3_h32 / launch_attn_x3_h128 / launch_attn_x3_hx whatever KC is (tests/test_gpu_long_temporal.py, test_gpu_long_h32.py,
+// test_gpu_long_h128.py, test_gpu_attn_hx.py);
 // beyond, tests/test_gpu_attn_x3_digests.py and test_gpu_attn_x3_width_digests.py pin the bits.  The price is the scores computed twice;
 // one score tile per stream (16 registers) is live at a time.
 //
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(512) void k_attn_x3_stream(const _Float16* __restri
   const int unit_raw = (int)(blockIdx.x / (unsigned)nqb), qb = (int)(blockIdx.x % (unsigned)nqb);
   const bool unit_ok = unit_raw < units;
   const int unit = unit_ok ? unit_raw : units - 1;    // surplus workgroups redo the last unit and store nothing
-  const int seg0 = (unit % UPT) * SUB;                // (b*J + j)*UPT + u, UPT units per token; the unit's first 64-column segment
+  const int col0 = (unit % UPT) * HS::COLS;           // (b*J + j)*UPT + u, UPT units per token; the unit's first plane column
   const int bj = unit / UPT;
   const int j = bj % J, b = bj / J;
   const int D3 = 3 * D;
@@ -76,15 +81,17 @@ __global__ __launch_bounds__(512) void k_attn_x3_stream(const _Float16* __restri
   const int tq = qb * (nthr >> 1) + 32 * wave + r;    // (a query block is blockDim / 2 queries)
   h8 qh[SUB][4], ql[SUB][4];
 #pragma unroll
-  for (int f = 0; f < SUB; ++f)
-    x3_q_global(Ph, Pl, (tok0 + (size_t)(tq < T ? tq : 0) * J) * D3 + (seg0 + f) * 64 + 8 * h, tq < T, qh[f], ql[f]);
+  for (int f = 0; f < SUB; ++f) {
+    const size_t qo = (tok0 + (size_t)(tq < T ? tq : 0) * J) * D3 + col0 + 64 * f + 8 * h;
+    if (f == 0) x3_q_global<(HS::seg_cols(0) / 16)>(Ph, Pl, qo, tq < T, qh[f], ql[f]);
+    else x3_q_global<(HS::seg_cols(SUB - 1) / 16)>(Ph, Pl, qo, tq < T, qh[f], ql[f]);
+  }
 
   // the chunk's K (and V) rows, every segment into its sub-planes
   auto stage = [&](auto with_v, int c, int nkt) {
-#pragma unroll
-    for (int f = 0; f < SUB; ++f)
-      x3_stage_rows<decltype(with_v)::value>(Ph, Pl, sKh + f * PL, sKl + f * PL, sVh + f * PL, sVl + f * PL, tok0, J, D, seg0 + f, c * CH, nkt,
-                                             T, tid, nthr);
+    constexpr bool V = decltype(with_v)::value;
+    x3_stage_segment<DH, V, 0>(Ph, Pl, sKh, sKl, sVh, sVl, tok0, J, D, col0, c * CH, nkt, T, tid, nthr);
+    if constexpr (SUB == 2) x3_stage_segment<DH, V, 1>(Ph, Pl, sKh + PL, sKl + PL, sVh + PL, sVl + PL, tok0, J, D, col0, c * CH, nkt, T, tid, nthr);
   };
   // S^T tile(s) kt of the staged chunk, keys >= T at -inf.  Only the unit's last key tile (gt == ntiles - 1) can hold such keys.
   // (Returned by value: with the tiles filled through a reference the compiler keeps more addresses live across the staging loops --
@@ -151,21 +158,26 @@ __global__ __launch_bounds__(512) void k_attn_x3_stream(const _Float16* __restri
   if (tq < T && unit_ok) {
     float amax = 0.0f;   // range guard
     const size_t tokq = tok0 + (size_t)tq * J;
+    // pair layout: the 32 columns of a pair group are one 128-byte line.  A unit of whole segments writes whole lines; at widths 48 and 96
+    // a line of the head can straddle two groups at a 16-column boundary, so every 4-column chunk takes pair_col of its own plane column
+    // (out rows of 2 ceil32(D) halves: the row pitch of the layout, 2 D wherever an engine runs)
+    const size_t orow = tokq * (HS::ALIGNED ? 2 * D : 2 * ((D + 31) & ~31));
 #pragma unroll
     for (int f = 0; f < SUB; ++f) {
-      const size_t vo = tokq * D3 + 2 * D + (seg0 + f) * 64;
-      const size_t oo = tokq * 2 * D + (seg0 + f) * 128;   // pair layout: a segment's 64 columns are two 128-byte lines
+      const int c0 = col0 + 64 * f;
+      const size_t vo = tokq * D3 + 2 * D + c0;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         const float inv = 1.0f / (8192.0f * l[HS::line_stream(dt)]);
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
+        for (int g4 = 0; g4 < HS::line_cols(f, dt) / 8; ++g4) {
           const int d = dt * 32 + 8 * g4 + 4 * h;
           h4 oh, ol;
           x3_out_chunk(oacc[f][dt], g4, inv, *reinterpret_cast<const h4*>(Ph + vo + d),
                        *reinterpret_cast<const h4*>(Pl + vo + d), amax, oh, ol);
-          *reinterpret_cast<h4*>(out_x3 + oo + pair_col(d)) = oh;
-          *reinterpret_cast<h4*>(out_x3 + oo + pair_col(d) + PAIR_LO) = ol;
+          _Float16* const op = out_x3 + orow + (HS::ALIGNED ? (size_t)(2 * c0) + pair_col(d) : pair_col(c0 + d));
+          *reinterpret_cast<h4*>(op) = oh;
+          *reinterpret_cast<h4*>(op + PAIR_LO) = ol;
         }
       }
     }
@@ -197,6 +209,7 @@ static hipError_t launch_attn_x3_stream(const void* qkv_hi, const void* qkv_lo, 
 bool attn_temporal_x3_long_ok(int T, int D, int H) { return attn_x3_stream_ok<64>(T, D, H); }
 bool attn_x3_h32_long_ok(int T, int D, int H) { return attn_x3_stream_ok<32>(T, D, H); }
 bool attn_x3_h128_long_ok(int T, int D, int H) { return attn_x3_stream_ok<128>(T, D, H); }
+bool attn_x3_hx_long_ok(int T, int D, int H) { return attn_x3_stream_ok<48>(T, D, H) || attn_x3_stream_ok<96>(T, D, H); }
 
 hipError_t launch_attn_temporal_x3_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                         hipStream_t s) {
@@ -207,6 +220,11 @@ hipError_t launch_attn_x3_h32_long(const void* qkv_hi, const void* qkv_lo, void*
 }
 hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s) {
   return launch_attn_x3_stream<128, 4>(qkv_hi, qkv_lo, out_x3, B, T, J, D, H, s);
+}
+// widths 48 and 96 (the width is D / H): the walks of <64, 8> and <128, 4>
+hipError_t launch_attn_x3_hx_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s) {
+  if (H > 0 && D == 48 * H) return launch_attn_x3_stream<48, 8>(qkv_hi, qkv_lo, out_x3, B, T, J, D, H, s);
+  return launch_attn_x3_stream<96, 4>(qkv_hi, qkv_lo, out_x3, B, T, J, D, H, s);
 }
 
 }  // namespace d3d

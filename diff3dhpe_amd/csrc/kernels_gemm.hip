@@ -82,13 +82,16 @@ __global__ __launch_bounds__(256, 2) void k_linear_f32(const float* __restrict__
   float4 ra[4], rb[4];
   const int srow = tid >> 3, sc4 = tid & 7;
 
+  // (K % 16 == 0: a float4 lies inside its row or behind it; the columns behind K of a last k-tile of 16 are zeros in both operands,
+  // which add exact zeros to every accumulator)
   auto gload = [&](int k0) {
+    const bool kin = k0 + sc4 * 4 < K;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int row = srow + 32 * p;
       const int gm = m0 + row, gn = n0 + row;
-      ra[p] = (gm < M) ? *reinterpret_cast<const float4*>(A + (size_t)gm * K + k0 + sc4 * 4) : make_float4(0, 0, 0, 0);
-      rb[p] = (gn < N) ? *reinterpret_cast<const float4*>(W + (size_t)gn * K + k0 + sc4 * 4) : make_float4(0, 0, 0, 0);
+      ra[p] = (gm < M && kin) ? *reinterpret_cast<const float4*>(A + (size_t)gm * K + k0 + sc4 * 4) : make_float4(0, 0, 0, 0);
+      rb[p] = (gn < N && kin) ? *reinterpret_cast<const float4*>(W + (size_t)gn * K + k0 + sc4 * 4) : make_float4(0, 0, 0, 0);
     }
   };
   auto lstore = [&]() {
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_f32(const float* __restrict__
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.0f;
 
-  const int nk = K / BK;
+  const int nk = (K + BK - 1) / BK;
   gload(0);
   const float* a_base = &As[(wm * 64 + r) * LDS_LD + 16 * h];
   const float* b_base = &Bs[(wn * 64 + r) * LDS_LD + 16 * h];
@@ -144,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_f32(const float* __restrict__
 
 hipError_t launch_linear_f32(const float* A, const float* W, const float* bias, const float* R, float* C, int M, int N,
                              int K, int epi, hipStream_t s) {
-  if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0) return hipErrorInvalidValue;
+  if (M <= 0 || N <= 0 || K <= 0 || (K % (BK / 2)) != 0) return hipErrorInvalidValue;   // whole k-tiles of 32, or a last one of 16
   if (epi == EPI_RESIDUAL && R == nullptr) return hipErrorInvalidValue;
   const int mtiles = (M + BM - 1) / BM, ntiles = (N + BN - 1) / BN;
   const int grid = ((mtiles + 7) / 8) * 8 * ntiles;

@@ -83,8 +83,12 @@ const char* d3d_last_error(void);
 int d3d_version(void);
 
 /* ---- construction: replaces HPE_model(name)(**kw) + GaussianDiffusion(model=...) (RUN:176-189) ------------------- */
-/* Head widths embed_dim / num_heads of 4, 8, 16, 32, 64 and 128 (D3D_PREC_BF16: 64 alone), embed_dim <= 1024; anything else:
- * D3D_EUNSUP.  Width 128 (embed_dim 1024 with the runner's 8 heads) runs the fp16-MFMA attention kernels of that width on a
+/* Head widths embed_dim / num_heads of 4, 8, 16, 32, 48, 64, 96 and 128 (D3D_PREC_BF16: 64 alone), embed_dim a multiple of 32 and
+ * <= 1024; anything else: D3D_EUNSUP.  One exception to the multiple of 32: an odd number of heads of 48 columns (embed_dim 48, 144, ...:
+ * a multiple of 16).  The fp16 plane forms of the GEMMs do not exist there (32-deep k-tiles, activations in groups of 32 columns), so
+ * such an engine runs the FP32 kernels whether D3D_PREC_FP32 or D3D_PREC_F16X3 was asked for -- the exact arithmetic, the fp32 GEMM
+ * zero-filling its last k-tile of 16 columns -- and D3D_PREC_BF16 refuses it.  Widths 48 and 96 (embed_dim 384 / 768 with the runner's 8 heads) run the fp16-MFMA attention
+ * kernels of those widths on a D3D_PREC_F16X3 engine (option "attn_hx") and the generic fp32 attention kernel on a D3D_PREC_FP32 engine.  Width 128 (embed_dim 1024 with the runner's 8 heads) runs the fp16-MFMA attention kernels of that width on a
  * D3D_PREC_F16X3 engine (option "attn_h128") and the exact fp32 MFMA attention kernels of that width on a D3D_PREC_FP32 engine
  * (option "attn_f32_h128"). */
 int d3d_engine_create(const d3d_config* cfg, d3d_engine** out);
@@ -294,6 +298,18 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     2610 -> 1377 ms at B = 16.  Every other head
  *                     width, F16X3 and BF16 engines: no effect.  d3d_workspace_bytes does not change.  "attn_f32_h128_last"
  *                     (d3d_engine_get_info) reports what the latest forward ran.
+ *   "attn_hx"    1 (default) / 0: F16X3 engines whose heads are 48 or 96 columns wide (embed_dim == 48 num_heads or 96 num_heads, e.g.
+ *                     384 or 768 with 8 heads) and num_joints <= 256 / 128.  With the key on, such an engine runs the folded flow with
+ *                     the two-kernel attention branch: its spatial blocks and, for num_frame <= 256 (width 48) / 128 (width 96), its
+ *                     temporal blocks on the resident fp16-MFMA kernel of these widths (a head is 48 or 96 adjacent columns of the
+ *                     plane rows from column 48 h / 96 h on, not whole 64-column segments; the columns behind the head in its last LDS
+ *                     row are zeros or not read, never the neighbouring head's), its temporal blocks for longer windows on the
+ *                     key-streaming kernel of that width (chunks of 256 / 128 frames, the scores computed twice: the exact two-pass
+ *                     softmax, bit-identical to the resident kernel wherever that runs) / 0: the plain row-kernel flow with the generic
+ *                     fp32 attention kernel in every block, which is also what a D3D_PREC_FP32 engine of these widths runs.  The two
+ *                     differ in the last bits, both inside the parity gate.  Measured: DESIGN.md section 5.  Every other head width,
+ *                     FP32 and BF16 engines (BF16: refused at these widths): no effect.  d3d_workspace_bytes does not change.
+ *                     "attn_hx_last" (d3d_engine_get_info) reports what the latest forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -366,6 +382,8 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * the key-streaming kernel of that width; 0 before any forward, with the option off, at every other head width and in the other
  * precisions), "attn_f32_h128" (the option value), "attn_f32_h128_last" (the same three bits for a D3D_PREC_FP32 engine and the exact
  * fp32 kernels for heads of 128 columns; 0 before any forward, with the option off, at every other head width and in the other
+ * precisions), "attn_hx" (the option value), "attn_hx_last" (the same three bits for a D3D_PREC_F16X3 engine with heads of 48 or 96
+ * columns and the F16X3 kernels of those widths; 0 before any forward, with the option off, at every other head width and in the other
  * precisions),
  * "small_tiles" (the option value), "small_tiles_last" (bit 0: the
  * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
@@ -644,6 +662,15 @@ int d3d_op_attention_h128(const float* qkv_dev, float* out_dev, int32_t B, int32
 /* The temporal core of such an engine from the key-streaming kernel of that width alone.  Any T >= 1; D == 128 H, anything else:
  * D3D_EUNSUP.  For T <= 128 bit for bit the result of d3d_op_attention_h128 (temporal = 1). */
 int d3d_op_attention_long_h128(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
+/* The attention core of an F16X3 engine with heads of 48 or 96 columns from the resident kernel of those widths alone (option
+ * "attn_hx"): fp32 qkv in, fp32 out, split into / merged from the hi / lo fp16 planes on the device as in d3d_op_attention
+ * (D3D_PREC_F16X3).  temporal != 0: groups of T keys, else of J keys.  The width is D / H: D == 48 H and a group length N <= 256, or
+ * D == 96 H and N <= 128; anything else (it takes head_dim 48 or 96 alone): D3D_EUNSUP. */
+int d3d_op_attention_hx(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                        void* stream);
+/* The temporal core of such an engine from the key-streaming kernel of its width alone.  Any T >= 1; D == 48 H or 96 H, anything else:
+ * D3D_EUNSUP.  Wherever d3d_op_attention_hx (temporal = 1) runs, bit for bit its result. */
+int d3d_op_attention_long_hx(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
 /* The resident exact fp32 attention kernel for heads of 128 columns alone (option "attn_f32_h128"): fp32 qkv in, fp32 out.  temporal as
  * in d3d_op_attention (0: N = J keys, 1: N = T keys).  D == 128 H and a group length N <= 128; anything else (head_dim 128 is the only
  * width it takes): D3D_EUNSUP.  Not the bits of d3d_op_attention, which keeps the generic kernel at this width. */
