@@ -1,7 +1,8 @@
-// The exact-fp32 MFMA attention arithmetic (v_mfma_f32_32x32x2_f32), once, for head widths DH = 32, 64 and 128: the resident kernels
-// k_attn_temporal_f32<NKT> (kernels_attn.hip), k_attn_temporal_f32_h32<NKT> (kernels_attn_f32_h32.hip) and k_attn_f32_h128<NKT>
-// (kernels_attn_f32_h128.hip) and the key-streaming kernels k_attn_f32_stream3<DH> (the template at the end of this header; widths 64 and 32) and
-// k_attn_f32_h128_stream (kernels_attn_f32_h128.hip) are their own walks around these pieces, so staging, query load, MFMA order, key
+// The exact-fp32 MFMA attention arithmetic (v_mfma_f32_32x32x2_f32), once, for head widths DH = 32, 48, 64, 96 and 128: the resident kernels
+// k_attn_temporal_f32<NKT> (kernels_attn.hip), k_attn_temporal_f32_h32<NKT> (kernels_attn_f32_h32.hip), k_attn_f32_h128<NKT>
+// (kernels_attn_f32_h128.hip) and k_attn_f32_hx<DH, NKT> (kernels_attn_f32_hx.hip; widths 48 and 96) and the key-streaming kernels
+// k_attn_f32_stream3<DH> (the template at the end of this header; widths 64 and 32), k_attn_f32_h128_stream (kernels_attn_f32_h128.hip) and
+// k_attn_f32_hx_stream<DH> (kernels_attn_f32_hx.hip) are their own walks around these pieces, so staging, query load, MFMA order, key
 // index, pad mask, exp argument, PV order and store each have one copy, and a streaming kernel gives its resident twin's bits by
 // construction (tests/test_gpu_attn_f32_digests.py pins the bits of all of them).  Compiler-scheduled, staged through registers,
 // builtins only: no inline assembly, no LDS-DMA, no persistent walk.
@@ -15,18 +16,22 @@
 //   softmax  exact and max-subtracted: keys >= N, which only the unit's last key tile can hold, score -inf (e = 0 exactly); m = the
 //            maximum over all keys (registers, then one cross-half shuffle in the kernel), e = expf(s - m), l = the sum of e per lane in
 //            key order (key tiles ascending, registers ascending), then one cross-half add.
-//   product  O^T[d][query] += V^T P^T with P straight from the accumulator registers as the B operand, into DH / 32 accumulator tiles
-//            of 32 x 32, one per 32 columns of the head; per key register the tiles ascending, keys ascending.
+//   product  O^T[d][query] += V^T P^T with P straight from the accumulator registers as the B operand, into NDT = ceil(DH / 32)
+//            accumulator tiles of 32 x 32, one per 32 columns of the head; per key register the tiles ascending, keys ascending.  Width 48:
+//            the second tile covers columns 32 .. 63 and only 32 .. 47 belong to the head; its V operand at columns >= 48 is the exact
+//            zero of the padded LDS row (V_LD = 32 NDT), never the next head's columns, and those rows of O^T are never stored.
 //
 // What differs between the widths is named in F32Tile<DH> and must stay different: each width keeps the bits it was introduced with.
 //
-// LDS: K rows padded to DH + 4 floats, V rows DH floats, 256 DH + 512 B per key tile (F32Tile::lds_bytes).  Banks of the K fragment read (ds_read_b128,
+// LDS: K rows padded to DH + 4 floats, V rows 32 NDT floats (DH wherever DH % 32 == 0; 64 at width 48, columns 48 .. 63 staged as zeros),
+// 128 (DH + 4 + 32 NDT) B per key tile (F32Tile::lds_bytes): 256 DH + 512 B at widths 32, 64, 96 and 128, 14 848 B at width 48.  Banks of the K fragment read (ds_read_b128,
 // bank = (a / 4) mod 64, served in four groups of 16 lanes: lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32): lane
 // (r, hh) reads dword (DH + 4) r + DH/2 hh + 4 u.  Within a group hh and u are constant, so the 16-byte slot of a lane is
-// ((DH/4 + 1) r + const) mod 16, and r -> (DH/4 + 1) r mod 16 is a bijection of r mod 16 for DH/4 = 8, 16, 32 (multipliers 9, 1, 1).  The
+// ((DH/4 + 1) r + const) mod 16, and r -> (DH/4 + 1) r mod 16 is a bijection of r mod 16 for DH/4 = 8, 12, 16, 24, 32 (multipliers 9, 13, 1,
+// 9, 1: all odd; const = DH/8 hh + u is a whole number of slots since DH/2 is a multiple of 4 at every width).  The
 // 16 rows of either group are distinct mod 16 ({0-3, 12-15, 4-11} and {4-11, 0-3, 12-15}), so the 16 lanes cover the 16 four-bank slots
 // once: conflict-free.  (Unpadded rows would put them on two slots at width 32 and on one at 64 and 128.)  The V read is a ds_read_b32
-// of dword DH key + 32 dt + r with key and dt uniform over a 32-lane half: bank r, conflict-free.  The staging writes are ds_write_b128
+// of dword V_LD key + 32 dt + r with key and dt uniform over a 32-lane half and V_LD a multiple of 32: bank r, conflict-free.  The staging writes are ds_write_b128
 // of 16 consecutive bytes per lane along a row.
 //
 // Row isolation: K / V rows >= N are staged as zeros -- in a streaming kernel in every chunk, never the previous chunk's bytes -- and
@@ -45,27 +50,29 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int DH>
 struct F32Tile {
-  static_assert(DH == 32 || DH == 64 || DH == 128, "head widths with a tile form");
-  static constexpr int K_LD = DH + 4, V_LD = DH;   // LDS row strides in floats
-  static constexpr int QR = DH / 2;                // query registers per lane
-  static constexpr int NDT = DH / 32;              // 32 x 32 accumulator tiles of O^T
+  static_assert(DH == 32 || DH == 48 || DH == 64 || DH == 96 || DH == 128, "head widths with a tile form");
+  static constexpr int NDT = (DH + 31) / 32;       // 32 x 32 accumulator tiles of O^T (width 48: the second one half used)
+  static constexpr int K_LD = DH + 4, V_LD = 32 * NDT;   // LDS row strides in floats; V columns >= DH are staged as zeros
+  static constexpr int QR = DH / 2;                // query registers per lane (a multiple of 4 at every width)
   // Scale.  64^-1/2 = 2^-3 is exact: width 64 scales q.  At 32 and 128 dh^-1/2 is no power of two and scaling q would round every operand
-  // of the dot product: the sums are multiplied by 1.0f / sqrtf(DH) AFTER the sum over d (k_attn_generic's constant and the reference's
+  // of the dot product (and so would it at 48 and 96): the sums are multiplied by 1.0f / sqrtf(DH) AFTER the sum over d (k_attn_generic's constant and the reference's
   // order, (q k^T) * scale), and that product is a rounded fp32 value wherever the maximum or the mask takes it.
   static constexpr bool SCALE_Q = DH == 64;
   // Exp argument at width 32: "s * scale - m" is ONE fma(s, scale, -m) in every key tile in front of the unit's last and the rounded
   // product, then the subtraction, in the last (where the -inf select of the pad mask stands between the two).  The resident kernel was
-  // introduced with what the compiler contracted; f32_exp_tile states it.  Width 128 never has the fused form.
+  // introduced with what the compiler contracted; f32_exp_tile states it.  Widths 48, 96 and 128 never have the fused form.
   static constexpr bool EXP_FMA_FRONT = DH == 32;
   // Normalisation.  Widths 32 and 64 divide by l before the second product (the streaming form needs l before the first V product: three
-  // passes over the keys); width 128 takes the unnormalised numerators and divides at the store (two passes).
-  static constexpr bool NORM_AT_STORE = DH == 128;
+  // passes over the keys); widths 48, 96 and 128 take the unnormalised numerators and divide at the store (two passes).
+  static constexpr bool NORM_AT_STORE = DH == 128 || DH == 48 || DH == 96;
   // Diagonal.  Width 64 puts the - 1 into P where the keys are resident (T <= 256).  With p[query] - 1 inside the product the accumulator
   // stands at |v| for the rest of the key walk and every later product is rounded to an ulp of |v| (4.56e-6 at N = 219; T = 769, hashed
   // inputs at scale 2.0: 6.4e-6 against fp64 where plain fp32 math loses 3.1e-6, tests/test_gpu_group_lengths.py), so beyond 256 keys,
-  // and always at widths 32 and 128, the products are summed alone and v[query] is subtracted once, at the store.
+  // and always at the other widths, the products are summed alone and v[query] is subtracted once, at the store.
   static constexpr bool DIAG_IN_P_RESIDENT = DH == 64;
-  static constexpr int STREAM_KC = DH == 128 ? 4 : 8;   // key tiles per chunk of the streaming kernel: a chunk fills the resident maximum
+  // key tiles per chunk of the streaming kernel: a chunk fills the resident maximum.  Width 96: six tiles (150 528 B) are the most K + V
+  // that 160 KiB of LDS hold, seven (175 616 B) do not fit
+  static constexpr int STREAM_KC = DH == 128 ? 4 : DH == 96 ? 6 : 8;
   static constexpr size_t lds_bytes(int nkt) { return (size_t)32 * nkt * (K_LD + V_LD) * sizeof(float); }   // K and V of nkt key tiles
 };
 
@@ -79,7 +86,8 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
 __device__ __forceinline__ int f32_key(int kt, int q, int hh) { return 32 * kt + (q & 3) + 8 * (q >> 2) + 4 * hh; }
 
 // Rows [row0, row0 + 32 nkt) of the unit's K (and V) into LDS rows [0, 32 nkt); rows >= N as zeros.  Four 16-byte slots per thread and
-// batch (and array), all of a batch's global loads issued before its LDS writes.  token(row) = tok0 + row * stride.
+// batch (and array), all of a batch's global loads issued before its LDS writes.  token(row) = tok0 + row * stride.  Where the V rows are
+// wider than the head (width 48) their pad columns are written as zeros with every staging, rows >= N included.
 template <int DH, bool WITH_V>
 __device__ __forceinline__ void f32_stage_rows(const float* __restrict__ qkv, float* Ks, float* Vs, size_t tok0, int stride, int D, int hd,
                                                int row0, int nkt, int N, int tid, int nthr) {
@@ -106,6 +114,8 @@ __device__ __forceinline__ void f32_stage_rows(const float* __restrict__ qkv, fl
       if (idx < slots) {
         *reinterpret_cast<float4*>(&Ks[row * K_LD + c4 * 4]) = kk[it];
         if (WITH_V) *reinterpret_cast<float4*>(&Vs[row * V_LD + c4 * 4]) = vv[it];
+        if constexpr (WITH_V && V_LD > DH)      // the pad columns DH .. V_LD of the row, by its first (V_LD - DH) / 4 slots
+          if (c4 < (V_LD - DH) / 4) *reinterpret_cast<float4*>(&Vs[row * V_LD + DH + c4 * 4]) = make_float4(0, 0, 0, 0);
       }
     }
   }
@@ -233,34 +243,35 @@ __device__ __forceinline__ void f32_sub_diag_tile(f32x16& p, int gt, int tq, int
 
 // O^T[d][query] += sum over the keys of staged tile kt of V[key][d] * p[key][query]; B operand = the accumulator registers as they stand
 template <int DH>
-__device__ __forceinline__ void f32_pv_tile(const float* Vs, const f32x16& p, f32x16 (&oacc)[DH / 32], int kt, int r, int hh) {
+__device__ __forceinline__ void f32_pv_tile(const float* Vs, const f32x16& p, f32x16 (&oacc)[F32Tile<DH>::NDT], int kt, int r, int hh) {
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     const float* vp = &Vs[f32_key(kt, q, hh) * F32Tile<DH>::V_LD + r];
 #pragma unroll
-    for (int dt = 0; dt < DH / 32; ++dt) oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * dt], p[q], oacc[dt], 0, 0, 0);
+    for (int dt = 0; dt < F32Tile<DH>::NDT; ++dt) oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * dt], p[q], oacc[dt], 0, 0, 0);
   }
 }
 
 template <int DH>
-__device__ __forceinline__ void f32_zero_acc(f32x16 (&oacc)[DH / 32]) {
+__device__ __forceinline__ void f32_zero_acc(f32x16 (&oacc)[F32Tile<DH>::NDT]) {
 #pragma unroll
-  for (int dt = 0; dt < DH / 32; ++dt)
+  for (int dt = 0; dt < F32Tile<DH>::NDT; ++dt)
 #pragma unroll
     for (int q = 0; q < 16; ++q) oacc[dt][q] = 0.f;
 }
 
 // rows d = 32 dt + (reg & 3) + 8 (reg >> 2) + 4 hh of this lane's query column, token tok: / l where F32Tile::NORM_AT_STORE, - v[query]
-// where sub_v (the diagonal that is not in P), once
+// where sub_v (the diagonal that is not in P), once; columns >= DH are neither read nor stored
 template <int DH>
-__device__ __forceinline__ void f32_store_query(const float* __restrict__ qkv, float* __restrict__ out, const f32x16 (&oacc)[DH / 32], float l,
+__device__ __forceinline__ void f32_store_query(const float* __restrict__ qkv, float* __restrict__ out, const f32x16 (&oacc)[F32Tile<DH>::NDT], float l,
                                                 size_t tok, int D, int hd, int hh, bool sub_v) {
   const float* vq = qkv + tok * (3 * D) + 2 * D + hd * DH;
   float* op = out + tok * D + hd * DH;
 #pragma unroll
-  for (int dt = 0; dt < DH / 32; ++dt)
+  for (int dt = 0; dt < F32Tile<DH>::NDT; ++dt)
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
+      if (32 * dt + 8 * g4 >= DH) continue;   // (width 48: rows 48 .. 63 of the second tile are no columns of the head; DH % 8 == 0)
       const int col = 32 * dt + 8 * g4 + 4 * hh;
       float4 o = make_float4(oacc[dt][4 * g4], oacc[dt][4 * g4 + 1], oacc[dt][4 * g4 + 2], oacc[dt][4 * g4 + 3]);
       if constexpr (F32Tile<DH>::NORM_AT_STORE) { o.x = o.x / l; o.y = o.y / l; o.z = o.z / l; o.w = o.w / l; }

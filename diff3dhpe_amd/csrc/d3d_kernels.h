@@ -393,7 +393,7 @@ bool attn_temporal_x3_long_ok(int T, int D, int H);
 hipError_t launch_attn_x3_h32(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h32_ok(int N, int D, int H);
 // ---- The exact fp32 MFMA attention kernels (v_mfma_f32_32x32x2_f32) of kernels_attn.hip (width 64, resident), kernels_attn_f32_h32.hip
-// (width 32, resident), kernels_attn_f32_long.hip and kernels_attn_f32_h32_long.hip (widths 64 and 32, key-streaming) and kernels_attn_f32_h128.hip (width 128, both) share
+// (width 32, resident), kernels_attn_f32_long.hip and kernels_attn_f32_h32_long.hip (widths 64 and 32, key-streaming), kernels_attn_f32_h128.hip (width 128, both) and kernels_attn_f32_hx.hip (widths 48 and 96, both) share
 // their arithmetic, staging, launch ladder and streaming geometry: attn_f32_tile.h.
 // ---- kernels_attn_f32_long.hip, k_attn_f32_stream3<64>: launch_attn_temporal_f32's attention for windows of any length:
 // the keys stream through LDS in chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out, no
@@ -454,6 +454,18 @@ bool attn_f32_h128_ok(int N, int D, int H);
 // 2^31 - 1.
 hipError_t launch_attn_f32_h128_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_h128_long_ok(int T, int D, int H);
+// ---- kernels_attn_f32_hx.hip: the same exact fp32 attention for heads of 48 and 96 columns (D == 48 H or 96 H, any head count; the
+// width is D / H), groups of N <= 256 (width 48) / N <= 192 (width 96) tokens resident in LDS.  The contract and the arithmetic of
+// launch_attn_f32_h128 (scale 1 / sqrt(DH) after the sum over d, unnormalised numerators, / l and - v[query] at the store); spatial blocks
+// call it with (B T, J, 1).  A head reads and writes its own DH columns alone (width 48: the half-used second accumulator tile takes
+// zeros, not the next head's columns).  The launch returns hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
+hipError_t launch_attn_f32_hx(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_f32_hx_ok(int N, int D, int H);
+// ---- kernels_attn_f32_hx.hip, k_attn_f32_hx_stream<48> / <96>: launch_attn_f32_hx's temporal attention for windows of any length:
+// chunks of 256 (width 48) / 192 (width 96) frames, two passes.  fp32 rows in, fp32 rows out; bit-identical to launch_attn_f32_hx
+// wherever that runs.  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_f32_hx_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_f32_hx_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

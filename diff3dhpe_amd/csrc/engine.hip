@@ -62,7 +62,7 @@ struct BlockPlan {
   bool fused_sp = false, fused_tp = false;
   // The attention kernel of the spatial / of the temporal blocks wherever the qkv GEMM and the attention are two launches: one value per
   // launch, listed with its shapes at launch_attention().  A BF16 plan runs launch_attn_bf16 and leaves both at GENERIC.
-  enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, F32_H128, F32_H128_LONG,
+  enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, F32_H128, F32_H128_LONG, F32_HX, F32_HX_LONG,
               X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG, X3_HX, X3_HX_LONG };
   Attn attn_sp = GENERIC, attn_tp = GENERIC;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
@@ -161,8 +161,13 @@ struct d3d_engine {
   bool opt_attn_f32_h128 = true;
   // "attn_hx" (on by default): an F16X3 engine whose heads are 48 or 96 columns wide (embed_dim 384 / 768 with 8 heads) runs the folded
   // flow with its attention on kernels_attn_x3_hx.hip (groups of up to 256 / 128 tokens) and kernels_attn_x3_long.hip at that width
-  // (longer windows); 0 = the plain row-kernel flow with the generic fp32 attention, which FP32 engines of these widths run in any case
+  // (longer windows); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of these widths: "attn_f32_hx"
   bool opt_attn_hx = true;
+  // "attn_f32_hx" (on by default): an FP32 engine whose heads are 48 or 96 columns wide runs the attention of its spatial blocks (up to
+  // 256 / 192 joints) and of its temporal blocks on kernels_attn_f32_hx.hip (windows of up to 256 / 192 frames resident, longer ones
+  // key-streaming); 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical.
+  // F16X3 / BF16 engines, every other head width and embed_dim % 32 != 0 (one or three heads of 48 columns): no effect
+  bool opt_attn_f32_hx = true;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -181,7 +186,7 @@ struct d3d_engine {
   // the plan of the most recent forward (of a two-stream sampling: of the first half-batch, the one that holds sequence 0); all zero
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
-  // and the seven keys of the attention kernels that ran, which attention_plan_info() states
+  // and the keys of the attention kernels that ran, which attention_plan_info() states
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -438,14 +443,16 @@ int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal,
     case BlockPlan::X3_HX_LONG:   le = launch_attn_x3_hx_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;               // D == 48 H / 96 H, longer windows (FOLD)
     case BlockPlan::F32_H128:     le = launch_attn_f32_h128(q, out, gB, gT, gJ, D, H, s); break;                         // D == 128 H, groups <= 128, FP32 engines
     case BlockPlan::F32_H128_LONG: le = launch_attn_f32_h128_long(q, out, gB, gT, gJ, D, H, s); break;                   // D == 128 H, T > 128, FP32 engines
+    case BlockPlan::F32_HX:       le = launch_attn_f32_hx(q, out, gB, gT, gJ, D, H, s); break;                           // D == 48 H / 96 H, groups <= 256 / 192, FP32 engines
+    case BlockPlan::F32_HX_LONG:  le = launch_attn_f32_hx_long(q, out, gB, gT, gJ, D, H, s); break;                      // D == 48 H / 96 H, longer windows, FP32 engines
   }
   HIP_TRY(le);
   return D3D_OK;
 }
 
 // The "*_last" info keys of the attention plan, from the flow and the two kernel choices: which block types ran which kernel family
-// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last", "attn_hx_last" and
-// "attn_f32_h128_last" bit 2 temporal streaming).  false = not one of the keys.
+// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last", "attn_hx_last",
+// "attn_f32_h128_last" and "attn_f32_hx_last" bit 2 temporal streaming).  false = not one of the keys.
 bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* value) {
   const bool fold = p.flow == BlockPlan::FOLD, plain = p.flow == BlockPlan::PLAIN;
   const BlockPlan::Attn sp = p.attn_sp, tp = p.attn_tp;
@@ -461,6 +468,8 @@ bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* valu
   else if (k == "long_temporal_f32_h32_last") *value = plain && tp == BlockPlan::F32_H32_LONG;
   else if (k == "attn_f32_h128_last")
     *value = plain ? (sp == BlockPlan::F32_H128 ? 1 : 0) | (tp == BlockPlan::F32_H128 ? 2 : 0) | (tp == BlockPlan::F32_H128_LONG ? 4 : 0) : 0;
+  else if (k == "attn_f32_hx_last")
+    *value = plain ? (sp == BlockPlan::F32_HX ? 1 : 0) | (tp == BlockPlan::F32_HX ? 2 : 0) | (tp == BlockPlan::F32_HX_LONG ? 4 : 0) : 0;
   else return false;
   return true;
 }
@@ -541,11 +550,15 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
     // the row-kernel flow.  F16X3: the fp16-MFMA kernel where the group length fits, q / k / v going to it as planes.  FP32: heads of 32
     // columns (no D == 64 H predicate holds there) on the kernels of that width where the group length fits; windows of more than 256
     // frames, which the resident fp32 MFMA kernels cannot hold in LDS, on the key-streaming ones; heads of 128 columns on the kernels of
-    // that width, each block type deciding alone (groups of up to 128 tokens resident, longer windows streaming).  Else kernels_attn.hip.
+    // that width, each block type deciding alone (groups of up to 128 tokens resident, longer windows streaming); heads of 48 or 96
+    // columns the same way on theirs (up to 256 / 192 tokens resident) where D % 32 == 0 -- the widths at which an F16X3 engine has its
+    // own flow; one or three heads of 48 columns keep the generic kernel in both precisions, bit for bit.  Else kernels_attn.hip.
     const bool fp32 = e->cfg.precision == D3D_PREC_FP32;
+    const bool f32_hx = fp32 && e->opt_attn_f32_hx && D % 32 == 0;
     p.attn_sp = x3 && attn_temporal_x3_ok(J, D, H)                                    ? BlockPlan::X3
               : fp32 && e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H)       ? BlockPlan::F32_H32
               : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_ok(J, D, H)             ? BlockPlan::F32_H128
+              : f32_hx && attn_f32_hx_ok(J, D, H)                                     ? BlockPlan::F32_HX
               : attn_spatial_fast_ok(J, D, H)                                         ? BlockPlan::F32_SPATIAL
                                                                                       : BlockPlan::GENERIC;
     p.attn_tp = x3 && attn_temporal_x3_ok(T, D, H)                                    ? BlockPlan::X3
@@ -554,6 +567,8 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
               : fp32 && e->opt_long_temporal_f32_h32 && T > 256 && attn_temporal_f32_h32_long_ok(T, D, H)  ? BlockPlan::F32_H32_LONG
               : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_ok(T, D, H)             ? BlockPlan::F32_H128
               : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_long_ok(T, D, H)        ? BlockPlan::F32_H128_LONG
+              : f32_hx && attn_f32_hx_ok(T, D, H)                                     ? BlockPlan::F32_HX
+              : f32_hx && attn_f32_hx_long_ok(T, D, H)                                ? BlockPlan::F32_HX_LONG
               : attn_temporal_fast_ok(T, D, H)                                        ? BlockPlan::F32_TEMPORAL
                                                                                       : BlockPlan::GENERIC;
   }
@@ -1049,7 +1064,8 @@ const char* d3d_last_error(void) { return g_err.c_str(); }
 // 143: option / info key "attn_f32_h128", info key "attn_f32_h128_last", d3d_op_attention_f32_h128, d3d_op_attention_long_f32_h128
 // 145: head_dim 48 and 96 admitted (FP32 and F16X3), option / info key "attn_hx", info key "attn_hx_last", d3d_op_attention_hx,
 // d3d_op_attention_long_hx
-int d3d_version(void) { return 145; }
+// 146: option / info key "attn_f32_hx", info key "attn_f32_hx_last", d3d_op_attention_f32_hx, d3d_op_attention_long_f32_hx
+int d3d_version(void) { return 146; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1550,6 +1566,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "attn_h128") e->opt_attn_h128 = value != 0;
   else if (k == "attn_f32_h128") e->opt_attn_f32_h128 = value != 0;
   else if (k == "attn_hx") e->opt_attn_hx = value != 0;
+  else if (k == "attn_f32_hx") e->opt_attn_f32_hx = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1616,7 +1633,7 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "graphs_captured") *value = (int64_t)e->graphs_captured;
   else if (k == "streams") *value = e->opt_streams;
   else if (k == "device") *value = e->device;
-  else if (attention_plan_info(e->last_plan, k, value)) {}   // the seven "*_last" keys of the attention kernels
+  else if (attention_plan_info(e->last_plan, k, value)) {}   // the "*_last" keys of the attention kernels
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
   else if (k == "long_temporal") *value = e->opt_long_temporal ? 1 : 0;
   else if (k == "long_temporal_f32") *value = e->opt_long_temporal_f32 ? 1 : 0;
@@ -1627,6 +1644,7 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "attn_h128") *value = e->opt_attn_h128 ? 1 : 0;
   else if (k == "attn_f32_h128") *value = e->opt_attn_f32_h128 ? 1 : 0;
   else if (k == "attn_hx") *value = e->opt_attn_hx ? 1 : 0;
+  else if (k == "attn_f32_hx") *value = e->opt_attn_f32_hx ? 1 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

@@ -604,4 +604,21 @@ int d3d_op_attention_long_f32_h128(const float* qkv, float* out, int32_t B, int3
   return D3D_OK;
 }
 
+int d3d_op_attention_f32_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                            void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_f32_hx_ok(temporal ? T : J, D, H))
+    return fail(D3D_EUNSUP, "fp32 attention for head_dim 48 or 96: groups of up to 256 (head_dim 48) / 192 (head_dim 96) tokens");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIP_TRY(temporal ? launch_attn_f32_hx(qkv, out, B, T, J, D, H, s) : launch_attn_f32_hx(qkv, out, B * T, J, 1, D, H, s));
+  return D3D_OK;
+}
+
+int d3d_op_attention_long_f32_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_f32_hx_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 48 or 96");
+  HIP_TRY(launch_attn_f32_hx_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
+  return D3D_OK;
+}
+
 }  // extern "C"

@@ -229,8 +229,10 @@ class Engine:
         MFMA kernels of that width (resident for groups of up to 128 tokens, key-streaming for num_frame > 128); 0 keeps the generic
         one-thread-per-row kernel, "attn_hx": 1 (default) keeps an F16X3 engine with heads of 48 or 96 columns (embed_dim 384 / 768, 8
         heads) on the folded flow, its attention on the fp16-MFMA kernels of those widths (resident for groups of up to 256 / 128 tokens,
-        key-streaming for longer windows); 0 gives it the plain row-kernel flow with the generic fp32 attention kernel); the library
-        reads no environment."""
+        key-streaming for longer windows); 0 gives it the plain row-kernel flow with the generic fp32 attention kernel, "attn_f32_hx": 1
+        (default) runs the attention of an FP32 engine with heads of 48 or 96 columns (embed_dim 384 / 768, 8 heads) on the exact fp32
+        MFMA kernels of those widths (resident for groups of up to 256 / 192 tokens, key-streaming for longer windows); 0 keeps the
+        generic one-thread-per-row kernel); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
@@ -253,7 +255,8 @@ class Engine:
         that width; 0 before any forward, with the option off, at every other width and in the other precisions), "attn_f32_h128"
         (the option), "attn_f32_h128_last" (the same three bits for an FP32 engine and the exact fp32 kernels of that width), "attn_hx"
         (the option), "attn_hx_last" (the same three bits for an F16X3 engine with heads of 48 or 96 columns and the kernels of those
-        widths)."""
+        widths), "attn_f32_hx" (the option), "attn_f32_hx_last" (the same three bits for an FP32 engine with heads of 48 or 96 columns
+        and the exact fp32 kernels of those widths)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -747,6 +750,20 @@ def op_attention_long_f32_h128(qkv: torch.Tensor, B: int, T: int, J: int, H: int
     qkv (B*T*J, 3*D) -> (B*T*J, D), D == 128 H, any T >= 1; for T <= 128 bit for bit op_attention_f32_h128(..., temporal=True);
     anything else raises D3DError."""
     return _attention_op("d3d_op_attention_long_f32_h128", qkv, B, T, J, H)
+
+
+def op_attention_f32_hx(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
+    """The resident exact fp32 attention kernel for heads of 48 or 96 columns alone (include/d3d.h d3d_op_attention_f32_hx): qkv
+    (B*T*J, 3*D) -> (B*T*J, D), D == 48 H (groups of up to 256 tokens) or 96 H (up to 192); temporal: T keys, else J; anything else raises
+    D3DError."""
+    return _attention_op("d3d_op_attention_f32_hx", qkv, B, T, J, H, int(bool(temporal)))
+
+
+def op_attention_long_f32_hx(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming fp32 temporal attention kernel for heads of 48 or 96 columns alone (include/d3d.h d3d_op_attention_long_f32_hx):
+    qkv (B*T*J, 3*D) -> (B*T*J, D), D == 48 H or 96 H, any T >= 1; wherever op_attention_f32_hx(..., temporal=True) runs bit for bit its
+    result; anything else raises D3DError."""
+    return _attention_op("d3d_op_attention_long_f32_hx", qkv, B, T, J, H)
 
 
 def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, groups: int, N: int, stride: int, H: int,

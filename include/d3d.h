@@ -88,7 +88,8 @@ int d3d_version(void);
  * a multiple of 16).  The fp16 plane forms of the GEMMs do not exist there (32-deep k-tiles, activations in groups of 32 columns), so
  * such an engine runs the FP32 kernels whether D3D_PREC_FP32 or D3D_PREC_F16X3 was asked for -- the exact arithmetic, the fp32 GEMM
  * zero-filling its last k-tile of 16 columns -- and D3D_PREC_BF16 refuses it.  Widths 48 and 96 (embed_dim 384 / 768 with the runner's 8 heads) run the fp16-MFMA attention
- * kernels of those widths on a D3D_PREC_F16X3 engine (option "attn_hx") and the generic fp32 attention kernel on a D3D_PREC_FP32 engine.  Width 128 (embed_dim 1024 with the runner's 8 heads) runs the fp16-MFMA attention kernels of that width on a
+ * kernels of those widths on a D3D_PREC_F16X3 engine (option "attn_hx") and the exact fp32 MFMA attention kernels of those widths on a
+ * D3D_PREC_FP32 engine (option "attn_f32_hx").  Width 128 (embed_dim 1024 with the runner's 8 heads) runs the fp16-MFMA attention kernels of that width on a
  * D3D_PREC_F16X3 engine (option "attn_h128") and the exact fp32 MFMA attention kernels of that width on a D3D_PREC_FP32 engine
  * (option "attn_f32_h128"). */
 int d3d_engine_create(const d3d_config* cfg, d3d_engine** out);
@@ -310,6 +311,23 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     differ in the last bits, both inside the parity gate.  Measured: DESIGN.md section 5.  Every other head width,
  *                     FP32 and BF16 engines (BF16: refused at these widths): no effect.  d3d_workspace_bytes does not change.
  *                     "attn_hx_last" (d3d_engine_get_info) reports what the latest forward ran.
+ *   "attn_f32_hx"     1 (default) / 0: FP32 engines whose heads are 48 or 96 columns wide with embed_dim a multiple of 32 (embed_dim ==
+ *                     48 num_heads or 96 num_heads, e.g. 384 or 768 with 8 heads) -- the exact reference arithmetic, and the engine a
+ *                     precision-"auto" model falls back to.  With the key on, the spatial blocks of such an engine (num_joints <= 256 at
+ *                     width 48, <= 192 at width 96) and, for num_frame up to the same limit, its temporal blocks run the resident exact
+ *                     fp32 kernel of these widths (v_mfma_f32_32x32x2_f32, K and V of a group resident in LDS, the scores scaled by
+ *                     1 / sqrt(head_dim) after the sum, exact two-pass softmax, the second product on the unnormalised numerators, the
+ *                     division by their sum and v[query] of the diagonal at the store: the arithmetic of "attn_f32_h128"; a head reads
+ *                     and writes its own columns alone -- at width 48 the half-used second 32-column tile takes zeros, never the
+ *                     neighbouring head's columns), its temporal blocks for longer windows the key-streaming kernel of that width
+ *                     (chunks of 256 / 192 frames, the scores computed twice, bit-identical to the resident kernel wherever that runs);
+ *                     each block type is decided on its own / 0: the generic one-thread-per-row kernel, as before version 146.  The
+ *                     two differ in the order of additions, so in the last bits, both inside the parity gate.  A 9-step sampling at
+ *                     depth 8, num_frame 243: embed_dim 384 66.5 -> 33.9 ms at B = 1, 456 -> 238 ms at B = 16; embed_dim 768
+ *                     144.0 -> 75.8 ms and 1385 -> 820 ms; num_frame 27, B = 1: 35.1 -> 28.3 and 62.9 -> 49.0 ms (DESIGN.md
+ *                     section 5).  Every other head width, an odd number of heads of 48 columns (embed_dim 48, 144: they keep the
+ *                     generic kernel in both precisions), F16X3 and BF16 engines: no effect.  d3d_workspace_bytes does not change.
+ *                     "attn_f32_hx_last" (d3d_engine_get_info) reports what the latest forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -384,7 +402,9 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * fp32 kernels for heads of 128 columns; 0 before any forward, with the option off, at every other head width and in the other
  * precisions), "attn_hx" (the option value), "attn_hx_last" (the same three bits for a D3D_PREC_F16X3 engine with heads of 48 or 96
  * columns and the F16X3 kernels of those widths; 0 before any forward, with the option off, at every other head width and in the other
- * precisions),
+ * precisions), "attn_f32_hx" (the option value), "attn_f32_hx_last" (the same three bits for a D3D_PREC_FP32 engine with heads of 48 or
+ * 96 columns and the exact fp32 kernels of those widths; 0 before any forward, with the option off, at every other head width, where
+ * embed_dim is no multiple of 32 and in the other precisions),
  * "small_tiles" (the option value), "small_tiles_last" (bit 0: the
  * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
  * kernel; 0 before any forward, with the option or "latency_mode" off, and in the other precisions).
@@ -681,6 +701,16 @@ int d3d_op_attention_f32_h128(const float* qkv_dev, float* out_dev, int32_t B, i
  * (temporal = 1). */
 int d3d_op_attention_long_f32_h128(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
                                    void* stream);
+/* The resident exact fp32 attention kernel for heads of 48 or 96 columns alone (option "attn_f32_hx"): fp32 qkv in, fp32 out.  temporal
+ * as in d3d_op_attention (0: N = J keys, 1: N = T keys).  The width is D / H: D == 48 H and a group length N <= 256, or D == 96 H and
+ * N <= 192; anything else (it takes head_dim 48 or 96 alone): D3D_EUNSUP.  Not the bits of d3d_op_attention, which keeps the generic
+ * kernel at these widths. */
+int d3d_op_attention_f32_hx(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                            void* stream);
+/* The temporal core of such an engine from the key-streaming fp32 kernel of its width alone.  Any T >= 1; D == 48 H or 96 H, anything
+ * else: D3D_EUNSUP.  Wherever d3d_op_attention_f32_hx (temporal = 1) runs, bit for bit its result. */
+int d3d_op_attention_long_f32_hx(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
+                                 void* stream);
 /* The fused qkv GEMM + attention kernel of the BF16 mode alone: out = attention(bf16(A) bf16(Wqkv)^T + bias) with q / k / v rounded to
  * bf16 (q third times dh^-1/2) and kept on chip -- bit for bit d3d_op_linear (D3D_PREC_BF16) followed by d3d_op_attention (D3D_PREC_BF16)
  * on the same tensors.  A: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias: (3 D); out: (groups * N, D) fp32.  Group u holds the N
