@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "d3d_engine_weight_info", "d3d_engine_set_weight", "d3d_engine_set_time_freqs", "d3d_engine_commit_weights",
     "d3d_engine_set_schedule", "d3d_engine_set_sqrt_alphas_cumprod", "d3d_ddim_times", "d3d_workspace_bytes",
     "d3d_denoise", "d3d_ddim_sample", "d3d_q_sample", "d3d_tta_mpjpe", "d3d_allgather_pred", "d3d_op_linear", "d3d_op_layernorm",
-    "d3d_op_attention", "d3d_op_attention_long", "d3d_op_attention_long_f32", "d3d_op_attention_h32", "d3d_op_attention_f32_h32", "d3d_op_attention_long_h32", "d3d_op_attention_long_f32_h32", "d3d_op_attention_h128", "d3d_op_attention_long_h128", "d3d_op_attention_f32_h128", "d3d_op_attention_long_f32_h128", "d3d_op_attention_hx", "d3d_op_attention_long_hx", "d3d_op_attention_f32_hx", "d3d_op_attention_long_f32_hx", "d3d_op_time_embedding", "d3d_engine_set_profiling", "d3d_engine_profile_reset",
+    "d3d_op_attention", "d3d_op_attention_long", "d3d_op_attention_long_f32", "d3d_op_attention_h32", "d3d_op_attention_f32_h32", "d3d_op_attention_long_h32", "d3d_op_attention_long_f32_h32", "d3d_op_attention_h128", "d3d_op_attention_long_h128", "d3d_op_attention_f32_h128", "d3d_op_attention_long_f32_h128", "d3d_op_attention_hx", "d3d_op_attention_long_hx", "d3d_op_attention_f32_hx", "d3d_op_attention_long_f32_hx", "d3d_op_attention_h16", "d3d_op_attention_long_h16", "d3d_op_attention_f32_h16", "d3d_op_attention_long_f32_h16", "d3d_op_time_embedding", "d3d_engine_set_profiling", "d3d_engine_profile_reset",
     "d3d_engine_profile_read", "d3d_kernel_class_name", "d3d_op_linear_bench", "d3d_op_linear_postnorm", "d3d_op_linear_splitk_postnorm", "d3d_op_linear_splitk_residual", "d3d_op_linear_splitk_gelu", "d3d_engine_set_graph_mode", "d3d_num_windows", "d3d_window_gather",
     "d3d_engine_set_trace", "d3d_engine_trace_read", "d3d_engine_range_flags", "d3d_op_head", "d3d_engine_set_option",
     "d3d_weighted_loss", "d3d_repeat_batch", "d3d_hypothesis_mean", "d3d_engine_get_info", "d3d_probe_machine",
@@ -113,6 +113,10 @@ def _bind(lib: C.CDLL) -> None:
         "d3d_op_attention_long_f32_hx": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
         "d3d_op_attention_hx": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
         "d3d_op_attention_long_hx": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
+        "d3d_op_attention_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        "d3d_op_attention_long_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
+        "d3d_op_attention_f32_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        "d3d_op_attention_long_f32_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
         "d3d_op_qkv_attn_bf16": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "d3d_op_qkv_attn_x3_small": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, i32, i32, vp, vp]),
     }

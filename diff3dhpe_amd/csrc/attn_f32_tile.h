@@ -1,6 +1,6 @@
-// The exact-fp32 MFMA attention arithmetic (v_mfma_f32_32x32x2_f32), once, for head widths DH = 32, 48, 64, 96 and 128: the resident kernels
+// The exact-fp32 MFMA attention arithmetic (v_mfma_f32_32x32x2_f32), once, for head widths DH = 16, 32, 48, 64, 96 and 128: the resident kernels
 // k_attn_temporal_f32<NKT> (kernels_attn.hip), k_attn_temporal_f32_h32<NKT> (kernels_attn_f32_h32.hip), k_attn_f32_h128<NKT>
-// (kernels_attn_f32_h128.hip) and k_attn_f32_hx<DH, NKT> (kernels_attn_f32_hx.hip; widths 48 and 96) and the key-streaming kernels
+// (kernels_attn_f32_h128.hip) and k_attn_f32_hx<DH, NKT> (kernels_attn_f32_hx.hip; widths 48, 96 and 16) and the key-streaming kernels
 // k_attn_f32_stream3<DH> (the template at the end of this header; widths 64 and 32), k_attn_f32_h128_stream (kernels_attn_f32_h128.hip) and
 // k_attn_f32_hx_stream<DH> (kernels_attn_f32_hx.hip) are their own walks around these pieces, so staging, query load, MFMA order, key
 // index, pad mask, exp argument, PV order and store each have one copy, and a streaming kernel gives its resident twin's bits by
@@ -19,15 +19,17 @@
 //   product  O^T[d][query] += V^T P^T with P straight from the accumulator registers as the B operand, into NDT = ceil(DH / 32)
 //            accumulator tiles of 32 x 32, one per 32 columns of the head; per key register the tiles ascending, keys ascending.  Width 48:
 //            the second tile covers columns 32 .. 63 and only 32 .. 47 belong to the head; its V operand at columns >= 48 is the exact
-//            zero of the padded LDS row (V_LD = 32 NDT), never the next head's columns, and those rows of O^T are never stored.
+//            zero of the padded LDS row (V_LD = 32 NDT), never the next head's columns, and those rows of O^T are never stored.  Width 16
+//            likewise: its one tile covers columns 0 .. 31, of which 16 .. 31 are staged zeros and rows 16 .. 31 of O^T are never stored.
 //
 // What differs between the widths is named in F32Tile<DH> and must stay different: each width keeps the bits it was introduced with.
 //
-// LDS: K rows padded to DH + 4 floats, V rows 32 NDT floats (DH wherever DH % 32 == 0; 64 at width 48, columns 48 .. 63 staged as zeros),
-// 128 (DH + 4 + 32 NDT) B per key tile (F32Tile::lds_bytes): 256 DH + 512 B at widths 32, 64, 96 and 128, 14 848 B at width 48.  Banks of the K fragment read (ds_read_b128,
+// LDS: K rows padded to DH + 4 floats, V rows 32 NDT floats (DH wherever DH % 32 == 0; 64 at width 48, columns 48 .. 63 staged as zeros;
+// 32 at width 16, columns 16 .. 31 staged as zeros),
+// 128 (DH + 4 + 32 NDT) B per key tile (F32Tile::lds_bytes): 256 DH + 512 B at widths 32, 64, 96 and 128, 14 848 B at width 48, 6 656 B at width 16.  Banks of the K fragment read (ds_read_b128,
 // bank = (a / 4) mod 64, served in four groups of 16 lanes: lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32): lane
 // (r, hh) reads dword (DH + 4) r + DH/2 hh + 4 u.  Within a group hh and u are constant, so the 16-byte slot of a lane is
-// ((DH/4 + 1) r + const) mod 16, and r -> (DH/4 + 1) r mod 16 is a bijection of r mod 16 for DH/4 = 8, 12, 16, 24, 32 (multipliers 9, 13, 1,
+// ((DH/4 + 1) r + const) mod 16, and r -> (DH/4 + 1) r mod 16 is a bijection of r mod 16 for DH/4 = 4, 8, 12, 16, 24, 32 (multipliers 5, 9, 13, 1,
 // 9, 1: all odd; const = DH/8 hh + u is a whole number of slots since DH/2 is a multiple of 4 at every width).  The
 // 16 rows of either group are distinct mod 16 ({0-3, 12-15, 4-11} and {4-11, 0-3, 12-15}), so the 16 lanes cover the 16 four-bank slots
 // once: conflict-free.  (Unpadded rows would put them on two slots at width 32 and on one at 64 and 128.)  The V read is a ds_read_b32
@@ -50,21 +52,22 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int DH>
 struct F32Tile {
-  static_assert(DH == 32 || DH == 48 || DH == 64 || DH == 96 || DH == 128, "head widths with a tile form");
-  static constexpr int NDT = (DH + 31) / 32;       // 32 x 32 accumulator tiles of O^T (width 48: the second one half used)
+  static_assert(DH == 16 || DH == 32 || DH == 48 || DH == 64 || DH == 96 || DH == 128, "head widths with a tile form");
+  static constexpr int NDT = (DH + 31) / 32;       // 32 x 32 accumulator tiles of O^T (width 48: the second one half used; width 16: the one)
   static constexpr int K_LD = DH + 4, V_LD = 32 * NDT;   // LDS row strides in floats; V columns >= DH are staged as zeros
   static constexpr int QR = DH / 2;                // query registers per lane (a multiple of 4 at every width)
   // Scale.  64^-1/2 = 2^-3 is exact: width 64 scales q.  At 32 and 128 dh^-1/2 is no power of two and scaling q would round every operand
   // of the dot product (and so would it at 48 and 96): the sums are multiplied by 1.0f / sqrtf(DH) AFTER the sum over d (k_attn_generic's constant and the reference's
-  // order, (q k^T) * scale), and that product is a rounded fp32 value wherever the maximum or the mask takes it.
+  // order, (q k^T) * scale), and that product is a rounded fp32 value wherever the maximum or the mask takes it.  16^-1/2 = 2^-2 is exact
+  // too, so scaling q or the sum gives the same bits there; width 16 scales the SUM, like every width it shares its kernels with.
   static constexpr bool SCALE_Q = DH == 64;
   // Exp argument at width 32: "s * scale - m" is ONE fma(s, scale, -m) in every key tile in front of the unit's last and the rounded
   // product, then the subtraction, in the last (where the -inf select of the pad mask stands between the two).  The resident kernel was
   // introduced with what the compiler contracted; f32_exp_tile states it.  Widths 48, 96 and 128 never have the fused form.
   static constexpr bool EXP_FMA_FRONT = DH == 32;
   // Normalisation.  Widths 32 and 64 divide by l before the second product (the streaming form needs l before the first V product: three
-  // passes over the keys); widths 48, 96 and 128 take the unnormalised numerators and divide at the store (two passes).
-  static constexpr bool NORM_AT_STORE = DH == 128 || DH == 48 || DH == 96;
+  // passes over the keys); widths 16, 48, 96 and 128 take the unnormalised numerators and divide at the store (two passes).
+  static constexpr bool NORM_AT_STORE = DH == 128 || DH == 48 || DH == 96 || DH == 16;
   // Diagonal.  Width 64 puts the - 1 into P where the keys are resident (T <= 256).  With p[query] - 1 inside the product the accumulator
   // stands at |v| for the rest of the key walk and every later product is rounded to an ulp of |v| (4.56e-6 at N = 219; T = 769, hashed
   // inputs at scale 2.0: 6.4e-6 against fp64 where plain fp32 math loses 3.1e-6, tests/test_gpu_group_lengths.py), so beyond 256 keys,
@@ -87,7 +90,7 @@ __device__ __forceinline__ int f32_key(int kt, int q, int hh) { return 32 * kt +
 
 // Rows [row0, row0 + 32 nkt) of the unit's K (and V) into LDS rows [0, 32 nkt); rows >= N as zeros.  Four 16-byte slots per thread and
 // batch (and array), all of a batch's global loads issued before its LDS writes.  token(row) = tok0 + row * stride.  Where the V rows are
-// wider than the head (width 48) their pad columns are written as zeros with every staging, rows >= N included.
+// wider than the head (widths 48 and 16) their pad columns are written as zeros with every staging, rows >= N included.
 template <int DH, bool WITH_V>
 __device__ __forceinline__ void f32_stage_rows(const float* __restrict__ qkv, float* Ks, float* Vs, size_t tok0, int stride, int D, int hd,
                                                int row0, int nkt, int N, int tid, int nthr) {
@@ -271,7 +274,7 @@ __device__ __forceinline__ void f32_store_query(const float* __restrict__ qkv, f
   for (int dt = 0; dt < F32Tile<DH>::NDT; ++dt)
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
-      if (32 * dt + 8 * g4 >= DH) continue;   // (width 48: rows 48 .. 63 of the second tile are no columns of the head; DH % 8 == 0)
+      if (32 * dt + 8 * g4 >= DH) continue;   // (width 48: rows 48 .. 63 of the second tile are no columns of the head, width 16: rows 16 .. 31 of the one; DH % 8 == 0)
       const int col = 32 * dt + 8 * g4 + 4 * hh;
       float4 o = make_float4(oacc[dt][4 * g4], oacc[dt][4 * g4 + 1], oacc[dt][4 * g4 + 2], oacc[dt][4 * g4 + 3]);
       if constexpr (F32Tile<DH>::NORM_AT_STORE) { o.x = o.x / l; o.y = o.y / l; o.z = o.z / l; o.w = o.w / l; }

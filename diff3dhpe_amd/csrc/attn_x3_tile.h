@@ -16,11 +16,13 @@
 constexpr float X3_C_EXP = 1.4426950408889634f / 64.0f;   // acc = 64 s: scale and log2(e) in one fma feeding v_exp_f32
 // The same constant for a head width DH.  The planes hold raw q and 8 k whatever the width, so acc = 8 q.k and the exponent argument is
 // acc log2(e) / (8 sqrt(DH)): X3_C_EXP itself at 64; at 32 (kernels_attn_x3_h32.hip), at 128 (kernels_attn_x3_h128.hip) and at 48
-// and 96 (kernels_attn_x3_hx.hip) evaluated in double and rounded once.
+// and 96 (kernels_attn_x3_hx.hip) evaluated in double and rounded once.  At 16 (kernels_attn_x3_h16.hip) sqrt(DH) = 4 and the constant is
+// log2(e) / 32 = 2 * X3_C_EXP, exactly: a power of two times a float.
 template <int DH>
 constexpr float x3_c_exp() {
-  static_assert(DH == 64 || DH == 32 || DH == 128 || DH == 48 || DH == 96, "head widths with a tile form");
+  static_assert(DH == 64 || DH == 32 || DH == 128 || DH == 48 || DH == 96 || DH == 16, "head widths with a tile form");
   return DH == 64 ? X3_C_EXP
+       : DH == 16 ? 2 * X3_C_EXP
        : DH == 32 ? (float)(1.4426950408889634 / (8.0 * 5.656854249492380195 /* sqrt(32) */))
        : DH == 48 ? (float)(1.4426950408889634 / (8.0 * 6.928203230275509174 /* sqrt(48) */))
        : DH == 96 ? (float)(1.4426950408889634 / (8.0 * 9.797958971132712393 /* sqrt(96) */))
@@ -202,6 +204,9 @@ __device__ __forceinline__ void x3_pv_tile(const f32x16& e, const unsigned char*
 // independent softmax streams, each with its own score tile, maximum and sum:
 //   DH = 32    a PAIR of heads in one segment; head p is stream p: d-steps 2 p, 2 p + 1 of the score product, 32-column half p of the PV
 //              product and of the output
+//   DH = 16    a QUAD of heads in one segment; head p is stream p: d-step p of the score product (a 16-deep d-step is exactly the head's
+//              columns), and the 16 rows 16 (p & 1) .. + 15 of an O^T accumulator of its own over 32-column line p >> 1 -- the other 16
+//              rows of that tile are the line neighbour's V times this head's E and are never stored
 //   DH = 64    one head, one segment, one stream
 //   DH = 128   one head in two segments: one score chain over segment 0 then segment 1, one stream, a PV step per segment
 // Widths 48 and 96 are no multiple of 64 columns: a head starts at plane column hd DH, wherever that falls, and ends inside its last
@@ -210,17 +215,21 @@ __device__ __forceinline__ void x3_pv_tile(const f32x16& e, const unsigned char*
 //              of the K and V rows are exact zeros)
 //   DH = 96    one head in two LDS rows, 64 + 32 columns: the chain of DH = 128 with two d-steps and one PV line in the second row
 //              (its upper 32 columns are neither staged nor read)
-// The MFMA order of every accumulator is the one of k_attn_x3_h32 / k_attn_temporal_x3 / k_attn_x3_h128 / k_attn_x3_hx.
+// The MFMA order of every accumulator is the one of k_attn_x3_h32 / k_attn_temporal_x3 / k_attn_x3_h128 / k_attn_x3_hx / k_attn_x3_h16.
 template <int DH>
 struct x3_head_shape {
-  static_assert(DH == 32 || DH == 64 || DH == 128 || DH == 48 || DH == 96, "head widths with a tile form");
+  static_assert(DH == 32 || DH == 64 || DH == 128 || DH == 48 || DH == 96 || DH == 16, "head widths with a tile form");
   static constexpr int SUB = DH > 64 ? 2 : 1;
-  static constexpr int STREAMS = DH == 32 ? 2 : 1;
-  static constexpr int COLS = DH == 32 ? 64 : DH;                  // plane columns of a unit
+  static constexpr int STREAMS = DH == 32 ? 2 : DH == 16 ? 4 : 1;
+  static constexpr int COLS = DH < 64 && 64 % DH == 0 ? 64 : DH;   // plane columns of a unit (a pair of 32, a quad of 16: one segment)
   static constexpr bool ALIGNED = COLS % 64 == 0;                  // a unit is whole 64-column segments of the plane rows
-  static constexpr bool heads_ok(int H) { return DH == 32 ? H >= 2 && H % 2 == 0 : H >= 1; }
-  static constexpr int units_per_token(int H) { return DH == 32 ? H / 2 : H; }
-  // the stream whose 1 / (2^13 l) scales 32-column line dt of a segment
+  static constexpr bool heads_ok(int H) { return H >= 1 && H % STREAMS == 0; }
+  static constexpr int units_per_token(int H) { return H / STREAMS; }
+  // O^T accumulators, oacc[ACCS][2].  Every width but 16: oacc[f][dt] is 32-column line dt of segment f, shared by nobody or (width 32)
+  // owned by one stream.  Width 16: two heads share a line, so head p has oacc[p][p >> 1] to itself (the pair's other entry is never
+  // touched) and only rows 16 (p & 1) .. + 15 of it are the head's.
+  static constexpr int ACCS = DH == 16 ? 4 : SUB;
+  // the stream whose 1 / (2^13 l) scales 32-column line dt of a segment (not at width 16, where a line has two)
   static constexpr int line_stream(int dt) { return DH == 32 ? dt : 0; }
   // the columns of segment f that belong to the unit, and of them those of 32-column line dt
   static constexpr int seg_cols(int f) { return COLS - 64 * f < 64 ? COLS - 64 * f : 64; }
@@ -232,6 +241,11 @@ struct x3_head_shape {
     if constexpr (DH == 32) {
       s[0] = x3_score_tile<0, 2>(sKh, sKl, row0, r, h, qh[0], ql[0]);
       s[1] = x3_score_tile<2, 2>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+    } else if constexpr (DH == 16) {
+      s[0] = x3_score_tile<0, 1>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+      s[1] = x3_score_tile<1, 1>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+      s[2] = x3_score_tile<2, 1>(sKh, sKl, row0, r, h, qh[0], ql[0]);
+      s[3] = x3_score_tile<3, 1>(sKh, sKl, row0, r, h, qh[0], ql[0]);
     } else if constexpr (DH == 64) {
       s[0] = x3_score_tile<>(sKh, sKl, row0, r, h, qh[0], ql[0]);
     } else if constexpr (DH == 48) {
@@ -243,12 +257,17 @@ struct x3_head_shape {
       x3_score_acc<DH == 96 ? 2 : 4>(s[0], sKh + pl, sKl + pl, row0, r, h, qh[1], ql[1]);
     }
   }
-  // O^T += V^T E^T over staged key tile kt; oacc[f][dt]: 32-column line dt of segment f
+  // O^T += V^T E^T over staged key tile kt; oacc: see ACCS
   static __device__ __forceinline__ void pv(const f32x16 (&e)[STREAMS], const unsigned char* sVh, const unsigned char* sVl, int pl, int kt, int T,
-                                            int lane, int h, f32x16 (&oacc)[SUB][2]) {
+                                            int lane, int h, f32x16 (&oacc)[ACCS][2]) {
     if constexpr (DH == 32) {
       x3_pv_tile<false, 0, 1>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
       x3_pv_tile<false, 1, 1>(e[1], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+    } else if constexpr (DH == 16) {
+      x3_pv_tile<false, 0, 1>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
+      x3_pv_tile<false, 0, 1>(e[1], sVh, sVl, 0, kt, T, lane, h, oacc[1]);
+      x3_pv_tile<false, 1, 1>(e[2], sVh, sVl, 0, kt, T, lane, h, oacc[2]);
+      x3_pv_tile<false, 1, 1>(e[3], sVh, sVl, 0, kt, T, lane, h, oacc[3]);
     } else if constexpr (DH == 64 || DH == 48) {
       x3_pv_tile<false>(e[0], sVh, sVl, 0, kt, T, lane, h, oacc[0]);
     } else if constexpr (DH == 96) {

@@ -466,6 +466,27 @@ bool attn_f32_hx_ok(int N, int D, int H);
 // wherever that runs.  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_f32_hx_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_hx_long_ok(int T, int D, int H);
+// ---- kernels_attn_x3_h16.hip: the F16X3 attention for heads of 16 columns (D == 16 H, H a multiple of 4: four adjacent heads share the
+// 128-byte LDS rows of the kernels above, each with its own d-step of the score product, softmax, sum and O^T accumulator), groups of
+// T <= 256 tokens.  The contract of launch_attn_temporal_x3: same planes in (raw q, 8 k, 8 v), same pair layout out (a head's 16 columns are
+// half a 128-byte line); spatial blocks call it with (B T, J, 1).
+hipError_t launch_attn_x3_h16(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h16_ok(int N, int D, int H);
+// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<16, 8>: launch_attn_x3_h16's temporal attention for windows of any length: the quad's
+// keys stream through LDS in chunks of 256 frames, the scores are computed twice.  Same planes in, same pair layout out; bit-identical to
+// launch_attn_x3_h16 wherever that runs (T <= 256).  The launch also refuses B J (H / 4) ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_x3_h16_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h16_long_ok(int T, int D, int H);
+// ---- kernels_attn_f32_hx.hip at DH = 16: the exact fp32 attention of launch_attn_f32_hx for heads of 16 columns (D == 16 H, any head
+// count), groups of N <= 256 tokens resident in LDS; the same contract and arithmetic (1 / sqrt(16) = 0.25 applied after the sum over d,
+// unnormalised numerators, / l and - v[query] at the store); spatial blocks call it with (B T, J, 1).  The half-used accumulator tile takes
+// zeros, not the next head's columns.  The launch returns hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
+hipError_t launch_attn_f32_h16(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_f32_h16_ok(int N, int D, int H);
+// ---- k_attn_f32_hx_stream<16>: its temporal attention for windows of any length: chunks of 256 frames, two passes; bit-identical to
+// launch_attn_f32_h16 wherever that runs.  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_f32_h16_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_f32_h16_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);
 hipError_t launch_unsplit_pair(const void* pair, float* x, size_t rows, int cols, hipStream_t s);
 bool attn_spatial_fast_ok(int J, int D, int H);

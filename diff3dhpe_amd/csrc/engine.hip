@@ -63,7 +63,7 @@ struct BlockPlan {
   // The attention kernel of the spatial / of the temporal blocks wherever the qkv GEMM and the attention are two launches: one value per
   // launch, listed with its shapes at launch_attention().  A BF16 plan runs launch_attn_bf16 and leaves both at GENERIC.
   enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, F32_H128, F32_H128_LONG, F32_HX, F32_HX_LONG,
-              X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG, X3_HX, X3_HX_LONG };
+              F32_H16, F32_H16_LONG, X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG, X3_HX, X3_HX_LONG, X3_H16, X3_H16_LONG };
   Attn attn_sp = GENERIC, attn_tp = GENERIC;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
@@ -79,6 +79,9 @@ struct BlockPlan {
 };
 
 }  // namespace
+
+// The defaults of "attn_h16" / "attn_f32_h16", decided by the table of DESIGN.md section 5 (experiments/attn_h16.py)
+constexpr bool ATTN_H16_DEFAULT = true, ATTN_F32_H16_DEFAULT = true;
 
 struct d3d_engine {
   d3d_config cfg{};
@@ -168,6 +171,14 @@ struct d3d_engine {
   // key-streaming); 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical.
   // F16X3 / BF16 engines, every other head width and embed_dim % 32 != 0 (one or three heads of 48 columns): no effect
   bool opt_attn_f32_hx = true;
+  // "attn_h16": an F16X3 engine whose heads are 16 columns wide in quads (embed_dim 128 with 8 heads; H % 4 == 0) runs the folded flow
+  // with its attention on kernels_attn_x3_h16.hip (groups of up to 256 tokens) and kernels_attn_x3_long.hip at that width (longer
+  // windows); 0 = the plain row-kernel flow with the generic fp32 attention.  Other head counts of that width: no effect
+  bool opt_attn_h16 = ATTN_H16_DEFAULT;
+  // "attn_f32_h16": an FP32 engine whose heads are 16 columns wide (any head count) runs the attention of its spatial blocks (up to 256
+  // joints) and of its temporal blocks on kernels_attn_f32_hx.hip at DH = 16 (windows of up to 256 frames resident, longer ones
+  // key-streaming); 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical
+  bool opt_attn_f32_h16 = ATTN_F32_H16_DEFAULT;
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -441,6 +452,10 @@ int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal,
     case BlockPlan::X3_H128_LONG: le = launch_attn_x3_h128_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;             // D == 128 H, T > 128 (FOLD)
     case BlockPlan::X3_HX:        le = launch_attn_x3_hx(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                    // D == 48 H / 96 H, groups <= 256 / 128 (FOLD)
     case BlockPlan::X3_HX_LONG:   le = launch_attn_x3_hx_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;               // D == 48 H / 96 H, longer windows (FOLD)
+    case BlockPlan::X3_H16:       le = launch_attn_x3_h16(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                   // D == 16 H, H % 4 == 0, groups <= 256 (FOLD)
+    case BlockPlan::X3_H16_LONG:  le = launch_attn_x3_h16_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 16 H, H % 4 == 0, T > 256 (FOLD)
+    case BlockPlan::F32_H16:      le = launch_attn_f32_h16(q, out, gB, gT, gJ, D, H, s); break;                          // D == 16 H, groups <= 256, FP32 engines
+    case BlockPlan::F32_H16_LONG: le = launch_attn_f32_h16_long(q, out, gB, gT, gJ, D, H, s); break;                     // D == 16 H, T > 256, FP32 engines
     case BlockPlan::F32_H128:     le = launch_attn_f32_h128(q, out, gB, gT, gJ, D, H, s); break;                         // D == 128 H, groups <= 128, FP32 engines
     case BlockPlan::F32_H128_LONG: le = launch_attn_f32_h128_long(q, out, gB, gT, gJ, D, H, s); break;                   // D == 128 H, T > 128, FP32 engines
     case BlockPlan::F32_HX:       le = launch_attn_f32_hx(q, out, gB, gT, gJ, D, H, s); break;                           // D == 48 H / 96 H, groups <= 256 / 192, FP32 engines
@@ -452,7 +467,7 @@ int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal,
 
 // The "*_last" info keys of the attention plan, from the flow and the two kernel choices: which block types ran which kernel family
 // (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last", "attn_hx_last",
-// "attn_f32_h128_last" and "attn_f32_hx_last" bit 2 temporal streaming).  false = not one of the keys.
+// "attn_h16_last", "attn_f32_h128_last", "attn_f32_hx_last" and "attn_f32_h16_last" bit 2 temporal streaming).  false = not one of the keys.
 bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* value) {
   const bool fold = p.flow == BlockPlan::FOLD, plain = p.flow == BlockPlan::PLAIN;
   const BlockPlan::Attn sp = p.attn_sp, tp = p.attn_tp;
@@ -463,6 +478,10 @@ bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* valu
     *value = fold ? (sp == BlockPlan::X3_H128 ? 1 : 0) | (tp == BlockPlan::X3_H128 ? 2 : 0) | (tp == BlockPlan::X3_H128_LONG ? 4 : 0) : 0;
   else if (k == "attn_hx_last")
     *value = fold ? (sp == BlockPlan::X3_HX ? 1 : 0) | (tp == BlockPlan::X3_HX ? 2 : 0) | (tp == BlockPlan::X3_HX_LONG ? 4 : 0) : 0;
+  else if (k == "attn_h16_last")
+    *value = fold ? (sp == BlockPlan::X3_H16 ? 1 : 0) | (tp == BlockPlan::X3_H16 ? 2 : 0) | (tp == BlockPlan::X3_H16_LONG ? 4 : 0) : 0;
+  else if (k == "attn_f32_h16_last")
+    *value = plain ? (sp == BlockPlan::F32_H16 ? 1 : 0) | (tp == BlockPlan::F32_H16 ? 2 : 0) | (tp == BlockPlan::F32_H16_LONG ? 4 : 0) : 0;
   else if (k == "long_temporal_f32_last") *value = plain && tp == BlockPlan::F32_LONG;
   else if (k == "attn_f32_h32_last") *value = plain ? (sp == BlockPlan::F32_H32 ? 1 : 0) | (tp == BlockPlan::F32_H32 ? 2 : 0) : 0;
   else if (k == "long_temporal_f32_h32_last") *value = plain && tp == BlockPlan::F32_H32_LONG;
@@ -491,14 +510,17 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
   const bool h128 = e->opt_attn_h128 && attn_x3_h128_ok(J, D, H) && (attn_x3_h128_ok(T, D, H) || attn_x3_h128_long_ok(T, D, H));
   // heads of 48 or 96 columns: the same pattern, the resident limit being the width's own (256 / 128 tokens)
   const bool hx = e->opt_attn_hx && attn_x3_hx_ok(J, D, H) && (attn_x3_hx_ok(T, D, H) || attn_x3_hx_long_ok(T, D, H));
-  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long || h128 || hx) && D % 32 == 0 &&
+  // heads of 16 columns in quads (H % 4 == 0): the same pattern, resident up to 256 tokens
+  const bool h16 = e->opt_attn_h16 && attn_x3_h16_ok(J, D, H) && (attn_x3_h16_ok(T, D, H) || attn_x3_h16_long_ok(T, D, H));
+  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long || h128 || hx || h16) && D % 32 == 0 &&
       e->opt_fold_layernorm) {
     p.flow = BlockPlan::FOLD;
-    // (the predicates of the widths exclude each other: D == 32 H, 128 H, 48 H or 96 H, 64 H)
-    p.attn_sp = h32 || h32_long ? BlockPlan::X3_H32 : h128 ? BlockPlan::X3_H128 : hx ? BlockPlan::X3_HX : BlockPlan::X3;
+    // (the predicates of the widths exclude each other: D == 32 H, 128 H, 48 H or 96 H, 16 H, 64 H)
+    p.attn_sp = h32 || h32_long ? BlockPlan::X3_H32 : h128 ? BlockPlan::X3_H128 : hx ? BlockPlan::X3_HX : h16 ? BlockPlan::X3_H16 : BlockPlan::X3;
     p.attn_tp = h32 ? BlockPlan::X3_H32 : h32_long ? BlockPlan::X3_H32_LONG
               : h128 ? (attn_x3_h128_ok(T, D, H) ? BlockPlan::X3_H128 : BlockPlan::X3_H128_LONG)
               : hx ? (attn_x3_hx_ok(T, D, H) ? BlockPlan::X3_HX : BlockPlan::X3_HX_LONG)
+              : h16 ? (attn_x3_h16_ok(T, D, H) ? BlockPlan::X3_H16 : BlockPlan::X3_H16_LONG)
               : tp_long ? BlockPlan::X3_LONG : BlockPlan::X3;   // (qkv_tattn_ok refuses T > 255: the long kernel is always the two-kernel branch)
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
@@ -555,10 +577,12 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
     // own flow; one or three heads of 48 columns keep the generic kernel in both precisions, bit for bit.  Else kernels_attn.hip.
     const bool fp32 = e->cfg.precision == D3D_PREC_FP32;
     const bool f32_hx = fp32 && e->opt_attn_f32_hx && D % 32 == 0;
+    const bool f32_h16 = fp32 && e->opt_attn_f32_h16;   // heads of 16 columns, any head count: resident up to 256 tokens, else streaming
     p.attn_sp = x3 && attn_temporal_x3_ok(J, D, H)                                    ? BlockPlan::X3
               : fp32 && e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H)       ? BlockPlan::F32_H32
               : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_ok(J, D, H)             ? BlockPlan::F32_H128
               : f32_hx && attn_f32_hx_ok(J, D, H)                                     ? BlockPlan::F32_HX
+              : f32_h16 && attn_f32_h16_ok(J, D, H)                                   ? BlockPlan::F32_H16
               : attn_spatial_fast_ok(J, D, H)                                         ? BlockPlan::F32_SPATIAL
                                                                                       : BlockPlan::GENERIC;
     p.attn_tp = x3 && attn_temporal_x3_ok(T, D, H)                                    ? BlockPlan::X3
@@ -569,6 +593,8 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
               : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_long_ok(T, D, H)        ? BlockPlan::F32_H128_LONG
               : f32_hx && attn_f32_hx_ok(T, D, H)                                     ? BlockPlan::F32_HX
               : f32_hx && attn_f32_hx_long_ok(T, D, H)                                ? BlockPlan::F32_HX_LONG
+              : f32_h16 && attn_f32_h16_ok(T, D, H)                                   ? BlockPlan::F32_H16
+              : f32_h16 && attn_f32_h16_long_ok(T, D, H)                              ? BlockPlan::F32_H16_LONG
               : attn_temporal_fast_ok(T, D, H)                                        ? BlockPlan::F32_TEMPORAL
                                                                                       : BlockPlan::GENERIC;
   }
@@ -1065,7 +1091,9 @@ const char* d3d_last_error(void) { return g_err.c_str(); }
 // 145: head_dim 48 and 96 admitted (FP32 and F16X3), option / info key "attn_hx", info key "attn_hx_last", d3d_op_attention_hx,
 // d3d_op_attention_long_hx
 // 146: option / info key "attn_f32_hx", info key "attn_f32_hx_last", d3d_op_attention_f32_hx, d3d_op_attention_long_f32_hx
-int d3d_version(void) { return 146; }
+// 147: option / info keys "attn_h16" and "attn_f32_h16", info keys "attn_h16_last" and "attn_f32_h16_last", d3d_op_attention_h16,
+// d3d_op_attention_long_h16, d3d_op_attention_f32_h16, d3d_op_attention_long_f32_h16
+int d3d_version(void) { return 147; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1567,6 +1595,8 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
   else if (k == "attn_f32_h128") e->opt_attn_f32_h128 = value != 0;
   else if (k == "attn_hx") e->opt_attn_hx = value != 0;
   else if (k == "attn_f32_hx") e->opt_attn_f32_hx = value != 0;
+  else if (k == "attn_h16") e->opt_attn_h16 = value != 0;
+  else if (k == "attn_f32_h16") e->opt_attn_f32_h16 = value != 0;
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1645,6 +1675,8 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "attn_f32_h128") *value = e->opt_attn_f32_h128 ? 1 : 0;
   else if (k == "attn_hx") *value = e->opt_attn_hx ? 1 : 0;
   else if (k == "attn_f32_hx") *value = e->opt_attn_f32_hx ? 1 : 0;
+  else if (k == "attn_h16") *value = e->opt_attn_h16 ? 1 : 0;
+  else if (k == "attn_f32_h16") *value = e->opt_attn_f32_h16 ? 1 : 0;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;

@@ -621,4 +621,40 @@ int d3d_op_attention_long_f32_hx(const float* qkv, float* out, int32_t B, int32_
   return D3D_OK;
 }
 
+int d3d_op_attention_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                         void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_x3_h16_ok(temporal ? T : J, D, H))
+    return fail(D3D_EUNSUP, "F16X3 attention for head_dim 16: a multiple of 4 heads, groups of up to 256 tokens");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return temporal ? launch_attn_x3_h16(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_h16(hi, lo, o, B * T, J, 1, D, H, s);
+  });
+}
+
+int d3d_op_attention_long_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_x3_h16_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 16, a multiple of 4 heads");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    return launch_attn_x3_h16_long(hi, lo, o, B, T, J, D, H, s);
+  });
+}
+
+int d3d_op_attention_f32_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                             void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_f32_h16_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "fp32 attention for head_dim 16: groups of up to 256 tokens");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIP_TRY(temporal ? launch_attn_f32_h16(qkv, out, B, T, J, D, H, s) : launch_attn_f32_h16(qkv, out, B * T, J, 1, D, H, s));
+  return D3D_OK;
+}
+
+int d3d_op_attention_long_f32_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  if (!attn_f32_h16_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 16");
+  HIP_TRY(launch_attn_f32_h16_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
+  return D3D_OK;
+}
+
 }  // extern "C"

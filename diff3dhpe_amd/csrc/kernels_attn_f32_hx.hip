@@ -1,5 +1,5 @@
 // GRAND attention cores in exact fp32 on the matrix pipe for heads of 48 and 96 columns (D == 48 H or 96 H: embed_dim 384 / 768 with the
-// runner's 8 heads; the width is D / H), on the pieces of attn_f32_tile.h at DH = 48 and 96: packed fp32 qkv rows in, fp32 rows out, no
+// runner's 8 heads; the width is D / H) and, further down, of 16 columns, on the pieces of attn_f32_tile.h at DH = 48 and 96: packed fp32 qkv rows in, fp32 rows out, no
 // pair-layout form (only FP32 engines take these kernels; option "attn_f32_hx").
 //
 //   resident   k_attn_f32_hx<DH, NKT>, one workgroup of NKT waves per (group, head), groups of N <= 32 NKT tokens `stride` tokens apart,
@@ -18,6 +18,12 @@
 // Width 48 is no multiple of the 32 x 32 accumulator tile: its second O^T tile covers columns 32 .. 63.  The V rows in LDS are 64 floats
 // with columns 48 .. 63 staged as zeros (never the next head's columns, never stale bytes), and the store skips those rows of the tile, so
 // a NaN in the neighbouring head cannot reach this one.
+//
+// Width 16 (D == 16 H: embed_dim 128 with 8 heads; option "attn_f32_h16") walks the same two templates at DH = 16 behind entry points of its
+// own (attn_f32_h16_ok / launch_attn_f32_h16 and their _long twins), resident up to 256 tokens, chunks of 256 frames.  Its one O^T tile is
+// half used, like width 48's second: V rows in LDS are 32 floats with columns 16 .. 31 staged as zeros -- never the next head's columns --
+// and rows 16 .. 31 of the tile are never stored.  1 / sqrt(16) = 0.25 is exact; the sums are scaled after the sum over d like the others.
+// 6 656 B of LDS per key tile, 53 248 B per chunk: three workgroups per CU at the largest.
 //
 // LDS: 14 848 B (width 48) / 25 088 B (width 96) per key tile; 118 784 B / 150 528 B per chunk of the streaming kernel and per group of
 // the resident one at its largest NKT -- under 160 KiB, one workgroup per CU there.
@@ -103,6 +109,16 @@ hipError_t launch_attn_f32_hx(const float* qkv, float* out, int B, int T, int J,
                               : launch_resident<96>(qkv, out, (unsigned)units, T, J, D, H, s);
 }
 
+// width 16: the same ladder at DH = 16 (8 key tiles)
+bool attn_f32_h16_ok(int N, int D, int H) { return H > 0 && D == 16 * H && N >= 1 && N <= 32 * F32Tile<16>::STREAM_KC; }
+
+hipError_t launch_attn_f32_h16(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s) {
+  if (!attn_f32_h16_ok(T, D, H) || !qkv || !out || B <= 0 || J <= 0) return hipErrorInvalidValue;
+  const long long units = (long long)B * J * H;
+  if (units > 0x7fffffffLL) return hipErrorInvalidValue;
+  return launch_resident<16>(qkv, out, (unsigned)units, T, J, D, H, s);
+}
+
 // =============================================================================================== streaming
 template <int DH>
 __global__ __launch_bounds__(512) void k_attn_f32_hx_stream(const float* __restrict__ qkv, float* __restrict__ out, int T, int J, int H,
@@ -173,6 +189,13 @@ hipError_t launch_attn_f32_hx_long(const float* qkv, float* out, int B, int T, i
   if (!attn_f32_hx_long_ok(T, D, H) || !qkv || !out || B <= 0 || J <= 0) return hipErrorInvalidValue;
   return hx_width(D, H) == 48 ? f32_launch_stream<k_attn_f32_hx_stream<48>, 48>(qkv, out, B, T, J, D, H, s)
                               : f32_launch_stream<k_attn_f32_hx_stream<96>, 96>(qkv, out, B, T, J, D, H, s);
+}
+
+bool attn_f32_h16_long_ok(int T, int D, int H) { return T >= 1 && H > 0 && D == 16 * H; }
+
+hipError_t launch_attn_f32_h16_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s) {
+  if (!attn_f32_h16_long_ok(T, D, H) || !qkv || !out || B <= 0 || J <= 0) return hipErrorInvalidValue;
+  return f32_launch_stream<k_attn_f32_hx_stream<16>, 16>(qkv, out, B, T, J, D, H, s);
 }
 
 }  // namespace d3d

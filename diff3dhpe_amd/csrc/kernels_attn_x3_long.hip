@@ -1,4 +1,4 @@
-// Temporal GRAND attention on the fp16 matrix pipe for windows of ANY length, at head widths 64, 32, 128, 48 and 96: the keys stream through
+// Temporal GRAND attention on the fp16 matrix pipe for windows of ANY length, at head widths 64, 32, 128, 48, 96 and 16: the keys stream through
 // LDS in chunks of 32 KC frames instead of all living there (kernels_attn_x3.hip, kernels_attn_x3_h32.hip, kernels_attn_x3_h128.hip: four
 // planes of resident rows = 128 of the 160 KiB).  One kernel template, k_attn_x3_stream<DH, KC>; what differs by width is
 // x3_head_shape<DH> (attn_x3_tile.h): the 64-column segments of a unit, its softmax streams, its score tile(s) and PV step(s).
@@ -7,6 +7,9 @@
 //   DH = 32    a unit is a PAIR of adjacent heads in one 128-byte row, chunks of 256 frames; sub-head p owns d-steps 2 p, 2 p + 1 of the score
 //              product and the 32-column half p of the PV product and of the output, and has its own maximum, numerators and sum.  The two
 //              are independent, so interleaving them per key tile leaves each one's MFMA and addition order as k_attn_x3_h32 has it
+//   DH = 16    a unit is a QUAD of adjacent heads in one 128-byte row, chunks of 256 frames; head p owns d-step p of the score product and an
+//              O^T accumulator of its own over 32-column line p >> 1, of which rows 16 (p & 1) .. + 15 are its 16 output columns (half a
+//              128-byte line of the pair layout; the other rows never reach memory).  Four independent streams, each in k_attn_x3_h16's order
 //   DH = 128   a unit is a head of two 64-column halves; every plane is two sub-planes of 32 KC rows, half 0 then half 1, chunks of
 //              128 frames (KC = 4: 4 planes x 128 rows x 256 B = 128 KiB).  One score chain over the eight d-steps, four 32-column quarters of PV
 //   DH = 48    a unit is a head of 48 plane columns from column 48 hd on -- not a whole 64-column segment: staged from that column, the rest
@@ -23,8 +26,8 @@
 //
 // So every exp2 sees the same m, l is summed in the same order and every accumulator takes the same MFMAs in the same order as in the
 // resident kernel of its width: for T <= 256 (DH = 128: T <= 128) the output is bit-identical to launch_attn_temporal_x3 /
-// launch_attn_x3_h32 / launch_attn_x3_h128 / launch_attn_x3_hx whatever KC is (tests/test_gpu_long_temporal.py, test_gpu_long_h32.py,
-// test_gpu_long_h128.py, test_gpu_attn_hx.py);
+// launch_attn_x3_h32 / launch_attn_x3_h128 / launch_attn_x3_hx / launch_attn_x3_h16 whatever KC is (tests/test_gpu_long_temporal.py,
+// test_gpu_long_h32.py, test_gpu_long_h128.py, test_gpu_attn_hx.py, test_gpu_attn_h16.py);
 // beyond, tests/test_gpu_attn_x3_digests.py and test_gpu_attn_x3_width_digests.py pin the bits.  The price is the scores computed twice;
 // one score tile per stream (16 registers) is live at a time.
 //
@@ -130,15 +133,15 @@ __global__ __launch_bounds__(512) void k_attn_x3_stream(const _Float16* __restri
     mb[p] = m[p] * x3_c_exp<DH>();
   }
 
-  // ---- pass 2: numerators, their sums, O^T[d][query] = sum_key V^T[d][key] * E^T[key][query] (oacc[f][dt]: 32-column line dt of segment f)
+  // ---- pass 2: numerators, their sums, O^T[d][query] = sum_key V^T[d][key] * E^T[key][query] (oacc[f][dt]: 32-column line dt of segment f; width 16: oacc[p][p >> 1], head p's own tile)
   float l[NS];
-  f32x16 oacc[SUB][2];
+  f32x16 oacc[HS::ACCS][2];
 #pragma unroll
   for (int p = 0; p < NS; ++p) l[p] = 0.f;
 #pragma unroll
   for (int q = 0; q < 16; ++q)
 #pragma unroll
-    for (int f = 0; f < SUB; ++f) { oacc[f][0][q] = 0.f; oacc[f][1][q] = 0.f; }
+    for (int f = 0; f < HS::ACCS; ++f) { oacc[f][0][q] = 0.f; oacc[f][1][q] = 0.f; }
   for (int c = 0; c < nchunks; ++c) {
     const int nkt = ntiles - c * KC < KC ? ntiles - c * KC : KC;
     stage(std::true_type{}, c, nkt);
@@ -162,22 +165,42 @@ __global__ __launch_bounds__(512) void k_attn_x3_stream(const _Float16* __restri
     // a line of the head can straddle two groups at a 16-column boundary, so every 4-column chunk takes pair_col of its own plane column
     // (out rows of 2 ceil32(D) halves: the row pitch of the layout, 2 D wherever an engine runs)
     const size_t orow = tokq * (HS::ALIGNED ? 2 * D : 2 * ((D + 31) & ~31));
+    if constexpr (DH == 16) {
+      // head p of the quad: rows 16 (p & 1) .. + 15 of its own accumulator (registers 8 (p & 1) .. + 7: chunks g4 = 2 (p & 1), + 1) are
+      // its 16 columns, half a 128-byte line; the tile's other rows hold the line neighbour's V times this head's E and stay in registers
+      const size_t vo = tokq * D3 + 2 * D + col0;
 #pragma unroll
-    for (int f = 0; f < SUB; ++f) {
-      const int c0 = col0 + 64 * f;
-      const size_t vo = tokq * D3 + 2 * D + c0;
+      for (int p = 0; p < NS; ++p) {
+        const float inv = 1.0f / (8192.0f * l[p]);
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const float inv = 1.0f / (8192.0f * l[HS::line_stream(dt)]);
-#pragma unroll
-        for (int g4 = 0; g4 < HS::line_cols(f, dt) / 8; ++g4) {
-          const int d = dt * 32 + 8 * g4 + 4 * h;
+        for (int g4 = 2 * (p & 1); g4 < 2 * (p & 1) + 2; ++g4) {
+          const int d = (p >> 1) * 32 + 8 * g4 + 4 * h;
           h4 oh, ol;
-          x3_out_chunk(oacc[f][dt], g4, inv, *reinterpret_cast<const h4*>(Ph + vo + d),
-                       *reinterpret_cast<const h4*>(Pl + vo + d), amax, oh, ol);
-          _Float16* const op = out_x3 + orow + (HS::ALIGNED ? (size_t)(2 * c0) + pair_col(d) : pair_col(c0 + d));
+          x3_out_chunk(oacc[p][p >> 1], g4, inv, *reinterpret_cast<const h4*>(Ph + vo + d), *reinterpret_cast<const h4*>(Pl + vo + d), amax,
+                       oh, ol);
+          _Float16* const op = out_x3 + orow + (size_t)(2 * col0) + pair_col(d);
           *reinterpret_cast<h4*>(op) = oh;
           *reinterpret_cast<h4*>(op + PAIR_LO) = ol;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int f = 0; f < SUB; ++f) {
+        const int c0 = col0 + 64 * f;
+        const size_t vo = tokq * D3 + 2 * D + c0;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          const float inv = 1.0f / (8192.0f * l[HS::line_stream(dt)]);
+#pragma unroll
+          for (int g4 = 0; g4 < HS::line_cols(f, dt) / 8; ++g4) {
+            const int d = dt * 32 + 8 * g4 + 4 * h;
+            h4 oh, ol;
+            x3_out_chunk(oacc[f][dt], g4, inv, *reinterpret_cast<const h4*>(Ph + vo + d),
+                         *reinterpret_cast<const h4*>(Pl + vo + d), amax, oh, ol);
+            _Float16* const op = out_x3 + orow + (HS::ALIGNED ? (size_t)(2 * c0) + pair_col(d) : pair_col(c0 + d));
+            *reinterpret_cast<h4*>(op) = oh;
+            *reinterpret_cast<h4*>(op + PAIR_LO) = ol;
+          }
         }
       }
     }
@@ -210,6 +233,7 @@ bool attn_temporal_x3_long_ok(int T, int D, int H) { return attn_x3_stream_ok<64
 bool attn_x3_h32_long_ok(int T, int D, int H) { return attn_x3_stream_ok<32>(T, D, H); }
 bool attn_x3_h128_long_ok(int T, int D, int H) { return attn_x3_stream_ok<128>(T, D, H); }
 bool attn_x3_hx_long_ok(int T, int D, int H) { return attn_x3_stream_ok<48>(T, D, H) || attn_x3_stream_ok<96>(T, D, H); }
+bool attn_x3_h16_long_ok(int T, int D, int H) { return attn_x3_stream_ok<16>(T, D, H); }
 
 hipError_t launch_attn_temporal_x3_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                         hipStream_t s) {
@@ -225,6 +249,10 @@ hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void
 hipError_t launch_attn_x3_hx_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s) {
   if (H > 0 && D == 48 * H) return launch_attn_x3_stream<48, 8>(qkv_hi, qkv_lo, out_x3, B, T, J, D, H, s);
   return launch_attn_x3_stream<96, 4>(qkv_hi, qkv_lo, out_x3, B, T, J, D, H, s);
+}
+// width 16: a quad of heads per unit, the walk of <32, 8> with four streams
+hipError_t launch_attn_x3_h16_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s) {
+  return launch_attn_x3_stream<16, 8>(qkv_hi, qkv_lo, out_x3, B, T, J, D, H, s);
 }
 
 }  // namespace d3d

@@ -232,7 +232,12 @@ class Engine:
         key-streaming for longer windows); 0 gives it the plain row-kernel flow with the generic fp32 attention kernel, "attn_f32_hx": 1
         (default) runs the attention of an FP32 engine with heads of 48 or 96 columns (embed_dim 384 / 768, 8 heads) on the exact fp32
         MFMA kernels of those widths (resident for groups of up to 256 / 192 tokens, key-streaming for longer windows); 0 keeps the
-        generic one-thread-per-row kernel); the library reads no environment."""
+        generic one-thread-per-row kernel, "attn_h16": 1 (default) keeps an F16X3 engine with a multiple of 4 heads of 16 columns
+        (embed_dim 128, 8 heads) on the folded flow, its attention on the fp16-MFMA kernels of that width (resident for groups of up to 256
+        tokens, key-streaming for longer windows); 0 gives it the plain row-kernel flow with the generic fp32 attention kernel,
+        "attn_f32_h16": 1 (default) runs the attention of an FP32 engine with heads of 16 columns on the exact fp32 MFMA kernels at that
+        width (resident for groups of up to 256 tokens, key-streaming for longer windows); 0 keeps the generic one-thread-per-row
+        kernel); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
@@ -256,7 +261,9 @@ class Engine:
         (the option), "attn_f32_h128_last" (the same three bits for an FP32 engine and the exact fp32 kernels of that width), "attn_hx"
         (the option), "attn_hx_last" (the same three bits for an F16X3 engine with heads of 48 or 96 columns and the kernels of those
         widths), "attn_f32_hx" (the option), "attn_f32_hx_last" (the same three bits for an FP32 engine with heads of 48 or 96 columns
-        and the exact fp32 kernels of those widths)."""
+        and the exact fp32 kernels of those widths), "attn_h16" (the option), "attn_h16_last" (the same three bits for an F16X3 engine
+        with a multiple of 4 heads of 16 columns and the kernels of that width), "attn_f32_h16" (the option), "attn_f32_h16_last" (the
+        same three bits for an FP32 engine with heads of 16 columns and the exact fp32 kernels at that width)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -764,6 +771,32 @@ def op_attention_long_f32_hx(qkv: torch.Tensor, B: int, T: int, J: int, H: int) 
     qkv (B*T*J, 3*D) -> (B*T*J, D), D == 48 H or 96 H, any T >= 1; wherever op_attention_f32_hx(..., temporal=True) runs bit for bit its
     result; anything else raises D3DError."""
     return _attention_op("d3d_op_attention_long_f32_hx", qkv, B, T, J, H)
+
+
+def op_attention_h16(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
+    """The resident F16X3 attention kernel for quads of heads of 16 columns alone (include/d3d.h d3d_op_attention_h16): qkv (B*T*J, 3*D) ->
+    (B*T*J, D), D == 16 H, H a multiple of 4, groups of up to 256 tokens; anything else raises D3DError.  temporal as op_attention."""
+    return _attention_op("d3d_op_attention_h16", qkv, B, T, J, H, int(bool(temporal)))
+
+
+def op_attention_long_h16(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming F16X3 temporal attention kernel for quads of heads of 16 columns alone (include/d3d.h d3d_op_attention_long_h16):
+    qkv (B*T*J, 3*D) -> (B*T*J, D), D == 16 H, H a multiple of 4, any T >= 1; for T <= 256 bit for bit op_attention_h16(..., temporal=True);
+    anything else raises D3DError."""
+    return _attention_op("d3d_op_attention_long_h16", qkv, B, T, J, H)
+
+
+def op_attention_f32_h16(qkv: torch.Tensor, B: int, T: int, J: int, H: int, temporal: bool) -> torch.Tensor:
+    """The resident exact fp32 attention kernel for heads of 16 columns alone (include/d3d.h d3d_op_attention_f32_h16): qkv (B*T*J, 3*D) ->
+    (B*T*J, D), D == 16 H (any head count), groups of up to 256 tokens (temporal: T keys, else J); anything else raises D3DError."""
+    return _attention_op("d3d_op_attention_f32_h16", qkv, B, T, J, H, int(bool(temporal)))
+
+
+def op_attention_long_f32_h16(qkv: torch.Tensor, B: int, T: int, J: int, H: int) -> torch.Tensor:
+    """The key-streaming fp32 temporal attention kernel for heads of 16 columns alone (include/d3d.h d3d_op_attention_long_f32_h16): qkv
+    (B*T*J, 3*D) -> (B*T*J, D), D == 16 H, any T >= 1; for T <= 256 bit for bit op_attention_f32_h16(..., temporal=True); anything else
+    raises D3DError."""
+    return _attention_op("d3d_op_attention_long_f32_h16", qkv, B, T, J, H)
 
 
 def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, groups: int, N: int, stride: int, H: int,

@@ -328,6 +328,28 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     section 5).  Every other head width, an odd number of heads of 48 columns (embed_dim 48, 144: they keep the
  *                     generic kernel in both precisions), F16X3 and BF16 engines: no effect.  d3d_workspace_bytes does not change.
  *                     "attn_f32_hx_last" (d3d_engine_get_info) reports what the latest forward ran.
+ *   "attn_h16"   1 (default) / 0: F16X3 engines whose heads are 16 columns wide and come in quads (embed_dim == 16 num_heads with
+ *                     num_heads a multiple of 4, e.g. 128 with 8 heads) and num_joints <= 256.  With the key on, such an engine runs the
+ *                     folded flow with the two-kernel attention branch: its spatial blocks and, for num_frame <= 256, its temporal blocks
+ *                     on the resident fp16-MFMA kernel of that width (four adjacent heads share a 128-byte LDS row; each head owns one
+ *                     16-deep step of the score product and has its own softmax, sum and output accumulator, of which only its own 16
+ *                     rows are ever stored), its temporal blocks for longer windows on the key-streaming kernel of that width (chunks of
+ *                     256 frames, the scores computed twice, bit-identical to the resident kernel wherever that runs) / 0: the plain
+ *                     row-kernel flow with the generic fp32 attention kernel in every block, as before version 147.  The two differ in
+ *                     the last bits, both inside the parity gate.  Measured: DESIGN.md section 5.  Other head counts of that width
+ *                     (embed_dim 32 with 2 heads, 96 with 6), every other head width, FP32 and BF16 engines: no effect.
+ *                     d3d_workspace_bytes does not change.  "attn_h16_last" (d3d_engine_get_info) reports what the latest forward ran.
+ *   "attn_f32_h16"    1 (default) / 0: FP32 engines whose heads are 16 columns wide (embed_dim == 16 num_heads, any head count) -- the
+ *                     exact reference arithmetic, and the engine a precision-"auto" model falls back to.  With the key on, the spatial
+ *                     blocks of such an engine (num_joints <= 256) and, for num_frame <= 256, its temporal blocks run the resident exact
+ *                     fp32 kernel at that width (v_mfma_f32_32x32x2_f32, the arithmetic of "attn_f32_hx"; the scores times the exact
+ *                     1 / sqrt(16) = 0.25 after the sum; the half-used 32-column output tile takes zeros, never the neighbouring head's
+ *                     columns), its temporal blocks for longer windows the key-streaming kernel (chunks of 256 frames, two passes,
+ *                     bit-identical to the resident kernel wherever that runs); each block type is decided on its own / 0: the generic
+ *                     one-thread-per-row kernel, as before version 147.  The two differ in the order of additions, so in the last
+ *                     bits, both inside the parity gate.  Measured: DESIGN.md section 5.  Every other head width, F16X3 and BF16
+ *                     engines: no effect.  d3d_workspace_bytes does not change.  "attn_f32_h16_last" (d3d_engine_get_info) reports what
+ *                     the latest forward ran.
  *   "proj_split" /    -1 (default): the rule.  0, 2, 4: that S for proj / fc1 in every forward that fits the kernel pair (at most 2 x CUs
  *   "fc1_split"       workgroups; fc1: M S <= 8192 rows), the default kernel elsewhere; any other value, or an S the engine's widths do not
  *                     allow (K / 32 / S >= 4 whole k-tiles, width 512): D3D_EUNSUP.  Read only while "latency_mode" is on; for
@@ -404,7 +426,11 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * columns and the F16X3 kernels of those widths; 0 before any forward, with the option off, at every other head width and in the other
  * precisions), "attn_f32_hx" (the option value), "attn_f32_hx_last" (the same three bits for a D3D_PREC_FP32 engine with heads of 48 or
  * 96 columns and the exact fp32 kernels of those widths; 0 before any forward, with the option off, at every other head width, where
- * embed_dim is no multiple of 32 and in the other precisions),
+ * embed_dim is no multiple of 32 and in the other precisions), "attn_h16" (the option value), "attn_h16_last" (the same three bits for a
+ * D3D_PREC_F16X3 engine with a multiple of 4 heads of 16 columns and the F16X3 kernels of that width; 0 before any forward, with the
+ * option off, at every other head width or head count and in the other precisions), "attn_f32_h16" (the option value),
+ * "attn_f32_h16_last" (the same three bits for a D3D_PREC_FP32 engine with heads of 16 columns and the exact fp32 kernels at that width; 0
+ * before any forward, with the option off, at every other head width and in the other precisions),
  * "small_tiles" (the option value), "small_tiles_last" (bit 0: the
  * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
  * kernel; 0 before any forward, with the option or "latency_mode" off, and in the other precisions).
@@ -711,6 +737,24 @@ int d3d_op_attention_f32_hx(const float* qkv_dev, float* out_dev, int32_t B, int
  * else: D3D_EUNSUP.  Wherever d3d_op_attention_f32_hx (temporal = 1) runs, bit for bit its result. */
 int d3d_op_attention_long_f32_hx(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
                                  void* stream);
+/* The attention core of an F16X3 engine with quads of heads of 16 columns from the resident kernel of that width alone (option
+ * "attn_h16"): fp32 qkv in, fp32 out, split into / merged from the hi / lo fp16 planes on the device as in d3d_op_attention
+ * (D3D_PREC_F16X3).  temporal != 0: groups of T keys, else of J keys.  D == 16 H, H a multiple of 4 and a group length N <= 256; anything
+ * else (head_dim 16 is the only width it takes): D3D_EUNSUP. */
+int d3d_op_attention_h16(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                         void* stream);
+/* The temporal core of such an engine from the key-streaming kernel of that width alone.  Any T >= 1; D == 16 H with H a multiple of 4,
+ * anything else: D3D_EUNSUP.  For T <= 256 bit for bit the result of d3d_op_attention_h16 (temporal = 1). */
+int d3d_op_attention_long_h16(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream);
+/* The resident exact fp32 attention kernel for heads of 16 columns alone (option "attn_f32_h16"): fp32 qkv in, fp32 out.  temporal as in
+ * d3d_op_attention (0: N = J keys, 1: N = T keys).  D == 16 H (any head count) and a group length N <= 256; anything else (head_dim 16 is
+ * the only width it takes): D3D_EUNSUP.  Not the bits of d3d_op_attention, which keeps the generic kernel at this width. */
+int d3d_op_attention_f32_h16(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
+                             void* stream);
+/* The temporal core of such an engine from the key-streaming fp32 kernel at that width alone.  Any T >= 1; D == 16 H, anything else:
+ * D3D_EUNSUP.  For T <= 256 bit for bit the result of d3d_op_attention_f32_h16 (temporal = 1). */
+int d3d_op_attention_long_f32_h16(const float* qkv_dev, float* out_dev, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H,
+                                  void* stream);
 /* The fused qkv GEMM + attention kernel of the BF16 mode alone: out = attention(bf16(A) bf16(Wqkv)^T + bias) with q / k / v rounded to
  * bf16 (q third times dh^-1/2) and kept on chip -- bit for bit d3d_op_linear (D3D_PREC_BF16) followed by d3d_op_attention (D3D_PREC_BF16)
  * on the same tensors.  A: (groups * N, D) fp32 token rows; Wqkv: (3 D, D); bias: (3 D); out: (groups * N, D) fp32.  Group u holds the N
