@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "d3d_engine_set_trace", "d3d_engine_trace_read", "d3d_engine_range_flags", "d3d_op_head", "d3d_engine_set_option",
     "d3d_weighted_loss", "d3d_repeat_batch", "d3d_hypothesis_mean", "d3d_engine_get_info", "d3d_probe_machine",
     "d3d_engine_range_post", "d3d_engine_range_take", "d3d_window_gather_s2f", "d3d_pose_metrics", "d3d_op_qkv_attn_bf16",
-    "d3d_op_qkv_attn_x3_small", "d3d_op_linear_folded", "d3d_op_linear_plane_residual", "d3d_op_layernorm_forms",
+    "d3d_op_qkv_attn_x3_small", "d3d_op_qkv_attn_x3_narrow", "d3d_op_linear_folded", "d3d_op_linear_plane_residual", "d3d_op_layernorm_forms",
 ]
 
 
@@ -119,6 +119,7 @@ def _bind(lib: C.CDLL) -> None:
         "d3d_op_attention_long_f32_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
         "d3d_op_qkv_attn_bf16": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "d3d_op_qkv_attn_x3_small": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "d3d_op_qkv_attn_x3_narrow": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, i32, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

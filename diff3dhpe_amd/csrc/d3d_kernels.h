@@ -270,6 +270,14 @@ long long qkv_attn_x3_small_workgroups(long long groups, int N);
 hipError_t launch_qkv_attn_x3_small(const void* Apair, const void* Wpair_tileorder, const float* bias_to, const float* csum_to, const float* st_in,
                                     int st_np, float eps, int w_exp, void* out_x3, int groups, int N, int stride, int J, int K, int D, int H,
                                     hipStream_t s);
+// "fused_narrow": the same kernel for heads of 32 columns in pairs (D = 32 H, H even) or of 16 columns in quads (D = 16 H, H % 4 == 0): a
+// pair / a quad is one 64-column segment, D / 64 workgroups per row tile, the images in the tile order of D / 64 pseudo-heads
+// (tile_order_src_row(r, D, D / 64)).  K == D >= 128; spatial groups of any J <= 127 joints, temporal ones of T <= 127 frames.  Bit-identical
+// to the folded qkv GEMM followed by launch_attn_x3_h32 / launch_attn_x3_h16.
+bool qkv_attn_x3_narrow_ok(int N, int stride, int J, int D, int H, int K);
+hipError_t launch_qkv_attn_x3_narrow(const void* Apair, const void* Wpair_tileorder, const float* bias_to, const float* csum_to, const float* st_in,
+                                     int st_np, float eps, int w_exp, void* out_x3, int groups, int N, int stride, int J, int K, int D, int H,
+                                     hipStream_t s);
 
 // ---- kernels_elem.hip -------------------------------------------------------------------------------------------
 // Row LayerNorm; optionally also writes a second LayerNorm of the first result (post-norm -> next block's norm1).

@@ -45,8 +45,8 @@ struct BlockW : BlockSrc {   // (the block's fp32 tensors, here in the device ar
   // LayerNorm-folded forms (X3Fold, d3d_kernels.h; fold_layernorm, weight_pack.h) for norm1 -> qkv and norm2 -> fc1
   const uint16_t *qkv_f3 = nullptr, *fc1_f3 = nullptr;
   const float *qkv_cs = nullptr, *qkv_fb = nullptr, *fc1_cs = nullptr, *fc1_fb = nullptr;
-  // fused qkv + attention kernels (kernels_qkv_sattn.hip, kernels_qkv_tattn.hip): the folded qkv weight / csum / bias with HEAD-MAJOR
-  // rows (tile_order_src_row, weight_pack.h)
+  // fused qkv + attention kernels (kernels_qkv_sattn.hip, kernels_qkv_tattn.hip, kernels_qkv_attn_x3_small.hip): the folded qkv weight /
+  // csum / bias with HEAD-MAJOR rows (tile_order_src_row, weight_pack.h; heads of 32 / 16 columns: by 64-column segment)
   const uint16_t* qkv_f3h = nullptr;
   const float *qkv_csh = nullptr, *qkv_fbh = nullptr;
   // exponent k of each weight's planes (2^k w; 12 unless a weight exceeds 15.99: split_weight_f16x3)
@@ -74,6 +74,9 @@ struct BlockPlan {
   // FOLD with "latency_mode" and "small_tiles": the fused qkv + attention step of the spatial / temporal blocks on 128-row tiles
   // (kernels_qkv_attn_x3_small.hip) where the 256-row launch would leave CUs without a workgroup; block 0 keeps its direct form
   bool small_sp = false, small_tp = false;
+  // FOLD with "fused_narrow" at head widths 32 / 16: the qkv GEMM and the attention of the spatial blocks (block 0 included) / of the
+  // temporal blocks (T <= 127) as one launch of the same kernel's narrow forms, in place of the GEMM + attn_sp / attn_tp pair
+  bool narrow_sp = false, narrow_tp = false;
   // BF16: whole-row proj / fc2 with their LayerNorms in the epilogue; qkv / fc1 on the hand-specialised GEMM kernel
   bool rows = false, bf16q_qkv = false, bf16q_fc1 = false;
 };
@@ -190,6 +193,10 @@ struct d3d_engine {
   // most 5/8 as many workgroups as the device has CUs (bit-identical to the two-kernel flow, so NOT to the grouped temporal form it
   // replaces); 0 (default) = every launch as without the key
   bool opt_small_tiles = false;
+  // "fused_narrow" (off by default): an F16X3 engine whose heads are 32 columns wide in pairs or 16 wide in quads runs the qkv GEMM and the
+  // attention of its spatial blocks, and of its temporal blocks for windows of up to 127 frames, as ONE kernel (the narrow forms of
+  // kernels_qkv_attn_x3_small.hip: q / k / v never reach HBM); bit-identical to the two launches it replaces.  Not tied to "latency_mode"
+  bool opt_fused_narrow = false;
   // fc1's partials (S M Dm floats) fit no region of the workspace that is dead at that point for every S: an engine-owned buffer,
   // FC1_SPLITK_SCRATCH_FLOATS per slot, allocated when "latency_mode" is switched on and freed when it is switched off.  Slot 1 serves
   // the second half-batch of a two-stream sampling (the halves run concurrently), allocated by the first such call.
@@ -558,6 +565,12 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
         p.small_tp = p.fused_tp && qkv_attn_x3_small_ok(T, J, J, D, H, D) && wg_tp < cus && fits((long long)B * J, T);
       }
     }
+    if (e->opt_fused_narrow && (long long)M * 4 * D < (1LL << 32)) {   // (the kernel's 32-bit row offsets)
+      // wherever the two-kernel branch would run the resident kernel of width 32 / 16 and the commit made the tile-order images
+      const auto narrow = [](BlockPlan::Attn a) { return a == BlockPlan::X3_H32 || a == BlockPlan::X3_H16; };
+      p.narrow_sp = narrow(p.attn_sp) && qkv_attn_x3_narrow_ok(J, 1, J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
+      p.narrow_tp = narrow(p.attn_tp) && qkv_attn_x3_narrow_ok(T, J, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
+    }
   } else if (e->cfg.precision == D3D_PREC_BF16) {
     p.flow = BlockPlan::BF16;
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_bf16_ok(T, J, D, H, B);
@@ -716,6 +729,13 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
       Prof p(e, temporal ? D3D_KC_QKV_TATTN : D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)N * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
       HIP_TRY(launch_qkv_attn_x3_small(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, temporal ? B * J : B * T, N,
                                        temporal ? J : 1, J, D, D, e->H, s));
+      TRACE(k, 3, 0, AOx, MDb);
+    } else if (temporal ? pl.narrow_tp : pl.narrow_sp) {
+      // "fused_narrow", head widths 32 / 16: the same fused step, a pair / a quad of heads per 64-column segment; block 0 included
+      const int N = temporal ? T : J;
+      Prof p(e, temporal ? D3D_KC_QKV_TATTN : D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)N * D, 2.0 * MD4 + 4.0 * 3.0 * D * D, s);
+      HIP_TRY(launch_qkv_attn_x3_narrow(XP, bw.qkv_f3h, bw.qkv_fbh, bw.qkv_csh, w.ST1, np1, e->ln_eps, bw.qkv_fe, AOx, temporal ? B * J : B * T, N,
+                                        temporal ? J : 1, J, D, D, e->H, s));
       TRACE(k, 3, 0, AOx, MDb);
     } else if (temporal && pl.fused_tp) {
       // temporal block: q, k, v of one (batch, joint) group stay in LDS and feed the T-key attention in the same kernel (kernels_qkv_tattn.hip)
@@ -1093,7 +1113,8 @@ const char* d3d_last_error(void) { return g_err.c_str(); }
 // 146: option / info key "attn_f32_hx", info key "attn_f32_hx_last", d3d_op_attention_f32_hx, d3d_op_attention_long_f32_hx
 // 147: option / info keys "attn_h16" and "attn_f32_h16", info keys "attn_h16_last" and "attn_f32_h16_last", d3d_op_attention_h16,
 // d3d_op_attention_long_h16, d3d_op_attention_f32_h16, d3d_op_attention_long_f32_h16
-int d3d_version(void) { return 147; }
+// 148: option / info key "fused_narrow", info key "fused_narrow_last", d3d_op_qkv_attn_x3_narrow
+int d3d_version(void) { return 148; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -1224,7 +1245,12 @@ int d3d_engine_commit_weights(d3d_engine* e) {
   std::vector<BlockSrc> src;
   for (int k = 0; k < e->nblk; ++k) src.push_back(block_tensors(k, host_w));
   PackedWeights pk;
-  if (x3 && !pack_f16x3(src, D, e->Dm, e->H, qkv_sattn_ok(e->J, e->D, e->H, e->D), qkv_tattn_ok(e->T, e->J, e->D, e->H, e->D), pk))
+  // the tile-order images: for the fused kernels of width 64 in the order of the H heads; for "fused_narrow" (widths 32 / 16, which no
+  // predicate of width 64 admits) in the order of D / 64 pseudo-heads -- a pair / a quad of heads is one 64-column segment
+  const bool narrow_s = qkv_attn_x3_narrow_ok(e->J, 1, e->J, e->D, e->H, e->D), narrow_t = qkv_attn_x3_narrow_ok(e->T, e->J, e->J, e->D, e->H, e->D);
+  const size_t tile_heads = narrow_s || narrow_t ? D / 64 : (size_t)e->H;
+  if (x3 && !pack_f16x3(src, D, e->Dm, tile_heads, narrow_s || qkv_sattn_ok(e->J, e->D, e->H, e->D),
+                        narrow_t || qkv_tattn_ok(e->T, e->J, e->D, e->H, e->D), pk))
     return fail(D3D_EHIP, "internal: head-major qkv planes got a different exponent");
   if (e->cfg.precision == D3D_PREC_BF16) pack_bf16(src, D, e->Dm, pk);
   e->weights_clamped = pk.clamped;
@@ -1607,6 +1633,10 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
     if (value != 0 && value != 1) return fail(D3D_EINVAL, "small_tiles must be 0 or 1");
     e->opt_small_tiles = value != 0;
   }
+  else if (k == "fused_narrow") {
+    if (value != 0 && value != 1) return fail(D3D_EINVAL, "fused_narrow must be 0 or 1");
+    e->opt_fused_narrow = value != 0;
+  }
   else if (k == "streams") {
     if (value != 1 && value != 2) return fail(D3D_EINVAL, "streams must be 1 or 2");
     e->opt_streams = (int)value;
@@ -1686,6 +1716,9 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "small_tiles") *value = e->opt_small_tiles ? 1 : 0;
   else if (k == "small_tiles_last")
     *value = e->last_plan.flow == BlockPlan::FOLD ? (e->last_plan.small_sp ? 1 : 0) | (e->last_plan.small_tp ? 2 : 0) : 0;
+  else if (k == "fused_narrow") *value = e->opt_fused_narrow ? 1 : 0;
+  else if (k == "fused_narrow_last")
+    *value = e->last_plan.flow == BlockPlan::FOLD ? (e->last_plan.narrow_sp ? 1 : 0) | (e->last_plan.narrow_tp ? 2 : 0) : 0;
   else if (k == "fc1_split") *value = e->opt_fc1_split;
   else if (k == "fused_spatial_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.fused_sp;
   else if (k == "bf16_fused_spatial_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_sp;

@@ -424,6 +424,46 @@ int d3d_op_qkv_attn_x3_small(const float* X, const float* Wqkv, const float* bia
   return finish(le, s);
 }
 
+int d3d_op_qkv_attn_x3_narrow(const float* X, const float* Wqkv, const float* bias, const float* gamma, const float* beta, float eps,
+                              int32_t groups, int32_t N, int32_t stride, int32_t D, int32_t H, int32_t temporal, float* out, void* stream) {
+  if (!X || !Wqkv || !bias || !gamma || !beta || !out || groups <= 0 || N <= 0 || stride <= 0 || D <= 0 || H <= 0 || groups % stride || !(eps > 0.f))
+    return fail(D3D_EINVAL, "bad argument");
+  const int J = temporal ? stride : N;
+  if ((!temporal && stride != 1) || !qkv_attn_x3_narrow_ok(N, stride, J, D, H, D) || (long long)groups * N * 4 * D >= (1LL << 32))
+    return fail(D3D_EUNSUP, "fused F16X3 qkv + attention for narrow heads: D = 32 H (H even) or 16 H (H % 4 == 0), D >= 128, groups of <= 127 tokens "
+                            "(spatial: stride 1)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // the LayerNorm fold and the tile-order images of the weight commit (D / 64 pseudo-heads), on the host
+  const size_t R3 = 3 * (size_t)D, nk = R3 * D, rows = (size_t)groups * N;
+  std::vector<float> hw(nk), hg(D), hb(D), hbias(R3), wg(nk), fold(2 * R3), fold_t(2 * R3);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(hw.data(), Wqkv, nk * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hg.data(), gamma, (size_t)D * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hb.data(), beta, (size_t)D * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hbias.data(), bias, R3 * sizeof(float), hipMemcpyDeviceToHost));
+  fold_layernorm(hw.data(), hbias.data(), hg.data(), hb.data(), R3, D, wg.data(), fold.data(), fold.data() + R3);
+  std::vector<uint16_t> pr(2 * nk, 0);
+  const int wexp = tile_order_copy(wg.data(), fold.data(), fold.data() + R3, D, (size_t)D / 64, pr.data(), fold_t.data(), fold_t.data() + R3);
+  // buffers of EXACTLY the operand sizes (the kernel reads no pad rows); the output starts as NaN planes: a row the kernel skipped shows
+  DevBuf<uint16_t> wp, xp, op;
+  DevBuf<float> fd, st;
+  HIP_TRY(wp.upload(pr.data(), pr.size()));
+  HIP_TRY(fd.upload(fold_t.data(), fold_t.size()));
+  HIP_TRY(xp.alloc(2 * rows * D));
+  HIP_TRY(op.alloc(2 * rows * D));
+  HIP_TRY(st.alloc(rows * 2));
+  hipError_t le = hipMemsetAsync(op.p, 0xff, 2 * rows * D * sizeof(uint16_t), s);
+  if (le == hipSuccess) {  // the stream entry row kernel: planes of 8 x + one (sum, sum of squares) per row
+    LnArgs a = ln_rows((int)rows, D, (int)rows);
+    a.x = X; a.skip_ln1 = 1; a.y_x3 = xp.p; a.stats = st.p;
+    le = launch_layernorm(a, s);
+  }
+  if (le == hipSuccess)
+    le = launch_qkv_attn_x3_narrow(xp.p, wp.p, fd.p + R3, fd.p, st.p, 1, eps, wexp, op.p, groups, N, stride, J, D, D, H, s);
+  if (le == hipSuccess) le = launch_unsplit_pair(op.p, out, rows, D, s);
+  return finish(le, s);
+}
+
 int d3d_op_layernorm(const float* x, const float* gamma, const float* beta, float* out, int32_t rows, int32_t D, float eps,
                      void* stream) {
   if (!x || !gamma || !beta || !out) return fail(D3D_EINVAL, "null tensor");

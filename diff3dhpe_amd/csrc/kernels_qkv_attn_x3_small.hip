@@ -28,10 +28,17 @@
 // LDS map (137 KiB, one workgroup per CU): [0, 40 K) stage 0 | [40 K, 80 K) stage 1; after the k-loop, from 0: Q hi | Q lo | K hi | K lo
 // planes of 128 rows x 128 B, V hi | V lo planes of 160 rows (rows 128 .. 159, read for the pad keys of the tile's last group, are
 // zeroed), one 4 KiB output patch per wave; behind them 1 KiB of per-row LayerNorm statistics.
+//
+// NARROW heads (the "fused_narrow" engine option, not tied to "latency_mode"): the same kernel for heads of 32 columns in pairs (D = 32 H)
+// or of 16 columns in quads (D = 16 H) -- a pair / a quad is one 64-column segment of the plane rows, the "head" of everything above, and
+// a row tile has D / 64 of them.  Only the attention step differs (qm_attention_narrow: every head of the segment with its own scores,
+// softmax and sum, as k_attn_x3_h32 / k_attn_x3_h16) and is bit-identical to the folded qkv GEMM followed by those kernels
+// (tests/test_gpu_fused_narrow.py).
 #include "d3d_kernels.h"
 #include "qkv_fused_kloop.h"
 
 #include <math.h>
+#include <type_traits>
 
 namespace d3d {
 namespace {
@@ -65,6 +72,7 @@ struct QmArgs {
   int K, D;                // GEMM depth, model width (8 heads x 64)
   int N, udiv;             // tokens of a group, token stride: token t of group u is row (u / udiv) * N * udiv + u % udiv + t * udiv
   int g, units, mtiles;    // groups per tile, groups of the launch, ceil(units / g)
+  int nseg;                // 64-column segments of a row = workgroups per M-tile: D / 64 (read by the narrow forms alone; 8 at width 64)
   unsigned* range;         // the engine's range-guard word
 };
 
@@ -137,14 +145,90 @@ __device__ __forceinline__ void qm_attention(unsigned char* lds, int wave, int l
     }
 }
 
+// The same job for heads NARROWER than the 64-column segment ("fused_narrow"): DH = 32, two heads per segment, or DH = 16, four.  The streams
+// of x3_head_shape<DH> one after the other, each with its own scores, softmax and sum, as k_attn_x3_h32 / k_attn_x3_h16 run them on the
+// planes in HBM: head p of a pair takes d-steps 2 p, 2 p + 1 and 32-column line p; head p of a quad takes d-step p and rows
+// 16 (p & 1) .. + 15 of an accumulator of its own over line p >> 1 (the other 16 rows, the line neighbour's V times this head's E, stay in
+// registers).  A line leaves through the patch as soon as its heads are done, so one stream's tiles are live at a time.
+template <int NKT, int DH>
+__device__ __forceinline__ void qm_attention_narrow(unsigned char* lds, int wave, int lane, int rb, int qt, int T, _Float16* out0, size_t tstride,
+                                                    unsigned* rw) {
+  static_assert(DH == 32 || DH == 16, "two or four heads per 64-column segment");
+  const unsigned char* const sQh = lds + QM_Q;
+  const unsigned char* const sKh = lds + QM_K;
+  const unsigned char* const sVh = lds + QM_V;
+  const unsigned char* const sVl = lds + QM_V + QM_VPLANE;
+  unsigned char* const patch = lds + QM_PATCH + wave * 4096;
+  const int tq = 32 * qt + (lane & 31);
+  const int tqc = tq < T ? tq : 0;                                   // rows >= T reuse row 0: never stored
+  _Float16* const po_ptr = out0 + (size_t)(32 * qt + (lane >> 3)) * tstride + 8 * (lane & 7);
+  float amax = 0.0f;            // range guard (rows tq >= T are never stored)
+  auto stream = [&](auto pc) {
+    constexpr int P = decltype(pc)::value;
+    constexpr int KS0 = DH == 32 ? 2 * P : P, NKS = DH == 32 ? 2 : 1;   // the head's d-steps of the segment
+    constexpr int DT = DH == 32 ? P : P >> 1;                           // its 32-column line
+    constexpr int G0 = DH == 32 ? 0 : 2 * (P & 1), NG = DH == 32 ? 4 : 2;   // its 8-column chunks of that line
+    // Every LDS address of a stream depends on (lane, rb) alone, so the compiler forms those of all streams up front and overlaps the
+    // streams' tiles (scratch at NKT = 4).  A scheduling barrier and an opaque copy of the lane per stream keep them one after the other.
+    __builtin_amdgcn_sched_barrier(0);
+    int lane_s = lane;
+    asm volatile("" : "+v"(lane_s));
+    const int r = lane_s & 31, h = lane_s >> 5;
+    h8 qh[4], ql[4];            // ([KS0, KS0 + NKS) alone are used)
+#pragma unroll
+    for (int ks = KS0; ks < KS0 + NKS; ++ks) {
+      const int qo = kswz(rb + tqc, 2 * ks + h);
+      qh[ks] = *reinterpret_cast<const h8*>(sQh + qo);
+      ql[ks] = *reinterpret_cast<const h8*>(sQh + QM_PLANE + qo);
+    }
+    f32x16 sacc[NKT];
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) sacc[kt] = x3_score_tile<KS0, NKS>(sKh, sKh + QM_PLANE, rb + kt * 32, r, h, qh, ql);
+    const float l = x3_softmax<NKT, DH>(sacc, h, T);
+    f32x16 oacc[2];             // ([DT] alone is used; at width 16 only the head's 16 rows of it are stored)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) oacc[DT][q] = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) x3_pv_tile<true, DT, 1>(sacc[kt], sVh, sVl, rb, kt, T, lane_s, h, oacc);
+    const float inv = 1.0f / (8192.0f * l);
+#pragma unroll
+    for (int g4 = G0; g4 < G0 + NG; ++g4) {
+      const int vo = vswz(rb + tqc, DT * 4 + g4) + 8 * h;
+      h4 oh, ol;
+      x3_out_chunk(oacc[DT], g4, inv, *reinterpret_cast<const h4*>(sVh + vo), *reinterpret_cast<const h4*>(sVl + vo), amax, oh, ol);
+      patch_wr(patch, r, h, g4, oh, ol);
+    }
+    if constexpr (DH == 32 || (P & 1)) {   // line DT is whole: out as 128-byte lines of the pair layout
+      asm volatile("" ::: "memory");       // (the rows read back were written by other lanes)
+      u32x4 po[4];                         // [pp]: row 32 qt + 8 pp + (lane >> 3), chunk lane & 7 of line DT
+#pragma unroll
+      for (int pp = 0; pp < 4; ++pp) po[pp] = patch_rd(patch, 8 * pp + (lane_s >> 3), lane_s & 7);
+      asm volatile("" ::: "memory");       // (the next line, and the wave's next job, reuse the patch)
+#pragma unroll
+      for (int pp = 0; pp < 4; ++pp)
+        if (32 * qt + 8 * pp + (lane_s >> 3) < T) *reinterpret_cast<u32x4*>(po_ptr + (size_t)(8 * pp) * tstride + DT * 64) = po[pp];
+    }
+  };
+  stream(std::integral_constant<int, 0>{});
+  stream(std::integral_constant<int, 1>{});
+  if constexpr (DH == 16) {
+    stream(std::integral_constant<int, 2>{});
+    stream(std::integral_constant<int, 3>{});
+  }
+  if (tq < T && amax > X3_HALF_MAX * 0.125f) range_raise(rw, RANGE_BIT_ACT);
+}
+
 }  // namespace
 
 // NKT = ceil(N / 32) key tiles of a group: 1 for the spatial blocks and temporal groups of <= 32 frames, up to 4 (N <= 127)
-template <int NKT>
+// DH: the head width -- 64: one head per 64-column segment, eight segments ("small_tiles"); 32 / 16: a pair / a quad of heads per segment,
+// D / 64 segments ("fused_narrow").  Everything but the attention step and the segment count is the width's own copy of the same code.
+template <int NKT, int DH = 64>
 __global__ __launch_bounds__(512) void k_qkv_attn_x3_small(QmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int b = (int)blockIdx.x;
-  KL_XCD_TILE_ORDER(a.mtiles, 8);      // all heads of an M-tile on one XCD, as the GEMMs walk
+  const int nseg = DH == 64 ? 8 : a.nseg;
+  KL_XCD_TILE_ORDER(a.mtiles, nseg);   // all heads of an M-tile on one XCD, as the GEMMs walk
   int mt = 0, hd = 0;
   tile_of(b, mt, hd);
   const int K = a.K;
@@ -269,7 +353,8 @@ __global__ __launch_bounds__(512) void k_qkv_attn_x3_small(QmArgs a) {
     const int unit = mt * a.g + u;
     if (32 * qt >= a.N || unit >= a.units) continue;                    // (wave-uniform)
     _Float16* const out0 = a.out + (size_t)qm_unit_row(a, unit) * 2 * a.D + hd * 128;
-    qm_attention<NKT>(lds, wave, lane, u * a.N, qt, a.N, out0, (size_t)a.udiv * 2 * a.D, a.range);
+    if constexpr (DH == 64) qm_attention<NKT>(lds, wave, lane, u * a.N, qt, a.N, out0, (size_t)a.udiv * 2 * a.D, a.range);
+    else qm_attention_narrow<NKT, DH>(lds, wave, lane, u * a.N, qt, a.N, out0, (size_t)a.udiv * 2 * a.D, a.range);
   }
 }
 
@@ -295,7 +380,7 @@ hipError_t launch_qkv_attn_x3_small(const void* Apair, const void* Wpair_tileord
   a.A = (const char*)Apair; a.W = (const char*)Wpair_tileorder; a.bias = bias_to; a.csum = csum_to; a.st_in = st_in;
   a.st_np = st_np; a.eps = eps; a.out_scale = ldexpf(1.0f, -(3 + w_exp));
   a.out = (_Float16*)out_x3; a.K = K; a.D = D; a.N = N; a.udiv = stride;
-  a.g = QM_ROWS / N; a.units = groups; a.mtiles = (groups + a.g - 1) / a.g;
+  a.g = QM_ROWS / N; a.units = groups; a.mtiles = (groups + a.g - 1) / a.g; a.nseg = 8;
   a.range = launch_range_word();
   if ((long long)a.mtiles * 8 > 0x7fffffffLL) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(a.mtiles * 8));
@@ -305,6 +390,50 @@ hipError_t launch_qkv_attn_x3_small(const void* Apair, const void* Wpair_tileord
     case 3: return launch_lds<k_qkv_attn_x3_small<3>>(grid, dim3(512), QM_LDS, s, a);
     default: return launch_lds<k_qkv_attn_x3_small<4>>(grid, dim3(512), QM_LDS, s, a);
   }
+}
+
+// "fused_narrow": the same tiles for heads of 32 columns in pairs (D = 32 H, H even) or of 16 columns in quads (D = 16 H, H % 4 == 0) -- a
+// pair / a quad is one 64-column segment, and the tile-order images are built with D / 64 pseudo-heads.  K = D >= 128 in whole pairs of
+// k-tiles (both widths make D a multiple of 64).  Spatial groups are the J <= 127 joints of a frame, ANY J: nothing here mirrors
+// kernels_qkv_sattn.hip; temporal ones the T <= 127 frames of a joint.
+static int qm_narrow_width(int D, int H) {
+  if (H >= 2 && H % 2 == 0 && D == 32 * H) return 32;
+  if (H >= 4 && H % 4 == 0 && D == 16 * H) return 16;
+  return 0;
+}
+bool qkv_attn_x3_narrow_ok(int N, int stride, int J, int D, int H, int K) {
+  if (!(qm_narrow_width(D, H) != 0 && K == D && K >= 128 && N >= 1 && N <= QM_ROWS && J >= 1)) return false;
+  return stride == 1 && N == J ? true : stride == J;
+}
+
+template <int DH>
+static hipError_t launch_narrow_nkt(const dim3 grid, int nkt, hipStream_t s, const QmArgs& a) {
+  switch (nkt) {
+    case 1: return launch_lds<k_qkv_attn_x3_small<1, DH>>(grid, dim3(512), QM_LDS, s, a);
+    case 2: return launch_lds<k_qkv_attn_x3_small<2, DH>>(grid, dim3(512), QM_LDS, s, a);
+    case 3: return launch_lds<k_qkv_attn_x3_small<3, DH>>(grid, dim3(512), QM_LDS, s, a);
+    default: return launch_lds<k_qkv_attn_x3_small<4, DH>>(grid, dim3(512), QM_LDS, s, a);
+  }
+}
+
+// arguments as launch_qkv_attn_x3_small; the images in the tile order of D / 64 pseudo-heads
+hipError_t launch_qkv_attn_x3_narrow(const void* Apair, const void* Wpair_tileorder, const float* bias_to, const float* csum_to, const float* st_in,
+                                     int st_np, float eps, int w_exp, void* out_x3, int groups, int N, int stride, int J, int K, int D, int H,
+                                     hipStream_t s) {
+  if (!qkv_attn_x3_narrow_ok(N, stride, J, D, H, K) || groups < 1 || groups % stride != 0 || st_np < 1 || !Apair || !Wpair_tileorder || !bias_to ||
+      !csum_to || !st_in || !out_x3 || Apair == out_x3)
+    return hipErrorInvalidValue;
+  if (w_exp < -14 || w_exp > 12) return hipErrorInvalidValue;
+  if ((long long)groups * N * 4 * K >= (1LL << 32)) return hipErrorInvalidValue;   // 32-bit lane offsets
+  QmArgs a{};
+  a.A = (const char*)Apair; a.W = (const char*)Wpair_tileorder; a.bias = bias_to; a.csum = csum_to; a.st_in = st_in;
+  a.st_np = st_np; a.eps = eps; a.out_scale = ldexpf(1.0f, -(3 + w_exp));
+  a.out = (_Float16*)out_x3; a.K = K; a.D = D; a.N = N; a.udiv = stride;
+  a.g = QM_ROWS / N; a.units = groups; a.mtiles = (groups + a.g - 1) / a.g; a.nseg = D / 64;
+  a.range = launch_range_word();
+  if ((long long)a.mtiles * a.nseg > 0x7fffffffLL) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(a.mtiles * a.nseg));
+  return qm_narrow_width(D, H) == 32 ? launch_narrow_nkt<32>(grid, (N + 31) / 32, s, a) : launch_narrow_nkt<16>(grid, (N + 31) / 32, s, a);
 }
 
 // workgroups of a launch over `groups` groups of N tokens (the engine's plan)

@@ -61,7 +61,9 @@ struct PackedWeights {
   bool clamped = false;           // a GEMM weight was not finite, or F16X3: a matrix's exponent is below F16X3_MIN_WEIGHT_EXP
 };
 // F16X3: the four GEMM weights of every block as planes, the LayerNorm-folded qkv / fc1 forms and, for the spatial (tile_order_s) /
-// temporal (tile_order_t) blocks, the folded qkv once more in tile order.  false: the internal exponent check failed.
+// temporal (tile_order_t) blocks, the folded qkv once more in tile order.  H: the heads of that order -- the model's at head width 64,
+// D / 64 pseudo-heads for the fused kernel of narrower heads (a pair of 32 columns, a quad of 16: one 64-column segment); nothing else
+// reads it.  false: the internal exponent check failed.
 bool pack_f16x3(const std::vector<BlockSrc>& src, size_t D, size_t Dm, size_t H, bool tile_order_s, bool tile_order_t, PackedWeights& out);
 // BF16: bf16 copies of the four GEMM weights of every block, [rows padded to 256][K]
 void pack_bf16(const std::vector<BlockSrc>& src, size_t D, size_t Dm, PackedWeights& out);

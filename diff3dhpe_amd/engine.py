@@ -237,7 +237,9 @@ class Engine:
         tokens, key-streaming for longer windows); 0 gives it the plain row-kernel flow with the generic fp32 attention kernel,
         "attn_f32_h16": 1 (default) runs the attention of an FP32 engine with heads of 16 columns on the exact fp32 MFMA kernels at that
         width (resident for groups of up to 256 tokens, key-streaming for longer windows); 0 keeps the generic one-thread-per-row
-        kernel); the library reads no environment."""
+        kernel, "fused_narrow": 0 (default); 1 runs the qkv GEMM and the attention of an F16X3 engine with heads of 32 columns in pairs
+        or 16 columns in quads (embed_dim 256 / 128 with 8 heads) as one kernel in its spatial blocks and, for num_frame <= 127, in its
+        temporal blocks -- q / k / v stay in LDS; bit-identical to 0); the library reads no environment."""
         _lib.check(_lib.lib().d3d_engine_set_option(self._h, key.encode(), int(value)))
 
     @_locked
@@ -263,7 +265,9 @@ class Engine:
         widths), "attn_f32_hx" (the option), "attn_f32_hx_last" (the same three bits for an FP32 engine with heads of 48 or 96 columns
         and the exact fp32 kernels of those widths), "attn_h16" (the option), "attn_h16_last" (the same three bits for an F16X3 engine
         with a multiple of 4 heads of 16 columns and the kernels of that width), "attn_f32_h16" (the option), "attn_f32_h16_last" (the
-        same three bits for an FP32 engine with heads of 16 columns and the exact fp32 kernels at that width)."""
+        same three bits for an FP32 engine with heads of 16 columns and the exact fp32 kernels at that width), "fused_narrow" (the
+        option), "fused_narrow_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent forward of an F16X3
+        engine ran the fused qkv + attention kernel for heads of 32 or 16 columns; else 0)."""
         v = C.c_int64(0)
         _lib.check(_lib.lib().d3d_engine_get_info(self._h, key.encode(), C.byref(v)))
         return int(v.value)
@@ -828,6 +832,22 @@ def op_qkv_attn_x3_small(x: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor
         _lib.check(_lib.lib().d3d_op_qkv_attn_x3_small(_ptr(a), _ptr(_f32c(Wqkv, dev)), _ptr(_f32c(bias, dev)), _ptr(_f32c(gamma, dev)),
                                                        _ptr(_f32c(beta, dev)), float(eps), int(groups), int(N), int(stride), D, int(H),
                                                        int(temporal), _ptr(out), st))
+    return out
+
+
+def op_qkv_attn_x3_narrow(x: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                          groups: int, N: int, stride: int, H: int, temporal: bool) -> torch.Tensor:
+    """The fused F16X3 qkv GEMM + attention kernel of "fused_narrow" alone (include/d3d.h d3d_op_qkv_attn_x3_narrow), for heads of 32
+    columns in pairs or 16 columns in quads: the arguments of op_qkv_attn_x3_small."""
+    dev = x.device
+    D = x.shape[-1]
+    a = _f32c(x, dev).reshape(groups * N, D)
+    out = torch.empty((groups * N, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().d3d_op_qkv_attn_x3_narrow(_ptr(a), _ptr(_f32c(Wqkv, dev)), _ptr(_f32c(bias, dev)), _ptr(_f32c(gamma, dev)),
+                                                        _ptr(_f32c(beta, dev)), float(eps), int(groups), int(N), int(stride), D, int(H),
+                                                        int(temporal), _ptr(out), st))
     return out
 
 

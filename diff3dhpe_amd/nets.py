@@ -126,6 +126,10 @@ class _MixSTEDenoiser(nn.Module):
     # with latency_mode: the fused qkv + attention launches of such a forward on 128-row tiles where the 256-row launch leaves CUs without a
     # workgroup (include/d3d.h "small_tiles").  Inside the 1e-4 gate; differs in the last bits from latency_mode alone.
     latency_small_tiles = False
+    # opt-in for heads of 32 or 16 columns (embed_dim 256 / 128 with 8 heads): the F16X3 engine runs the qkv GEMM and the attention of its
+    # spatial blocks and, for num_frame <= 127, of its temporal blocks as one kernel (include/d3d.h "fused_narrow").  Bit-identical to
+    # the default path; other widths and fp32 / bf16 engines ignore it.
+    fused_narrow = False
     range_check = os.environ.get("D3D_CHECK_RANGE", "1").strip().lower() not in ("0", "false", "no", "off")
     # One process per GPU is the measured multi-GPU form (torchrun; parallel.py).  nn.DataParallel over SEVERAL devices in one
     # process (RUN:216-218 with --gpu_id 0,1,...) drives one engine per device from DataParallel's worker threads: everything that
@@ -276,6 +280,10 @@ class _MixSTEDenoiser(nn.Module):
             with eng.lock:
                 eng.set_option("small_tiles", int(bool(self.latency_small_tiles)))   # (read only while "latency_mode" is on)
                 eng._small_tiles = bool(self.latency_small_tiles)
+        if not fallback and want == "f16x3" and getattr(eng, "_fused_narrow", False) != bool(self.fused_narrow):
+            with eng.lock:
+                eng.set_option("fused_narrow", int(bool(self.fused_narrow)))   # (drops the engine's captured graphs)
+                eng._fused_narrow = bool(self.fused_narrow)
         sig = self._src_sig if self._src_sig is not None else self._param_signature()
         if sigs.get(idx) != sig:
             eng.load_weights(self._named_tensors())

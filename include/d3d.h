@@ -365,6 +365,17 @@ int d3d_engine_set_graph_mode(d3d_engine* e, int32_t on);
  *                     temporal kernel it replaces is not: results stay inside the parity gate, but differ in the last bits from the
  *                     same engine with the key off.  d3d_workspace_bytes does not change.  "small_tiles_last" (d3d_engine_get_info)
  *                     reports what the latest forward ran.  Other values: D3D_EINVAL.
+ *   "fused_narrow"    0 (default) / 1: F16X3 engines whose heads are 32 columns wide in pairs (embed_dim == 32 num_heads, num_heads even) or
+ *                     16 columns wide in quads (embed_dim == 16 num_heads, num_heads % 4 == 0), embed_dim >= 128.  Such an engine runs the
+ *                     folded flow with the qkv GEMM and the attention of every block as two launches, q / k / v planes going through
+ *                     HBM ("attn_h32" / "attn_h16").  With the key on, its spatial blocks (num_joints <= 127, block 0 included) and, for
+ *                     num_frame <= 127, its temporal blocks run both steps as ONE kernel on 128-row tiles of whole token groups x one
+ *                     64-column segment -- a pair / a quad of heads -- with q / k / v kept in LDS; temporal blocks of longer windows keep
+ *                     their kernels.  Bit-identical to the key off.  The selection is a function of (options, shapes) alone and does
+ *                     not read "latency_mode".  Every other head width, odd head pairs / quads, FP32 and BF16 engines: no effect.
+ *                     Measured: DESIGN.md section 5 (ahead at every batch of 64 measured, level for single sequences; the temporal step
+ *                     of one-group tiles, T = 81, is slower than its two launches), hence opt-in.  d3d_workspace_bytes does not change.
+ *                     "fused_narrow_last" (d3d_engine_get_info) reports what the latest forward ran.  Other values: D3D_EINVAL.
  *   "deep_stages"     1 (default) / 0: the one-tile-per-workgroup F16X3 GEMM launches (batches of a few sequences: proj on 128 x 128
  *                     tiles, qkv / proj / fc1 on 256 x 128) keep three / four k-tiles of operands staged instead of two, the wait in front
  *                     of a k-tile's barrier a counted vmcnt -- a k-tile no longer lasts a DMA round trip (proj at B = 1, T = 243: 20.8 ->
@@ -433,7 +444,10 @@ int d3d_hypothesis_mean(const float* pred_dev, float* out_dev, int32_t B, int64_
  * before any forward, with the option off, at every other head width and in the other precisions),
  * "small_tiles" (the option value), "small_tiles_last" (bit 0: the
  * spatial blocks, bit 1: the temporal blocks of the most recent d3d_denoise / d3d_ddim_sample call ran the 128-row fused qkv + attention
- * kernel; 0 before any forward, with the option or "latency_mode" off, and in the other precisions).
+ * kernel; 0 before any forward, with the option or "latency_mode" off, and in the other precisions),
+ * "fused_narrow" (the option value), "fused_narrow_last" (bit 0: the spatial blocks, bit 1: the temporal blocks of the most recent
+ * d3d_denoise / d3d_ddim_sample call ran the fused qkv + attention kernel for heads of 32 or 16 columns; 0 before any forward, with the
+ * option off, at every other head width or head count and in the other precisions).
  * Unknown key: D3D_EINVAL. */
 int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value);
 
@@ -773,6 +787,15 @@ int d3d_op_qkv_attn_bf16(const float* A_dev, const float* Wqkv_dev, const float*
 int d3d_op_qkv_attn_x3_small(const float* X_dev, const float* Wqkv_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev,
                              float eps, int32_t groups, int32_t N, int32_t stride, int32_t D, int32_t H, int32_t temporal, float* out_dev,
                              void* stream);
+
+/* The fused qkv GEMM + attention kernel of "fused_narrow" alone (F16X3), for heads of 32 columns in pairs or 16 columns in quads: the
+ * arithmetic and arguments of d3d_op_qkv_attn_x3_small -- bit for bit the folded qkv GEMM followed by d3d_op_attention_h32 /
+ * d3d_op_attention_h16 on the same tensors.  Spatial blocks groups = B * T, N = J <= 127 (any joint count), stride = 1, temporal = 0;
+ * temporal blocks groups = B * J, N = T <= 127, stride = J, temporal = 1.  D == 32 H with H even or D == 16 H with H % 4 == 0, D >= 128,
+ * groups % stride == 0; anything else: D3D_EUNSUP / D3D_EINVAL. */
+int d3d_op_qkv_attn_x3_narrow(const float* X_dev, const float* Wqkv_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev,
+                              float eps, int32_t groups, int32_t N, int32_t stride, int32_t D, int32_t H, int32_t temporal, float* out_dev,
+                              void* stream);
 
 /* ---- machine probes (measurement support; no reference counterpart) ------------------------------------------------ */
 /* What THIS device sustains for the two resources that co-limit the F16X3 GEMM k-loop, measured over about ms_target
