@@ -12,8 +12,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libd3d_hip.so")
-SOURCES = ["engine.hip", "engine_ops.hip", "weight_pack.hip", "kernels_gemm.hip", "kernels_gemm_f16x3.hip", "kernels_gemm_x3p.hip", "kernels_elem.hip", "kernels_attn.hip", "kernels_attn_x3.hip", "kernels_attn_x3_long.hip", "kernels_attn_x3_h32.hip", "kernels_attn_f32_long.hip", "kernels_attn_f32_h32.hip", "kernels_attn_f32_h32_long.hip", "kernels_attn_x3_h128.hip", "kernels_attn_x3_hx.hip", "kernels_attn_x3_h16.hip", "kernels_attn_f32_h128.hip", "kernels_attn_f32_hx.hip", "kernels_attn_bf16.hip", "kernels_qkv_sattn.hip", "kernels_qkv_tattn.hip", "kernels_fc1_x3.hip", "kernels_proj_x3.hip", "kernels_gemm_bf16q.hip", "kernels_qkv_attn_bf16.hip", "kernels_qkv_attn_x3_small.hip", "kernels_fc2_splitk.hip", "kernels_splitk_reduce.hip", "probes.hip"]
-HEADERS = ["d3d_kernels.h", "engine_internal.h", "weight_pack.h", "gemm_x3p_prelude.h", "gemm_x3p_epilogue.h", "x3q_epilogue_acc.h", "qkv_fused_kloop.h", "kloop_common.h", "attn_lds.h", "attn_x3_tile.h", "attn_f32_tile.h", os.path.join("..", "..", "include", "d3d.h")]
+SOURCES = ["engine.hip", "engine_ops.hip", "attn_dispatch.hip", "weight_pack.hip", "kernels_gemm.hip", "kernels_gemm_f16x3.hip", "kernels_gemm_x3p.hip", "kernels_elem.hip", "kernels_attn.hip", "kernels_attn_x3.hip", "kernels_attn_x3_long.hip", "kernels_attn_x3_h32.hip", "kernels_attn_f32_long.hip", "kernels_attn_f32_h32.hip", "kernels_attn_f32_h32_long.hip", "kernels_attn_x3_h128.hip", "kernels_attn_x3_hx.hip", "kernels_attn_x3_h16.hip", "kernels_attn_f32_h128.hip", "kernels_attn_f32_hx.hip", "kernels_attn_bf16.hip", "kernels_qkv_sattn.hip", "kernels_qkv_tattn.hip", "kernels_fc1_x3.hip", "kernels_proj_x3.hip", "kernels_gemm_bf16q.hip", "kernels_qkv_attn_bf16.hip", "kernels_qkv_attn_x3_small.hip", "kernels_fc2_splitk.hip", "kernels_splitk_reduce.hip", "probes.hip"]
+HEADERS = ["d3d_kernels.h", "engine_internal.h", "attn_dispatch.h", "weight_pack.h", "gemm_x3p_prelude.h", "gemm_x3p_epilogue.h", "x3q_epilogue_acc.h", "qkv_fused_kloop.h", "kloop_common.h", "attn_lds.h", "attn_x3_tile.h", "attn_f32_tile.h", os.path.join("..", "..", "include", "d3d.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # The row kernels are plain scalar code; the SLP vectoriser packs it into v_pk_*_f32 with op_sel broadcasts, one form of which deviates
 # on gfx950 beside another wave's MFMAs (x3q_epilogue_acc.h splat2_rt; tests/test_abi_host.py pins its absence).  They are memory-bound:

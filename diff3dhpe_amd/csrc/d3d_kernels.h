@@ -384,115 +384,79 @@ hipError_t launch_attn_spatial_f32(const float* qkv, float* out, void* out_x3, i
 hipError_t launch_attn_temporal_f32(const float* qkv, float* out, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 hipError_t launch_attn_generic(const float* qkv, float* out, void* out_x3, int B, int T, int J, int D, int H, int temporal,
                                hipStream_t s);
-// ---- kernels_attn_x3.hip: temporal attention on fp16 MFMA with F16X3 accuracy; qkv as hi/lo planes ([rows][3D] each,
-// written by the qkv GEMM with outsplit = 1), output in the pair layout
+// ---- The attention kernel families of attn_dispatch.h beyond kernels_attn.hip: one contract per operand form -------------------------
+// Every launcher takes (B, T, J, D, H): B J groups of T tokens, J tokens apart; spatial blocks call it with (B T, J, 1).  A resident
+// launcher holds a group's keys in LDS and serves what its *_ok(N, D, H) predicate accepts (N = the group length); its *_long twin
+// streams the keys through LDS in chunks and serves a window of any length, bit-identical to the resident kernel wherever that runs.
+// A launch returns hipErrorInvalidValue where its predicate fails or its grid -- for a streaming launch B J (units per token)
+// ceil(T / 256) workgroups -- exceeds 2^31 - 1.
+//
+// Planes form (F16X3 accuracy on fp16 MFMA, attn_x3_tile.h): qkv as hi / lo fp16 planes, [rows][3 D] each, as the qkv GEMM writes them
+// with outsplit = 1 (raw q, 8 k, 8 v); the output in the pair layout, its rows 2 ceil32(D) halves apart (2 D wherever D % 32 == 0, as in
+// every engine).  The streaming kernels (kernels_attn_x3_long.hip, k_attn_x3_stream<DH, KC>) compute the scores twice, for the exact
+// maximum and for the numerators.
+//
+// Rows form (exact fp32 on v_mfma_f32_32x32x2_f32, attn_f32_tile.h: arithmetic, staging, launch ladder and streaming geometry shared
+// with the width-64 kernels of kernels_attn.hip): fp32 rows in, fp32 rows out, no pair-layout form (FP32 engines only).  The scores are
+// scaled by 1 / sqrt(DH) after the sum over d and v[query] is subtracted at the store (widths 128, 48 / 96 and 16: the second product
+// takes the unnormalised numerators and the store divides by their sum), so the bits are not those of launch_attn_generic.  A head
+// reads and writes its own DH columns alone (a half-used accumulator tile takes zeros).  The streaming kernels make three passes at
+// widths 64 and 32 (maximum, sum, normalised product), two elsewhere (maximum; numerators, their sum and the product).
+//
+//   launcher (+ _long)             D / H     heads (units per token)                 resident N <=  chunk      instantiated in
+//   launch_attn_temporal_x3        64        any (H)                                 256            256        kernels_attn_x3.hip; _long: kernels_attn_x3_long.hip <64, 8>
+//   launch_attn_x3_h32             32        even (H / 2: a pair shares an LDS row)  256            256        kernels_attn_x3_h32.hip; <32, 8>
+//   launch_attn_x3_h128            128       any (H: two 64-column halves a head)    128            128        kernels_attn_x3_h128.hip; <128, 4>
+//   launch_attn_x3_hx              48 / 96   any (H: DH adjacent plane columns)      256 / 128      256 / 128  kernels_attn_x3_hx.hip; <48, 8> / <96, 4>
+//   launch_attn_x3_h16             16        H % 4 == 0 (H / 4: a quad shares a row) 256            256        kernels_attn_x3_h16.hip; <16, 8>
+//   launch_attn_temporal_f32_long  64        any (H)                                 (no twin here) 256        kernels_attn_f32_long.hip, k_attn_f32_stream3<64>
+//   launch_attn_temporal_f32_h32   32        any (H)                                 256            256        kernels_attn_f32_h32.hip; kernels_attn_f32_h32_long.hip
+//   launch_attn_f32_h128           128       any (H)                                 128            128        kernels_attn_f32_h128.hip
+//   launch_attn_f32_hx             48 / 96   any (H)                                 256 / 192      256 / 192  kernels_attn_f32_hx.hip, k_attn_f32_hx_stream<48> / <96>
+//   launch_attn_f32_h16            16        any (H)                                 256            256        kernels_attn_f32_hx.hip at DH = 16
+// launch_attn_temporal_f32_long's resident twin is launch_attn_temporal_f32 of kernels_attn.hip (T <= 256).
+// launch_attn_spatial_f32_h32 is the VALU form of width 32 for 15 .. 17 joints; it takes the block's own (B, T, J), as the launchers of
+// kernels_attn.hip do.
 hipError_t launch_attn_temporal_x3(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                    hipStream_t s);
 bool attn_temporal_x3_ok(int T, int D, int H);
-// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<64, 8>: the same attention for windows of any length (the keys stream through LDS in
-// chunks of 256 frames; the scores are computed twice, for the exact maximum and for the numerators).  Same planes in, same pair layout out; bit-identical to
-// launch_attn_temporal_x3 wherever that runs (T <= 256).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_temporal_x3_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H,
                                         hipStream_t s);
 bool attn_temporal_x3_long_ok(int T, int D, int H);
-// ---- kernels_attn_x3_h32.hip: the same attention for heads of 32 columns (D == 32 H, H even: two adjacent heads share the 128-byte LDS
-// rows of the kernels above), groups of T <= 256 tokens.  The contract of launch_attn_temporal_x3: same planes in (raw q, 8 k, 8 v), same
-// pair layout out; spatial blocks call it with (B T, J, 1).
 hipError_t launch_attn_x3_h32(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_x3_h32_ok(int N, int D, int H);
-// ---- The exact fp32 MFMA attention kernels (v_mfma_f32_32x32x2_f32) of kernels_attn.hip (width 64, resident), kernels_attn_f32_h32.hip
-// (width 32, resident), kernels_attn_f32_long.hip and kernels_attn_f32_h32_long.hip (widths 64 and 32, key-streaming), kernels_attn_f32_h128.hip (width 128, both) and kernels_attn_f32_hx.hip (widths 48 and 96, both) share
-// their arithmetic, staging, launch ladder and streaming geometry: attn_f32_tile.h.
-// ---- kernels_attn_f32_long.hip, k_attn_f32_stream3<64>: launch_attn_temporal_f32's attention for windows of any length:
-// the keys stream through LDS in chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out, no
-// pair-layout form; bit-identical to launch_attn_temporal_f32 wherever that runs (T <= 256).  The launch also refuses
-// B J H ceil(T / 256) workgroups beyond 2^31 - 1.
+hipError_t launch_attn_x3_h32_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h32_long_ok(int T, int D, int H);
+hipError_t launch_attn_x3_h128(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h128_ok(int N, int D, int H);
+hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h128_long_ok(int T, int D, int H);
+hipError_t launch_attn_x3_hx(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_hx_ok(int N, int D, int H);
+hipError_t launch_attn_x3_hx_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_hx_long_ok(int T, int D, int H);
+hipError_t launch_attn_x3_h16(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h16_ok(int N, int D, int H);
+hipError_t launch_attn_x3_h16_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
+bool attn_x3_h16_long_ok(int T, int D, int H);
 hipError_t launch_attn_temporal_f32_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_temporal_f32_long_ok(int T, int D, int H);
-// ---- kernels_attn_f32_h32.hip: the exact fp32 cores of kernels_attn.hip for heads of 32 columns (D == 32 H, any head count).  fp32 rows
-// in, fp32 rows out, no pair-layout form (FP32 engines only).  Temporal: v_mfma_f32_32x32x2_f32, T <= 256; spatial: the VALU form, 15 .. 17
-// joints.  The scores are scaled by 1 / sqrt(32) after the sum over d and v[query] is subtracted at the store, so the bits are not those of
-// launch_attn_generic.  The launches return hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
 hipError_t launch_attn_temporal_f32_h32(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 hipError_t launch_attn_spatial_f32_h32(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_temporal_f32_h32_ok(int T, int D, int H);
 bool attn_spatial_f32_h32_ok(int J, int D, int H);
-// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<32, 8>: launch_attn_x3_h32's temporal attention for windows of any length (D == 32 H,
-// H even): the head pair's keys stream through LDS in chunks of 256 frames, the scores are computed twice.  Same planes in, same pair layout out;
-// bit-identical to launch_attn_x3_h32 wherever that runs (T <= 256).  The launch also refuses B J (H / 2) ceil(T / 256) workgroups beyond
-// 2^31 - 1.
-hipError_t launch_attn_x3_h32_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
-bool attn_x3_h32_long_ok(int T, int D, int H);
-// ---- kernels_attn_f32_h32_long.hip, k_attn_f32_stream3<32>: launch_attn_temporal_f32_h32's attention for windows of any length (D == 32 H, any head count):
-// chunks of 256 frames, three passes (maximum, sum, normalised product).  fp32 rows in, fp32 rows out; bit-identical to
-// launch_attn_temporal_f32_h32 wherever that runs (T <= 256).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_temporal_f32_h32_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_temporal_f32_h32_long_ok(int T, int D, int H);
-// ---- kernels_attn_x3_h128.hip: the F16X3 attention for heads of 128 columns (D == 128 H, any head count: a head is two adjacent
-// 64-column halves, each in LDS rows of the kernels above), groups of T <= 128 tokens.  The contract of launch_attn_temporal_x3: same
-// planes in (raw q, 8 k, 8 v), same pair layout out; spatial blocks call it with (B T, J, 1).
-hipError_t launch_attn_x3_h128(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
-bool attn_x3_h128_ok(int N, int D, int H);
-// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<128, 4>: launch_attn_x3_h128's temporal attention for windows of any length: the
-// head's keys stream through LDS in chunks of 128 frames, the scores are computed twice.  Same planes in, same pair layout out; bit-identical to
-// launch_attn_x3_h128 wherever that runs (T <= 128).  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
-hipError_t launch_attn_x3_h128_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
-bool attn_x3_h128_long_ok(int T, int D, int H);
-// ---- kernels_attn_x3_hx.hip: the F16X3 attention for heads of 48 and 96 columns (D == 48 H or 96 H, any head count; the width is D / H),
-// groups of T <= 256 (width 48) / T <= 128 (width 96) tokens.  A head is DH adjacent plane columns from column hd DH on, not whole
-// 64-column segments.  The contract of launch_attn_temporal_x3: same planes in (raw q, 8 k, 8 v), same pair layout out, its rows
-// 2 ceil32(D) halves apart (2 D wherever D % 32 == 0, as in every engine); spatial blocks call it with (B T, J, 1).
-hipError_t launch_attn_x3_hx(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
-bool attn_x3_hx_ok(int N, int D, int H);
-// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<48, 8> / <96, 4>: launch_attn_x3_hx's temporal attention for windows of any length:
-// chunks of 256 (width 48) / 128 (width 96) frames, the scores computed twice.  Same planes in, same pair layout out; bit-identical to
-// launch_attn_x3_hx wherever that runs.  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
-hipError_t launch_attn_x3_hx_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
-bool attn_x3_hx_long_ok(int T, int D, int H);
-// ---- kernels_attn_f32_h128.hip: the exact fp32 attention (v_mfma_f32_32x32x2_f32) for heads of 128 columns (D == 128 H, any head
-// count), groups of N <= 128 tokens resident in LDS.  fp32 rows in, fp32 rows out, no pair-layout form (FP32 engines only); spatial blocks
-// call it with (B T, J, 1), so any joint count 1 .. 128 is served.  The scores are scaled by 1 / sqrt(128) after the sum over d, the
-// second product takes the unnormalised numerators, and the store divides by their sum and subtracts v[query], so the bits are not those
-// of launch_attn_generic.  The launch returns hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
 hipError_t launch_attn_f32_h128(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_h128_ok(int N, int D, int H);
-// ---- kernels_attn_f32_h128.hip, k_attn_f32_h128_stream: launch_attn_f32_h128's temporal attention for windows of any length: the keys
-// stream through LDS in chunks of 128 frames, two passes (maximum; numerators, their sum and the product).  fp32 rows in, fp32 rows out;
-// bit-identical to launch_attn_f32_h128 wherever that runs (T <= 128).  The launch also refuses B J H ceil(T / 256) workgroups beyond
-// 2^31 - 1.
 hipError_t launch_attn_f32_h128_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_h128_long_ok(int T, int D, int H);
-// ---- kernels_attn_f32_hx.hip: the same exact fp32 attention for heads of 48 and 96 columns (D == 48 H or 96 H, any head count; the
-// width is D / H), groups of N <= 256 (width 48) / N <= 192 (width 96) tokens resident in LDS.  The contract and the arithmetic of
-// launch_attn_f32_h128 (scale 1 / sqrt(DH) after the sum over d, unnormalised numerators, / l and - v[query] at the store); spatial blocks
-// call it with (B T, J, 1).  A head reads and writes its own DH columns alone (width 48: the half-used second accumulator tile takes
-// zeros, not the next head's columns).  The launch returns hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
 hipError_t launch_attn_f32_hx(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_hx_ok(int N, int D, int H);
-// ---- kernels_attn_f32_hx.hip, k_attn_f32_hx_stream<48> / <96>: launch_attn_f32_hx's temporal attention for windows of any length:
-// chunks of 256 (width 48) / 192 (width 96) frames, two passes.  fp32 rows in, fp32 rows out; bit-identical to launch_attn_f32_hx
-// wherever that runs.  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_f32_hx_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_hx_long_ok(int T, int D, int H);
-// ---- kernels_attn_x3_h16.hip: the F16X3 attention for heads of 16 columns (D == 16 H, H a multiple of 4: four adjacent heads share the
-// 128-byte LDS rows of the kernels above, each with its own d-step of the score product, softmax, sum and O^T accumulator), groups of
-// T <= 256 tokens.  The contract of launch_attn_temporal_x3: same planes in (raw q, 8 k, 8 v), same pair layout out (a head's 16 columns are
-// half a 128-byte line); spatial blocks call it with (B T, J, 1).
-hipError_t launch_attn_x3_h16(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
-bool attn_x3_h16_ok(int N, int D, int H);
-// ---- kernels_attn_x3_long.hip, k_attn_x3_stream<16, 8>: launch_attn_x3_h16's temporal attention for windows of any length: the quad's
-// keys stream through LDS in chunks of 256 frames, the scores are computed twice.  Same planes in, same pair layout out; bit-identical to
-// launch_attn_x3_h16 wherever that runs (T <= 256).  The launch also refuses B J (H / 4) ceil(T / 256) workgroups beyond 2^31 - 1.
-hipError_t launch_attn_x3_h16_long(const void* qkv_hi, const void* qkv_lo, void* out_x3, int B, int T, int J, int D, int H, hipStream_t s);
-bool attn_x3_h16_long_ok(int T, int D, int H);
-// ---- kernels_attn_f32_hx.hip at DH = 16: the exact fp32 attention of launch_attn_f32_hx for heads of 16 columns (D == 16 H, any head
-// count), groups of N <= 256 tokens resident in LDS; the same contract and arithmetic (1 / sqrt(16) = 0.25 applied after the sum over d,
-// unnormalised numerators, / l and - v[query] at the store); spatial blocks call it with (B T, J, 1).  The half-used accumulator tile takes
-// zeros, not the next head's columns.  The launch returns hipErrorInvalidValue where the predicate fails or the grid exceeds 2^31 - 1.
 hipError_t launch_attn_f32_h16(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_h16_ok(int N, int D, int H);
-// ---- k_attn_f32_hx_stream<16>: its temporal attention for windows of any length: chunks of 256 frames, two passes; bit-identical to
-// launch_attn_f32_h16 wherever that runs.  The launch also refuses B J H ceil(T / 256) workgroups beyond 2^31 - 1.
 hipError_t launch_attn_f32_h16_long(const float* qkv, float* out, int B, int T, int J, int D, int H, hipStream_t s);
 bool attn_f32_h16_long_ok(int T, int D, int H);
 hipError_t launch_split_qkv(const float* x, void* hi, void* lo, size_t rows, int D, hipStream_t s);

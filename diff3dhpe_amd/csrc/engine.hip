@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/d3d.h"
+#include "attn_dispatch.h"
 #include "d3d_kernels.h"
 #include "engine_internal.h"
 
@@ -56,15 +57,11 @@ struct BlockW : BlockSrc {   // (the block's fp32 tensors, here in the device ar
 // Which kernels one forward of B sequences runs: every choice the block loops branch on, made once by plan_blocks() from the options,
 // the shapes, B and the CU count.  The entry points keep the plan they ran; d3d_engine_get_info reads its "*_last" keys from it.
 struct BlockPlan {
-  enum Flow { PLAIN, FOLD, BF16 };
-  Flow flow = PLAIN;          // run_blocks / run_blocks_fold / run_blocks_bf16
+  // The flow (run_blocks / run_blocks_fold / run_blocks_bf16) and the attention kernel of the spatial / of the temporal blocks wherever
+  // the qkv GEMM and the attention are two launches: attn_choose() of attn_dispatch.h.  A BF16 plan runs launch_attn_bf16.
+  AttnChoice attn;
   // FOLD, BF16: the qkv GEMM and the attention of the spatial / temporal blocks as one kernel
   bool fused_sp = false, fused_tp = false;
-  // The attention kernel of the spatial / of the temporal blocks wherever the qkv GEMM and the attention are two launches: one value per
-  // launch, listed with its shapes at launch_attention().  A BF16 plan runs launch_attn_bf16 and leaves both at GENERIC.
-  enum Attn { GENERIC, F32_SPATIAL, F32_TEMPORAL, F32_H32, F32_LONG, F32_H32_LONG, F32_H128, F32_H128_LONG, F32_HX, F32_HX_LONG,
-              F32_H16, F32_H16_LONG, X3, X3_LONG, X3_H32, X3_H32_LONG, X3_H128, X3_H128_LONG, X3_HX, X3_HX_LONG, X3_H16, X3_H16_LONG };
-  Attn attn_sp = GENERIC, attn_tp = GENERIC;
   // FOLD: block 0's q / k / v from the raw input channels and the commit-time tables instead of the K = D qkv GEMM ("block0_direct")
   bool b0_direct = false;
   // FOLD: fc1 / proj on their own kernels; the post-norm inside the fc2 epilogue
@@ -75,16 +72,13 @@ struct BlockPlan {
   // (kernels_qkv_attn_x3_small.hip) where the 256-row launch would leave CUs without a workgroup; block 0 keeps its direct form
   bool small_sp = false, small_tp = false;
   // FOLD with "fused_narrow" at head widths 32 / 16: the qkv GEMM and the attention of the spatial blocks (block 0 included) / of the
-  // temporal blocks (T <= 127) as one launch of the same kernel's narrow forms, in place of the GEMM + attn_sp / attn_tp pair
+  // temporal blocks (T <= 127) as one launch of the same kernel's narrow forms, in place of the GEMM + attn.sp / attn.tp pair
   bool narrow_sp = false, narrow_tp = false;
   // BF16: whole-row proj / fc2 with their LayerNorms in the epilogue; qkv / fc1 on the hand-specialised GEMM kernel
   bool rows = false, bf16q_qkv = false, bf16q_fc1 = false;
 };
 
 }  // namespace
-
-// The defaults of "attn_h16" / "attn_f32_h16", decided by the table of DESIGN.md section 5 (experiments/attn_h16.py)
-constexpr bool ATTN_H16_DEFAULT = true, ATTN_F32_H16_DEFAULT = true;
 
 struct d3d_engine {
   d3d_config cfg{};
@@ -135,53 +129,12 @@ struct d3d_engine {
   // tiles runs as a split-K x split-N GEMM + an ordered reduce / post-norm row kernel (d3d_kernels.h fc2_splitk_choose).  Changes the
   // order of additions: results stay inside the parity gate but are no longer bit-identical to the default path's.
   bool opt_latency_mode = false;
-  // "long_temporal" (on by default): an F16X3 engine whose window is longer than 256 frames keeps the folded flow, its temporal blocks on
-  // the key-streaming attention kernel (kernels_attn_x3_long.hip at width 64); 0 = the plain row-kernel flow with the generic fp32 attention
-  bool opt_long_temporal = true;
-  // "long_temporal_f32" (on by default): an FP32 engine whose window is longer than 256 frames runs its temporal blocks' attention on the
-  // key-streaming fp32 MFMA kernel (kernels_attn_f32_long.hip); 0 = the generic one-thread-per-row kernel.  F16X3 / BF16 engines: no effect
-  bool opt_long_temporal_f32 = true;
-  // "attn_h32": an F16X3 engine whose heads are 32 columns wide (embed_dim 256 with 8 heads) runs the folded flow with the attention of
-  // every block on kernels_attn_x3_h32.hip (windows of up to 256 frames); 0 = the plain row-kernel flow with the generic fp32 attention
-  bool opt_attn_h32 = true;
-  // "attn_f32_h32": an FP32 engine whose heads are 32 columns wide runs the attention of its spatial blocks (15 .. 17 joints) and of its
-  // temporal blocks (windows of up to 256 frames) on kernels_attn_f32_h32.hip; 0 = the generic one-thread-per-row kernel.  Changes the
-  // order of additions: inside the parity gate, not bit-identical.  F16X3 / BF16 engines and every D == 64 H engine: no effect
-  bool opt_attn_f32_h32 = true;
-  // "long_temporal_h32" (on by default): an F16X3 engine whose heads are 32 columns wide and whose window is longer than 256 frames keeps
-  // the folded flow, its temporal blocks on kernels_attn_x3_long.hip at width 32 and its spatial blocks on kernels_attn_x3_h32.hip; 0 = the
-  // plain row-kernel flow with the generic fp32 attention
-  bool opt_long_temporal_h32 = true;
-  // "long_temporal_f32_h32" (on by default): an FP32 engine of that width and window runs its temporal blocks' attention on
-  // kernels_attn_f32_h32_long.hip; 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not
-  // bit-identical.  F16X3 / BF16 engines: no effect
-  bool opt_long_temporal_f32_h32 = true;
-  // "attn_h128" (on by default): an F16X3 engine whose heads are 128 columns wide (embed_dim 1024 with 8 heads) runs the folded flow with
-  // its attention on kernels_attn_x3_h128.hip (groups of up to 128 tokens) and kernels_attn_x3_long.hip at width 128 (windows of more than
-  // 128 frames); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of that width: "attn_f32_h128"
-  bool opt_attn_h128 = true;
-  // "attn_f32_h128": an FP32 engine whose heads are 128 columns wide runs the attention of its spatial blocks (up to 128 joints) and of
-  // its temporal blocks on kernels_attn_f32_h128.hip (windows of up to 128 frames resident, longer ones key-streaming); 0 = the generic
-  // one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical.  F16X3 / BF16 engines and every
-  // other head width: no effect
-  bool opt_attn_f32_h128 = true;
-  // "attn_hx" (on by default): an F16X3 engine whose heads are 48 or 96 columns wide (embed_dim 384 / 768 with 8 heads) runs the folded
-  // flow with its attention on kernels_attn_x3_hx.hip (groups of up to 256 / 128 tokens) and kernels_attn_x3_long.hip at that width
-  // (longer windows); 0 = the plain row-kernel flow with the generic fp32 attention.  FP32 engines of these widths: "attn_f32_hx"
-  bool opt_attn_hx = true;
-  // "attn_f32_hx" (on by default): an FP32 engine whose heads are 48 or 96 columns wide runs the attention of its spatial blocks (up to
-  // 256 / 192 joints) and of its temporal blocks on kernels_attn_f32_hx.hip (windows of up to 256 / 192 frames resident, longer ones
-  // key-streaming); 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical.
-  // F16X3 / BF16 engines, every other head width and embed_dim % 32 != 0 (one or three heads of 48 columns): no effect
-  bool opt_attn_f32_hx = true;
-  // "attn_h16": an F16X3 engine whose heads are 16 columns wide in quads (embed_dim 128 with 8 heads; H % 4 == 0) runs the folded flow
-  // with its attention on kernels_attn_x3_h16.hip (groups of up to 256 tokens) and kernels_attn_x3_long.hip at that width (longer
-  // windows); 0 = the plain row-kernel flow with the generic fp32 attention.  Other head counts of that width: no effect
-  bool opt_attn_h16 = ATTN_H16_DEFAULT;
-  // "attn_f32_h16": an FP32 engine whose heads are 16 columns wide (any head count) runs the attention of its spatial blocks (up to 256
-  // joints) and of its temporal blocks on kernels_attn_f32_hx.hip at DH = 16 (windows of up to 256 frames resident, longer ones
-  // key-streaming); 0 = the generic one-thread-per-row kernel.  Changes the order of additions: inside the parity gate, not bit-identical
-  bool opt_attn_f32_h16 = ATTN_F32_H16_DEFAULT;
+  // The options that gate an attention kernel family, one bit each (AttnOpt, attn_dispatch.h: "long_temporal", "long_temporal_f32",
+  // "attn_h32", "attn_f32_h32", "long_temporal_h32", "long_temporal_f32_h32", "attn_h128", "attn_f32_h128", "attn_hx", "attn_f32_hx",
+  // "attn_h16", "attn_f32_h16"; what each selects: include/d3d.h).  An F16X3 key off = the plain row-kernel flow with the generic fp32
+  // attention; an fp32 key off = the generic one-thread-per-row kernel (the fp32 MFMA kernels change the order of additions: inside the
+  // parity gate, not bit-identical to it).
+  unsigned attn_opts = attn_option_defaults();
   // "deep_stages" of THIS engine: -1 = follow the process-wide default (the key with a NULL engine), 0 / 1 = this engine's own setting.
   // Read into the calling thread's launch context by EngineScope, so two engines driven from two threads never see each other's value.
   int opt_deep_stages = -1;
@@ -204,7 +157,7 @@ struct d3d_engine {
   // the plan of the most recent forward (of a two-stream sampling: of the first half-batch, the one that holds sequence 0); all zero
   // before any.  d3d_engine_get_info: "fc2_split_last" / "proj_split_last" / "fc1_split_last" = the S that ran (0: the whole launch),
   // "bf16_fused_spatial_last" / "..temporal_last" = whether a BF16 forward ran kernels_qkv_attn_bf16.hip in those blocks,
-  // and the keys of the attention kernels that ran, which attention_plan_info() states
+  // and the keys of the attention kernels that ran, which attn_plan_key() (attn_dispatch.h) states
   BlockPlan last_plan;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -432,103 +385,23 @@ int compute_temb(d3d_engine* e, const float* times_dev, int n, float* out, float
   return D3D_OK;
 }
 
-// The launch of every BlockPlan::Attn value, for a spatial or a temporal block of B sequences.  qkv: the block's q / k / v, (M, 3 D)
-// fp32 rows for the fp32 kernels; for the X3 kernels the fp16 hi plane at the same address and the lo plane M 3 D halves behind it.
-// out: fp32 rows; out_x3: the pair layout -- written instead of out by the kernels_attn.hip launches where it is not null (F16X3
-// engines), the only output of the X3 kernels, not a form the other fp32 kernels have (FP32 engines only).  The X3 kernels attend over
-// the T tokens of (batch, joint) groups, J tokens apart: a spatial block is B T batches of J consecutive tokens and one joint.
-int launch_attention(const d3d_engine* e, BlockPlan::Attn kernel, bool temporal, const void* qkv, float* out, void* out_x3, int B,
-                     hipStream_t s) {
-  const int T = e->T, J = e->J, D = e->D, H = e->H, gB = temporal ? B : B * T, gT = temporal ? T : J, gJ = temporal ? J : 1;
-  const float* q = static_cast<const float*>(qkv);
-  const uint16_t *qh = static_cast<const uint16_t*>(qkv), *ql = qh + (size_t)B * T * J * 3 * D;
-  hipError_t le = hipErrorInvalidValue;
-  switch (kernel) {
-    case BlockPlan::GENERIC:      le = launch_attn_generic(q, out, out_x3, B, T, J, D, H, temporal ? 1 : 0, s); break;   // any shape
-    case BlockPlan::F32_SPATIAL:  le = launch_attn_spatial_f32(q, out, out_x3, B, T, J, D, H, s); break;                 // D == 64 H, 15 .. 17 joints
-    case BlockPlan::F32_TEMPORAL: le = launch_attn_temporal_f32(q, out, out_x3, B, T, J, D, H, s); break;                // D == 64 H, T <= 256
-    case BlockPlan::F32_H32:      // D == 32 H, FP32 engines: T <= 256 / 15 .. 17 joints
-      le = temporal ? launch_attn_temporal_f32_h32(q, out, B, T, J, D, H, s) : launch_attn_spatial_f32_h32(q, out, B, T, J, D, H, s); break;
-    case BlockPlan::F32_LONG:     le = launch_attn_temporal_f32_long(q, out, B, T, J, D, H, s); break;                   // D == 64 H, T > 256, FP32 engines
-    case BlockPlan::F32_H32_LONG: le = launch_attn_temporal_f32_h32_long(q, out, B, T, J, D, H, s); break;               // D == 32 H, T > 256, FP32 engines
-    case BlockPlan::X3:           le = launch_attn_temporal_x3(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 64 H, groups <= 256
-    case BlockPlan::X3_LONG:      le = launch_attn_temporal_x3_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;         // D == 64 H, T > 256 (FOLD)
-    case BlockPlan::X3_H32:       le = launch_attn_x3_h32(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                   // D == 32 H, groups <= 256 (FOLD)
-    case BlockPlan::X3_H32_LONG:  le = launch_attn_x3_h32_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 32 H, T > 256 (FOLD)
-    case BlockPlan::X3_H128:      le = launch_attn_x3_h128(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                  // D == 128 H, groups <= 128 (FOLD)
-    case BlockPlan::X3_H128_LONG: le = launch_attn_x3_h128_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;             // D == 128 H, T > 128 (FOLD)
-    case BlockPlan::X3_HX:        le = launch_attn_x3_hx(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                    // D == 48 H / 96 H, groups <= 256 / 128 (FOLD)
-    case BlockPlan::X3_HX_LONG:   le = launch_attn_x3_hx_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;               // D == 48 H / 96 H, longer windows (FOLD)
-    case BlockPlan::X3_H16:       le = launch_attn_x3_h16(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;                   // D == 16 H, H % 4 == 0, groups <= 256 (FOLD)
-    case BlockPlan::X3_H16_LONG:  le = launch_attn_x3_h16_long(qh, ql, out_x3, gB, gT, gJ, D, H, s); break;              // D == 16 H, H % 4 == 0, T > 256 (FOLD)
-    case BlockPlan::F32_H16:      le = launch_attn_f32_h16(q, out, gB, gT, gJ, D, H, s); break;                          // D == 16 H, groups <= 256, FP32 engines
-    case BlockPlan::F32_H16_LONG: le = launch_attn_f32_h16_long(q, out, gB, gT, gJ, D, H, s); break;                     // D == 16 H, T > 256, FP32 engines
-    case BlockPlan::F32_H128:     le = launch_attn_f32_h128(q, out, gB, gT, gJ, D, H, s); break;                         // D == 128 H, groups <= 128, FP32 engines
-    case BlockPlan::F32_H128_LONG: le = launch_attn_f32_h128_long(q, out, gB, gT, gJ, D, H, s); break;                   // D == 128 H, T > 128, FP32 engines
-    case BlockPlan::F32_HX:       le = launch_attn_f32_hx(q, out, gB, gT, gJ, D, H, s); break;                           // D == 48 H / 96 H, groups <= 256 / 192, FP32 engines
-    case BlockPlan::F32_HX_LONG:  le = launch_attn_f32_hx_long(q, out, gB, gT, gJ, D, H, s); break;                      // D == 48 H / 96 H, longer windows, FP32 engines
-  }
-  HIP_TRY(le);
+// The attention launch of a spatial or a temporal block of B sequences.  qkv: the block's q / k / v, (M, 3 D) fp32 rows for the fp32
+// kernels; for the planes kernels the fp16 hi plane at the same address and the lo plane M 3 D halves behind it.  out / out_x3: AttnArgs.
+int launch_attention(const d3d_engine* e, AttnPick kernel, bool temporal, const void* qkv, float* out, void* out_x3, int B, hipStream_t s) {
+  const void* lo = kernel.fam().form == ATTN_PLANES ? static_cast<const uint16_t*>(qkv) + (size_t)B * e->T * e->J * 3 * e->D : nullptr;
+  HIP_TRY(kernel.regime(temporal).launch(AttnArgs{qkv, lo, out, out_x3, B, e->T, e->J, e->D, e->H, temporal, s}));
   return D3D_OK;
-}
-
-// The "*_last" info keys of the attention plan, from the flow and the two kernel choices: which block types ran which kernel family
-// (plain keys: the temporal blocks, or at "attn_h32_last" both; bit 0 spatial, bit 1 temporal, at "attn_h128_last", "attn_hx_last",
-// "attn_h16_last", "attn_f32_h128_last", "attn_f32_hx_last" and "attn_f32_h16_last" bit 2 temporal streaming).  false = not one of the keys.
-bool attention_plan_info(const BlockPlan& p, const std::string& k, int64_t* value) {
-  const bool fold = p.flow == BlockPlan::FOLD, plain = p.flow == BlockPlan::PLAIN;
-  const BlockPlan::Attn sp = p.attn_sp, tp = p.attn_tp;
-  if (k == "long_temporal_last") *value = fold && tp == BlockPlan::X3_LONG;
-  else if (k == "attn_h32_last") *value = fold && sp == BlockPlan::X3_H32 && tp == BlockPlan::X3_H32;
-  else if (k == "long_temporal_h32_last") *value = fold && tp == BlockPlan::X3_H32_LONG;
-  else if (k == "attn_h128_last")
-    *value = fold ? (sp == BlockPlan::X3_H128 ? 1 : 0) | (tp == BlockPlan::X3_H128 ? 2 : 0) | (tp == BlockPlan::X3_H128_LONG ? 4 : 0) : 0;
-  else if (k == "attn_hx_last")
-    *value = fold ? (sp == BlockPlan::X3_HX ? 1 : 0) | (tp == BlockPlan::X3_HX ? 2 : 0) | (tp == BlockPlan::X3_HX_LONG ? 4 : 0) : 0;
-  else if (k == "attn_h16_last")
-    *value = fold ? (sp == BlockPlan::X3_H16 ? 1 : 0) | (tp == BlockPlan::X3_H16 ? 2 : 0) | (tp == BlockPlan::X3_H16_LONG ? 4 : 0) : 0;
-  else if (k == "attn_f32_h16_last")
-    *value = plain ? (sp == BlockPlan::F32_H16 ? 1 : 0) | (tp == BlockPlan::F32_H16 ? 2 : 0) | (tp == BlockPlan::F32_H16_LONG ? 4 : 0) : 0;
-  else if (k == "long_temporal_f32_last") *value = plain && tp == BlockPlan::F32_LONG;
-  else if (k == "attn_f32_h32_last") *value = plain ? (sp == BlockPlan::F32_H32 ? 1 : 0) | (tp == BlockPlan::F32_H32 ? 2 : 0) : 0;
-  else if (k == "long_temporal_f32_h32_last") *value = plain && tp == BlockPlan::F32_H32_LONG;
-  else if (k == "attn_f32_h128_last")
-    *value = plain ? (sp == BlockPlan::F32_H128 ? 1 : 0) | (tp == BlockPlan::F32_H128 ? 2 : 0) | (tp == BlockPlan::F32_H128_LONG ? 4 : 0) : 0;
-  else if (k == "attn_f32_hx_last")
-    *value = plain ? (sp == BlockPlan::F32_HX ? 1 : 0) | (tp == BlockPlan::F32_HX ? 2 : 0) | (tp == BlockPlan::F32_HX_LONG ? 4 : 0) : 0;
-  else return false;
-  return true;
 }
 
 // The plan of a forward of B sequences.  A pure function of the options, the shapes, B and the CU count, so an eager run, a capture
 // and a replay agree.
 BlockPlan plan_blocks(const d3d_engine* e, int B) {
   const int T = e->T, J = e->J, D = e->D, Dm = e->Dm, H = e->H, M = B * T * J, cus = device_cu_count();
-  const bool x3 = e->cfg.precision == D3D_PREC_F16X3;
   BlockPlan p;
-  // windows of more than 256 frames: no F16X3 attention kernel holds their keys in LDS; the long kernel streams them
-  const bool tp_long = e->opt_long_temporal && T > 256 && attn_temporal_x3_long_ok(T, D, H);
-  // heads of 32 columns: the one attention kernel of that width takes both block types (no D == 64 H predicate holds there, so the fused
-  // kernels, block 0 direct and the post-norm in fc2 stay off by their own predicates)
-  const bool h32 = e->opt_attn_h32 && attn_x3_h32_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
-  // the same width with a window of more than 256 frames: the spatial blocks keep that kernel (groups of J), the temporal blocks stream
-  const bool h32_long = e->opt_long_temporal_h32 && T > 256 && attn_x3_h32_long_ok(T, D, H) && attn_x3_h32_ok(J, D, H);
-  // heads of 128 columns: the spatial blocks need their groups resident (J <= 128); the temporal blocks stream beyond 128 frames (as at 32)
-  const bool h128 = e->opt_attn_h128 && attn_x3_h128_ok(J, D, H) && (attn_x3_h128_ok(T, D, H) || attn_x3_h128_long_ok(T, D, H));
-  // heads of 48 or 96 columns: the same pattern, the resident limit being the width's own (256 / 128 tokens)
-  const bool hx = e->opt_attn_hx && attn_x3_hx_ok(J, D, H) && (attn_x3_hx_ok(T, D, H) || attn_x3_hx_long_ok(T, D, H));
-  // heads of 16 columns in quads (H % 4 == 0): the same pattern, resident up to 256 tokens
-  const bool h16 = e->opt_attn_h16 && attn_x3_h16_ok(J, D, H) && (attn_x3_h16_ok(T, D, H) || attn_x3_h16_long_ok(T, D, H));
-  if (x3 && (((attn_temporal_x3_ok(T, D, H) || tp_long) && attn_temporal_x3_ok(J, D, H)) || h32 || h32_long || h128 || hx || h16) && D % 32 == 0 &&
-      e->opt_fold_layernorm) {
-    p.flow = BlockPlan::FOLD;
-    // (the predicates of the widths exclude each other: D == 32 H, 128 H, 48 H or 96 H, 16 H, 64 H)
-    p.attn_sp = h32 || h32_long ? BlockPlan::X3_H32 : h128 ? BlockPlan::X3_H128 : hx ? BlockPlan::X3_HX : h16 ? BlockPlan::X3_H16 : BlockPlan::X3;
-    p.attn_tp = h32 ? BlockPlan::X3_H32 : h32_long ? BlockPlan::X3_H32_LONG
-              : h128 ? (attn_x3_h128_ok(T, D, H) ? BlockPlan::X3_H128 : BlockPlan::X3_H128_LONG)
-              : hx ? (attn_x3_hx_ok(T, D, H) ? BlockPlan::X3_HX : BlockPlan::X3_HX_LONG)
-              : h16 ? (attn_x3_h16_ok(T, D, H) ? BlockPlan::X3_H16 : BlockPlan::X3_H16_LONG)
-              : tp_long ? BlockPlan::X3_LONG : BlockPlan::X3;   // (qkv_tattn_ok refuses T > 255: the long kernel is always the two-kernel branch)
+  p.attn = attn_choose(e->cfg.precision, e->attn_opts, e->opt_fold_layernorm, T, J, D, H);
+  if (p.attn.flow == ATTN_FLOW_FOLD) {
+    // (heads of 32 columns: no D == 64 H predicate holds there, so the fused kernels, block 0 direct and the post-norm in fc2 stay off by
+    // their own predicates; qkv_tattn_ok refuses T > 255: a streaming kernel is always the two-kernel branch)
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_ok(J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_ok(T, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
     // block 0 from the raw channels: every forward of this flow whose block 0 has the tables (fused or not, any B, any time rows)
@@ -567,12 +440,11 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
     }
     if (e->opt_fused_narrow && (long long)M * 4 * D < (1LL << 32)) {   // (the kernel's 32-bit row offsets)
       // wherever the two-kernel branch would run the resident kernel of width 32 / 16 and the commit made the tile-order images
-      const auto narrow = [](BlockPlan::Attn a) { return a == BlockPlan::X3_H32 || a == BlockPlan::X3_H16; };
-      p.narrow_sp = narrow(p.attn_sp) && qkv_attn_x3_narrow_ok(J, 1, J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
-      p.narrow_tp = narrow(p.attn_tp) && qkv_attn_x3_narrow_ok(T, J, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
+      const auto narrow = [](AttnPick a) { return a.fam().narrow && !a.stream; };
+      p.narrow_sp = narrow(p.attn.sp) && qkv_attn_x3_narrow_ok(J, 1, J, D, H, D) && e->blk[0].qkv_f3h != nullptr;
+      p.narrow_tp = narrow(p.attn.tp) && qkv_attn_x3_narrow_ok(T, J, J, D, H, D) && e->blk[1].qkv_f3h != nullptr;
     }
-  } else if (e->cfg.precision == D3D_PREC_BF16) {
-    p.flow = BlockPlan::BF16;
+  } else if (p.attn.flow == ATTN_FLOW_BF16) {
     p.fused_sp = e->opt_fused_spatial && qkv_sattn_bf16_ok(T, J, D, H, B);
     p.fused_tp = e->opt_fused_temporal && qkv_tattn_bf16_ok(T, J, D, H, B);
     p.rows = e->opt_fused_postnorm && bf16_rows_ok(D, D) && bf16_rows_ok(D, Dm);
@@ -581,36 +453,7 @@ BlockPlan plan_blocks(const d3d_engine* e, int B) {
     };
     p.bf16q_qkv = own(3 * D);
     p.bf16q_fc1 = own(Dm);
-  } else {
-    // the row-kernel flow.  F16X3: the fp16-MFMA kernel where the group length fits, q / k / v going to it as planes.  FP32: heads of 32
-    // columns (no D == 64 H predicate holds there) on the kernels of that width where the group length fits; windows of more than 256
-    // frames, which the resident fp32 MFMA kernels cannot hold in LDS, on the key-streaming ones; heads of 128 columns on the kernels of
-    // that width, each block type deciding alone (groups of up to 128 tokens resident, longer windows streaming); heads of 48 or 96
-    // columns the same way on theirs (up to 256 / 192 tokens resident) where D % 32 == 0 -- the widths at which an F16X3 engine has its
-    // own flow; one or three heads of 48 columns keep the generic kernel in both precisions, bit for bit.  Else kernels_attn.hip.
-    const bool fp32 = e->cfg.precision == D3D_PREC_FP32;
-    const bool f32_hx = fp32 && e->opt_attn_f32_hx && D % 32 == 0;
-    const bool f32_h16 = fp32 && e->opt_attn_f32_h16;   // heads of 16 columns, any head count: resident up to 256 tokens, else streaming
-    p.attn_sp = x3 && attn_temporal_x3_ok(J, D, H)                                    ? BlockPlan::X3
-              : fp32 && e->opt_attn_f32_h32 && attn_spatial_f32_h32_ok(J, D, H)       ? BlockPlan::F32_H32
-              : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_ok(J, D, H)             ? BlockPlan::F32_H128
-              : f32_hx && attn_f32_hx_ok(J, D, H)                                     ? BlockPlan::F32_HX
-              : f32_h16 && attn_f32_h16_ok(J, D, H)                                   ? BlockPlan::F32_H16
-              : attn_spatial_fast_ok(J, D, H)                                         ? BlockPlan::F32_SPATIAL
-                                                                                      : BlockPlan::GENERIC;
-    p.attn_tp = x3 && attn_temporal_x3_ok(T, D, H)                                    ? BlockPlan::X3
-              : fp32 && e->opt_attn_f32_h32 && attn_temporal_f32_h32_ok(T, D, H)      ? BlockPlan::F32_H32
-              : fp32 && e->opt_long_temporal_f32 && T > 256 && attn_temporal_f32_long_ok(T, D, H)          ? BlockPlan::F32_LONG
-              : fp32 && e->opt_long_temporal_f32_h32 && T > 256 && attn_temporal_f32_h32_long_ok(T, D, H)  ? BlockPlan::F32_H32_LONG
-              : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_ok(T, D, H)             ? BlockPlan::F32_H128
-              : fp32 && e->opt_attn_f32_h128 && attn_f32_h128_long_ok(T, D, H)        ? BlockPlan::F32_H128_LONG
-              : f32_hx && attn_f32_hx_ok(T, D, H)                                     ? BlockPlan::F32_HX
-              : f32_hx && attn_f32_hx_long_ok(T, D, H)                                ? BlockPlan::F32_HX_LONG
-              : f32_h16 && attn_f32_h16_ok(T, D, H)                                   ? BlockPlan::F32_H16
-              : f32_h16 && attn_f32_h16_long_ok(T, D, H)                              ? BlockPlan::F32_H16_LONG
-              : attn_temporal_fast_ok(T, D, H)                                        ? BlockPlan::F32_TEMPORAL
-                                                                                      : BlockPlan::GENERIC;
-  }
+  }   // (the row-kernel flow: nothing beyond its two attention kernels)
   return p;
 }
 
@@ -765,7 +608,7 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
     {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD4, s);
-      const int rc = launch_attention(e, temporal ? pl.attn_tp : pl.attn_sp, temporal, QKVh, nullptr, AOx, B, s);
+      const int rc = launch_attention(e, temporal ? pl.attn.tp : pl.attn.sp, temporal, QKVh, nullptr, AOx, B, s);
       if (rc) return rc;
     }
     TRACE(k, 3, 0, AOx, MDb);
@@ -973,8 +816,8 @@ int run_blocks(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float
   const int T = e->T, J = e->J, D = e->D;
   const int M = B * T * J;
   const double MD4 = (double)M * D * 4.0;
-  if (pl.flow == BlockPlan::FOLD) return run_blocks_fold(e, pl, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
-  if (pl.flow == BlockPlan::BF16) return run_blocks_bf16(e, pl, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
+  if (pl.attn.flow == ATTN_FLOW_FOLD) return run_blocks_fold(e, pl, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
+  if (pl.attn.flow == ATTN_FLOW_BF16) return run_blocks_bf16(e, pl, x2d, y, y_bcast, tvec, tvec_stride, B, w, s);
   {
     Prof p(e, D3D_KC_EMBED, 2.0 * M * D * e->cin, MD4 + (double)M * e->cin * 4.0, s);
     HIP_TRY(launch_embed(x2d, y, e->fus_w, e->fus_b, e->spos, tvec, tvec_stride, w.X, B, T, J, D, e->cfg.in_chans,
@@ -1010,8 +853,8 @@ int run_blocks(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float
     const bool temporal = (k & 1) != 0;
     // F16X3: the qkv GEMM hands q/k/v to the fp16-MFMA attention kernel as hi/lo planes.  A spatial block is the same
     // kernel over groups of J consecutive tokens (one "joint", "frames" = the J tokens of a frame, B*T "batches").
-    const BlockPlan::Attn kernel = temporal ? pl.attn_tp : pl.attn_sp;
-    const bool attn_x3 = kernel == BlockPlan::X3;
+    const AttnPick kernel = temporal ? pl.attn.tp : pl.attn.sp;
+    const bool attn_x3 = kernel.fam().form == ATTN_PLANES;
     uint16_t* QKVh = reinterpret_cast<uint16_t*>(w.QKV);
     uint16_t* QKVl = QKVh + (size_t)M * 3 * D;
     qcols_ = attn_x3 ? D : 0;
@@ -1611,18 +1454,7 @@ int d3d_engine_set_option(d3d_engine* e, const char* key, int64_t value) {
       if (rc) { e->opt_latency_mode = false; return rc; }
     }
   }
-  else if (k == "long_temporal") e->opt_long_temporal = value != 0;
-  else if (k == "long_temporal_f32") e->opt_long_temporal_f32 = value != 0;
-  else if (k == "attn_h32") e->opt_attn_h32 = value != 0;
-  else if (k == "attn_f32_h32") e->opt_attn_f32_h32 = value != 0;
-  else if (k == "long_temporal_h32") e->opt_long_temporal_h32 = value != 0;
-  else if (k == "long_temporal_f32_h32") e->opt_long_temporal_f32_h32 = value != 0;
-  else if (k == "attn_h128") e->opt_attn_h128 = value != 0;
-  else if (k == "attn_f32_h128") e->opt_attn_f32_h128 = value != 0;
-  else if (k == "attn_hx") e->opt_attn_hx = value != 0;
-  else if (k == "attn_f32_hx") e->opt_attn_f32_hx = value != 0;
-  else if (k == "attn_h16") e->opt_attn_h16 = value != 0;
-  else if (k == "attn_f32_h16") e->opt_attn_f32_h16 = value != 0;
+  else if (const int ao = attn_option_index(key); ao >= 0) e->attn_opts = value != 0 ? e->attn_opts | 1u << ao : e->attn_opts & ~(1u << ao);
   else if (k == "proj_split" || k == "fc1_split") {
     const bool proj = k == "proj_split";
     if (value != -1 && value != 0 && !(proj ? proj_splitk_ok(e->D, e->D, (int)value) : fc1_splitk_ok(e->Dm, e->D, (int)value)))
@@ -1693,20 +1525,9 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "graphs_captured") *value = (int64_t)e->graphs_captured;
   else if (k == "streams") *value = e->opt_streams;
   else if (k == "device") *value = e->device;
-  else if (attention_plan_info(e->last_plan, k, value)) {}   // the "*_last" keys of the attention kernels
+  else if (attn_plan_key(e->last_plan.attn, key, value)) {}   // the "*_last" keys of the attention kernels
   else if (k == "latency_mode") *value = e->opt_latency_mode ? 1 : 0;
-  else if (k == "long_temporal") *value = e->opt_long_temporal ? 1 : 0;
-  else if (k == "long_temporal_f32") *value = e->opt_long_temporal_f32 ? 1 : 0;
-  else if (k == "attn_h32") *value = e->opt_attn_h32 ? 1 : 0;
-  else if (k == "attn_f32_h32") *value = e->opt_attn_f32_h32 ? 1 : 0;
-  else if (k == "long_temporal_h32") *value = e->opt_long_temporal_h32 ? 1 : 0;
-  else if (k == "long_temporal_f32_h32") *value = e->opt_long_temporal_f32_h32 ? 1 : 0;
-  else if (k == "attn_h128") *value = e->opt_attn_h128 ? 1 : 0;
-  else if (k == "attn_f32_h128") *value = e->opt_attn_f32_h128 ? 1 : 0;
-  else if (k == "attn_hx") *value = e->opt_attn_hx ? 1 : 0;
-  else if (k == "attn_f32_hx") *value = e->opt_attn_f32_hx ? 1 : 0;
-  else if (k == "attn_h16") *value = e->opt_attn_h16 ? 1 : 0;
-  else if (k == "attn_f32_h16") *value = e->opt_attn_f32_h16 ? 1 : 0;
+  else if (const int ao = attn_option_index(key); ao >= 0) *value = e->attn_opts >> ao & 1u;
   else if (k == "deep_stages") *value = e->opt_deep_stages < 0 ? (x3q_deep_stages_default() ? 1 : 0) : e->opt_deep_stages;
   else if (k == "fc2_split_last") *value = e->last_plan.fc2_split;
   else if (k == "proj_split_last") *value = e->last_plan.proj_split;
@@ -1715,14 +1536,14 @@ int d3d_engine_get_info(const d3d_engine* e, const char* key, int64_t* value) {
   else if (k == "proj_split") *value = e->opt_proj_split;
   else if (k == "small_tiles") *value = e->opt_small_tiles ? 1 : 0;
   else if (k == "small_tiles_last")
-    *value = e->last_plan.flow == BlockPlan::FOLD ? (e->last_plan.small_sp ? 1 : 0) | (e->last_plan.small_tp ? 2 : 0) : 0;
+    *value = e->last_plan.attn.flow == ATTN_FLOW_FOLD ? (e->last_plan.small_sp ? 1 : 0) | (e->last_plan.small_tp ? 2 : 0) : 0;
   else if (k == "fused_narrow") *value = e->opt_fused_narrow ? 1 : 0;
   else if (k == "fused_narrow_last")
-    *value = e->last_plan.flow == BlockPlan::FOLD ? (e->last_plan.narrow_sp ? 1 : 0) | (e->last_plan.narrow_tp ? 2 : 0) : 0;
+    *value = e->last_plan.attn.flow == ATTN_FLOW_FOLD ? (e->last_plan.narrow_sp ? 1 : 0) | (e->last_plan.narrow_tp ? 2 : 0) : 0;
   else if (k == "fc1_split") *value = e->opt_fc1_split;
-  else if (k == "fused_spatial_last") *value = e->last_plan.flow == BlockPlan::FOLD && e->last_plan.fused_sp;
-  else if (k == "bf16_fused_spatial_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_sp;
-  else if (k == "bf16_fused_temporal_last") *value = e->last_plan.flow == BlockPlan::BF16 && e->last_plan.fused_tp;
+  else if (k == "fused_spatial_last") *value = e->last_plan.attn.flow == ATTN_FLOW_FOLD && e->last_plan.fused_sp;
+  else if (k == "bf16_fused_spatial_last") *value = e->last_plan.attn.flow == ATTN_FLOW_BF16 && e->last_plan.fused_sp;
+  else if (k == "bf16_fused_temporal_last") *value = e->last_plan.attn.flow == ATTN_FLOW_BF16 && e->last_plan.fused_tp;
   else return fail(D3D_EINVAL, "unknown info key: " + k);
   return D3D_OK;
 }

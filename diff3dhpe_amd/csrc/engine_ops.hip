@@ -6,6 +6,7 @@
 #include <functional>
 #include <vector>
 
+#include "attn_dispatch.h"
 #include "d3d_kernels.h"
 #include "engine_internal.h"
 
@@ -110,36 +111,44 @@ int finish(hipError_t le, hipStream_t s) {
 }
 
 // The round trip of the single-op hooks of the F16X3 attention kernels: fp32 qkv (rows, 3 D) -> hi / lo planes (as the qkv GEMM
-// epilogue writes them) -> the kernel alone, launch(hi, lo, out_pair) -> pair layout -> fp32 out (rows, D).
+// epilogue writes them) -> the kernel alone, launch(hi, lo, out_pair) -> pair layout -> fp32 out (rows, D).  The pair-layout rows are
+// 2 ceil32(D) halves apart: where D is no multiple of 32 (an odd head count at width 48 -- no engine, only these ops) the rows are
+// unpacked at that pitch and their first D columns copied out.
 template <class Launch>
 int attention_x3_round_trip(const float* qkv, float* out, size_t rows, int D, hipStream_t s, Launch launch) {
-  const size_t nq = rows * 3 * D, no = rows * D;
-  DevBuf<uint16_t> tmp;
-  HIP_TRY(tmp.alloc(2 * nq + 2 * no));
-  hipError_t le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
-  if (le == hipSuccess) le = launch(tmp.p, tmp.p + nq, tmp.p + 2 * nq);
-  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, out, rows, D, s);
-  return finish(le, s);
-}
-
-// The round trip of the width-48 / 96 kernels.  Their pair-layout rows are 2 ceil32(D) halves apart: where D is no multiple of 32 (an odd
-// head count at width 48 -- no engine, only these ops) the rows are unpacked at that pitch and their first D columns copied out.
-template <class Launch>
-int attention_hx_round_trip(const float* qkv, float* out, size_t rows, int D, hipStream_t s, Launch launch) {
-  if (D % 32 == 0) return attention_x3_round_trip(qkv, out, rows, D, s, launch);
   const int Dp = (D + 31) & ~31;
   const size_t nq = rows * 3 * D, np = rows * Dp;
   DevBuf<uint16_t> tmp;
   DevBuf<float> wide;
   HIP_TRY(tmp.alloc(2 * nq + 2 * np));
-  HIP_TRY(wide.alloc(np));
-  hipError_t le = hipMemsetAsync(tmp.p + 2 * nq, 0, 2 * np * sizeof(uint16_t), s);   // the columns behind D are read back, not written
+  if (Dp != D) HIP_TRY(wide.alloc(np));
+  hipError_t le = Dp != D ? hipMemsetAsync(tmp.p + 2 * nq, 0, 2 * np * sizeof(uint16_t), s) : hipSuccess;   // (columns behind D: read back, not written)
   if (le == hipSuccess) le = launch_split_qkv(qkv, tmp.p, tmp.p + nq, rows, D, s);
   if (le == hipSuccess) le = launch(tmp.p, tmp.p + nq, tmp.p + 2 * nq);
-  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, wide.p, rows, Dp, s);
-  if (le == hipSuccess)
+  if (le == hipSuccess) le = launch_unsplit_pair(tmp.p + 2 * nq, Dp != D ? wide.p : out, rows, Dp, s);
+  if (le == hipSuccess && Dp != D)
     le = hipMemcpy2DAsync(out, (size_t)D * sizeof(float), wide.p, (size_t)Dp * sizeof(float), (size_t)D * sizeof(float), rows, hipMemcpyDeviceToDevice, s);
   return finish(le, s);
+}
+
+// The body of every width-specific attention hook: one regime of one family of attn_dispatch.h (resident, for the spatial or the temporal
+// blocks, or key-streaming) on fp32 qkv (B T J, 3 D) -> fp32 out (B T J, D).  The fp32 kernels run in place of the caller's buffers; the
+// planes kernels through the round trip above.
+int attention_op(AttnFamilyId family, bool streaming, const float* qkv, float* out, int B, int T, int J, int D, int H, bool temporal,
+                 void* stream) {
+  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
+  const AttnPick pick{family, streaming ? 1 : 0};
+  const AttnRegime& r = pick.regime(temporal);
+  if (!r.ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, r.unsup);
+  AttnArgs a{qkv, nullptr, out, nullptr, B, T, J, D, H, temporal, reinterpret_cast<hipStream_t>(stream)};
+  if (pick.fam().form == ATTN_ROWS) {
+    HIP_TRY(r.launch(a));
+    return D3D_OK;
+  }
+  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, a.s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
+    a.qkv = hi; a.qkv_lo = lo; a.out_x3 = o;
+    return r.launch(a);
+  });
 }
 
 }  // namespace
@@ -535,166 +544,60 @@ int d3d_op_attention(const float* qkv, float* out, int32_t B, int32_t T, int32_t
   return D3D_OK;
 }
 
+// The width-specific hooks: (family, streaming) of attn_dispatch.h; the streaming kernels serve temporal blocks alone
 int d3d_op_attention_long(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_temporal_x3_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 64");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return launch_attn_temporal_x3_long(hi, lo, o, B, T, J, D, H, s);
-  });
+  return attention_op(AF_X3, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
 int d3d_op_attention_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_h32_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "F16X3 attention for head_dim 32: an even head count, group length <= 256");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return temporal ? launch_attn_x3_h32(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_h32(hi, lo, o, B * T, J, 1, D, H, s);
-  });
+  return attention_op(AF_X3_H32, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_f32_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (temporal) {
-    if (!attn_temporal_f32_h32_ok(T, D, H)) return fail(D3D_EUNSUP, "fp32 temporal attention for head_dim 32: window length <= 256");
-    HIP_TRY(launch_attn_temporal_f32_h32(qkv, out, B, T, J, D, H, s));
-  } else {
-    if (!attn_spatial_f32_h32_ok(J, D, H)) return fail(D3D_EUNSUP, "fp32 spatial attention for head_dim 32: 15 to 17 joints");
-    HIP_TRY(launch_attn_spatial_f32_h32(qkv, out, B, T, J, D, H, s));
-  }
-  return D3D_OK;
+  return attention_op(AF_F32_H32, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_long_f32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_temporal_f32_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 64");
-  HIP_TRY(launch_attn_temporal_f32_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
+  return attention_op(AF_F32, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
 int d3d_op_attention_long_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_h32_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention for head_dim 32: an even head count");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return launch_attn_x3_h32_long(hi, lo, o, B, T, J, D, H, s);
-  });
+  return attention_op(AF_X3_H32, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
 int d3d_op_attention_long_f32_h32(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_temporal_f32_h32_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 32");
-  HIP_TRY(launch_attn_temporal_f32_h32_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
+  return attention_op(AF_F32_H32, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
-int d3d_op_attention_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
-                          void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_h128_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "F16X3 attention for head_dim 128: groups of up to 128 tokens");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return temporal ? launch_attn_x3_h128(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_h128(hi, lo, o, B * T, J, 1, D, H, s);
-  });
+int d3d_op_attention_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
+  return attention_op(AF_X3_H128, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_long_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_h128_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 128");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return launch_attn_x3_h128_long(hi, lo, o, B, T, J, D, H, s);
-  });
+  return attention_op(AF_X3_H128, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
-int d3d_op_attention_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
-                        void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_hx_ok(temporal ? T : J, D, H))
-    return fail(D3D_EUNSUP, "F16X3 attention for head_dim 48 or 96: groups of up to 256 (head_dim 48) / 128 (head_dim 96) tokens");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_hx_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return temporal ? launch_attn_x3_hx(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_hx(hi, lo, o, B * T, J, 1, D, H, s);
-  });
+int d3d_op_attention_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
+  return attention_op(AF_X3_HX, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_long_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_hx_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 48 or 96");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_hx_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return launch_attn_x3_hx_long(hi, lo, o, B, T, J, D, H, s);
-  });
+  return attention_op(AF_X3_HX, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
-int d3d_op_attention_f32_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
-                              void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_f32_h128_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "fp32 attention for head_dim 128: groups of up to 128 tokens");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIP_TRY(temporal ? launch_attn_f32_h128(qkv, out, B, T, J, D, H, s) : launch_attn_f32_h128(qkv, out, B * T, J, 1, D, H, s));
-  return D3D_OK;
+int d3d_op_attention_f32_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
+  return attention_op(AF_F32_H128, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_long_f32_h128(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_f32_h128_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 128");
-  HIP_TRY(launch_attn_f32_h128_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
+  return attention_op(AF_F32_H128, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
-int d3d_op_attention_f32_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
-                            void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_f32_hx_ok(temporal ? T : J, D, H))
-    return fail(D3D_EUNSUP, "fp32 attention for head_dim 48 or 96: groups of up to 256 (head_dim 48) / 192 (head_dim 96) tokens");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIP_TRY(temporal ? launch_attn_f32_hx(qkv, out, B, T, J, D, H, s) : launch_attn_f32_hx(qkv, out, B * T, J, 1, D, H, s));
-  return D3D_OK;
+int d3d_op_attention_f32_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
+  return attention_op(AF_F32_HX, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_long_f32_hx(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_f32_hx_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 48 or 96");
-  HIP_TRY(launch_attn_f32_hx_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
+  return attention_op(AF_F32_HX, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
-int d3d_op_attention_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
-                         void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_h16_ok(temporal ? T : J, D, H))
-    return fail(D3D_EUNSUP, "F16X3 attention for head_dim 16: a multiple of 4 heads, groups of up to 256 tokens");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return temporal ? launch_attn_x3_h16(hi, lo, o, B, T, J, D, H, s) : launch_attn_x3_h16(hi, lo, o, B * T, J, 1, D, H, s);
-  });
+int d3d_op_attention_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
+  return attention_op(AF_X3_H16, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_long_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_x3_h16_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming F16X3 attention: head_dim 16, a multiple of 4 heads");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return attention_x3_round_trip(qkv, out, (size_t)B * T * J, D, s, [&](const uint16_t* hi, const uint16_t* lo, uint16_t* o) {
-    return launch_attn_x3_h16_long(hi, lo, o, B, T, J, D, H, s);
-  });
+  return attention_op(AF_X3_H16, true, qkv, out, B, T, J, D, H, true, stream);
 }
-
-int d3d_op_attention_f32_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
-                             void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_f32_h16_ok(temporal ? T : J, D, H)) return fail(D3D_EUNSUP, "fp32 attention for head_dim 16: groups of up to 256 tokens");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIP_TRY(temporal ? launch_attn_f32_h16(qkv, out, B, T, J, D, H, s) : launch_attn_f32_h16(qkv, out, B * T, J, 1, D, H, s));
-  return D3D_OK;
+int d3d_op_attention_f32_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal, void* stream) {
+  return attention_op(AF_F32_H16, false, qkv, out, B, T, J, D, H, temporal != 0, stream);
 }
-
 int d3d_op_attention_long_f32_h16(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, void* stream) {
-  if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
-  if (!attn_f32_h16_long_ok(T, D, H)) return fail(D3D_EUNSUP, "key-streaming fp32 attention: head_dim 16");
-  HIP_TRY(launch_attn_f32_h16_long(qkv, out, B, T, J, D, H, reinterpret_cast<hipStream_t>(stream)));
-  return D3D_OK;
+  return attention_op(AF_F32_H16, true, qkv, out, B, T, J, D, H, true, stream);
 }
 
 }  // extern "C"
