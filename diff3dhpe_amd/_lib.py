@@ -9,11 +9,11 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libd3d_hip.so")
 
-PREC_FP32, PREC_F16X3, PREC_BF16 = 0, 1, 2
+PREC_FP32, PREC_F16X3, PREC_BF16, PREC_F16 = 0, 1, 2, 3
 KC_COUNT = 13
 RANGE_ACT, RANGE_WEIGHT, RANGE_STATS, RANGE_INDEX, RANGE_RECOMPUTE = 1, 2, 4, 8, 16
 RANGE_PRECISION = RANGE_ACT | RANGE_WEIGHT | RANGE_STATS        # the bits that mean "not fp32-accurate in F16X3"
-PRECISIONS = {"fp32": PREC_FP32, "f16x3": PREC_F16X3, "bf16": PREC_BF16}
+PRECISIONS = {"fp32": PREC_FP32, "f16x3": PREC_F16X3, "bf16": PREC_BF16, "f16": PREC_F16}
 
 # every symbol include/d3d.h declares (tests/test_abi_host.py checks the library exports all of them)
 ABI_SYMBOLS = [
@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "d3d_engine_profile_read", "d3d_kernel_class_name", "d3d_op_linear_bench", "d3d_op_linear_postnorm", "d3d_op_linear_splitk_postnorm", "d3d_op_linear_splitk_residual", "d3d_op_linear_splitk_gelu", "d3d_engine_set_graph_mode", "d3d_num_windows", "d3d_window_gather",
     "d3d_engine_set_trace", "d3d_engine_trace_read", "d3d_engine_range_flags", "d3d_op_head", "d3d_engine_set_option",
     "d3d_weighted_loss", "d3d_repeat_batch", "d3d_hypothesis_mean", "d3d_engine_get_info", "d3d_probe_machine",
-    "d3d_engine_range_post", "d3d_engine_range_take", "d3d_window_gather_s2f", "d3d_pose_metrics", "d3d_op_qkv_attn_bf16",
+    "d3d_engine_range_post", "d3d_engine_range_take", "d3d_window_gather_s2f", "d3d_pose_metrics", "d3d_op_qkv_attn_bf16", "d3d_op_qkv_attn_f16",
     "d3d_op_qkv_attn_x3_small", "d3d_op_qkv_attn_x3_narrow", "d3d_op_linear_folded", "d3d_op_linear_plane_residual", "d3d_op_layernorm_forms",
 ]
 
@@ -118,6 +118,7 @@ def _bind(lib: C.CDLL) -> None:
         "d3d_op_attention_f32_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
         "d3d_op_attention_long_f32_h16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
         "d3d_op_qkv_attn_bf16": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "d3d_op_qkv_attn_f16": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "d3d_op_qkv_attn_x3_small": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, i32, i32, vp, vp]),
         "d3d_op_qkv_attn_x3_narrow": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, i32, i32, vp, vp]),
     }

@@ -171,7 +171,7 @@ AttnChoice attn_choose(int precision, unsigned opts, bool fold_layernorm, int T,
       return c;
     }
   }
-  if (precision == D3D_PREC_BF16) {
+  if (precision == D3D_PREC_BF16 || precision == D3D_PREC_F16) {   // (one flow for both 16-bit operand modes)
     c.flow = ATTN_FLOW_BF16;
     return c;
   }

@@ -216,20 +216,23 @@ hipError_t launch_unsplit_x3(const void* pair, float* x, size_t rows, int cols, 
                              hipStream_t s);   // op hooks only
 // bf16 operand mode (D3D_PREC_BF16): A / W plain bf16 rows (K % 64 == 0, rows padded as above), one bf16 MFMA per product, fp32
 // accumulate.  EPI_NONE / EPI_GELU write Cb = bf16 [M][N] (columns < qcols scaled by 2^-3), EPI_RESIDUAL writes fp32 C = R + ...
+// f16 = true, here and on every launcher of this group: the fp16 operand mode (D3D_PREC_F16) -- the same kernels instantiated for fp16
+// rows (FX_F16): the f16 twin of each bf16 MFMA, every 16-bit output rounded to fp16 (nearest even, subnormals kept, inf beyond 65504).
 hipError_t launch_linear_bf16(const void* A, const void* W, const float* bias, const float* R, float* C, void* Cb, int M, int N,
-                              int K, int epi, int qcols, hipStream_t s);
+                              int K, int epi, int qcols, hipStream_t s, bool f16 = false);
 // Whole-row form (N == 512, 128-row tiles): X[M,N] fp32 is the residual stream, updated IN PLACE,
 //   y = X + A W^T + bias;   if pn.g: y = LN(y; pn.g, pn.b, pn.eps) [+ pos] [+ tvec];   X = y;
 //   if pn.g2: Hb = bf16(LN(y; pn.g2, pn.b2, pn.eps2))   (bf16 [M][N], the next GEMM's operand)
 // -- proj + norm2 (pn.g == nullptr) and fc2 + post-norm + next norm1 of a bf16-mode block without any row kernel.
 bool bf16_rows_ok(int N, int K);
 hipError_t launch_linear_bf16_rows(const void* A, const void* W, const float* bias, float* X, void* Hb, int M, int N, int K,
-                                   const X3PostNorm& pn, hipStream_t s);
+                                   const X3PostNorm& pn, hipStream_t s, bool f16 = false);
 // kernels_gemm_bf16q.hip: the plain bf16 GEMMs (qkv, fc1) on the hand-specialised two-phase k-loop; bit-identical to launch_linear_bf16's forms
 bool gemm_bf16q_ok(int N, int K);
-hipError_t launch_gemm_bf16q(const void* A, const void* W, const float* bias, void* Cb, int M, int N, int K, int epi, int qcols, hipStream_t s);
-hipError_t launch_f32_to_bf16(const float* x, void* y, size_t n, hipStream_t s);
-hipError_t launch_bf16_to_f32(const void* x, float* y, size_t n, hipStream_t s);
+hipError_t launch_gemm_bf16q(const void* A, const void* W, const float* bias, void* Cb, int M, int N, int K, int epi, int qcols, hipStream_t s,
+                             bool f16 = false);
+hipError_t launch_f32_to_bf16(const float* x, void* y, size_t n, hipStream_t s, bool f16 = false);
+hipError_t launch_bf16_to_f32(const void* x, float* y, size_t n, hipStream_t s, bool f16 = false);
 hipError_t launch_scale_cols(float* x, size_t rows, int cols, int ncols_scaled, float f, hipStream_t s);   // op hooks only
 
 // ---- kernels_qkv_sattn.hip: spatial blocks, qkv GEMM (LayerNorm-folded) + J-key attention in one kernel, J = 15, 16, 17 --------------------
@@ -302,6 +305,7 @@ struct LnArgs {
   int rows_per_batch;
   int rows, D;
   unsigned* range;   // filled in by launch_layernorm: the range-guard word the plane outputs report to
+  int h_f16;         // 1: the h_bf16 rows are fp16 (D3D_PREC_F16: round to nearest even, subnormals kept)
 };
 hipError_t launch_layernorm(const LnArgs& a, hipStream_t s);
 
@@ -465,7 +469,7 @@ bool attn_spatial_fast_ok(int J, int D, int H);
 // ---- kernels_attn_bf16.hip: the same core on v_mfma_f32_32x32x16_bf16, one MFMA per product (D3D_PREC_BF16).  qkv: ONE bf16
 // buffer [rows][3D] (q third pre-scaled by dh^-0.5, written by launch_linear_bf16 with qcols = D); out: bf16 [rows][D].
 // Spatial blocks: call with (B * T, J, 1).  softmax - I is normalised and rounded to bf16 before the second product.
-hipError_t launch_attn_bf16(const void* qkv_bf16, void* out_bf16, int B, int T, int J, int D, int H, hipStream_t s);
+hipError_t launch_attn_bf16(const void* qkv_bf16, void* out_bf16, int B, int T, int J, int D, int H, hipStream_t s, bool f16 = false);
 bool attn_bf16_ok(int T, int D, int H);
 // ---- kernels_qkv_attn_bf16.hip: the bf16 qkv GEMM and that attention in ONE kernel (k_qkv_sattn_bf16 / k_qkv_tattn_bf16): q / k / v stay
 // in LDS; bit-identical to launch_linear_bf16 / launch_gemm_bf16q (qcols = D) followed by launch_attn_bf16.  A: bf16 [groups * N][D]
@@ -475,7 +479,7 @@ bool attn_bf16_ok(int T, int D, int H);
 bool qkv_sattn_bf16_ok(int T, int J, int D, int H, int B);
 bool qkv_tattn_bf16_ok(int T, int J, int D, int H, int B);
 hipError_t launch_qkv_attn_bf16(const void* A, const void* W, const float* bias, void* out, int groups, int N, int stride, int D, int H,
-                                int temporal, hipStream_t s);
+                                int temporal, hipStream_t s, bool f16 = false);
 bool attn_temporal_fast_ok(int T, int D, int H);
 
 }  // namespace d3d

@@ -722,11 +722,15 @@ int run_blocks_fold(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
 // bf16 (fc1 epilogue), weights -> bf16 (commit).  Same op sequence as run_blocks (S2S:222-247, 111-135); leaves the final
 // Temporal_norm output as fp32 in w.X.  Measured first with three LayerNorm row kernels per block, then
 // given the whole-row proj / fc2 forms below; the row-kernel flow stays behind "fused_postnorm" = 0.
+// fp16 operand mode (D3D_PREC_F16): this flow with every launch in its fp16-operand form -- the same rounding points, each now a round to
+// nearest even to fp16 (subnormals kept, +-inf beyond 65504: the mode is unscaled and has no range guard), the f16 twin of each bf16
+// MFMA.  Plan bits, option and info keys are shared; "bf16" in a name below reads "16-bit operand".
 int run_blocks_bf16(d3d_engine* e, const BlockPlan& pl, const float* x2d, const float* y, int y_bcast, const float* tvec,
                     int64_t tvec_stride, int B, const Workspace& w, hipStream_t s) {
   const int T = e->T, J = e->J, D = e->D;
   const int M = B * T * J;
   const double MD4 = (double)M * D * 4.0, MD2 = (double)M * D * 2.0;
+  const bool f16 = e->cfg.precision == D3D_PREC_F16;
   uint16_t* HNb = reinterpret_cast<uint16_t*>(w.HN);     // bf16 [Mp][D]: LayerNorm output, then the attention output
   uint16_t* QKVb = reinterpret_cast<uint16_t*>(w.QKV);   // bf16 [M][3D]; in a fused block (below) bf16 [M][D]: the attention output
   uint16_t* HIDb = reinterpret_cast<uint16_t*>(w.HID);   // bf16 [Mp][Dm]
@@ -738,11 +742,12 @@ int run_blocks_bf16(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
                     int qcols, int sub) -> hipError_t {
     Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)N * K, 2.0 * ((double)M * K + (double)N * K) + (double)M * N * (R ? 8.0 : 2.0), s, sub);
     if (sub == D3D_KC_LINEAR_QKV ? pl.bf16q_qkv : sub == D3D_KC_LINEAR_FC1 && pl.bf16q_fc1)
-      return launch_gemm_bf16q(A, W, bias, Cb, M, N, K, epi, qcols, s);
-    return launch_linear_bf16(A, W, bias, R, C, Cb, M, N, K, epi, qcols, s);
+      return launch_gemm_bf16q(A, W, bias, Cb, M, N, K, epi, qcols, s, f16);
+    return launch_linear_bf16(A, W, bias, R, C, Cb, M, N, K, epi, qcols, s, f16);
   };
   auto lnorm = [&](LnArgs a) -> hipError_t {
     Prof p(e, D3D_KC_LAYERNORM, 8.0 * M * D, MD4 * (1 + (a.y ? 1 : 0)) + MD2, s);
+    a.h_f16 = f16 ? 1 : 0;
     return launch_layernorm(a, s);
   };
   {  // h = bf16(norm1_0(x))
@@ -755,7 +760,7 @@ int run_blocks_bf16(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
   // (measured first un-fused, as planned: 59 of 323 ms per sampling were LayerNorm kernels at 5 TB/s).
   auto linear_rows = [&](const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* Hb, int K, const X3PostNorm& pn, int sub) -> hipError_t {
     Prof p(e, D3D_KC_LINEAR, 2.0 * M * (double)D * K, 2.0 * ((double)M * K + (double)D * K) + (double)M * D * (Hb ? 10.0 : 8.0), s, sub);
-    return launch_linear_bf16_rows(A, W, bias, w.X, Hb, M, D, K, pn, s);
+    return launch_linear_bf16_rows(A, W, bias, w.X, Hb, M, D, K, pn, s, f16);
   };
   // qkv GEMM + attention of a block in ONE kernel (kernels_qkv_attn_bf16.hip; "fused_spatial" / "fused_temporal"): q / k / v never reach
   // HBM.  Every head's tile reads whole rows of HNb, so the attention output cannot go there: it takes w.QKV, dead in such a block.
@@ -767,15 +772,15 @@ int run_blocks_bf16(d3d_engine* e, const BlockPlan& pl, const float* x2d, const 
     if (temporal ? pl.fused_tp : pl.fused_sp) {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_QKV_TATTN : D3D_KC_QKV_SATTN, 2.0 * M * 3.0 * D * D + 4.0 * M * (double)N * D, 2.0 * MD2 + 2.0 * 3.0 * D * D, s);
-      HIP_TRY(launch_qkv_attn_bf16(HNb, bw.qkv_x3, bw.qkvb, QKVb, temporal ? B * J : B * T, N, temporal ? J : 1, D, e->H, temporal ? 1 : 0, s));
+      HIP_TRY(launch_qkv_attn_bf16(HNb, bw.qkv_x3, bw.qkvb, QKVb, temporal ? B * J : B * T, N, temporal ? J : 1, D, e->H, temporal ? 1 : 0, s, f16));
       AOb = QKVb;
     } else {
     HIP_TRY(linear(HNb, bw.qkv_x3, bw.qkvb, nullptr, nullptr, QKVb, 3 * D, D, EPI_NONE, D, D3D_KC_LINEAR_QKV));
     {
       const int N = temporal ? T : J;
       Prof p(e, temporal ? D3D_KC_ATTN_TEMPORAL : D3D_KC_ATTN_SPATIAL, 4.0 * M * (double)N * D, 4.0 * MD2, s);
-      if (temporal) HIP_TRY(launch_attn_bf16(QKVb, HNb, B, T, J, D, e->H, s));
-      else HIP_TRY(launch_attn_bf16(QKVb, HNb, B * T, J, 1, D, e->H, s));
+      if (temporal) HIP_TRY(launch_attn_bf16(QKVb, HNb, B, T, J, D, e->H, s, f16));
+      else HIP_TRY(launch_attn_bf16(QKVb, HNb, B * T, J, 1, D, e->H, s, f16));
     }
     }
     // x = post_norm(x + hidden W2^T + b2) [+ Temporal_pos_embed before TTE0] [+ next block's time vector]; h = bf16(next.norm1(x))
@@ -957,7 +962,7 @@ const char* d3d_last_error(void) { return g_err.c_str(); }
 // 147: option / info keys "attn_h16" and "attn_f32_h16", info keys "attn_h16_last" and "attn_f32_h16_last", d3d_op_attention_h16,
 // d3d_op_attention_long_h16, d3d_op_attention_f32_h16, d3d_op_attention_long_f32_h16
 // 148: option / info key "fused_narrow", info key "fused_narrow_last", d3d_op_qkv_attn_x3_narrow
-int d3d_version(void) { return 148; }
+int d3d_version(void) { return 149; }
 
 int d3d_ddim_times(int32_t num_timesteps, int32_t sampling_timesteps, int32_t* out) {
   // torch.linspace(-1, N-1, S+1) in fp32 (two-sided evaluation around the midpoint), .int() truncation, reversed
@@ -998,12 +1003,16 @@ int d3d_engine_create(const d3d_config* c, d3d_engine** out) {
     if (dh != 4 && dh != 8 && dh != 16 && dh != 32 && dh != 48 && dh != 64 && dh != 96 && dh != 128)
       return fail(D3D_EUNSUP, "head_dim must be 4,8,16,32,48,64,96 or 128");
   }
-  if (c->precision != D3D_PREC_FP32 && c->precision != D3D_PREC_F16X3 && c->precision != D3D_PREC_BF16)
-    return fail(D3D_EUNSUP, "precision must be D3D_PREC_FP32, D3D_PREC_F16X3 or D3D_PREC_BF16");
+  if (c->precision != D3D_PREC_FP32 && c->precision != D3D_PREC_F16X3 && c->precision != D3D_PREC_BF16 && c->precision != D3D_PREC_F16)
+    return fail(D3D_EUNSUP, "precision must be D3D_PREC_FP32, D3D_PREC_F16X3, D3D_PREC_BF16 or D3D_PREC_F16");
   if (c->precision == D3D_PREC_BF16 &&
       (!attn_bf16_ok(c->num_frame, c->embed_dim, c->num_heads) || !attn_bf16_ok(c->num_joints, c->embed_dim, c->num_heads) ||
        c->num_joints > 32 || c->embed_dim % 64 || c->mlp_hidden % 64))
     return fail(D3D_EUNSUP, "D3D_PREC_BF16 needs head_dim 64, num_frame <= 256, num_joints <= 32 and widths that are multiples of 64");
+  if (c->precision == D3D_PREC_F16 &&   // (the bf16 mode's kernels: its admission exactly)
+      (!attn_bf16_ok(c->num_frame, c->embed_dim, c->num_heads) || !attn_bf16_ok(c->num_joints, c->embed_dim, c->num_heads) ||
+       c->num_joints > 32 || c->embed_dim % 64 || c->mlp_hidden % 64))
+    return fail(D3D_EUNSUP, "D3D_PREC_F16 needs head_dim 64, num_frame <= 256, num_joints <= 32 and widths that are multiples of 64");
   d3d_engine* e = new d3d_engine();
   e->cfg = *c;
   if (half_tile) e->cfg.precision = D3D_PREC_FP32;   // F16X3 asked for: every kernel of the engine is the exact FP32 one
@@ -1095,7 +1104,7 @@ int d3d_engine_commit_weights(d3d_engine* e) {
   if (x3 && !pack_f16x3(src, D, e->Dm, tile_heads, narrow_s || qkv_sattn_ok(e->J, e->D, e->H, e->D),
                         narrow_t || qkv_tattn_ok(e->T, e->J, e->D, e->H, e->D), pk))
     return fail(D3D_EHIP, "internal: head-major qkv planes got a different exponent");
-  if (e->cfg.precision == D3D_PREC_BF16) pack_bf16(src, D, e->Dm, pk);
+  if (e->cfg.precision == D3D_PREC_BF16 || e->cfg.precision == D3D_PREC_F16) pack_bf16(src, D, e->Dm, pk, e->cfg.precision == D3D_PREC_F16);
   e->weights_clamped = pk.clamped;
   // "block0_direct": G and P of block 0 where it can take the direct form (a spatial F16X3 block on the fused kernel's tile geometry,
   // embedding straight into the planes); they follow Wg in one allocation, G padded to whole 64-float lines

@@ -168,15 +168,17 @@ int d3d_op_linear(const float* A, const float* W, const float* bias, const float
 
 int d3d_op_linear_bench(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
                         int32_t K, int32_t epi, int32_t precision, int32_t variant, int32_t reps, float* avg_ms, void* stream) {
-  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16) return fail(D3D_EUNSUP, "precision not implemented");
+  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16 && precision != D3D_PREC_F16)
+    return fail(D3D_EUNSUP, "precision not implemented");
   if (!A || !W || !C || reps < 1) return fail(D3D_EINVAL, "bad argument");
   if (K % 32 && !(precision == D3D_PREC_FP32 && K % 16 == 0))
     return fail(D3D_EUNSUP, "K must be a multiple of 32 (D3D_PREC_FP32: of 16, a last k-tile of 16 columns is zero-filled)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (precision == D3D_PREC_BF16) {
+  if (precision == D3D_PREC_BF16 || precision == D3D_PREC_F16) {
     // the bf16 operand mode: operands rounded to bf16 on the device (rows padded to 256, zero), the product through launch_linear_bf16;
-    // EPI_NONE / EPI_GELU results come back through the kernel's bf16 output (rounded once more)
-    if (K % 64 || N % 8) return fail(D3D_EUNSUP, "bf16 mode: K % 64 == 0 and N % 8 == 0");
+    // EPI_NONE / EPI_GELU results come back through the kernel's bf16 output (rounded once more).  D3D_PREC_F16: the same with fp16.
+    const bool f16 = precision == D3D_PREC_F16;
+    if (K % 64 || N % 8) return fail(D3D_EUNSUP, "bf16 / f16 mode: K % 64 == 0 and N % 8 == 0");
     if (epi == EPI_RESIDUAL && !R) return fail(D3D_EINVAL, "residual required");
     const size_t mp = pad256(M), np = pad256(N);
     DevBuf<uint16_t> ab, wb, cb;
@@ -185,11 +187,11 @@ int d3d_op_linear_bench(const float* A, const float* W, const float* bias, const
     HIP_TRY(cb.alloc((size_t)M * N));
     hipError_t le = hipMemsetAsync(ab.p, 0, mp * K * 2, s);
     if (le == hipSuccess) le = hipMemsetAsync(wb.p, 0, np * K * 2, s);
-    if (le == hipSuccess) le = launch_f32_to_bf16(A, ab.p, (size_t)M * K, s);
-    if (le == hipSuccess) le = launch_f32_to_bf16(W, wb.p, (size_t)N * K, s);
-    auto once = [&]() -> hipError_t { return launch_linear_bf16(ab.p, wb.p, bias, R, C, cb.p, M, N, K, epi, 0, s); };
+    if (le == hipSuccess) le = launch_f32_to_bf16(A, ab.p, (size_t)M * K, s, f16);
+    if (le == hipSuccess) le = launch_f32_to_bf16(W, wb.p, (size_t)N * K, s, f16);
+    auto once = [&]() -> hipError_t { return launch_linear_bf16(ab.p, wb.p, bias, R, C, cb.p, M, N, K, epi, 0, s, f16); };
     if (le == hipSuccess) le = run_timed(once, reps, avg_ms, s, /*warm clocks*/ 3);
-    if (le == hipSuccess && epi != EPI_RESIDUAL) le = launch_bf16_to_f32(cb.p, C, (size_t)M * N, s);
+    if (le == hipSuccess && epi != EPI_RESIDUAL) le = launch_bf16_to_f32(cb.p, C, (size_t)M * N, s, f16);
     return finish(le, s);
   }
   X3Operands o;
@@ -372,12 +374,14 @@ int d3d_op_linear_plane_residual(const float* A, const float* W, const float* bi
   return finish(le, s);
 }
 
-int d3d_op_qkv_attn_bf16(const float* A, const float* Wqkv, const float* bias, int32_t groups, int32_t N, int32_t stride, int32_t D,
-                         int32_t H, int32_t temporal, float* out, void* stream) {
+// (f16: the fp16 operand mode's form of the kernel, d3d_op_qkv_attn_f16)
+static int op_qkv_attn_16(const float* A, const float* Wqkv, const float* bias, int32_t groups, int32_t N, int32_t stride, int32_t D,
+                          int32_t H, int32_t temporal, float* out, void* stream, bool f16) {
   if (!A || !Wqkv || !bias || !out || groups <= 0 || N <= 0 || stride <= 0 || D <= 0 || H <= 0 || groups % stride) return fail(D3D_EINVAL, "bad argument");
   const int T = temporal ? N : groups / stride, J = temporal ? stride : N, B = temporal ? groups / stride : 1;
   if (!(temporal ? qkv_tattn_bf16_ok(T, J, D, H, B) : qkv_sattn_bf16_ok(T, J, D, H, B)))
-    return fail(D3D_EUNSUP, "fused bf16 qkv + attention: head_dim 64, D % 128 == 0, D >= 256, groups of <= 255 tokens (spatial: <= 32)");
+    return fail(D3D_EUNSUP, f16 ? "fused f16 qkv + attention: head_dim 64, D % 128 == 0, D >= 256, groups of <= 255 tokens (spatial: <= 32)"
+                                : "fused bf16 qkv + attention: head_dim 64, D % 128 == 0, D >= 256, groups of <= 255 tokens (spatial: <= 32)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // operands rounded to bf16 on the device into buffers of EXACTLY the operand sizes (the kernel reads no pad rows), the fused kernel
   // alone, its bf16 output widened to fp32
@@ -386,12 +390,20 @@ int d3d_op_qkv_attn_bf16(const float* A, const float* Wqkv, const float* bias, i
   HIP_TRY(ab.alloc(na));
   HIP_TRY(wb.alloc(nw));
   HIP_TRY(ob.alloc(na));
-  hipError_t le = launch_f32_to_bf16(A, ab.p, na, s);
-  if (le == hipSuccess) le = launch_f32_to_bf16(Wqkv, wb.p, nw, s);
+  hipError_t le = launch_f32_to_bf16(A, ab.p, na, s, f16);
+  if (le == hipSuccess) le = launch_f32_to_bf16(Wqkv, wb.p, nw, s, f16);
   if (le == hipSuccess) le = hipMemsetAsync(ob.p, 0xff, na * 2, s);   // (NaN: a row the kernel skipped shows)
-  if (le == hipSuccess) le = launch_qkv_attn_bf16(ab.p, wb.p, bias, ob.p, groups, N, stride, D, H, temporal ? 1 : 0, s);
-  if (le == hipSuccess) le = launch_bf16_to_f32(ob.p, out, na, s);
+  if (le == hipSuccess) le = launch_qkv_attn_bf16(ab.p, wb.p, bias, ob.p, groups, N, stride, D, H, temporal ? 1 : 0, s, f16);
+  if (le == hipSuccess) le = launch_bf16_to_f32(ob.p, out, na, s, f16);
   return finish(le, s);
+}
+int d3d_op_qkv_attn_bf16(const float* A, const float* Wqkv, const float* bias, int32_t groups, int32_t N, int32_t stride, int32_t D,
+                         int32_t H, int32_t temporal, float* out, void* stream) {
+  return op_qkv_attn_16(A, Wqkv, bias, groups, N, stride, D, H, temporal, out, stream, false);
+}
+int d3d_op_qkv_attn_f16(const float* A, const float* Wqkv, const float* bias, int32_t groups, int32_t N, int32_t stride, int32_t D,
+                        int32_t H, int32_t temporal, float* out, void* stream) {
+  return op_qkv_attn_16(A, Wqkv, bias, groups, N, stride, D, H, temporal, out, stream, true);
 }
 
 int d3d_op_qkv_attn_x3_small(const float* X, const float* Wqkv, const float* bias, const float* gamma, const float* beta, float eps,
@@ -510,23 +522,26 @@ int d3d_op_layernorm_forms(const float* x, const float* gamma1, const float* bet
 
 int d3d_op_attention(const float* qkv, float* out, int32_t B, int32_t T, int32_t J, int32_t D, int32_t H, int32_t temporal,
                      int32_t precision, int32_t force_generic, void* stream) {
-  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16) return fail(D3D_EUNSUP, "precision not implemented");
+  if (precision != D3D_PREC_FP32 && precision != D3D_PREC_F16X3 && precision != D3D_PREC_BF16 && precision != D3D_PREC_F16)
+    return fail(D3D_EUNSUP, "precision not implemented");
   if (!qkv || !out || B <= 0 || T <= 0 || J <= 0 || D <= 0 || H <= 0 || D % H) return fail(D3D_EINVAL, "bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t rows = (size_t)B * T * J, nq = rows * 3 * D, no = rows * D;
-  if (precision == D3D_PREC_BF16) {
-    // fp32 qkv -> bf16 (q third scaled by 2^-3, as the qkv GEMM epilogue writes it) -> bf16-MFMA attention -> fp32
+  if (precision == D3D_PREC_BF16 || precision == D3D_PREC_F16) {
+    // fp32 qkv -> bf16 (q third scaled by 2^-3, as the qkv GEMM epilogue writes it) -> bf16-MFMA attention -> fp32; D3D_PREC_F16: fp16
+    const bool f16 = precision == D3D_PREC_F16;
     const int N = temporal ? T : J;
-    if (!attn_bf16_ok(N, D, H)) return fail(D3D_EUNSUP, "bf16 attention: head_dim 64, group length <= 256");
+    if (!attn_bf16_ok(N, D, H)) return fail(D3D_EUNSUP, "bf16 / f16 attention: head_dim 64, group length <= 256");
     DevBuf<float> qs;
     DevBuf<uint16_t> tmp;
     HIP_TRY(qs.alloc(nq));
     HIP_TRY(tmp.alloc(nq + no));
     hipError_t le = hipMemcpyAsync(qs.p, qkv, nq * sizeof(float), hipMemcpyDeviceToDevice, s);
     if (le == hipSuccess) le = launch_scale_cols(qs.p, rows, 3 * D, D, 0.125f, s);
-    if (le == hipSuccess) le = launch_f32_to_bf16(qs.p, tmp.p, nq, s);
-    if (le == hipSuccess) le = temporal ? launch_attn_bf16(tmp.p, tmp.p + nq, B, T, J, D, H, s) : launch_attn_bf16(tmp.p, tmp.p + nq, B * T, J, 1, D, H, s);
-    if (le == hipSuccess) le = launch_bf16_to_f32(tmp.p + nq, out, no, s);
+    if (le == hipSuccess) le = launch_f32_to_bf16(qs.p, tmp.p, nq, s, f16);
+    if (le == hipSuccess)
+      le = temporal ? launch_attn_bf16(tmp.p, tmp.p + nq, B, T, J, D, H, s, f16) : launch_attn_bf16(tmp.p, tmp.p + nq, B * T, J, 1, D, H, s, f16);
+    if (le == hipSuccess) le = launch_bf16_to_f32(tmp.p + nq, out, no, s, f16);
     return finish(le, s);
   }
   if (precision == D3D_PREC_F16X3 && temporal && !force_generic && attn_temporal_x3_ok(T, D, H)) {

@@ -30,17 +30,31 @@ __device__ __forceinline__ void unsplit8(const uint4 rh, const uint4 rl, f2 (&o)
 }
 
 
-// 8 values -> bf16 (round to nearest even: v_cvt_pk_bf16_f32) of osc * v
+// 8 values -> bf16 (round to nearest even: v_cvt_pk_bf16_f32) of osc * v; F16: -> fp16 (v_cvt_f16_f32: nearest even, subnormals
+// kept, inf beyond the fp16 range -- what torch's .to(float16) gives; NOT v_cvt_pkrtz_f16_f32, which rounds towards zero)
 typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
+template <bool F16 = false>
 __device__ __forceinline__ uint4 cvt8_bf16(const f2 (&v)[4], float osc) {
-  bf8v o;
+  if constexpr (F16) {
+    h8 o;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const f2 sc = v[e] * osc;
-    o[2 * e] = (__bf16)sc.x;
-    o[2 * e + 1] = (__bf16)sc.y;
+    for (int e = 0; e < 4; ++e) {
+      f2 sc = v[e] * osc;
+      asm("" : "+v"(sc));   // the fp32 value is what is rounded: no v_fma_mix*_f16 of the arithmetic in front (kernels_attn_bf16.hip f16_point)
+      o[2 * e] = (_Float16)sc.x;
+      o[2 * e + 1] = (_Float16)sc.y;
+    }
+    return __builtin_bit_cast(uint4, o);
+  } else {
+    bf8v o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const f2 sc = v[e] * osc;
+      o[2 * e] = (__bf16)sc.x;
+      o[2 * e + 1] = (__bf16)sc.y;
+    }
+    return __builtin_bit_cast(uint4, o);
   }
-  return __builtin_bit_cast(uint4, o);
 }
 
 // sum over the 16 lanes of a DPP row (all 16 lanes get the total): quad xor 1, xor 2, half-row mirror, row mirror
@@ -303,7 +317,7 @@ __device__ __forceinline__ void x3q_epilogue8(f32x4 (&acc)[TM][4], float* patch,
         if (!ok) continue;
       }
       if constexpr (OUTSPLIT == 3) {
-        *reinterpret_cast<uint4*>(Chb + (obh + (unsigned)(2 * i + p) * rsteph)) = cvt8_bf16(v, osc);
+        *reinterpret_cast<uint4*>(Chb + (obh + (unsigned)(2 * i + p) * rsteph)) = cvt8_bf16<(FX & FX_F16) != 0>(v, osc);
       } else if (OUTSPLIT) {
         h8 oh, ol;
         if constexpr ((FX & FX_SO) != 0) {   // range guard of this form: by the consumer of its row statistics (x3q_tile, FX_LNF) -- this
@@ -501,7 +515,8 @@ __device__ __forceinline__ void x3q_epilogue_pn(f32x4 (&acc)[TM][4], float* patc
 //   sweep 2  y = pn.g ? LN(v) [+ pos] [+ tvec] : v;  y -> C (= R: in place);  if pn.g and pn.g2: (sum, M2) of y -> xch2
 //   sweep 3  if pn.g2: bf16(LN(y; g2, b2)) -> Cb      (statistics from xch2, or from xch when there was no first norm)
 // Rows stay in the 128 registers the accumulators vacate; the un-normalised sum never makes a second trip through HBM.
-template <int TM, int WN, bool CHECK>
+// F16 (FX_F16): sweep 3 rounds to fp16 instead.
+template <int TM, int WN, bool CHECK, bool F16 = false>
 __device__ __forceinline__ void x3q_epilogue_rows_bf16(f32x4 (&acc)[TM][4], float* patch, float* xch, float* xch2,
                                                        const float* __restrict__ bias, float* Ct, _Float16* Cbt, const X3Tail& fx,
                                                        int mt0, int nt0, int wn, int lane, int M, int N, int gl, int gh) {
@@ -653,7 +668,7 @@ __device__ __forceinline__ void x3q_epilogue_rows_bf16(f32x4 (&acc)[TM][4], floa
       f2 h[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) h[e] = fma2((vv[i][p][e] - mean2) * rstd2, g2[e], b2[e]);
-      *reinterpret_cast<uint4*>(Hb + (obh + (unsigned)(2 * i + p) * rsteph)) = cvt8_bf16(h, 1.0f);
+      *reinterpret_cast<uint4*>(Hb + (obh + (unsigned)(2 * i + p) * rsteph)) = cvt8_bf16<F16>(h, 1.0f);
     }
     __builtin_amdgcn_sched_barrier(0);
   }

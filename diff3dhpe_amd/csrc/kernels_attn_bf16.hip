@@ -23,21 +23,46 @@ namespace d3d {
 
 #include "attn_lds.h"   // f32x16 / s4v, kswz / vkey / vswz
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-
 namespace {
 constexpr int BDH = 64;
+// The operand element of a kernel: bf16 (D3D_PREC_BF16), or fp16 (F16 = true, D3D_PREC_F16).  E(float) rounds to nearest even in both;
+// fp16 keeps subnormals and gives inf beyond 65504.  v_mfma_f32_32x32x16_bf16 / _f16 share their lane layouts.
+template <bool F16> struct Op16 {
+  typedef __bf16 E;
+  typedef __bf16 V8 __attribute__((ext_vector_type(8)));
+  typedef __bf16 V4 __attribute__((ext_vector_type(4)));
+};
+template <> struct Op16<true> {
+  typedef _Float16 E;
+  typedef _Float16 V8 __attribute__((ext_vector_type(8)));
+  typedef _Float16 V4 __attribute__((ext_vector_type(4)));
+};
+// An fp16 rounding point rounds an fp32 VALUE (as torch's .to(float16) does).  Left to itself the compiler folds the multiply or fma in
+// front of some conversions into v_fma_mix{lo,hi}_f16, which rounds the exact product ONCE -- a different result wherever the fp32
+// rounding moves the value across an fp16 boundary, and a different one from kernel to kernel (the fused kernel and the stand-alone
+// attention kernel got different mixes of the two forms and were not bit-identical).  The register is made opaque: v_cvt of the fp32 value.
+__device__ __forceinline__ float f16_point(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+template <bool F16, typename V8>
+__device__ __forceinline__ f32x16 op16_mfma32(V8 a, V8 b, f32x16 c) {
+  if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
 }  // namespace
 
 // QT: 32-query tiles per wave (1 or 2).  QT = 2 halves the workgroup (NKT / 2 waves, each taking query tiles w and w + NKT / 2 one
 // after the other against the K / V rows staged once): a T = 243 unit is then a 4-wave workgroup with 64 KiB of LDS, and TWO of
 // them share a CU as independent instruction streams -- one's K / V loads and output stores sit under the other's MFMAs and
 // softmax (the 8-wave form has the CU to itself and serialises load -> compute -> store).
-template <int NKT, int MU, int QT = 1>
+template <int NKT, int MU, int QT = 1, bool F16 = false>
 __global__ __launch_bounds__(64 * ((NKT + QT - 1) / QT) * MU) __attribute__((amdgpu_waves_per_eu(QT)))   // (QT = 2: <= 256 VGPRs, two workgroups per CU)
-void k_attn_bf16(const __bf16* __restrict__ qkv, __bf16* __restrict__ out, int T, int J,
+void k_attn_bf16(const typename Op16<F16>::E* __restrict__ qkv, typename Op16<F16>::E* __restrict__ out, int T, int J,
                                                              int H, int D, int units) {
+  typedef typename Op16<F16>::E E;
+  typedef typename Op16<F16>::V8 bf8;   // (the names of the bf16 form, for either element type)
+  typedef typename Op16<F16>::V4 bf4;
   static_assert(MU == 1 || NKT == 1, "several units per workgroup only for single-tile groups");
   static_assert(QT == 1 || (MU == 1 && NKT % QT == 0), "query-tile passes only for whole multiples");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
@@ -133,7 +158,7 @@ void k_attn_bf16(const __bf16* __restrict__ qkv, __bf16* __restrict__ out, int T
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const bf8 kf = *reinterpret_cast<const bf8*>(kb[ks] + kt * 4096);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kt], 0, 0, 0);
+      sacc[kt] = op16_mfma32<F16>(kf, qf[ks], sacc[kt]);
     }
   }
   // ---- exact softmax over the keys of this query column (fp32); only the last key tile can hold padding keys
@@ -187,7 +212,7 @@ void k_attn_bf16(const __bf16* __restrict__ qkv, __bf16* __restrict__ out, int T
     for (int s = 0; s < 2; ++s) {
       bf8 pf;
 #pragma unroll
-      for (int jj = 0; jj < 8; ++jj) pf[jj] = (__bf16)(sacc[kt][8 * s + jj] * inv);
+      for (int jj = 0; jj < 8; ++jj) pf[jj] = F16 ? (E)f16_point(sacc[kt][8 * s + jj] * inv) : (E)(sacc[kt][8 * s + jj] * inv);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         const s4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(vb[dt][0] + (2 * kt + s) * 2048));
@@ -196,21 +221,21 @@ void k_attn_bf16(const __bf16* __restrict__ qkv, __bf16* __restrict__ out, int T
         const bf4 a0b = __builtin_bit_cast(bf4, a0), a1b = __builtin_bit_cast(bf4, a1);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { vf[e] = a0b[e]; vf[4 + e] = a1b[e]; }
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[dt], 0, 0, 0);
+        oacc[dt] = op16_mfma32<F16>(vf, pf, oacc[dt]);
       }
       __builtin_amdgcn_sched_barrier(0);   // keeps the conversions / V^T reads of later k-steps from being hoisted (VGPR pressure)
     }
   }
   // ---- O rows out as bf16: lane (query tq, half h) holds d = dt * 32 + 8 g4 + 4 h + e
   if (tq < T && unit_ok) {
-    __bf16* orow = out + (tok0 + (size_t)tq * J) * D + hd * BDH;
+    E* orow = out + (tok0 + (size_t)tq * J) * D + hd * BDH;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         bf4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (__bf16)oacc[dt][4 * g4 + e];
+        for (int e = 0; e < 4; ++e) o[e] = (E)oacc[dt][4 * g4 + e];
         *reinterpret_cast<bf4*>(orow + dt * 32 + 8 * g4 + 4 * h) = o;
       }
   }
@@ -219,30 +244,35 @@ void k_attn_bf16(const __bf16* __restrict__ qkv, __bf16* __restrict__ out, int T
 
 bool attn_bf16_ok(int T, int D, int H) { return T >= 1 && T <= 256 && H > 0 && D == H * BDH; }
 
-template <int NKT, int MU = 1, int QT = 1>
-static hipError_t launch_nkt(const __bf16* qkv, __bf16* out, int B, int T, int J, int D, int H, hipStream_t s) {
+template <bool F16, int NKT, int MU = 1, int QT = 1>
+static hipError_t launch_nkt(const void* qkv_, void* out_, int B, int T, int J, int D, int H, hipStream_t s) {
+  const typename Op16<F16>::E* qkv = (const typename Op16<F16>::E*)qkv_;
+  typename Op16<F16>::E* out = (typename Op16<F16>::E*)out_;
   const size_t lds_bytes = (size_t)MU * 2 * 32 * NKT * 128;
   const long long units = (long long)B * J * H;
   if (units > 0x7fffffffLL) return hipErrorInvalidValue;
-  return launch_lds<k_attn_bf16<NKT, MU, QT>>(dim3((unsigned)((units + MU - 1) / MU)), dim3(64 * ((NKT + QT - 1) / QT) * MU), lds_bytes, s,
+  return launch_lds<k_attn_bf16<NKT, MU, QT, F16>>(dim3((unsigned)((units + MU - 1) / MU)), dim3(64 * ((NKT + QT - 1) / QT) * MU), lds_bytes, s,
                                               qkv, out, T, J, H, D, (int)units);
 }
 
 // qkv: bf16 [B*T*J][3D] (q third pre-scaled by dh^-0.5); out: bf16 [B*T*J][D].  Spatial blocks: call with (B*T, J, 1).
-hipError_t launch_attn_bf16(const void* qkv_bf16, void* out_bf16, int B, int T, int J, int D, int H, hipStream_t s) {
-  if (!attn_bf16_ok(T, D, H) || !qkv_bf16 || !out_bf16 || B <= 0 || J <= 0) return hipErrorInvalidValue;
-  const __bf16* q = (const __bf16*)qkv_bf16;
-  __bf16* o = (__bf16*)out_bf16;
+template <bool F16>
+static hipError_t launch_attn_form(const void* q, void* o, int B, int T, int J, int D, int H, hipStream_t s) {
   switch ((T + 31) / 32) {
-    case 1: return ((long long)B * J * H >= 4096 ? launch_nkt<1, 8> : launch_nkt<1, 1>)(q, o, B, T, J, D, H, s);
-    case 2: return launch_nkt<2>(q, o, B, T, J, D, H, s);
-    case 3: return launch_nkt<3>(q, o, B, T, J, D, H, s);
-    case 4: return launch_nkt<4>(q, o, B, T, J, D, H, s);
-    case 5: return launch_nkt<5>(q, o, B, T, J, D, H, s);
-    case 6: return launch_nkt<6, 1, 2>(q, o, B, T, J, D, H, s);
-    case 7: return launch_nkt<7>(q, o, B, T, J, D, H, s);
-    default: return launch_nkt<8, 1, 2>(q, o, B, T, J, D, H, s);   // two 4-wave workgroups per CU
+    case 1: return ((long long)B * J * H >= 4096 ? launch_nkt<F16, 1, 8> : launch_nkt<F16, 1, 1>)(q, o, B, T, J, D, H, s);
+    case 2: return launch_nkt<F16, 2>(q, o, B, T, J, D, H, s);
+    case 3: return launch_nkt<F16, 3>(q, o, B, T, J, D, H, s);
+    case 4: return launch_nkt<F16, 4>(q, o, B, T, J, D, H, s);
+    case 5: return launch_nkt<F16, 5>(q, o, B, T, J, D, H, s);
+    case 6: return launch_nkt<F16, 6, 1, 2>(q, o, B, T, J, D, H, s);
+    case 7: return launch_nkt<F16, 7>(q, o, B, T, J, D, H, s);
+    default: return launch_nkt<F16, 8, 1, 2>(q, o, B, T, J, D, H, s);   // two 4-wave workgroups per CU
   }
+}
+// f16: the buffers hold fp16 (D3D_PREC_F16)
+hipError_t launch_attn_bf16(const void* qkv_bf16, void* out_bf16, int B, int T, int J, int D, int H, hipStream_t s, bool f16) {
+  if (!attn_bf16_ok(T, D, H) || !qkv_bf16 || !out_bf16 || B <= 0 || J <= 0) return hipErrorInvalidValue;
+  return f16 ? launch_attn_form<true>(qkv_bf16, out_bf16, B, T, J, D, H, s) : launch_attn_form<false>(qkv_bf16, out_bf16, B, T, J, D, H, s);
 }
 
 }  // namespace d3d

@@ -149,7 +149,20 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_layernorm(LnArgs a) {
   }
   if (a.h || a.h_x3 || a.h_bf16) {
     if (a.y || a.y_x3) ln_row<NV>(v, D, lane, a.g2, a.b2, a.eps2);
-    if (a.h_bf16) {   // bf16 operand rows (round to nearest even)
+    if (a.h_bf16 && a.h_f16) {   // fp16 operand rows (round to nearest even, subnormals kept)
+      typedef _Float16 hf4 __attribute__((ext_vector_type(4)));
+      _Float16* hp = reinterpret_cast<_Float16*>(a.h_bf16) + (size_t)row * D;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = 4 * (lane + 64 * i);
+        if (c < D) {
+          hf4 o;
+          asm("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i].z), "+v"(v[i].w));   // round the fp32 values (no v_fma_mix*_f16 of the normalisation's fma)
+          o[0] = (_Float16)v[i].x; o[1] = (_Float16)v[i].y; o[2] = (_Float16)v[i].z; o[3] = (_Float16)v[i].w;
+          *reinterpret_cast<hf4*>(hp + c) = o;
+        }
+      }
+    } else if (a.h_bf16) {   // bf16 operand rows (round to nearest even)
       typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
       __bf16* hp = reinterpret_cast<__bf16*>(a.h_bf16) + (size_t)row * D;
 #pragma unroll

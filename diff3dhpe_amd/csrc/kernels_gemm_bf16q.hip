@@ -9,8 +9,13 @@
 typedef __bf16 bq_bf8 __attribute__((ext_vector_type(8)));
 #define QF_MMA(ACC, BH, BL, AH, AL)                                                                                                   \
   do {                                                                                                                                \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bq_bf8, BH), __builtin_bit_cast(bq_bf8, AH), ACC, 0, 0, 0);      \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bq_bf8, BL), __builtin_bit_cast(bq_bf8, AL), ACC, 0, 0, 0);      \
+    if constexpr (F16) {   /* (the kernel's template parameter: fp16 operand rows, the f16 twin of the pair) */                       \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(BH, AH, ACC, 0, 0, 0);                                                             \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(BL, AL, ACC, 0, 0, 0);                                                             \
+    } else {                                                                                                                          \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bq_bf8, BH), __builtin_bit_cast(bq_bf8, AH), ACC, 0, 0, 0);    \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bq_bf8, BL), __builtin_bit_cast(bq_bf8, AL), ACC, 0, 0, 0);    \
+    }                                                                                                                                 \
   } while (0)
 #include "qkv_fused_kloop.h"
 
@@ -38,8 +43,10 @@ struct BqArgs {
   unsigned* range;
 };
 
-template <int EPI>
+// F16: fp16 operand rows (D3D_PREC_F16) -- the f16 MFMA pair and the FX_F16 epilogue; the bf16 instantiations are what they were.
+template <int EPI, bool F16>
 __global__ __launch_bounds__(512) void k_gemm_bf16q(BqArgs a) {
+  constexpr int FXQ = F16 ? (FX_BF16 | FX_F16) : FX_BF16;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   QF_GEMM_WALK(a.Ap, a.Wp, a.mtiles, a.ntiles, a.Kp);   // (K2 = K: 16-bit words per operand row)
   for (int item = 0; item < nitems; ++item) {
@@ -54,11 +61,11 @@ __global__ __launch_bounds__(512) void k_gemm_bf16q(BqArgs a) {
       const size_t tbase = (size_t)mt0 * a.N + nt0;
       float* const patch = reinterpret_cast<float*>(lds + BQ_PATCH) + wave * (2 * 16 * 64);
       if (m0 + QF_BM <= a.M)     // (wave-uniform: a whole tile)
-        x3q_epilogue8<QF_TM, 2, 4, EPI, 3, FX_BF16, false>(acc, patch, lds, a.bias, nullptr, a.out + tbase, nullptr, nullptr, nullptr, nullptr,
-                                                            mt0, nt0, wm * 16 * QF_TM, lane, a.M, a.N, a.qcols, 0, QF_TM, 1.0f, a.range);
+        x3q_epilogue8<QF_TM, 2, 4, EPI, 3, FXQ, false>(acc, patch, lds, a.bias, nullptr, a.out + tbase, nullptr, nullptr, nullptr, nullptr,
+                                                        mt0, nt0, wm * 16 * QF_TM, lane, a.M, a.N, a.qcols, 0, QF_TM, 1.0f, a.range);
       else                       // the ragged last M-tile: rows >= M are computed from the operand buffer's pad rows and not stored
-        x3q_epilogue8<QF_TM, 2, 4, EPI, 3, FX_BF16, true>(acc, patch, lds, a.bias, nullptr, a.out + tbase, nullptr, nullptr, nullptr, nullptr,
-                                                           mt0, nt0, wm * 16 * QF_TM, lane, a.M, a.N, a.qcols, 0, QF_TM, 1.0f, a.range);
+        x3q_epilogue8<QF_TM, 2, 4, EPI, 3, FXQ, true>(acc, patch, lds, a.bias, nullptr, a.out + tbase, nullptr, nullptr, nullptr, nullptr,
+                                                       mt0, nt0, wm * 16 * QF_TM, lane, a.M, a.N, a.qcols, 0, QF_TM, 1.0f, a.range);
     }
     mt = mtn; nt = ntn;
     __syncthreads();   // the patches (stage 1) are read before the next tile's second k-tile is staged there
@@ -72,7 +79,8 @@ bool gemm_bf16q_ok(int N, int K) { return N % 256 == 0 && K % 128 == 0 && K >= 2
 
 // Cb[M][N] (bf16) = epi(A[Mp][K] W[N][K]^T + bias), q scaling for columns < qcols; A's buffer spans whole 256-row tiles (pad rows finite or not:
 // their results are not stored).  epi: EPI_NONE or EPI_GELU.
-hipError_t launch_gemm_bf16q(const void* A, const void* W, const float* bias, void* Cb, int M, int N, int K, int epi, int qcols, hipStream_t s) {
+hipError_t launch_gemm_bf16q(const void* A, const void* W, const float* bias, void* Cb, int M, int N, int K, int epi, int qcols, hipStream_t s,
+                             bool f16) {
   if (!gemm_bf16q_ok(N, K) || M < 1 || !A || !W || !bias || !Cb || (epi != EPI_NONE && epi != EPI_GELU)) return hipErrorInvalidValue;
   BqArgs a{};
   a.Ap = (const _Float16*)A; a.Wp = (const _Float16*)W; a.bias = bias; a.out = (_Float16*)Cb;
@@ -80,8 +88,11 @@ hipError_t launch_gemm_bf16q(const void* A, const void* W, const float* bias, vo
   a.range = launch_range_word();
   int grid = 0;
   if (hipError_t ge = persistent_grid((long long)a.mtiles * a.ntiles, grid)) return ge;
-  return epi == EPI_GELU ? launch_lds<k_gemm_bf16q<EPI_GELU>>(dim3(grid), dim3(512), BQ_LDS, s, a)
-                         : launch_lds<k_gemm_bf16q<EPI_NONE>>(dim3(grid), dim3(512), BQ_LDS, s, a);
+  if (f16)
+    return epi == EPI_GELU ? launch_lds<k_gemm_bf16q<EPI_GELU, true>>(dim3(grid), dim3(512), BQ_LDS, s, a)
+                           : launch_lds<k_gemm_bf16q<EPI_NONE, true>>(dim3(grid), dim3(512), BQ_LDS, s, a);
+  return epi == EPI_GELU ? launch_lds<k_gemm_bf16q<EPI_GELU, false>>(dim3(grid), dim3(512), BQ_LDS, s, a)
+                         : launch_lds<k_gemm_bf16q<EPI_NONE, false>>(dim3(grid), dim3(512), BQ_LDS, s, a);
 }
 
 }  // namespace d3d

@@ -54,7 +54,10 @@ namespace d3d {
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 template <int FX>
 __device__ __forceinline__ void x3_mma(f32x4& acc, const h8& bh, const h8& bl, const h8& ah, const h8& al) {
-  if constexpr ((FX & FX_BF16) != 0) {
+  if constexpr ((FX & FX_BF16) != 0 && (FX & FX_F16) != 0) {   // fp16 operand rows: the f16 twin of the bf16 pair (same lane layout)
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, ah, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, al, acc, 0, 0, 0);
+  } else if constexpr ((FX & FX_BF16) != 0) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, bh), __builtin_bit_cast(bf8, ah), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, bl), __builtin_bit_cast(bf8, al), acc, 0, 0, 0);
   } else {
@@ -575,7 +578,7 @@ __device__ __forceinline__ void x3q_tile(const _Float16* __restrict__ Ap, const 
     float* xch = reinterpret_cast<float*>(lds + STAGE + 65536);
     // (one copy per instantiation: with a checked and an unchecked copy under a branch the accumulators spill)
     if constexpr ((FX & FX_BF16) != 0)   // bf16 mode: fp32 stream in place (C), bf16 operand rows of the following LayerNorm (Ch)
-      x3q_epilogue_rows_bf16<TM, WN, !FULL>(acc, patch, xch, xch + 2 * BM * WN, bias, Ct, Cht, fx, mt0, nt0, wn, lane, M, N, gl, gh);
+      x3q_epilogue_rows_bf16<TM, WN, !FULL, (FX & FX_F16) != 0>(acc, patch, xch, xch + 2 * BM * WN, bias, Ct, Cht, fx, mt0, nt0, wn, lane, M, N, gl, gh);
     else
       x3q_epilogue_pn<TM, WN, OUTSPLIT, !FULL>(acc, patch, xch, bias, Ct, Cht, Rpt, fx, mt0, nt0, wn, lane, M, N, gl, gh);
     done = true;
@@ -757,6 +760,8 @@ static X3Walk x3q_walk(int tiles, int grid, bool four_way = true) {
 #define D3D_X3_FORMS(X)                                                                                                  \
   /* bf16 operand mode: the three forms its block flow uses (launch_linear_bf16) */                                      \
   X(FX_BF16, EPI_NONE, 3) X(FX_BF16, EPI_GELU, 3) X(FX_BF16, EPI_RESIDUAL, 0)                                            \
+  /* fp16 operand mode (D3D_PREC_F16): the same three with the FX_F16 modifier */                                        \
+  X(FX_BF16 | FX_F16, EPI_NONE, 3) X(FX_BF16 | FX_F16, EPI_GELU, 3) X(FX_BF16 | FX_F16, EPI_RESIDUAL, 0)                 \
   /* plain: the fp32-stream flow and the op hooks */                                                                     \
   X(0, EPI_NONE, 0) X(0, EPI_GELU, 0) X(0, EPI_RESIDUAL, 0) X(0, EPI_NONE, 1) X(0, EPI_GELU, 2) X(0, EPI_NONE, 2)        \
   /* folded forms of the engine's plane-resident block (engine.hip run_blocks): qkv, proj, fc1, fc2 */                   \
@@ -767,10 +772,11 @@ static X3Walk x3q_walk(int tiles, int grid, bool four_way = true) {
 
 // fold -> (fx bits, device tail) of a launch; -1 for a folded LayerNorm without its column sums / partial count.  The LDS the
 // statistics take beyond the operand stages differs between the launchers and stays with them.
-static int x3q_fold_tail(const X3Fold* fold, int w_exp, bool bf16, X3Tail& tail) {
-  tail.out_scale = bf16 ? 1.0f : ldexpf(1.0f, -(3 + w_exp));
+// op16: 0, or the FX bits of a 16-bit operand mode (FX_BF16, FX_BF16 | FX_F16: unscaled operands).
+static int x3q_fold_tail(const X3Fold* fold, int w_exp, int op16, X3Tail& tail) {
+  tail.out_scale = op16 ? 1.0f : ldexpf(1.0f, -(3 + w_exp));
   tail.range = launch_range_word();
-  int fx = bf16 ? FX_BF16 : 0;
+  int fx = op16;
   if (fold) {
     if (fold->st_in) fx |= FX_LNF;
     if (fold->Rp) fx |= FX_RP;
@@ -785,13 +791,13 @@ static int x3q_fold_tail(const X3Fold* fold, int w_exp, bool bf16, X3Tail& tail)
 template <int TM, int WM, int WN, int NST = 2>
 static hipError_t launch_x3q(const _Float16* Ap, const _Float16* Wp, const float* bias, const float* R, float* C, _Float16* Ch,
                              _Float16* Cl, int M, int N, int K, int epi, int outsplit, int qcols, hipStream_t s,
-                             const X3Fold* fold = nullptr, int w_exp = 12, bool bf16 = false) {
+                             const X3Fold* fold = nullptr, int w_exp = 12, int op16 = 0) {
   constexpr int BM = 16 * TM * WM, BN = 64 * WN;
   const int mtiles = (M + BM - 1) / BM, ntiles = (N + BN - 1) / BN;
   const int grid = ((mtiles + 7) / 8) * 8 * ntiles;
   size_t lds_bytes = NST * (size_t)((BM + BN) * 128);
   X3Tail tail{};
-  const int fx = x3q_fold_tail(fold, w_exp, bf16, tail);
+  const int fx = x3q_fold_tail(fold, w_exp, op16, tail);
   if (fx < 0) return hipErrorInvalidValue;
   if (fx & FX_LNF) lds_bytes += (size_t)BM * 8;   // row statistics beyond the operand stages
   else if (fx & FX_SO) lds_bytes += 8 * 1024;     // a kilobyte per wave for the rows' statistics (x3q_epilogue8)
@@ -816,7 +822,7 @@ static hipError_t launch_x3q(const _Float16* Ap, const _Float16* Wp, const float
 template <int TM = 8>
 static hipError_t launch_x3q_persist(const _Float16* Ap, const _Float16* Wp, const float* bias, const float* R, float* C,
                                      _Float16* Ch, _Float16* Cl, int M, int N, int K, int epi, int outsplit, int qcols,
-                                     hipStream_t s, const X3Fold* fold, int w_exp, bool bf16 = false) {
+                                     hipStream_t s, const X3Fold* fold, int w_exp, int op16 = 0) {
   constexpr int BM = 32 * TM;
   const int mtiles = (M + BM - 1) / BM, ntiles = (N + 255) / 256;
   const int tiles = mtiles * ntiles;
@@ -828,7 +834,7 @@ static hipError_t launch_x3q_persist(const _Float16* Ap, const _Float16* Wp, con
   constexpr size_t STAGE = (size_t)(BM + 256) * 128;
   size_t lds_bytes = std::max(2 * STAGE, STAGE + 65536);     // two operand stages; the epilogue patches (64 KiB) start at stage 1
   X3Tail tail{};
-  const int fx = x3q_fold_tail(fold, w_exp, bf16, tail);
+  const int fx = x3q_fold_tail(fold, w_exp, op16, tail);
   if (fx < 0) return hipErrorInvalidValue;
   if (fx & FX_LNF) lds_bytes += (size_t)BM * 8 + 16384;   // (rstd, -mean rstd) per row + the raw partials staged by LDS-DMA
   else if (fx & FX_SO) lds_bytes += 8 * 1024;              // a kilobyte per wave for the rows' statistics (x3q_epilogue8)
@@ -906,7 +912,7 @@ hipError_t launch_linear_x3p_splitk(const void* Apair, const void* Wpair, float*
 bool bf16_rows_ok(int N, int K) { return N == 512 && K % 64 == 0; }
 
 hipError_t launch_linear_bf16_rows(const void* A, const void* W, const float* bias, float* X, void* Hb, int M, int N, int K,
-                                   const X3PostNorm& pn, hipStream_t s) {
+                                   const X3PostNorm& pn, hipStream_t s, bool f16) {
   if (!bf16_rows_ok(N, K) || M <= 0 || !A || !W || !bias || !X) return hipErrorInvalidValue;
   if (pn.g2 ? (!Hb || !pn.b2) : false) return hipErrorInvalidValue;
   if (pn.g && !pn.b) return hipErrorInvalidValue;
@@ -916,6 +922,7 @@ hipError_t launch_linear_bf16_rows(const void* A, const void* W, const float* bi
   tail.out_scale = 1.0f;
   tail.range = launch_range_word();
   tail.pn = pn;
+  if (f16) return launch_x3q_rows<0, FX_PN | FX_BF16 | FX_F16>((const _Float16*)A, (const _Float16*)W, bias, X, (_Float16*)Hb, M, N, K / 2, tail, s);
   return launch_x3q_rows<0, FX_PN | FX_BF16>((const _Float16*)A, (const _Float16*)W, bias, X, (_Float16*)Hb, M, N, K / 2, tail, s);
 }
 
@@ -962,25 +969,29 @@ static hipError_t launch_x3q_auto(const _Float16* ap, const _Float16* wp, const 
 //   EPI_RESIDUAL        -> C fp32 = R + ... (the fp32 residual stream; R may alias C)
 // Same 256x256 persistent walk / 256x128 choice as launch_x3q_auto; values are tile-shape independent.
 hipError_t launch_linear_bf16(const void* A, const void* W, const float* bias, const float* R, float* C, void* Cb, int M, int N,
-                              int K, int epi, int qcols, hipStream_t s) {
+                              int K, int epi, int qcols, hipStream_t s, bool f16) {
   if (M <= 0 || N <= 0 || K <= 0 || (K % 64) != 0 || (N % 8) != 0 || !A || !W) return hipErrorInvalidValue;
+  const int op16 = f16 ? (FX_BF16 | FX_F16) : FX_BF16;
   if (epi == EPI_RESIDUAL ? (!R || !C) : !Cb) return hipErrorInvalidValue;
   const _Float16 *ap = (const _Float16*)A, *wp = (const _Float16*)W;
   _Float16* cb = (_Float16*)Cb;
   const int outsplit = epi == EPI_RESIDUAL ? 0 : 3;
   const int K2 = K / 2;                     // pair columns: 4 K2 bytes per row, K2 / 32 staged lines per row
   if (x3q_big(M, N) && (K2 / PBK) % 2 == 0)
-    return launch_x3q_persist(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, true);
-  if (x3q_big(M, N)) return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, true);
-  return launch_x3q<4, 4, 2>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, true);
+    return launch_x3q_persist(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, op16);
+  if (x3q_big(M, N)) return launch_x3q<8, 2, 4>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, op16);
+  return launch_x3q<4, 4, 2>(ap, wp, bias, R, C, cb, nullptr, M, N, K2, epi, outsplit, qcols, s, nullptr, 12, op16);
 }
 
 // fp32 [rows, cols] -> bf16 (round to nearest even), and back: weight commit on the device side of the op hooks, tests
-__global__ __launch_bounds__(256) void k_f32_to_bf16(const float* __restrict__ x, __bf16* __restrict__ y, size_t n) {
+// (E: __bf16 or _Float16 -- the fp16 operand mode; both conversions round to nearest even, fp16 keeps subnormals)
+template <typename E>
+__global__ __launch_bounds__(256) void k_f32_to_bf16(const float* __restrict__ x, E* __restrict__ y, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) y[i] = (__bf16)x[i];
+  if (i < n) y[i] = (E)x[i];
 }
-__global__ __launch_bounds__(256) void k_bf16_to_f32(const __bf16* __restrict__ x, float* __restrict__ y, size_t n) {
+template <typename E>
+__global__ __launch_bounds__(256) void k_bf16_to_f32(const E* __restrict__ x, float* __restrict__ y, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) y[i] = (float)x[i];
 }
@@ -995,14 +1006,16 @@ hipError_t launch_scale_cols(float* x, size_t rows, int cols, int ncols_scaled, 
   hipLaunchKernelGGL(k_scale_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, cols, ncols_scaled, f);
   return hipGetLastError();
 }
-hipError_t launch_f32_to_bf16(const float* x, void* y, size_t n, hipStream_t s) {
+hipError_t launch_f32_to_bf16(const float* x, void* y, size_t n, hipStream_t s, bool f16) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (__bf16*)y, n);
+  if (f16) hipLaunchKernelGGL(k_f32_to_bf16<_Float16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (_Float16*)y, n);
+  else hipLaunchKernelGGL(k_f32_to_bf16<__bf16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (__bf16*)y, n);
   return hipGetLastError();
 }
-hipError_t launch_bf16_to_f32(const void* x, float* y, size_t n, hipStream_t s) {
+hipError_t launch_bf16_to_f32(const void* x, float* y, size_t n, hipStream_t s, bool f16) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bf16_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const __bf16*)x, y, n);
+  if (f16) hipLaunchKernelGGL(k_bf16_to_f32<_Float16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const _Float16*)x, y, n);
+  else hipLaunchKernelGGL(k_bf16_to_f32<__bf16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const __bf16*)x, y, n);
   return hipGetLastError();
 }
 

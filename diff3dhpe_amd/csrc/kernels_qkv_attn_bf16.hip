@@ -27,8 +27,13 @@
 typedef __bf16 qa_bf8 __attribute__((ext_vector_type(8)));
 #define QF_MMA(ACC, BH, BL, AH, AL)                                                                                                   \
   do {                                                                                                                                \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(qa_bf8, BH), __builtin_bit_cast(qa_bf8, AH), ACC, 0, 0, 0);      \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(qa_bf8, BL), __builtin_bit_cast(qa_bf8, AL), ACC, 0, 0, 0);      \
+    if constexpr (F16) {   /* (the kernel's template parameter: fp16 operand rows, the f16 twin of the pair) */                       \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(BH, AH, ACC, 0, 0, 0);                                                             \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(BL, AL, ACC, 0, 0, 0);                                                             \
+    } else {                                                                                                                          \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(qa_bf8, BH), __builtin_bit_cast(qa_bf8, AH), ACC, 0, 0, 0);    \
+      ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(qa_bf8, BL), __builtin_bit_cast(qa_bf8, AL), ACC, 0, 0, 0);    \
+    }                                                                                                                                 \
   } while (0)
 #include "qkv_fused_kloop.h"
 
@@ -42,6 +47,25 @@ namespace {
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
+typedef _Float16 hf8 __attribute__((ext_vector_type(8)));
+typedef _Float16 hf4 __attribute__((ext_vector_type(4)));
+// The operand element of a kernel: bf16 (D3D_PREC_BF16), or fp16 (F16 = true, D3D_PREC_F16).  E(float) rounds to nearest even in both;
+// fp16 keeps subnormals and gives inf beyond 65504.  The two 32x32x16 MFMAs share their lane layouts.
+template <bool F16> struct Op16 { typedef __bf16 E; typedef bf8 V8; typedef bf4 V4; };
+template <> struct Op16<true> { typedef _Float16 E; typedef hf8 V8; typedef hf4 V4; };
+// An fp16 rounding point rounds an fp32 VALUE (as torch's .to(float16) does).  Left to itself the compiler folds the multiply or fma in
+// front of some conversions into v_fma_mix{lo,hi}_f16, which rounds the exact product ONCE -- a different result wherever the fp32
+// rounding moves the value across an fp16 boundary, and a different one from kernel to kernel (the fused kernel and the stand-alone
+// attention kernel got different mixes of the two forms and were not bit-identical).  The register is made opaque: v_cvt of the fp32 value.
+__device__ __forceinline__ float f16_point(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+template <bool F16, typename V8>
+__device__ __forceinline__ f32x16 op16_mfma32(V8 a, V8 b, f32x16 c) {
+  if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
 
 QF_SHAPE(8, 3, 256, 192, 4, 3);                                          // 256 x 192 stage of 57344 bytes, 64-deep bf16 k-tiles
 constexpr int QA_ROWS = 255;                                             // token rows of a tile at most
@@ -54,7 +78,7 @@ struct QaArgs {
   const char* A;        // bf16 operand rows [M][D] (norm1(x))
   const char* W;        // bf16 qkv weight rows [3 D][D]
   const float* bias;    // [3 D]
-  __bf16* out;          // attention output, bf16 [M][D]
+  void* out;            // attention output, bf16 (fp16) [M][D]
   int D, H;             // model width (the GEMM depth), heads (D / 64)
   int N, udiv;          // tokens of a group, token stride: token t of group u is row (u / udiv) * N * udiv + u % udiv + t * udiv
   int g, units, mtiles; // groups per tile, groups of the launch, ceil(units / g)
@@ -79,8 +103,12 @@ __device__ __forceinline__ int qa_wrow(const QaArgs& a, int s0, int hd) {
 }
 
 // One 32-query tile `qt` of the group whose rows start at tile row rb: k_attn_bf16's arithmetic on the LDS planes.
-template <int NKT>
-__device__ __forceinline__ void qa_attention(const unsigned char* lds, int lane, int rb, int qt, int T, __bf16* out0, size_t tstride, bool store) {
+template <int NKT, bool F16>
+__device__ __forceinline__ void qa_attention(const unsigned char* lds, int lane, int rb, int qt, int T, typename Op16<F16>::E* out0, size_t tstride,
+                                             bool store) {
+  typedef typename Op16<F16>::E E;
+  typedef typename Op16<F16>::V8 bf8;   // (the names of the bf16 form, for either element type)
+  typedef typename Op16<F16>::V4 bf4;
   const unsigned char* const sQ = lds + QA_PQ;
   const unsigned char* const sK = lds + QA_PK;
   const unsigned char* const sV = lds + QA_PV;
@@ -115,7 +143,7 @@ __device__ __forceinline__ void qa_attention(const unsigned char* lds, int lane,
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const bf8 kf = *reinterpret_cast<const bf8*>(kb[ks] + kt * 4096);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kt], 0, 0, 0);
+      sacc[kt] = op16_mfma32<F16>(kf, qf[ks], sacc[kt]);
     }
   }
   // ---- exact softmax over the keys of this query column (fp32); only the last key tile can hold keys of other groups
@@ -163,7 +191,7 @@ __device__ __forceinline__ void qa_attention(const unsigned char* lds, int lane,
     for (int s = 0; s < 2; ++s) {
       bf8 pf;
 #pragma unroll
-      for (int jj = 0; jj < 8; ++jj) pf[jj] = (__bf16)(sacc[kt][8 * s + jj] * inv);
+      for (int jj = 0; jj < 8; ++jj) pf[jj] = F16 ? (E)f16_point(sacc[kt][8 * s + jj] * inv) : (E)(sacc[kt][8 * s + jj] * inv);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         const s4v a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(uintptr_t)(vb[dt][0] + (2 * kt + s) * 2048));
@@ -175,30 +203,32 @@ __device__ __forceinline__ void qa_attention(const unsigned char* lds, int lane,
         if (kt == NKT - 1) {   // pad keys are other groups' rows here: zeros, as the two-kernel flow stages them (0 x NaN / Inf of a neighbour)
 #pragma unroll
           for (int jj = 0; jj < 8; ++jj)
-            if (kt * 32 + 16 * s + 8 * (jj >> 2) + 4 * h + (jj & 3) >= T) vf[jj] = (__bf16)0.0f;
+            if (kt * 32 + 16 * s + 8 * (jj >> 2) + 4 * h + (jj & 3) >= T) vf[jj] = (E)0.0f;
         }
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[dt], 0, 0, 0);
+        oacc[dt] = op16_mfma32<F16>(vf, pf, oacc[dt]);
       }
       __builtin_amdgcn_sched_barrier(0);   // keeps the conversions / V^T reads of later k-steps from being hoisted (VGPR pressure)
     }
   }
   // ---- O rows out as bf16: lane (query tq, half h) holds d = dt * 32 + 8 g4 + 4 h + e
   if (tq < T && store) {
-    __bf16* orow = out0 + (size_t)tq * tstride;
+    E* orow = out0 + (size_t)tq * tstride;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         bf4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (__bf16)oacc[dt][4 * g4 + e];
+        for (int e = 0; e < 4; ++e) o[e] = (E)oacc[dt][4 * g4 + e];
         *reinterpret_cast<bf4*>(orow + dt * 32 + 8 * g4 + 4 * h) = o;
       }
   }
 }
 
-template <int NKT>
+template <int NKT, bool F16>
 __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
+  typedef typename Op16<F16>::E E;
+  typedef typename Op16<F16>::V4 bf4;
   const int G = (int)gridDim.x, b = (int)blockIdx.x;
   const int H = a.H;
   const int tiles = a.mtiles * H;
@@ -282,7 +312,7 @@ __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
           const float bj[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
           bf4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (__bf16)(__builtin_fmaf(acc[i][j][e], 1.0f, bj[e]) * osc);
+          for (int e = 0; e < 4; ++e) o[e] = F16 ? (E)f16_point(__builtin_fmaf(acc[i][j][e], 1.0f, bj[e]) * osc) : (E)(__builtin_fmaf(acc[i][j][e], 1.0f, bj[e]) * osc);
           *reinterpret_cast<bf4*>(j == 0 ? pkq + QA_PQ : (j == 1 ? pkq + QA_PK : pv)) = o;
         }
       }
@@ -298,8 +328,8 @@ __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
         const int unit = mt * a.g + u;
         const bool ok = unit < a.units;                                   // (wave-uniform)
         if (!ok) continue;
-        __bf16* const out0 = a.out + (size_t)qa_unit_row(a, unit) * a.D + 64 * hd;
-        qa_attention<NKT>(lds, lane, u * a.N, qt, a.N, out0, (size_t)a.udiv * a.D, true);
+        E* const out0 = reinterpret_cast<E*>(a.out) + (size_t)qa_unit_row(a, unit) * a.D + 64 * hd;
+        qa_attention<NKT, F16>(lds, lane, u * a.N, qt, a.N, out0, (size_t)a.udiv * a.D, true);
       }
     }
     mt = mtn; hd = hdn;
@@ -310,15 +340,16 @@ __device__ __forceinline__ void qa_tiles(const QaArgs& a, unsigned char* lds) {
 }  // namespace
 
 // spatial blocks: groups of N <= 32 tokens (the joints of a frame), one key tile
+template <bool F16>
 __global__ __launch_bounds__(512) void k_qkv_sattn_bf16(QaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  qa_tiles<1>(a, lds);
+  qa_tiles<1, F16>(a, lds);
 }
 // temporal blocks: groups of N <= 255 tokens (the frames of one joint), NKT = ceil(N / 32) key tiles
-template <int NKT>
+template <int NKT, bool F16>
 __global__ __launch_bounds__(512) void k_qkv_tattn_bf16(QaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  qa_tiles<NKT>(a, lds);
+  qa_tiles<NKT, F16>(a, lds);
 }
 
 // Shapes the fused kernels exist for: head width 64, GEMM depth D a multiple of 128 from 256 on (whole pairs of 64-deep k-tiles, as
@@ -338,25 +369,31 @@ static hipError_t qa_launch(const QaArgs& a, hipStream_t s) {
 
 // A: bf16 [groups * N][D]; W: bf16 [3 D][D]; bias: [3 D]; out: bf16 [groups * N][D] (not A: every head reads whole rows of A).
 // Group u holds rows (u / stride) * N * stride + u % stride + t * stride, t < N -- spatial blocks: (B * T, J, 1), temporal: (B * J, T, J).
+template <bool F16>
+static hipError_t qa_launch_form(const QaArgs& a, int temporal, hipStream_t s) {
+  if (!temporal) return qa_launch<k_qkv_sattn_bf16<F16>>(a, s);
+  switch ((a.N + 31) / 32) {
+    case 1: return qa_launch<k_qkv_tattn_bf16<1, F16>>(a, s);
+    case 2: return qa_launch<k_qkv_tattn_bf16<2, F16>>(a, s);
+    case 3: return qa_launch<k_qkv_tattn_bf16<3, F16>>(a, s);
+    case 4: return qa_launch<k_qkv_tattn_bf16<4, F16>>(a, s);
+    case 5: return qa_launch<k_qkv_tattn_bf16<5, F16>>(a, s);
+    case 6: return qa_launch<k_qkv_tattn_bf16<6, F16>>(a, s);
+    case 7: return qa_launch<k_qkv_tattn_bf16<7, F16>>(a, s);
+    default: return qa_launch<k_qkv_tattn_bf16<8, F16>>(a, s);
+  }
+}
+
+// f16: fp16 operand rows / weights / output (D3D_PREC_F16).
 hipError_t launch_qkv_attn_bf16(const void* A, const void* W, const float* bias, void* out, int groups, int N, int stride, int D, int H,
-                                int temporal, hipStream_t s) {
+                                int temporal, hipStream_t s, bool f16) {
   if (!A || !W || !bias || !out || A == out || stride < 1 || groups < 1 || groups % stride != 0) return hipErrorInvalidValue;
   if (!qkv_attn_bf16_shape_ok(groups, N, D, H) || (!temporal && N > 32)) return hipErrorInvalidValue;
   QaArgs a{};
-  a.A = (const char*)A; a.W = (const char*)W; a.bias = bias; a.out = (__bf16*)out;
+  a.A = (const char*)A; a.W = (const char*)W; a.bias = bias; a.out = out;
   a.D = D; a.H = H; a.N = N; a.udiv = stride;
   a.g = QA_ROWS / N; a.units = groups; a.mtiles = (groups + a.g - 1) / a.g;
-  if (!temporal) return qa_launch<k_qkv_sattn_bf16>(a, s);
-  switch ((N + 31) / 32) {
-    case 1: return qa_launch<k_qkv_tattn_bf16<1>>(a, s);
-    case 2: return qa_launch<k_qkv_tattn_bf16<2>>(a, s);
-    case 3: return qa_launch<k_qkv_tattn_bf16<3>>(a, s);
-    case 4: return qa_launch<k_qkv_tattn_bf16<4>>(a, s);
-    case 5: return qa_launch<k_qkv_tattn_bf16<5>>(a, s);
-    case 6: return qa_launch<k_qkv_tattn_bf16<6>>(a, s);
-    case 7: return qa_launch<k_qkv_tattn_bf16<7>>(a, s);
-    default: return qa_launch<k_qkv_tattn_bf16<8>>(a, s);
-  }
+  return f16 ? qa_launch_form<true>(a, temporal, s) : qa_launch_form<false>(a, temporal, s);
 }
 
 }  // namespace d3d

@@ -44,6 +44,9 @@ int tile_order_copy(const float* wg, const float* csum, const float* fb, size_t 
 void block0_tables_host(const float* wg, const float* We, const float* be, const float* spos, int D, int H, int cin, int J, float* G, float* P);
 // fp32 -> bf16, round to nearest even (as torch's .to(bfloat16) and v_cvt_pk_bf16_f32); *nonfinite is set when the RESULT is inf or NaN
 uint16_t bf16_rne(float f, bool* nonfinite = nullptr);
+// fp32 -> fp16, round to nearest even with subnormals kept (as torch's .to(float16) and v_cvt_f16_f32); a finite value from 65520 on
+// becomes inf; *nonfinite as above
+uint16_t f16_rne(float f, bool* nonfinite = nullptr);
 
 // ---- the whole engine's images: one block's host weights in, images + the offset of every BlockW field (engine.hip) out
 struct BlockSrc { const float *n1g, *n1b, *qkvw, *qkvb, *projw, *projb, *n2g, *n2b, *fc1w, *fc1b, *fc2w, *fc2b; };
@@ -65,7 +68,8 @@ struct PackedWeights {
 // D / 64 pseudo-heads for the fused kernel of narrower heads (a pair of 32 columns, a quad of 16: one 64-column segment); nothing else
 // reads it.  false: the internal exponent check failed.
 bool pack_f16x3(const std::vector<BlockSrc>& src, size_t D, size_t Dm, size_t H, bool tile_order_s, bool tile_order_t, PackedWeights& out);
-// BF16: bf16 copies of the four GEMM weights of every block, [rows padded to 256][K]
-void pack_bf16(const std::vector<BlockSrc>& src, size_t D, size_t Dm, PackedWeights& out);
+// BF16: bf16 copies of the four GEMM weights of every block, [rows padded to 256][K]; f16 (D3D_PREC_F16): fp16 copies, same layout --
+// `clamped` then also covers a finite weight beyond the fp16 range (its image is inf)
+void pack_bf16(const std::vector<BlockSrc>& src, size_t D, size_t Dm, PackedWeights& out, bool f16 = false);
 
 }  // namespace d3d

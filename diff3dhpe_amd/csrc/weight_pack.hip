@@ -106,6 +106,32 @@ uint16_t bf16_rne(float f, bool* nonfinite) {
   return h;
 }
 
+uint16_t f16_rne(float f, bool* nonfinite) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+  const uint32_t a = u & 0x7fffffffu;
+  uint16_t h;
+  if (a > 0x7f800000u) {
+    h = (uint16_t)(0x7e00u | ((a >> 13) & 0x3ffu));                    // NaN stays NaN (quiet), payload's top bits kept
+  } else if (a >= 0x477ff000u) {
+    h = 0x7c00u;                                                       // >= 65520 (the tie between 65504 and 2^16 goes to even = 2^16), inf
+  } else if (a >= 0x38800000u) {                                       // normal fp16: rebias the exponent (127 -> 15), round 13 bits away
+    const uint32_t v = a - 0x38000000u;
+    h = (uint16_t)((v + 0xfffu + ((v >> 13) & 1u)) >> 13);             // (a mantissa carry runs into the exponent: correct)
+  } else if (a < 0x33000000u) {
+    h = 0;                                                             // < 2^-25: zero (2^-25 itself is the tie between 0 and 2^-24 -> 0, below)
+  } else {                                                             // subnormal fp16: multiples of 2^-24
+    const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u;       // value = m 2^(e - 150); wanted: m 2^(e - 126) in units of 2^-24
+    const uint32_t sh = 126u - e;                                      // 14 .. 24
+    const uint32_t q = m >> sh, rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    h = (uint16_t)(q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u));   // (rounding up to 0x400 is the least normal: correct)
+  }
+  h |= sign;
+  if (nonfinite && (h & 0x7c00u) == 0x7c00u) *nonfinite = true;
+  return h;
+}
+
 bool pack_f16x3(const std::vector<BlockSrc>& src, size_t D, size_t Dm, size_t H, bool tile_order_s, bool tile_order_t, PackedWeights& out) {
   // fp16 hi/lo pair layout of the four GEMM weights of every block, rows padded to a multiple of 256 (zero rows) so
   // the LDS-DMA of edge tiles never leaves the allocation (kernels_gemm_x3p.hip contract)
@@ -154,7 +180,7 @@ bool pack_f16x3(const std::vector<BlockSrc>& src, size_t D, size_t Dm, size_t H,
   return true;
 }
 
-void pack_bf16(const std::vector<BlockSrc>& src, size_t D, size_t Dm, PackedWeights& out) {
+void pack_bf16(const std::vector<BlockSrc>& src, size_t D, size_t Dm, PackedWeights& out, bool f16) {
   // [rows padded to 256][K]: the staging of edge tiles never leaves the allocation (kernels_gemm_x3p.hip contract)
   const size_t nblk = src.size(), per_blk = pad256(3 * D) * D + pad256(D) * D + pad256(Dm) * D + pad256(D) * Dm;
   out = PackedWeights{};
@@ -162,7 +188,7 @@ void pack_bf16(const std::vector<BlockSrc>& src, size_t D, size_t Dm, PackedWeig
   out.blk.assign(nblk, BlockOff{});
   size_t o = 0;
   auto conv = [&](const float* W, size_t rows, size_t cols, size_t& dst) {
-    for (size_t i = 0; i < rows * cols; ++i) out.planes[o + i] = bf16_rne(W[i], &out.clamped);
+    for (size_t i = 0; i < rows * cols; ++i) out.planes[o + i] = f16 ? f16_rne(W[i], &out.clamped) : bf16_rne(W[i], &out.clamped);
     dst = o;
     o += pad256(rows) * cols;
   };

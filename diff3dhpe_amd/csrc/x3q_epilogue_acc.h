@@ -73,6 +73,8 @@ constexpr int FX_SO = 4;    // per-row (sum, sum of squares) of the output rows 
 constexpr int FX_PN = 8;    // the tile spans whole rows: post-norm of the new rows in the epilogue (X3PostNorm)
 constexpr int FX_BF16 = 16; // bf16 operand mode (D3D_PREC_BF16): operands are plain bf16 rows, a 128-byte line = 64 k values, ONE bf16
                             // MFMA per product (two per line); OUTSPLIT 3 = bf16 row-major output (the next GEMM's / the attention's operand)
+constexpr int FX_F16 = 32;  // modifier of FX_BF16 (meaningless alone): the 16-bit operand rows are fp16 (D3D_PREC_F16) -- the f16 twin of each
+                            // bf16 MFMA, outputs rounded to fp16 (nearest even, subnormals kept, inf beyond 65504); everything else is FX_BF16's
 
 // GELU + pair output straight from the accumulators (fc1 -> hidden activation).  The hidden activation is only ever the A
 // operand of the fc2 GEMM, so its k order inside a 32-column group is free: "accumulator order" (pair_col_acc, d3d_kernels.h;

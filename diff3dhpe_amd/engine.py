@@ -804,7 +804,7 @@ def op_attention_long_f32_h16(qkv: torch.Tensor, B: int, T: int, J: int, H: int)
 
 
 def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, groups: int, N: int, stride: int, H: int,
-                     temporal: bool) -> torch.Tensor:
+                     temporal: bool, _symbol: str = "d3d_op_qkv_attn_bf16") -> torch.Tensor:
     """The fused bf16 qkv GEMM + attention kernel alone (include/d3d.h d3d_op_qkv_attn_bf16): A (groups * N, D) token rows,
     Wqkv (3 D, D), bias (3 D,) -> (groups * N, D).  Group u holds rows (u // stride) * N * stride + u % stride + t * stride."""
     dev = A.device
@@ -813,9 +813,15 @@ def op_qkv_attn_bf16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, gr
     out = torch.empty((groups * N, D), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().d3d_op_qkv_attn_bf16(_ptr(a), _ptr(_f32c(Wqkv, dev)), _ptr(_f32c(bias, dev)), int(groups), int(N),
-                                                   int(stride), D, int(H), int(temporal), _ptr(out), st))
+        _lib.check(getattr(_lib.lib(), _symbol)(_ptr(a), _ptr(_f32c(Wqkv, dev)), _ptr(_f32c(bias, dev)), int(groups), int(N),
+                                                int(stride), D, int(H), int(temporal), _ptr(out), st))
     return out
+
+
+def op_qkv_attn_f16(A: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, groups: int, N: int, stride: int, H: int,
+                    temporal: bool) -> torch.Tensor:
+    """The same kernel in its fp16-operand form (include/d3d.h d3d_op_qkv_attn_f16); arguments as op_qkv_attn_bf16."""
+    return op_qkv_attn_bf16(A, Wqkv, bias, groups, N, stride, H, temporal, _symbol="d3d_op_qkv_attn_f16")
 
 
 def op_qkv_attn_x3_small(x: torch.Tensor, Wqkv: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,

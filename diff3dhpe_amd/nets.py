@@ -115,6 +115,7 @@ class _MixSTEDenoiser(nn.Module):
     #   "f16x3" fp32-accurate GEMMs / attention from 3 fp16 MFMAs on hi/lo operand splits; a set range flag RAISES D3DError
     #   "fp32"  exact fp32 MFMA everywhere
     #   "bf16"  second-class (bf16 operands; cannot meet the 1e-4 gate; BASELINE configs[1])
+    #   "f16"   second-class (fp16 operands on the bf16 mode's kernels: about an eighth of its error, no range guard -- inf beyond 65504)
     # "auto", "f16x3" and "fp32" pass the 1e-4 parity gate.  The reference loads arbitrary checkpoints (RUN:226-235): results that
     # are silently not fp32-accurate are not an option, hence the guard is on by default (D3D_CHECK_RANGE=0 or range_check = False
     # turns the read off: one ~2 us kernel + one event wait per call).

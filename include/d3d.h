@@ -48,6 +48,17 @@ extern "C" {
                              * gate (bf16 operands cost ~5e-2 max-abs at random init); it is gated against the CPU
                              * oracle's bf16-operand emulation instead (same rounding points).  Needs head_dim 64, num_frame <= 256,
                              * num_joints <= 32, widths % 64 == 0; never the default of the Python layer or of bench.py. */
+#define D3D_PREC_F16 3      /* SECOND-CLASS like D3D_PREC_BF16, and the same engine: fp16 operands at bf16's rounding points (LayerNorm
+                             * output, q / k / v with the exact q pre-scale 2^-3, softmax - I, attention output, GELU output, weights at
+                             * commit), the f16 twin of each bf16 MFMA, the same kernels instantiated for the other element type.  Three
+                             * more mantissa bits: about an eighth of the bf16 mode's distance to fp32, still
+                             * outside the 1e-4 gate; gated against the oracle's fp16-operand emulation.  Every conversion rounds to
+                             * nearest even and keeps fp16 subnormals, as torch's .to(float16); the operands are UNSCALED and there is NO
+                             * range guard: a finite value beyond +-65504 at a rounding point becomes +-inf (a weight: the commit reports
+                             * it as it reports a non-finite weight).  Admission, workspace, options and info keys are the bf16 mode's:
+                             * "fused_spatial", "fused_temporal", "fused_postnorm", "bf16_gemm_kernel" and "bf16_fused_*_last" serve both
+                             * 16-bit operand modes -- wherever this header says "BF16 mode / engines" of an option it holds for
+                             * D3D_PREC_F16 engines too.  Never chosen by the Python layer's "auto". */
 
 /*
  * Threads
@@ -777,6 +788,12 @@ int d3d_op_attention_long_f32_h16(const float* qkv_dev, float* out_dev, int32_t 
  * N <= 32), groups % stride == 0; anything else: D3D_EUNSUP / D3D_EINVAL. */
 int d3d_op_qkv_attn_bf16(const float* A_dev, const float* Wqkv_dev, const float* bias_dev, int32_t groups, int32_t N, int32_t stride,
                          int32_t D, int32_t H, int32_t temporal, float* out_dev, void* stream);
+/* The same kernel in its fp16-operand form (D3D_PREC_F16): operands, q / k / v, softmax - I and the output rounded to fp16.  q is rounded
+ * once, AFTER its scale by dh^-1/2 (as the engine's un-fused qkv GEMM rounds it): bit for bit d3d_op_linear (D3D_PREC_F16, residual form
+ * with R = 0: q / k / v not rounded yet) followed by d3d_op_attention (D3D_PREC_F16).  Through d3d_op_linear's fp16 output the q third is
+ * rounded twice, which differs where q * dh^-1/2 is an fp16 subnormal.  Arguments and refusals as d3d_op_qkv_attn_bf16. */
+int d3d_op_qkv_attn_f16(const float* A_dev, const float* Wqkv_dev, const float* bias_dev, int32_t groups, int32_t N, int32_t stride,
+                        int32_t D, int32_t H, int32_t temporal, float* out_dev, void* stream);
 
 /* The fused qkv GEMM + attention kernel of "small_tiles" alone (F16X3): out = attention(LayerNorm(X; gamma, beta, eps) Wqkv^T + bias), the
  * LayerNorm folded into the GEMM as the weight commit folds it, q / k / v kept on chip as hi / lo fp16 planes -- bit for bit the folded
